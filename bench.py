@@ -91,7 +91,16 @@ def parse():
                          "pairs of the run instead of the synthetic scans (scripts/lidar_odom_kitti.sh:6); clouds are ragged, `data` says \"kitti\"")
     ap.add_argument("--kitti-prefilter", action="store_true",
                     help="with --kitti-dir: every scan first goes through the device prefilter (0.5-100 m gate + 0.1 m VoxelGrid, launch/dlo_kitti.launch:30-36)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path (the job `value` is measured on) returned in its LAST step as DIR/<name>.npy "
+                         "(float32 / float64, rank 0's pairs): final_transformation, score, trans_probability, iterations, converged, sweeps, status, "
+                         "hits_last, pair_ids -- two builds run with the same arguments see the same inputs and can be compared output for output")
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.prefiltered:
+        ap.error("--dump-outputs covers the headline job; --prefiltered is a row of its own")
+    return a
 
 
 def free_port():
@@ -110,10 +119,17 @@ def launch_command(n_gpus, argv, port):
             "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
 
 
-def self_launch(a, argv, visible_devices=None, execve=None):
-    """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: become N ranks (torch.distributed.run) instead of
-    running ONE rank that reports n_gpus = 1.  Refuses (non-zero exit) when fewer than N devices are visible -- never a silent
-    smaller run.  (LV_SLAM_BENCH_BACKEND=gloo, the functional check of tests/test_bench_gpu.py, lets ranks share a GPU.)"""
+def run_launcher(path, cmd, env):
+    """Run the N-rank launcher as a fresh child process and leave with its exit status (this process may already hold the GPU runtime,
+    which asked for the device count: it is not replaced in place)."""
+    import subprocess
+    raise SystemExit(subprocess.call(cmd, executable=path, env=env))
+
+
+def self_launch(a, argv, visible_devices=None, launch=None):
+    """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: run as N ranks (torch.distributed.run, a child
+    process) instead of running ONE rank that reports n_gpus = 1.  Refuses (non-zero exit) when fewer than N devices are visible -- never a
+    silent smaller run.  (LV_SLAM_BENCH_BACKEND=gloo, the functional check of tests/test_bench_gpu.py, lets ranks share a GPU.)"""
     backend = os.environ.get("LV_SLAM_BENCH_BACKEND", "nccl")
     visible = torch.cuda.device_count() if visible_devices is None else visible_devices
     if visible < (a.gpus if backend == "nccl" else 1):
@@ -122,7 +138,7 @@ def self_launch(a, argv, visible_devices=None, execve=None):
     env = dict(os.environ)
     env["LV_SLAM_BENCH_LAUNCHER"] = "bench.py re-executed itself under torch.distributed.run"
     print("bench: " + " ".join(cmd), file=sys.stderr, flush=True)
-    (execve or os.execve)(cmd[0], cmd, env)
+    (launch or run_launcher)(cmd[0], cmd, env)
 
 
 def se3_err(A, B):
@@ -630,6 +646,25 @@ def prefiltered_row(a, ndt, synth, dev, dev_index):
     print(json.dumps(out), flush=True)
 
 RES_DT = np.dtype([("final", "<f4", 16), ("tp", "<f8"), ("score", "<f8"), ("it", "<i4"), ("conv", "<i4"), ("sweeps", "<i4"), ("status", "<i4"), ("hits", "<i8")])
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res_bytes, pair_ids, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: one step's result records (what batch_align / stream_collect hand the caller, include/mi355_ndt.h) as one .npy per
+    field, row i = pair_ids[i]; integer fields as float64 (exact).  Beyond `limit` bytes a fixed seeded sample of the rows is written."""
+    r = np.frombuffer(res_bytes, dtype=RES_DT)
+    arrays = {"final_transformation": r["final"].reshape(-1, 4, 4).transpose(0, 2, 1).astype(np.float32),    # column-major records -> [pair][row][col]
+              "score": r["score"].astype(np.float64), "trans_probability": r["tp"].astype(np.float64),
+              "iterations": r["it"].astype(np.float64), "converged": r["conv"].astype(np.float64), "sweeps": r["sweeps"].astype(np.float64),
+              "status": r["status"].astype(np.float64), "hits_last": r["hits"].astype(np.float64), "pair_ids": np.asarray(pair_ids, np.float64)}
+    per_row = sum(v[:1].nbytes for v in arrays.values())
+    if per_row * len(r) > limit:
+        keep = np.sort(np.random.default_rng(0).choice(len(r), limit // per_row, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+    return sorted(name + ".npy" for name in arrays)
 
 
 def spread_order(n):
@@ -881,7 +916,7 @@ def timed_job(ctx, eng, W, nb, job_total, steps, warmup, min_seconds=0.5):
                         "packed_on_device": True, "host_hop": not on_dev,
                         "timed_with": "HIP events around all_gather_into_tensor on the stream the collective is ordered on, max over ranks" if on_dev else
                                       "host clock around the device-to-host copy + gloo all_gather (functional check only), max over ranks"}
-    return {"dt": dt, "steps": steps, "step_ms": step_ms, "prof": prof, "res": res, "res_np": res_np, "guesses": guesses,
+    return {"dt": dt, "steps": steps, "step_ms": step_ms, "prof": prof, "res": res, "res_np": res_np, "guesses": guesses, "last_step": (bytes(res), list(ids)),
             "gather_ms_per_step": None if gather_ms is None else round(gather_ms, 4), "gather_check": gather_check, "B": nb}
 
 
@@ -1004,7 +1039,9 @@ def timed_stream_job(ctx, eng, W, nb, job_total, steps, warmup, n_batches=3, n_c
     if ref is not None:                                # word for word against the synchronous align of the same batches
         same = all(bytes(res[k]) == bytes(ref[k]) for k in range(min(n_batches, len(ref))))
         assert same, "streamed results differ from the synchronous results of the same pairs"
+    k_last = (state["col"] - 1) % n_batches            # the batch of the last timed step (its results were the last collected)
     return {"dt": dt, "steps": steps, "step_ms": step_ms, "prof": prof, "res": res[0], "res_np": np.frombuffer(res[0], dtype=RES_DT), "guesses": guesses,
+            "last_step": (bytes(res[k_last]), W["ids"][k_last * nb:(k_last + 1) * nb]),
             "gather_ms_per_step": None if gather_ms is None else round(gather_ms, 4), "gather_check": gather_check, "B": nb, "n_batches": n_batches, "n_contexts": n_contexts,
             "bit_identical_to_synchronous": same,
             "launches": int(prof["stream_launches"]), "pairs_handed_over": int(prof["stream_carried"]), "batches_rerun": int(prof["stream_redone"]),
@@ -1178,7 +1215,7 @@ def other_configs_block(ctx, a, synth, W_head):
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
-        self_launch(a, sys.argv[1:])                  # (does not return: the process becomes torch.distributed.run)
+        self_launch(a, sys.argv[1:])                  # (does not return: exits with the status of torch.distributed.run)
         raise SystemExit("bench.py: the launcher returned")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1435,6 +1472,10 @@ def main():
         out["value_host_clouds"] = max(host_path["registrations_per_s"], host_path["streamed"]["registrations_per_s"])
         out["value_host_clouds_mode"] = "streamed (mi355ndt_stream_submit_host, one engine)" if host_path["streamed"]["registrations_per_s"] >= host_path["registrations_per_s"] else "two synchronous engines"
         out["host_clouds"] = host_path
+    if a.dump_outputs:                            # the last timed step of the job `value` and `ms_per_step` are measured on
+        res_last, ids_last = (JS if streamed_wins else J)["last_step"]
+        out["dump_outputs"] = {"dir": os.path.abspath(a.dump_outputs), "job": out["value_mode"], "pairs": len(ids_last),
+                               "files": dump_outputs(a.dump_outputs, res_last, ids_last)}
     print(json.dumps(out), flush=True)
     eng.close()                                   # release HIP objects before interpreter teardown (profilers hook exit)
     if dist is not None:

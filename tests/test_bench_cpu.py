@@ -77,10 +77,10 @@ def test_gpus_n_without_a_launcher_re_executes_itself_as_n_ranks(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"])
     a = bench.parse()
     seen = {}
-    def fake_execve(path, argv, env):
+    def fake_launch(path, argv, env):
         seen.update(path=path, argv=list(argv), env=dict(env))
     monkeypatch.delenv("LV_SLAM_BENCH_BACKEND", raising=False)
-    bench.self_launch(a, sys.argv[1:], visible_devices=8, execve=fake_execve)
+    bench.self_launch(a, sys.argv[1:], visible_devices=8, launch=fake_launch)
     cmd = seen["argv"]
     assert seen["path"] == sys.executable and cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in cmd and "--nproc-per-node=8" in cmd
@@ -90,13 +90,45 @@ def test_gpus_n_without_a_launcher_re_executes_itself_as_n_ranks(monkeypatch):
     assert "re-executed itself" in seen["env"]["LV_SLAM_BENCH_LAUNCHER"]
     assert cmd == bench.launch_command(8, sys.argv[1:], cmd[cmd.index("--master-port") + 1])
     with pytest.raises(SystemExit) as e:                                              # 4 devices for 8 ranks: refuse, non-zero exit
-        bench.self_launch(a, sys.argv[1:], visible_devices=4, execve=fake_execve)
+        bench.self_launch(a, sys.argv[1:], visible_devices=4, launch=fake_launch)
     assert e.value.code not in (0, None) and "only 4 GPU(s) visible" in str(e.value.code)
     # a world size that contradicts --gpus is refused too (main reads WORLD_SIZE before anything else)
     monkeypatch.setenv("WORLD_SIZE", "1")
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "WORLD_SIZE=1" in str(e.value.code)
+
+
+def test_dump_outputs_writes_every_result_field(tmp_path, monkeypatch):
+    """--dump-outputs: one result record per pair -> one float32 / float64 .npy per field, the 4x4 transforms row-major; past the size limit a
+    fixed seeded sample of whole rows; --steps below 1 is refused."""
+    import numpy as np
+    import pytest
+    import bench
+    n = 50
+    r = np.zeros(n, dtype=bench.RES_DT)
+    F = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    F[:, :3, 3] = np.arange(3 * n, dtype=np.float32).reshape(n, 3)
+    r["final"] = F.transpose(0, 2, 1).reshape(n, 16)                      # the records are column-major (Eigen::Matrix4f)
+    r["score"], r["tp"], r["it"], r["conv"], r["sweeps"], r["hits"] = np.arange(n) * 0.5, 1.0, 7, 1, 8, 2**40 + 3
+    ids = list(range(100, 100 + n))
+    files = bench.dump_outputs(str(tmp_path / "all"), r.tobytes(), ids)
+    assert files == sorted(os.listdir(tmp_path / "all")) and len(files) == 9
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) and len(v) == n for v in got.values())
+    assert np.array_equal(got["final_transformation"], F) and got["pair_ids"].tolist() == ids and got["hits_last"][0] == 2**40 + 3
+    assert np.array_equal(got["score"], r["score"]) and (got["iterations"] == 7).all() and (got["converged"] == 1).all()
+    per_row = 16 * 4 + 8 * 8
+    small = bench.dump_outputs(str(tmp_path / "s1"), r.tobytes(), ids, limit=10 * per_row)
+    again = bench.dump_outputs(str(tmp_path / "s2"), r.tobytes(), ids, limit=10 * per_row)
+    p1, p2 = np.load(tmp_path / "s1" / "pair_ids.npy"), np.load(tmp_path / "s2" / "pair_ids.npy")
+    assert small == again and len(p1) == 10 and np.array_equal(p1, p2) and np.all(np.diff(p1) > 0)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in small) <= 10 * per_row                # (128 = the .npy header)
+    k = (p1 - 100).astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "final_transformation.npy"), F[k])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
 
 
 def test_hsa_ipc_mode_is_owned_by_bench_py():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the one-launch align's counters: round-4 tree (tools/ab_r04) against HEAD, same box, same workload (sync path, config 3)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/ab_pmc; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 ARGS="--cpu-seconds 0 --no-host-clouds --config4-pairs 0 --seq-frames 0 --no-other-configs --steps 3 --warmup 1"

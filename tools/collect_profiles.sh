@@ -2,7 +2,7 @@
 # Runs on the GPU box (through gpurun): rocprofv3 kernel trace + separate PMC passes over bench.py, the bench lines of the
 # BASELINE configurations (parity and CPU legs ON), the latency-mode tools.  Everything lands under gpurun_out/final/;
 # profiles/summarize.py turns it into the committed files.   usage: tools/collect_profiles.sh [part ...]   (default: all parts)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/final
 mkdir -p $O
 PARTS=${@:-"trace pmc tol bench extra"}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One gpurun call's worth of work (GPU box).  usage: gpurun -- 'bash tools/gpu_job.sh <stage>...'; everything lands under gpurun_out/<stage>/
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R
 for stage in "$@"; do
   O=$R/gpurun_out/$stage; mkdir -p $O

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-kernel times of one bench.py run under rocprofv3 (runs on the GPU box through gpurun).
 # usage: tools/kstats.sh <tag> [bench.py arguments...]   -> gpurun_out/<tag>/kstats.txt (engine kernels only) + the bench line
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 O=$R/gpurun_out/$TAG
 rm -rf $O; mkdir -p $O

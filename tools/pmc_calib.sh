@@ -3,7 +3,7 @@
 # independent VALU instructions.  4 * SQ_ACTIVE_INST_VALU / (1024 SIMDs * GRBM_GUI_ACTIVE / 8) of such a kernel at 2 waves per SIMD (the
 # sweep's occupancy) is what "the vector ALU is busy all the time" reads as on this chip; the sweep's own ratio is divided by it.
 # usage: tools/pmc_calib.sh   -> gpurun_out/pmc_calib/calib.json
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/pmc_calib
 rm -rf $O; mkdir -p $O
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 $R/tools/valu_rate.hip -o $O/valu_rate || exit 1

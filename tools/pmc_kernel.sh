@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / TCP counters of one engine kernel over a short bench.py run (GPU box, through gpurun).  Counters are collected in their
 # own passes, without any trace domain.   usage: tools/pmc_kernel.sh <kernel regex> <tag> [bench.py arguments...]
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 KRE=$1; TAG=$2; shift; shift
 O=$R/gpurun_out/pmc_$TAG
 rm -rf $O; mkdir -p $O

@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters of full sweep launches (tools/sweep_only.py workload).  usage: tools/pmc_sweep.sh <mode> <variant>
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/pmc_$1_$2
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

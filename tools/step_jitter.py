@@ -1,5 +1,5 @@
 import sys, os, time, gc
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from lv_slam_amd import ndt, synth
 B, NAZ = 271, 1024

@@ -2,7 +2,7 @@
 # Kernel + copy timeline of the last steps of bench.py's STREAMED job (GPU box, through gpurun): every kernel and copy of the engine in start
 # order with its duration and the idle time of the stream in front of it -- how the streamed step was taken apart (DESIGN.md 4.2b,
 # docs/experiments.md 10d).   usage: tools/stream_timeline.sh <tag> [bench.py arguments...]   -> gpurun_out/<tag>/timeline.txt
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 O=$R/gpurun_out/$TAG
 rm -rf $O; mkdir -p $O

@@ -281,6 +281,15 @@ int mi355ndt_batch_build_targets(mi355ndt_handle* h);
 /* align every pair; guesses = n_pairs x 16 floats column-major; out = n_pairs results. Synchronous. */
 int mi355ndt_batch_align(mi355ndt_handle* h, const float* guesses_colmajor, mi355ndt_result* out);
 int mi355ndt_batch_size(const mi355ndt_handle* h);
+/* getFitnessScore(max_range) for every batch slot: source p moved by T[p], exact nearest target-p point per source point, mean of the
+ * squared distances <= max_range; DBL_MAX and 0 inliers when nothing is in range or target p is empty.  T_colmajor = n_pairs x 16
+ * floats column-major, or NULL = each pair's final pose of the last mi355ndt_batch_align (the identity before any align of the current
+ * batch).  n_inliers may be NULL.  Synchronous.  scores[p] / n_inliers[p] are bit for bit what mi355ndt_fitness_score_T returns on a
+ * one-pair engine holding pair p's clouds and T[p], also for a target without a grid (MI355NDT_ERR_GRID: exhaustive search).  One
+ * exception: a pair with an EMPTY source (or target) scores DBL_MAX, 0 here, where the one-pair call refuses (MI355NDT_ERR_STATE).  Builds the
+ * targets first if they are not built; MI355NDT_ERR_STATE in stream mode.  The loop detector's verification of K candidates against one
+ * new keyframe (loop_detector.hpp:148-281) is one batch_align + one call of this (lv_slam_amd/loop_closure.py). */
+int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, double max_range, double* scores, long long* n_inliers);
 /* Pose records of the last mi355ndt_batch_align for the multi-GPU gather, written on the device into a caller-owned DEVICE
  * buffer of `capacity` 96-byte records {float final[16] column-major; float score; int32 iterations; int32 converged;
  * int32 pair_id; int32 pad[4]}: record k describes batch slot k and carries pair_id = id_base + k * id_stride (round-robin

@@ -92,6 +92,10 @@ struct mi355ndt_handle {
   unsigned* d_rs_hist = nullptr; unsigned* d_rs_offs = nullptr; size_t rs_cap = 0;   // segmented radix sort: tile histograms / offsets
   unsigned *d_cstart = nullptr, *d_cend = nullptr; size_t cell_cap = 0; bool cells_ready = false; int last_cb = 0;
   double* d_fit = nullptr; size_t fit_cap = 0;
+  // batched fitness (mi355ndt_batch_fitness_scores): occupied-cell index of every target (ndt_fitness.hpp), built on the first call after a
+  // target build; the launch's item table and transforms
+  BitWord* d_fwords = nullptr; size_t fwords_cap = 0; unsigned* d_fruns = nullptr; size_t fruns_cap = 0; bool fit_index_ready = false;
+  int* d_fit_items = nullptr; size_t fit_items_cap = 0; float* d_fit_T = nullptr; size_t fit_T_cap = 0;
   // prefilter workspace
   float *d_pf_in = nullptr, *d_pf_out = nullptr; unsigned char* d_pf_keep = nullptr; unsigned *d_pf_keys = nullptr, *d_pf_vals = nullptr;
   int *d_pf_flag = nullptr, *d_pf_pos = nullptr, *d_pf_mm = nullptr; PfGrid* d_pf_grid = nullptr; void* d_pf_tmp = nullptr;
@@ -435,7 +439,7 @@ int mi355ndt_destroy(mi355ndt_handle* h) {
   void* ptrs[] = {h->d_tgt_own, h->d_src_own, h->d_tgt_cnt, h->d_src_cnt, h->d_grid, h->d_nwords, h->d_word_off,
                   h->d_keys_a, h->d_keys_b, h->d_vals_a, h->d_vals_b, h->d_words, h->d_recs, h->d_vox_idx, h->d_vox_n,
                   h->d_state, h->d_partials, h->d_guess, h->d_results, h->d_active, h->d_hook, h->d_aligned, h->d_hits, h->d_seg_start, h->d_heads, h->d_head_cnt, h->d_sums,
-                  h->d_cent, h->d_icov64, h->d_kdw, h->d_rs_hist, h->d_rs_offs, h->d_active_list, h->d_ctl, h->d_cstart, h->d_cend, h->d_fit, h->d_pf_in, h->d_pf_out, h->d_pf_keep, h->d_pf_keys,
+                  h->d_cent, h->d_icov64, h->d_kdw, h->d_rs_hist, h->d_rs_offs, h->d_active_list, h->d_ctl, h->d_cstart, h->d_cend, h->d_fit, h->d_fwords, h->d_fruns, h->d_fit_items, h->d_fit_T, h->d_pf_in, h->d_pf_out, h->d_pf_keep, h->d_pf_keys,
                   h->d_pf_vals, h->d_pf_flag, h->d_pf_pos, h->d_pf_mm, h->d_pf_grid, h->d_pf_tmp, h->d_score_pts, h->d_score_part,
                   h->d_ring, h->d_arrived, h->d_actl, h->d_atab, h->d_sorted, h->d_recs_fast};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1031,6 +1035,7 @@ static int build_targets_impl(mi355ndt_handle* h) {
   h->targets_built = true;
   h->grid_resolution = h->prm.resolution;
   h->cells_ready = false;
+  h->fit_index_ready = false;
   h->last_cb = cb;
   return compute_enqueued(h);                     // asynchronous: a later upload into these rows has to wait for the kernels above
 }
@@ -1787,6 +1792,131 @@ int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], dou
 int mi355ndt_get_fitness_score(mi355ndt_handle* h, double max_range, double* score, long long* n_inliers) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   return mi355ndt_fitness_score_T(h, h->last_final, max_range, score, n_inliers);
+}
+
+// getFitnessScore(max_range) for every batch slot (include/mi355_ndt.h): per pair, word for word what mi355ndt_fitness_score_T returns on a
+// one-pair engine holding the same clouds and transform -- the same block partials (k_fitness_batch / k_fitness_brute_batch), summed on
+// the host in block order from 0.0 as there.
+int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, double max_range, double* scores, long long* n_inliers) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!scores) return MI355NDT_ERR_BAD_ARG;
+  if (h->n_pairs <= 0 || !h->d_tgt || !h->d_src) return MI355NDT_ERR_STATE;
+  HIPCHK(h, hipSetDevice(h->device));
+  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
+  if (!h->targets_built) { int rc = mi355ndt_batch_build_targets(h); if (rc) return rc; }
+  const int B = h->n_pairs;
+  const size_t tp = h->tgt_pitch;
+  hipStream_t s = h->stream;
+  std::vector<GridDesc> gd(B);
+  HIPCHK(h, hipMemcpyAsync(gd.data(), h->d_grid, (size_t)B * sizeof(GridDesc), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  // which pairs go where: an empty target or source scores DBL_MAX with no launch, a grid -> k_fitness_batch, no grid -> k_fitness_brute_batch
+  const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+  std::vector<int> part0(B, 0), nblk(B, 0);
+  int n_part = 0;
+  // the index covers EVERY pair with a grid, whatever its source holds now (k_fit_* index every GRID_OK pair, and a source set later
+  // does not rebuild it): the pool is sized over all of them
+  size_t total_words = 0;
+  bool any_ok = false;
+  for (int b = 0; b < B; b++) {
+    if (gd[b].status != GRID_OK) continue;
+    any_ok = true;
+    total_words = std::max(total_words, (size_t)gd[b].word_off + (size_t)gd[b].nwords);
+  }
+  for (int b = 0; b < B; b++) {
+    const int ns = h->h_src_cnt[b];
+    if (gd[b].status == GRID_EMPTY || ns <= 0) continue;   // (an empty source: DBL_MAX, 0 -- the single call refuses it, MI355NDT_ERR_STATE)
+    nblk[b] = (ns + 255) / 256;
+    part0[b] = n_part;
+    n_part += nblk[b];
+  }
+  if (any_ok && !h->fit_index_ready) {
+    HIPCHK(h, grow(h->d_fwords, h->fwords_cap, total_words));
+    HIPCHK(h, grow(h->d_fruns, h->fruns_cap, (size_t)B * (tp + 1)));
+    HIPCHK(h, hipMemsetAsync(h->d_fwords, 0, total_words * sizeof(BitWord), s));
+    const dim3 pg((unsigned)((tp + 255) / 256), (unsigned)B);
+    k_fit_mark<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->last_cb);
+    k_fit_rank<<<B, 1024, 0, s>>>(h->d_grid, h->d_fwords);
+    k_fit_runs<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->d_fruns, h->last_cb);
+    HIPCHK(h, hipGetLastError());
+    h->fit_index_ready = true;
+  }
+  // item tables of the two launches (FitItem, ndt_fitness.hpp): 16 ints of group starts, then the items group by group.  A pair goes to
+  // the least loaded of the eight groups, in pair order.
+  auto make_table = [&](bool with_grid, std::vector<int>& t, int& group_max) {
+    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int> pg(B, -1);
+    for (int b = 0; b < B; b++) {
+      if (nblk[b] == 0 || (gd[b].status == GRID_OK) != with_grid) continue;
+      int g = 0;
+      for (int k = 1; k < 8; k++) if (load[k] < load[g]) g = k;
+      pg[b] = g;
+      load[g] += nblk[b];
+    }
+    t.assign(16, 0);
+    for (int g = 0; g < 8; g++) {
+      t[g] = (int)((t.size() - 16) / 6);
+      for (int b = 0, blk = 0; b < B; b++) {
+        if (pg[b] != g) continue;
+        // rings needed to cover sqrt(max_range) (+1 cell of slack), as mi355ndt_fitness_score_T computes them
+        const double rr = with_grid ? std::sqrt(std::min(max_range, 1e30)) / (double)gd[b].leaf + 2.0 : 0.0;
+        const int ring_max = rr > (double)(1 << 30) ? (1 << 30) : (int)rr;
+        t.insert(t.end(), {b, blk, part0[b], h->h_src_cnt[b], h->h_tgt_cnt[b], ring_max});
+        blk += nblk[b];
+      }
+    }
+    t[8] = (int)((t.size() - 16) / 6);
+    group_max = *std::max_element(load, load + 8);
+  };
+  std::vector<int> tab, tab_brute;
+  int gmax = 0, gmax_brute = 0;
+  make_table(true, tab, gmax);
+  make_table(false, tab_brute, gmax_brute);
+  const size_t brute_at = tab.size();
+  tab.insert(tab.end(), tab_brute.begin(), tab_brute.end());
+  // transforms: the caller's, the final poses the last align left in d_results (read there, no host round trip), or the identity
+  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const float* dT = nullptr;
+  int Tstride = 16;
+  if (n_part > 0) {
+    static_assert(sizeof(mi355ndt_result) % sizeof(float) == 0 && offsetof(mi355ndt_result, final_colmajor) == 0, "final pose at the head of a result");
+    if (T_colmajor) {
+      HIPCHK(h, grow(h->d_fit_T, h->fit_T_cap, (size_t)B * 16));
+      HIPCHK(h, hipMemcpyAsync(h->d_fit_T, T_colmajor, (size_t)B * 16 * sizeof(float), hipMemcpyHostToDevice, s));
+      dT = h->d_fit_T;
+    } else if (h->aligned_once) {
+      dT = reinterpret_cast<const float*>(h->d_results);
+      Tstride = (int)(sizeof(mi355ndt_result) / sizeof(float));
+    } else {
+      HIPCHK(h, grow(h->d_fit_T, h->fit_T_cap, (size_t)16));
+      HIPCHK(h, hipMemcpyAsync(h->d_fit_T, ident, sizeof ident, hipMemcpyHostToDevice, s));
+      dT = h->d_fit_T;
+      Tstride = 0;
+    }
+    HIPCHK(h, grow(h->d_fit_items, h->fit_items_cap, tab.size()));
+    HIPCHK(h, hipMemcpyAsync(h->d_fit_items, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(h, grow(h->d_fit, h->fit_cap, (size_t)2 * n_part));
+    static_assert(sizeof(FitItem) == 6 * sizeof(int), "FitItem is six ints");
+    const int* t_ok = h->d_fit_items;
+    const int* t_brute = h->d_fit_items + brute_at;
+    if (gmax) k_fitness_batch<<<8u * (unsigned)gmax, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_ok + 16), t_ok, h->d_src, h->src_pitch, h->d_tgt, tp,
+                                                                h->d_vals_b, h->d_grid, h->d_fwords, h->d_fruns, dT, Tstride, mr, h->d_fit);
+    if (gmax_brute) k_fitness_brute_batch<<<8u * (unsigned)gmax_brute, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_brute + 16), t_brute, h->d_src, h->src_pitch,
+                                                                                  h->d_tgt, tp, dT, Tstride, mr, h->d_fit);
+    HIPCHK(h, hipGetLastError());
+  }
+  std::vector<double> part((size_t)2 * n_part);
+  if (n_part > 0) HIPCHK(h, hipMemcpyAsync(part.data(), h->d_fit, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  for (int b = 0; b < B; b++) {
+    double sum = 0, cnt = 0;
+    for (int k = 0; k < nblk[b]; k++) { sum += part[2 * ((size_t)part0[b] + k)]; cnt += part[2 * ((size_t)part0[b] + k) + 1]; }
+    scores[b] = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
+    if (n_inliers) n_inliers[b] = (long long)cnt;
+  }
+  return MI355NDT_OK;
 }
 
 // replaces calculateScore(cloud) (ndt_omp.h:232, ndt_omp_impl2.hpp:1006-1040)

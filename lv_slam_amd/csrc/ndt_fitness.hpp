@@ -21,6 +21,20 @@ __global__ void __launch_bounds__(256) k_cellrange(const KeyT* __restrict__ keys
   if (i + 1 == pitch || keys[i + 1] != key) cend[cell] = (unsigned)i + 1u;
 }
 
+// deterministic block reduction of the 256 lanes' (squared distance, inlier) terms: shuffle-xor inside each wave, then the four wave sums
+// in wave order; out[0] = sum, out[1] = count.  Every fitness kernel ends with it, so a pair's block partials are the same whichever kernel made them.
+__device__ __forceinline__ void fit_block_reduce(double sum, unsigned long long cnt, double* out) {
+  for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o); cnt += __shfl_xor(cnt, o); }
+  __shared__ double rs[4];
+  __shared__ unsigned long long rc[4];
+  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = sum; rc[threadIdx.x >> 6] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out[0] = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+    out[1] = (double)(rc[0] + rc[1] + rc[2] + rc[3]);
+  }
+}
+
 __global__ void __launch_bounds__(256) k_fitness(const float* __restrict__ src, size_t spitch, int n_src,
                                                  const float* __restrict__ tgt, size_t tpitch, const unsigned* __restrict__ vals,
                                                  const GridDesc* __restrict__ gd, const unsigned* __restrict__ cstart, const unsigned* __restrict__ cend,
@@ -83,26 +97,18 @@ __global__ void __launch_bounds__(256) k_fitness(const float* __restrict__ src, 
       if (best <= max_range) { sum = (double)best; cnt = 1; }
     }
   }
-  // deterministic block reduction
-  for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o); cnt += __shfl_xor(cnt, o); }
-  __shared__ double rs[4];
-  __shared__ unsigned long long rc[4];
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = sum; rc[threadIdx.x >> 6] = cnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = ((rs[0] + rs[1]) + rs[2]) + rs[3];
-    partial[2 * blockIdx.x + 1] = (double)(rc[0] + rc[1] + rc[2] + rc[3]);
-  }
+  fit_block_reduce(sum, cnt, partial + 2 * blockIdx.x);
 }
 
 // The same score for a target that has no voxel grid (the leaf-too-small guard or the engine's cell cap: GRID_OVERFLOW / GRID_CAP) --
 // pcl::Registration::getFitnessScore searches a kd-tree over the target CLOUD and does not care.  Exhaustive search, the target
 // staged through LDS 256 points at a time; same distance arithmetic, same reduction as k_fitness.
-__global__ void __launch_bounds__(256) k_fitness_brute(const float* __restrict__ src, size_t spitch, int n_src,
-                                                       const float* __restrict__ tgt, size_t tpitch, int n_tgt,
-                                                       const float* __restrict__ Tcm, float max_range, double* partial) {
+// (block `blk` of one pair: source points blk * 256 .. blk * 256 + 255; the batched form calls it for every block of every pair without a grid)
+__device__ __forceinline__ void fitness_brute_block(const float* __restrict__ src, size_t spitch, int n_src,
+                                                    const float* __restrict__ tgt, size_t tpitch, int n_tgt,
+                                                    const float* __restrict__ Tcm, float max_range, int blk, double* out) {
   __shared__ float tx[256], ty[256], tz[256];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blk * 256 + threadIdx.x;
   float q[3] = {0.f, 0.f, 0.f};
   bool live = false;
   if (i < n_src) {
@@ -131,14 +137,208 @@ __global__ void __launch_bounds__(256) k_fitness_brute(const float* __restrict__
   double sum = 0.0;
   unsigned long long cnt = 0;
   if (live && best <= max_range) { sum = (double)best; cnt = 1; }
-  for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o); cnt += __shfl_xor(cnt, o); }
-  __shared__ double rs[4];
-  __shared__ unsigned long long rc[4];
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = sum; rc[threadIdx.x >> 6] = cnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = ((rs[0] + rs[1]) + rs[2]) + rs[3];
-    partial[2 * blockIdx.x + 1] = (double)(rc[0] + rc[1] + rc[2] + rc[3]);
+  fit_block_reduce(sum, cnt, out);
+}
+__global__ void __launch_bounds__(256) k_fitness_brute(const float* __restrict__ src, size_t spitch, int n_src,
+                                                       const float* __restrict__ tgt, size_t tpitch, int n_tgt,
+                                                       const float* __restrict__ Tcm, float max_range, double* partial) {
+  fitness_brute_block(src, spitch, n_src, tgt, tpitch, n_tgt, Tcm, max_range, blockIdx.x, partial + 2 * blockIdx.x);
+}
+
+
+// ------------------------------------------------------------------------------------ batched fitness score (mi355ndt_batch_fitness_scores)
+// The dense cstart / cend table of the single-pair path costs 8 B per grid cell, gigabytes over a batch.  The batched form reads an index
+// of the OCCUPIED cells instead, built by the first batched fitness call after a target build, in pools of its own:
+//   words[gd.word_off + w]   (BitWord, the NDT bitmap's layout and offsets, not its pool): occupancy of cells 64w .. 64w + 63 -- every cell
+//                            holding a target point, whatever min_points says -- and `prefix` = occupied cells before them (rank);
+//   runs[b * (pitch + 1) + k]: sorted position (d_vals_b segment) of the first point of the pair's k-th occupied cell; runs[n_occ] = the
+//                            number of binned points.
+// Cells are sorted by linear index, so the occupied cells of a cell range [a, e) are ranks rank(a) .. rank(e) - 1 and their points the
+// sorted positions runs[rank(a)] .. runs[rank(e)] - 1: one row of a ring face costs two word reads however long it is.
+__device__ __forceinline__ unsigned fit_rank(const BitWord* __restrict__ W, unsigned c) {
+  const BitWord w = W[c >> 6];
+  return w.prefix + (unsigned)__popcll(w.bits & ((1ull << (c & 63)) - 1ull));
+}
+
+// occupancy bits: every run head of a pair's sorted segment sets its cell's bit.  The lanes of a wave hold ascending cells, so the lanes
+// that share a word are contiguous: a segmented OR across them leaves one atomicOr per (wave, word) instead of one per cell.
+__global__ void __launch_bounds__(256) k_fit_mark(const unsigned* __restrict__ keys, size_t pitch, const GridDesc* __restrict__ gd, BitWord* words, int cb) {
+  const int b = blockIdx.y;
+  if (gd[b].status != GRID_OK) return;
+  const unsigned cmask = (1u << cb) - 1u;
+  const unsigned* K = keys + (size_t)b * pitch;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned cell = cmask;
+  bool head = false;
+  if (i < pitch) {
+    cell = K[i] & cmask;
+    head = cell != cmask && (i == 0 || (K[i - 1] & cmask) != cell);
+  }
+  const unsigned w = cell >> 6;                   // (not binned: cmask >> 6, at or above every real word, and no bit)
+  unsigned long long bits = head ? 1ull << (cell & 63) : 0ull;
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long vb = __shfl_down(bits, o);
+    const unsigned vw = __shfl_down(w, o);
+    if (lane + o < 64 && vw == w) bits |= vb;
+  }
+  const unsigned wp = __shfl_up(w, 1);
+  if (bits && (lane == 0 || wp != w)) atomicOr(&words[gd[b].word_off + w].bits, bits);
+}
+
+// rank of every word: exclusive popcount prefix over the pair's words (one block per pair; the trailing all-zero word gets n_occ)
+__global__ void __launch_bounds__(1024) k_fit_rank(const GridDesc* __restrict__ gd, BitWord* words) {
+  __shared__ unsigned sm[17];
+  const int b = blockIdx.x;
+  if (gd[b].status != GRID_OK) return;
+  BitWord* W = words + gd[b].word_off;
+  const int nw = gd[b].nwords;
+  unsigned base = 0;
+  for (int w0 = 0; w0 < nw; w0 += 1024) {
+    const int w = w0 + threadIdx.x;
+    const unsigned c = w < nw ? (unsigned)__popcll(W[w].bits) : 0u;
+    unsigned tot;
+    const unsigned ex = block_exscan<1024>(c, &tot, sm);
+    if (w < nw) W[w].prefix = base + ex;
+    base += tot;
   }
 }
 
+// run starts by rank; the end of the last run closes the table
+__global__ void __launch_bounds__(256) k_fit_runs(const unsigned* __restrict__ keys, size_t pitch, const GridDesc* __restrict__ gd,
+                                                  const BitWord* __restrict__ words, unsigned* runs, int cb) {
+  const int b = blockIdx.y;
+  if (gd[b].status != GRID_OK) return;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pitch) return;
+  const unsigned cmask = (1u << cb) - 1u;
+  const unsigned* K = keys + (size_t)b * pitch;
+  const unsigned cell = K[i] & cmask;
+  if (cell == cmask) return;
+  const bool head = i == 0 || (K[i - 1] & cmask) != cell;
+  const bool last = i + 1 == pitch || (K[i + 1] & cmask) == cmask;
+  if (!head && !last) return;
+  const unsigned k = fit_rank(words + gd[b].word_off, cell);
+  unsigned* R = runs + (size_t)b * (pitch + 1);
+  if (head) R[k] = (unsigned)i;
+  if (last) R[k + 1] = (unsigned)i + 1u;
+}
+
+// One scored pair of a batched launch.  The launch is a flat grid over (pair, 256-point block): workgroup L serves group g = L % 8 (the
+// workgroups that share an XCD, cdna_hip_programming.md 5.5 T1) and the (L / 8)-th block of that group's pairs, which are listed back
+// to back (block0 = the pair's first block within its group).  A pair's blocks therefore share one XCD's L2 with its target points and
+// index.  part0 = the pair's first partial slot; the host sums a pair's partials in block order.
+struct FitItem { int pair, block0, part0, n_src, n_tgt, ring_max; };
+
+__device__ __forceinline__ bool fit_item(const FitItem* __restrict__ items, const int* __restrict__ gstart, FitItem& it, int& bx) {
+  const int g = blockIdx.x & 7, s = blockIdx.x >> 3;
+  int lo = gstart[g], hi = gstart[g + 1];
+  if (lo >= hi) return false;
+  while (hi - lo > 1) {                           // last item of the group with block0 <= s
+    const int mid = (lo + hi) >> 1;
+    if (items[mid].block0 <= s) lo = mid; else hi = mid;
+  }
+  it = items[lo];
+  bx = s - it.block0;
+  return bx * 256 < it.n_src;
+}
+
+// k_fitness for every pair with a grid: the same transform, the same rings, the same stopping rule, the same distance arithmetic and
+// block reduction; only the way a ring finds its occupied cells differs (rows of the z / y faces by rank, the x faces of the other rows by
+// one bit each).  The nearest distance is a minimum over the same set of points, so it does not depend on the order they are visited in.
+__global__ void __launch_bounds__(256) k_fitness_batch(const FitItem* __restrict__ items, const int* __restrict__ gstart,
+                                                       const float* __restrict__ src, size_t spitch, const float* __restrict__ tgt, size_t tpitch,
+                                                       const unsigned* __restrict__ vals, const GridDesc* __restrict__ gd,
+                                                       const BitWord* __restrict__ words, const unsigned* __restrict__ runs,
+                                                       const float* __restrict__ Tcm, int Tstride, float max_range, double* partial) {
+  FitItem it;
+  int bx;
+  if (!fit_item(items, gstart, it, bx)) return;
+  const int b = it.pair;
+  const GridDesc& g = gd[b];
+  const float* S = src + (size_t)b * 3 * spitch;
+  const float* X = tgt + (size_t)b * 3 * tpitch;
+  const unsigned* V = vals + (size_t)b * tpitch;
+  const BitWord* W = words + g.word_off;
+  const unsigned* R = runs + (size_t)b * (tpitch + 1);
+  const float* Tb = Tcm + (size_t)b * Tstride;
+  double sum = 0.0;
+  unsigned long long cnt = 0;
+  const int i = bx * 256 + threadIdx.x;
+  if (i < it.n_src) {
+    const float px = S[i], py = S[spitch + i], pz = S[2 * spitch + i];
+    float q[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) q[a] = ((Tb[0 * 4 + a] * px + Tb[1 * 4 + a] * py) + Tb[2 * 4 + a] * pz) + Tb[3 * 4 + a];   // PCL 1.8 scalar form
+    if (finite3(q[0], q[1], q[2])) {
+      int cq[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const float cf = floorf(q[a] * g.inv_leaf);
+        const long long ci = cf >= 1.0e9f ? 1000000000ll : (cf <= -1.0e9f ? -1000000000ll : (long long)cf);
+        const long long cl = ci - (long long)g.min_b[a];
+        cq[a] = (int)(cl > (1ll << 29) ? (1ll << 29) : (cl < -(1ll << 29) ? -(1ll << 29) : cl));
+      }
+      const int c0 = cq[0], c1 = cq[1], c2 = cq[2];
+      const int o0 = c0 < 0 ? -c0 : (c0 >= g.div_b[0] ? c0 - g.div_b[0] + 1 : 0);
+      const int o1 = c1 < 0 ? -c1 : (c1 >= g.div_b[1] ? c1 - g.div_b[1] + 1 : 0);
+      const int o2 = c2 < 0 ? -c2 : (c2 >= g.div_b[2] ? c2 - g.div_b[2] + 1 : 0);
+      const int r_first = max(o0, max(o1, o2));
+      const int r_last = min(it.ring_max, r_first + max(g.div_b[0], max(g.div_b[1], g.div_b[2])) + 1);
+      float best = __int_as_float(0x7f800000);
+      auto visit = [&](unsigned j0, unsigned j1) {
+        for (unsigned j = j0; j < j1; j++) {
+          const unsigned pi = V[j];
+          const float dx = q[0] - X[pi], dy = q[1] - X[tpitch + pi], dz = q[2] - X[2 * tpitch + pi];
+          const float d2 = (dx * dx + dy * dy) + dz * dz;          // FLANN L2_Simple accumulation order
+          best = d2 < best ? d2 : best;
+        }
+      };
+      for (int r = r_first; r <= r_last; r++) {
+        const float reach = ((float)(r - 1) - 1e-3f) * g.leaf;
+        if (r > 1 && (best <= reach * reach || reach * reach > max_range)) break;
+        const int z0 = max(c2 - r, 0), z1 = min(c2 + r, g.div_b[2] - 1);
+        const int y0 = max(c1 - r, 0), y1 = min(c1 + r, g.div_b[1] - 1);
+        const int x0 = max(c0 - r, 0), x1 = min(c0 + r, g.div_b[0] - 1);
+        if (x0 > x1) continue;                    // (the ring misses the grid's x extent: k_fitness visits no cell of it either)
+        for (int z = z0; z <= z1; z++) {
+          const bool zface = (z == c2 - r || z == c2 + r);
+          for (int y = y0; y <= y1; y++) {
+            const bool yface = (y == c1 - r || y == c1 + r);
+            const unsigned row = (unsigned)(y * g.mul1 + z * g.mul2);
+            if (zface || yface) {                 // the whole row x0 .. x1: its occupied cells are one rank interval
+              const unsigned k0 = fit_rank(W, row + (unsigned)x0), k1 = fit_rank(W, row + (unsigned)x1 + 1u);
+              if (k0 != k1) visit(R[k0], R[k1]);
+            } else {                              // interior row: the two x faces only
+#pragma unroll
+              for (int f = 0; f < 2; f++) {
+                const int x = f ? c0 + r : c0 - r;
+                if (x < x0 || x > x1) continue;
+                const unsigned c = row + (unsigned)x;
+                const BitWord w = W[c >> 6];
+                if ((w.bits >> (c & 63)) & 1ull) {
+                  const unsigned k = w.prefix + (unsigned)__popcll(w.bits & ((1ull << (c & 63)) - 1ull));
+                  visit(R[k], R[k + 1]);
+                }
+              }
+            }
+          }
+        }
+      }
+      if (best <= max_range) { sum = (double)best; cnt = 1; }
+    }
+  }
+  fit_block_reduce(sum, cnt, partial + 2 * ((size_t)it.part0 + bx));
+}
+
+// the pairs without a grid (GRID_OVERFLOW / GRID_CAP), in a launch of their own: k_fitness_brute per block
+__global__ void __launch_bounds__(256) k_fitness_brute_batch(const FitItem* __restrict__ items, const int* __restrict__ gstart,
+                                                             const float* __restrict__ src, size_t spitch, const float* __restrict__ tgt, size_t tpitch,
+                                                             const float* __restrict__ Tcm, int Tstride, float max_range, double* partial) {
+  FitItem it;
+  int bx;
+  if (!fit_item(items, gstart, it, bx)) return;
+  const int b = it.pair;
+  fitness_brute_block(src + (size_t)b * 3 * spitch, spitch, it.n_src, tgt + (size_t)b * 3 * tpitch, tpitch, it.n_tgt,
+                      Tcm + (size_t)b * Tstride, max_range, bx, partial + 2 * ((size_t)it.part0 + bx));
+}

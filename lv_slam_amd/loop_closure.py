@@ -1,0 +1,104 @@
+"""Loop-closure verification on the batch surface.
+
+The reference's loop detector (include/global_graph/loop_detector.hpp) verifies the candidate keyframes of a new keyframe one by one: the
+new keyframe is the target, every candidate in turn is the source, aligned from the guess `new.inverse() * candidate` (z zeroed) and
+scored with getFitnessScore(fitness_score_max_range); the converged candidate with the lowest score wins if that score is within
+fitness_score_thresh.  `matching` (:148-205) walks all candidates; `matching_and_bow` (:211-281) walks the DBoW3 top results in BoW
+order and stops early.
+
+Every align of that loop is independent of the others given the target: what one candidate yields does not depend on which candidates
+were aligned before it.  So aligning all K candidates in ONE batch (mi355ndt_batch_align), scoring them in one call
+(mi355ndt_batch_fitness_scores) and then applying the reference's selection rule to the precomputed (converged, score, final) triples
+selects the same loop, with the same relative pose and score, as the reference's sequential loop.  The rules below also report how many
+aligns the sequential loop would have run (matching_and_bow stops early; the batch aligns every candidate it was given).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import ndt
+
+DBL_MAX = 1.7976931348623157e308
+BOW_MIN_SCORE = 0.04            # matching_and_bow: a BoW score below this ends the walk (loop_detector.hpp:240)
+
+
+def loop_guess(new_pose, cand_pose) -> np.ndarray:
+    """(new_pose.inverse() * cand_pose).matrix().cast<float>() with guess(2, 3) = 0 (loop_detector.hpp:171-172, 250-251).
+    The poses are the keyframes' 4x4 isometries (node estimates, f64); the inverse is the rigid one, [R^T, -R^T t]."""
+    N = np.asarray(new_pose, np.float64)
+    Cp = np.asarray(cand_pose, np.float64)
+    if N.shape != (4, 4) or Cp.shape != (4, 4):
+        raise ValueError("poses must be 4x4")
+    inv = np.eye(4)
+    inv[:3, :3] = N[:3, :3].T
+    inv[:3, 3] = -(N[:3, :3].T @ N[:3, 3])
+    G = (inv @ Cp).astype(np.float32)
+    G[3] = np.float32([0, 0, 0, 1])
+    G[2, 3] = 0.0
+    return G
+
+
+def select_matching(converged, scores, finals, thresh: float):
+    """LoopDetector::matching's rule (loop_detector.hpp:168-197) over precomputed per-candidate results, in candidate order.
+    A candidate is skipped when it has not converged or its score is above the best so far, so a tie goes to the LATER candidate.
+    Returns (index or None, relative_pose or None, best_score, aligns the reference would have run); None when best_score > thresh."""
+    best, idx, pose = DBL_MAX, None, None
+    for i, (c, s) in enumerate(zip(converged, scores)):
+        if not c or s > best:
+            continue
+        best, idx, pose = float(s), i, np.asarray(finals[i])
+    if best > thresh:
+        return None, None, best, len(scores)
+    return idx, pose, best, len(scores)
+
+
+def select_matching_and_bow(converged, scores, finals, bow, thresh: float):
+    """LoopDetector::matching_and_bow's rule (loop_detector.hpp:240-270).  `bow` = the DBoW3 query results in their order, as
+    (bow_score, candidate index) pairs.  Before each candidate the walk ends when its BoW score is below 0.04 or the best score so far
+    is already within `thresh`; otherwise the candidate counts as aligned, and is skipped when it has not converged or scores above
+    the best.  Returns (index or None, relative_pose or None, best_score, aligns the reference would have run)."""
+    best, matched, pose, aligns = DBL_MAX, None, None, 0
+    for b, cid in bow:
+        if b < BOW_MIN_SCORE or best <= thresh:
+            break
+        # the reference assigns best_matched before it checks the candidate (:246-247); once the best score is within `thresh` the
+        # next round ends the walk, so a loop that is returned always names the candidate that gave best_score
+        matched = int(cid)
+        aligns += 1
+        if not converged[cid] or scores[cid] > best:
+            continue
+        best, pose = float(scores[cid]), np.asarray(finals[cid])
+    if best > thresh:
+        return None, None, best, aligns
+    return matched, pose, best, aligns
+
+
+def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
+    """Verify loop candidates against one new keyframe on the batch surface: the target in every slot, candidate k as the source of
+    slot k, ONE batch_align from `guesses` ([K,4,4], e.g. loop_guess per candidate), ONE batch_fitness_scores(max_range), then
+    select_matching (bow=None) or select_matching_and_bow (bow = [(bow_score, candidate index), ...] in query order; only the candidates
+    it names are aligned).  The engine's parameters are the registration's (resolution, epsilon, iterations, search method).
+    Returns select_*'s tuple: (candidate index or None, relative pose, best score, aligns the sequential reference would have run)."""
+    K = len(candidates)
+    if K == 0:
+        return None, None, DBL_MAX, 0                   # (the reference returns nullptr for no candidates)
+    G = np.asarray(guesses, np.float32)
+    if G.shape != (K, 4, 4):
+        raise ValueError(f"guesses must be [{K},4,4]")
+    slots = list(range(K)) if bow is None else list(dict.fromkeys(int(c) for _, c in bow))
+    if not slots:
+        return None, None, DBL_MAX, 0
+    tgt = ndt._as_points(target)
+    srcs = [ndt._as_points(candidates[c]) for c in slots]
+    engine.batch_reserve(len(slots), max(len(tgt), 1), max(max(len(s) for s in srcs), 1))
+    for k, s in enumerate(srcs):
+        engine.batch_set_target(k, tgt)
+        engine.batch_set_source(k, s)
+    res = engine.batch_align(G[slots])
+    sc, _ = engine.batch_fitness_scores(max_range)
+    converged, scores, finals = [False] * K, [DBL_MAX] * K, [None] * K
+    for k, c in enumerate(slots):
+        converged[c], scores[c], finals[c] = res[k]["converged"], float(sc[k]), res[k]["final"]
+    if bow is None:
+        return select_matching(converged, scores, finals, thresh)
+    return select_matching_and_bow(converged, scores, finals, bow, thresh)

@@ -82,7 +82,7 @@ SYMBOLS = [
     "mi355ndt_set_target", "mi355ndt_set_source", "mi355ndt_promote_source_to_target", "mi355ndt_align", "mi355ndt_get_aligned", "mi355ndt_get_incremental",
     "mi355ndt_get_fitness_score", "mi355ndt_fitness_score_T", "mi355ndt_prefilter", "mi355ndt_use_prefiltered", "mi355ndt_derivatives", "mi355ndt_compute_hessian", "mi355ndt_derivatives_T", "mi355ndt_get_grid", "mi355ndt_get_voxels",
     "mi355ndt_batch_reserve", "mi355ndt_batch_set_target", "mi355ndt_batch_set_source", "mi355ndt_batch_set_clouds", "mi355ndt_batch_bind_device",
-    "mi355ndt_batch_build_targets", "mi355ndt_batch_align", "mi355ndt_batch_size", "mi355ndt_batch_pose_records",
+    "mi355ndt_batch_build_targets", "mi355ndt_batch_align", "mi355ndt_batch_size", "mi355ndt_batch_pose_records", "mi355ndt_batch_fitness_scores",
     "mi355ndt_profile_enable", "mi355ndt_profile_reset", "mi355ndt_profile_get", "mi355ndt_synchronize",
     "mi355ndt_set_latency_mode", "mi355ndt_sequence_run",
     "mi355ndt_calculate_score", "mi355ndt_convert_transform", "mi355ndt_set_option", "mi355ndt_get_option",
@@ -144,6 +144,7 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_batch_align.argtypes = [vp, vp, vp]
     L.mi355ndt_batch_size.argtypes = [vp]
     L.mi355ndt_batch_pose_records.argtypes = [vp, i, i, vp, sz]
+    L.mi355ndt_batch_fitness_scores.argtypes = [vp, vp, C.c_double, vp, vp]
     L.mi355ndt_profile_enable.argtypes = [vp, i]
     L.mi355ndt_profile_reset.argtypes = [vp]
     L.mi355ndt_profile_get.argtypes = [vp, C.POINTER(Profile)]
@@ -403,6 +404,30 @@ class Engine:
     def batch_pose_records(self, id_base: int, id_stride: int, d_records_ptr: int, capacity: int):
         """96-byte pose records of the last batch_align, packed on the device into a caller-owned device buffer (dist.py layout)."""
         self._chk(self.lib.mi355ndt_batch_pose_records(self.h, id_base, id_stride, C.c_void_p(d_records_ptr), capacity), "batch_pose_records")
+
+    def batch_fitness_scores(self, max_range: float = float("inf"), T=None):
+        """getFitnessScore(max_range) of every batch slot in one call: (scores float64[n], inliers int64[n]).  T = [n,4,4], one [4,4]
+        for all pairs, or None = each pair's final pose of the last batch_align (identity before any).  Bit for bit fitness_score() of a
+        one-pair engine holding the same clouds and transform; a pair with an empty source or target scores (DBL_MAX, 0), where
+        fitness_score() refuses."""
+        n = self.lib.mi355ndt_batch_size(self.h)
+        if n < 0:
+            raise NDTError(n, "batch_fitness_scores")
+        mr = 1.7976931348623157e308 if max_range == float("inf") else float(max_range)
+        t = None
+        if T is not None:
+            M = np.asarray(T, np.float32)
+            if M.shape == (4, 4):
+                M = np.broadcast_to(M, (n, 4, 4))
+            if M.shape != (n, 4, 4):
+                raise ValueError(f"T must be [{n},4,4] or [4,4]")
+            t = np.ascontiguousarray(np.transpose(M, (0, 2, 1))).reshape(n, 16)
+        scores = np.zeros(max(n, 1), np.float64)
+        inliers = np.zeros(max(n, 1), np.int64)
+        self._chk(self.lib.mi355ndt_batch_fitness_scores(self.h, None if t is None else t.ctypes.data_as(C.c_void_p), mr,
+                                                         scores.ctypes.data_as(C.c_void_p), inliers.ctypes.data_as(C.c_void_p)),
+                  "batch_fitness_scores")
+        return scores[:n], inliers[:n]
 
     def synchronize(self):
         self._chk(self.lib.mi355ndt_synchronize(self.h), "synchronize")

@@ -111,6 +111,7 @@ typedef struct mi355ndt_profile {
   long long cloud_promotions; /* mi355ndt_promote_source_to_target calls (device-to-device instead of an upload) */
   long long stream_reserved_slots; /* stream mode: workgroup slots the persistent launches leave to the next batch's build (the effective MI355NDT_OPT_STREAM_RESERVE; 0 = the build runs between the launches) */
   long long stream_launch_slots;   /* stream mode: workgroups of one persistent launch (CUs x workgroups per CU - the reserved slots) */
+  long long score_only_sweeps;     /* sweeps of the one-launch align that evaluated the score alone (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) */
 } mi355ndt_profile;
 
 typedef struct mi355ndt_handle mi355ndt_handle;
@@ -233,7 +234,13 @@ enum mi355ndt_option {
    * work item (512 points) widened to f64 from there on, leaf sums of the target build as a tree instead of in input order.  The point
    * transform and the voxel lookup are untouched (same leaves for the same pose).  Served for DIRECT1 / DIRECT7 with the dead More-Thuente
    * loop (every configuration lv_slam ships); other configurations ignore the option.  Measured cost in accuracy: BASELINE.md 5a. */
-  MI355NDT_OPT_ARITH = 7
+  MI355NDT_OPT_ARITH = 7,
+  /* 1 (default): in the one-launch align, a pair's last derivative sweep -- the one whose convergence test (ndt_omp_impl2.hpp:175-179) is decided
+   * when the step is scheduled, because it reads only the iteration count and the step length -- evaluates the score alone: its gradient and
+   * Hessian are never read.  0: every sweep evaluates all 43 sums.  Same results bit for bit; mi355ndt_profile.score_only_sweeps counts the
+   * score-only sweeps.  The environment variable MI355NDT_SCORE_ONLY_LAST_SWEEP sets the default for engines created afterwards.  Not changed
+   * in stream mode. */
+  MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP = 8
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);

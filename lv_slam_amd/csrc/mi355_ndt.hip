@@ -112,6 +112,7 @@ struct mi355ndt_handle {
   int items_per_pair = 0;                         // sweep work items per pair (= rows_per_pair in batch mode, 4 x rows_per_pair in latency mode)
   bool async_force = false;                       // MI355NDT_OPT_ASYNC_ALIGN = 2 / MI355NDT_ASYNC=2: the one-launch align also for batches smaller than the resident waves (tests, fuzzing)
   bool async_align = true;                        // MI355NDT_OPT_ASYNC_ALIGN: batch aligns as ONE persistent launch (ndt_async.hpp); MI355NDT_ASYNC=0 turns it off
+  int score_only_last = 1;                        // MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP: the one-launch align's last sweep of a pair evaluates the score alone
   int* d_ring = nullptr; size_t ring_cap_total = 0; unsigned* d_arrived = nullptr; size_t arrived_cap = 0; AsyncCtl* d_actl = nullptr;
   AsyncCtl* h_pin_actl = nullptr;
   AsyncTab* d_atab = nullptr;                     // the launch's context table (ndt_async.hpp)
@@ -141,7 +142,7 @@ struct mi355ndt_handle {
   int dyn_shift = -1;                             // < 0: per search mode (make_sweep_const); MI355NDT_SWEEP_DYN_SHIFT overrides (tuning runs)
   int* h_pin_active = nullptr;
   hipEvent_t ev_burst[2] = {nullptr, nullptr};   // one per in-flight burst of align rounds
-  unsigned long long* d_hits = nullptr;         // (point,voxel) evaluations, all sweeps
+  unsigned long long* d_hits = nullptr;         // [0] (point,voxel) evaluations, all sweeps; [1] score-only sweeps of the one-launch align
   float* d_hook = nullptr;                      // 16 + 9 floats, 6 doubles
   float* d_aligned = nullptr; size_t aligned_cap = 0;
   float* h_pin_aligned = nullptr; size_t pin_aligned_cap = 0;   // pinned landing buffer of get_aligned
@@ -406,6 +407,7 @@ int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle**
   if (const char* e = std::getenv("MI355NDT_FINE_TILES")) { const int v = std::atoi(e); if (v == 1 || v == 2) h->fine_tiles = v; }
   if (const char* e = std::getenv("MI355NDT_ARITH")) h->arith = std::atoi(e) == 1 ? 1 : 0;   // default of MI355NDT_OPT_ARITH for engines created afterwards (tools, A/B runs)
   if (const char* e = std::getenv("MI355NDT_ASYNC")) { h->async_align = std::atoi(e) != 0; h->async_force = std::atoi(e) == 2; }
+  if (const char* e = std::getenv("MI355NDT_SCORE_ONLY_LAST_SWEEP")) h->score_only_last = std::atoi(e) != 0;   // default of MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP (A/B runs)
   if (const char* e = std::getenv("MI355NDT_SWEEP_DYN_SHIFT")) { const int v = std::atoi(e); if (v >= 0 && v <= 30) h->dyn_shift = v; }
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
@@ -415,7 +417,8 @@ int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle**
       hipHostMalloc((void**)&h->h_pin_active, 128 * sizeof(int)) != hipSuccess ||
       hipMalloc((void**)&h->d_active, 128 * sizeof(int)) != hipSuccess ||
       hipMalloc((void**)&h->d_ctl, 2 * sizeof(SweepCtl)) != hipSuccess ||
-      hipMalloc((void**)&h->d_hits, sizeof(unsigned long long)) != hipSuccess ||
+      hipMalloc((void**)&h->d_hits, 2 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemsetAsync(h->d_hits, 0, 2 * sizeof(unsigned long long), h->stream) != hipSuccess ||   // (the counters start at zero, not at what the allocation held)
       hipMalloc((void**)&h->d_hook, 64 * sizeof(double)) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_compute, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_burst[0], hipEventDisableTiming) != hipSuccess ||
@@ -848,7 +851,7 @@ int mi355ndt_profile_reset(mi355ndt_handle* h) {
     e->P = mi355ndt_profile{};
   }
   h->P = mi355ndt_profile{};
-  (void)hipMemsetAsync(h->d_hits, 0, sizeof(unsigned long long), h->stream);
+  (void)hipMemsetAsync(h->d_hits, 0, 2 * sizeof(unsigned long long), h->stream);
   (void)hipStreamSynchronize(h->stream);
   return MI355NDT_OK;
 }
@@ -869,12 +872,13 @@ int mi355ndt_profile_get(mi355ndt_handle* h, mi355ndt_profile* out) {
       h->P.cloud_uploads += e->P.cloud_uploads; e->P.cloud_uploads = 0; h->P.cloud_upload_bytes += e->P.cloud_upload_bytes; e->P.cloud_upload_bytes = 0;
       h->P.cloud_transfers += e->P.cloud_transfers; e->P.cloud_transfers = 0; }
   }
-  unsigned long long hh = 0;                      // (point, voxel) evaluations since the last reset, summed on the device
-  HIPCHK(h, hipMemcpy(&hh, h->d_hits, sizeof hh, hipMemcpyDeviceToHost));
+  unsigned long long hh[2] = {0, 0};              // (point, voxel) evaluations and score-only sweeps since the last reset, summed on the device
+  HIPCHK(h, hipMemcpy(hh, h->d_hits, sizeof hh, hipMemcpyDeviceToHost));
   *out = h->P;
   if (h->stream_on) { out->stream_reserved_slots = h->s_reserve_wg; out->stream_launch_slots = h->s_launch_slots; }
-  out->sweep_hits += (long long)hh;
-  out->sweep_alg_bytes += 64.0 * (double)hh;
+  out->sweep_hits += (long long)hh[0];
+  out->sweep_alg_bytes += 64.0 * (double)hh[0];
+  out->score_only_sweeps = (long long)hh[1];
   return MI355NDT_OK;
 }
 
@@ -1302,7 +1306,7 @@ static void fill_async_ctx(const mi355ndt_handle* e, AsyncCtx& c) {
   SweepConst sc;
   make_sweep_const(e, sc);
   c.src = e->d_src; c.pitch = e->src_pitch; c.st = e->d_state; c.gd = e->d_grid; c.words = e->d_words; c.recs = sweep_recs(e, sc); c.cent = e->d_cent;
-  c.partials = e->d_partials; c.src_cnt = e->d_src_cnt; c.arrived = e->d_arrived; c.results = e->d_results; c.n_done = nullptr; c.must_finish = 1; c.pose = nullptr; c.pose_base = 0; c.pose_stride = 0; c.pad_ = 0;
+  c.partials = e->d_partials; c.src_cnt = e->d_src_cnt; c.arrived = e->d_arrived; c.results = e->d_results; c.n_done = nullptr; c.must_finish = 1; c.pose = nullptr; c.pose_base = 0; c.pose_stride = 0; c.score_only = e->score_only_last;
 }
 extern "C" {
 static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt_result* out) {
@@ -1995,7 +1999,8 @@ int mi355ndt_convert_transform(const double x[6], float out[16]) {
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
-  if (h->stream_on && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN)) NOT_IN_STREAM(h);
+  if (h->stream_on && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
+                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP)) NOT_IN_STREAM(h);
   if (option == MI355NDT_OPT_F32_SUM_ORDER) {
     if (value != 0 && value != 1) return MI355NDT_ERR_BAD_ARG;
     h->f32_sum_order = value;
@@ -2010,6 +2015,11 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
     if (value < 0 || value > 2) return MI355NDT_ERR_BAD_ARG;
     h->async_align = value != 0;
     h->async_force = value == 2;                 // 2: also for batches smaller than the GPU's resident waves (testing)
+    return MI355NDT_OK;
+  }
+  if (option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) {
+    if (value != 0 && value != 1) return MI355NDT_ERR_BAD_ARG;
+    h->score_only_last = value;
     return MI355NDT_OK;
   }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_ABORT) {
@@ -2039,6 +2049,7 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (option == MI355NDT_OPT_F32_SUM_ORDER) { *value = h->f32_sum_order; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ARITH) { *value = h->arith; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) { *value = h->async_force ? 2 : (h->async_align ? 1 : 0); return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) { *value = h->score_only_last; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_ABORT) { *value = h->debug_abort_pos == 0xFFFFFFFFu ? -1 : (int)h->debug_abort_pos; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_RINGS) { *value = (int)h->debug_ring_mask; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_STREAM_THRESHOLD) { *value = h->s_thresh_opt; return MI355NDT_OK; }
@@ -2314,7 +2325,7 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
     }
     rc = mi355ndt_set_stream(e, h->s_reserve_wg > 0 ? h->s_build_stream : h->stream);
     if (rc) return fail(rc);
-    e->f32_sum_order = h->f32_sum_order; e->arith = h->arith; e->async_align = h->async_align; e->dyn_shift = h->dyn_shift;
+    e->f32_sum_order = h->f32_sum_order; e->arith = h->arith; e->async_align = h->async_align; e->dyn_shift = h->dyn_shift; e->score_only_last = h->score_only_last;
     e->async_build = true;
     e->ev_pool_target = 128;
     rc = ensure_pair_arrays(e, max_pairs);          // every per-pair array at its final size: no allocation, no wait inside submit

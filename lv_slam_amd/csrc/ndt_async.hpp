@@ -44,7 +44,8 @@ struct AsyncCtx {
   int must_finish;              // the context's buffers are recycled after this launch: its pairs are never handed over
   // (may be null) the batch's 96-byte pose records for the multi-GPU gather, written by the updater that finalises a pair:
   // record b carries pair_id = pose_base + b * pose_stride -- packed on the device with no kernel of its own
-  int pose_base; PoseRecord* pose; int pose_stride, pad_;
+  int pose_base; PoseRecord* pose; int pose_stride;
+  int score_only;               // MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP: the context's updates may mark a pair's last sweep (PairState::last_sweep)
 };
 struct AsyncTab { AsyncCtx c[ASYNC_MAX_CTX]; };
 // A pointer that comes out of memory is a FLAT pointer to the compiler: flat loads are slower than global ones, also count against the LDS
@@ -59,7 +60,7 @@ struct AsyncCtxG {
   NDT_GP(double) partials; NDT_GP(const int) src_cnt; NDT_GP(unsigned) arrived; NDT_GP(mi355ndt_result) results;
   NDT_GP(unsigned) n_done;
   int must_finish;
-  int pose_base; NDT_GP(PoseRecord) pose; int pose_stride, pad_;
+  int pose_base; NDT_GP(PoseRecord) pose; int pose_stride, score_only;
 };
 static_assert(sizeof(AsyncCtxG) == sizeof(AsyncCtx) && offsetof(AsyncCtxG, pose) == offsetof(AsyncCtx, pose) && offsetof(AsyncCtxG, n_done) == offsetof(AsyncCtx, n_done),
               "AsyncCtxG mirrors AsyncCtx");
@@ -69,7 +70,7 @@ __device__ __forceinline__ AsyncCtx async_ctx_load(const AsyncTab* __restrict__ 
   c.src = (const float*)g.src; c.pitch = g.pitch; c.st = (PairState*)g.st; c.gd = (const GridDesc*)g.gd; c.words = (const BitWord*)g.words;
   c.recs = (const VoxelRec*)g.recs; c.cent = (const float*)g.cent; c.partials = (double*)g.partials; c.src_cnt = (const int*)g.src_cnt;
   c.arrived = (unsigned*)g.arrived; c.results = (mi355ndt_result*)g.results; c.n_done = (unsigned*)g.n_done; c.must_finish = g.must_finish;
-  c.pose_base = g.pose_base; c.pose = (PoseRecord*)g.pose; c.pose_stride = g.pose_stride; c.pad_ = 0;
+  c.pose_base = g.pose_base; c.pose = (PoseRecord*)g.pose; c.pose_stride = g.pose_stride; c.score_only = g.score_only;
   return c;
 }
 // stream mode, per context, in device memory: what the host wants to know about a context's batch after every launch
@@ -148,6 +149,8 @@ NDT_KERNEL void k_async_prepare(const AsyncTab tab, AsyncTab* tab_dev, const int
 // are still in the launch, a pair that wants another sweep is SUSPENDED instead -- its state is complete in memory, its ticket word goes
 // into ctl->carry, and the next launch's prepare kernel turns it into one of that launch's first tickets.  The count only ever falls, so
 // at most `stop_thresh` pairs are suspended; which ones is a matter of timing, what they compute is not (a pair's bits depend on the pair alone).
+// A sweep marked as the pair's last (PairState::last_sweep, which its items read with the pose) left rows that carry the score and the hit
+// count alone: the update adds those two columns with the same tree, runs no solve, and finalises the pair.  hits_total[1] (profiling) counts them.
 __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, const int tw, const int n_pts, const int rows_per_pair, PairState& Ssh, volatile double* sol,
                                              int* ring, const int ring_cap, AsyncCtl* ctl, const unsigned n_live, const int stop_thresh, unsigned long long* hits_total,
                                              const double step_max, const double eps, const int max_iterations
@@ -222,13 +225,17 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
-  if (lane < NACC) {
+  const bool last = __builtin_amdgcn_readfirstlane(Ssh.last_sweep) != 0;   // (the state has landed in LDS)
+  if (lane < NACC && (!last || lane == 0 || lane == NACC - 1)) {             // (a score-only row: the other columns are stale)
     double v = 0.0;
     v += aw0; v += aw1; v += aw2; v += aw3;
     if (lane == 0) Ssh.score = v;
     else if (lane < 7) Ssh.g[lane - 1] = v;
     else if (lane < 43) Ssh.H[lane - 7] = v;
-    else { Ssh.hits = (long long)v; if (hits_total) atomicAdd(hits_total, (unsigned long long)v); }
+    else {
+      Ssh.hits = (long long)v;
+      if (hits_total) { atomicAdd(hits_total, (unsigned long long)v); if (last) atomicAdd(hits_total + 1, 1ull); }
+    }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -242,7 +249,11 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
   bool reb_ok = want_reb && Ssh.reb_tag == (long long)Ssh.sweeps;
   unsigned long long rbw = 0;
   if (reb_ok && lane < 14) rbw = __hip_atomic_load(sg + RB0 + lane, RLX_AGENT);
-  newton_solve_side(Ssh, sol);                     // lanes 0..6: impl2:138-140 (same functions and operands as k_update's second wave)
+  if (!last) newton_solve_side(Ssh, sol);          // lanes 0..6: impl2:138-140 (same functions and operands as k_update's second wave)
+  else if (lane == 0) {                            // a last sweep ends the pair in the convergence test, before the solve is read; should that test
+    for (int a = 0; a < 6; a++) sol[a] = 0.0;      // ever disagree with the flag, the zero step ends the pair there (impl2:147-152) -- no wait on a solve that never comes
+    sol[6] = 1.0;
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   TL_STAMP(13);                                    // solve
@@ -260,7 +271,7 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   const bool rebased = reb_ok;                     // (a tag that never came: newton_update computes the re-basing itself, same bits)
-  int rc = newton_update(Ssh, &results[b], step_max, eps, max_iterations, 0, sol, rebased);
+  int rc = newton_update(Ssh, &results[b], step_max, eps, max_iterations, 0, sol, rebased, C.score_only != 0);
   rc = __builtin_amdgcn_readfirstlane(rc);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -461,32 +472,38 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
 #ifndef ASYNC_D1_PIPE
 #define ASYNC_D1_PIPE 1
 #endif
-    if constexpr (K == 1 && ASYNC_D1_PIPE && ORD != 2) {   // DIRECT1 (exact arithmetic): the claim's items as one software pipeline (ndt_sweep.hpp), same rows bit for bit
-      sweep_rows_d1<PCA, ORD, CLAIM_D1>(b, rem, C.src, C.pitch, C.gd, C.words, C.recs, C.partials, I, sc, exp_tab, pose_w, n_b, b
+    // the pair's last sweep (PairState::last_sweep, word 21 of the pose words): the score-only body, chosen once per item (wave-uniform)
+    const bool last = __builtin_amdgcn_readlane(pose_w, POSE_W_LAST) != 0;
+    auto items = [&](auto so_c) {
+      constexpr bool SO = decltype(so_c)::value;
+      if constexpr (K == 1 && ASYNC_D1_PIPE && ORD != 2) {   // DIRECT1 (exact arithmetic): the claim's items as one software pipeline (ndt_sweep.hpp), same rows bit for bit
+        sweep_rows_d1<PCA, ORD, CLAIM_D1, SO>(b, rem, C.src, C.pitch, C.gd, C.words, C.recs, C.partials, I, sc, exp_tab, pose_w, n_b, b
 #ifdef NDT_TIMELINE
-                                     , tl, tl_last
+                                       , tl, tl_last
 #endif
-                                     );
-    } else if constexpr (K == 1 && ORD == 2 && FAST_D1_POINT) {   // DIRECT1, tolerance arithmetic: the claim's items as one stream of tiles, lane = point
-      float T[12], Rj[9];
+                                       );
+      } else if constexpr (K == 1 && ORD == 2 && FAST_D1_POINT) {   // DIRECT1, tolerance arithmetic: the claim's items as one stream of tiles, lane = point
+        float T[12], Rj[9];
 #pragma unroll
-      for (int a_ = 0; a_ < 12; a_++) T[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, a_));
+        for (int a_ = 0; a_ < 12; a_++) T[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, a_));
 #pragma unroll
-      for (int a_ = 0; a_ < 9; a_++) Rj[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a_));
-      sweep_rows_d1p<PCA, CLAIM_D1, true>(b, rem, C.src, C.pitch, T, Rj, n_b, C.gd[b], C.words, C.recs, C.partials, I, sc
+        for (int a_ = 0; a_ < 9; a_++) Rj[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a_));
+        sweep_rows_d1p<PCA, CLAIM_D1, true>(b, rem, C.src, C.pitch, T, Rj, n_b, C.gd[b], C.words, C.recs, C.partials, I, sc
 #ifdef NDT_TIMELINE
-                                          , tl, tl_last
+                                            , tl, tl_last
 #endif
-                                          );
-    } else {
+                                            );
+      } else {
 #pragma unroll 1
-      for (int k = 0; k < CLAIM; k++)
-        sweep_item<PCA, K, 8, false, ORD, true>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b
+        for (int k = 0; k < CLAIM; k++)
+          sweep_item<PCA, K, 8, false, ORD, true, SO>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b
 #ifdef NDT_TIMELINE
-                                                , tl, tl_last
+                                                  , tl, tl_last
 #endif
-                                                );
-    }
+                                                  );
+      }
+    };
+    if (last) items(std::true_type()); else items(std::false_type());
     // Three memory round trips between two items, each carrying everything that does not depend on the next one:
     //  1. the row stores drain (the row is complete in memory before the arrival that may hand it to an updater) -- and the claim of the
     //     next position, which depends on nothing, returns with them;

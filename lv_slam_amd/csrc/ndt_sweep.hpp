@@ -104,6 +104,23 @@ __device__ __forceinline__ void eval_hit(const float u_in[3], const float r[3], 
 #undef NDT_ACC
 }
 
+// Score-only evaluation (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): the prefix of eval_hit up to s_inc -- y, q, the exponential, e1, the validity
+// gate -- and the same term added to the same accumulator, for the last sweep of an align, whose gradient and Hessian are never read.
+template <bool PCA, int ORD = 0>
+__device__ __forceinline__ void eval_score(const float u[3], const float C[9], const double d1, const float d2f, const double w, const bool ok_in,
+                                           double& acc0, const double* __restrict__ exp_tab) {
+  float y[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) y[j] = sum3<ORD>(u[0] * C[j], u[1] * C[3 + j], u[2] * C[6 + j]);
+  const float qf = sum3<ORD>(u[0] * y[0], u[1] * y[1], u[2] * y[2]);
+  const float e0 = ndtm::exp_f32arg((-d2f * qf) * 0.5f, exp_tab);                // impl2:581
+  float s_inc = (float)(-d1 * (double)e0);                                       // impl2:583
+  const float e1 = d2f * e0;                                                     // impl2:585
+  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);                  // impl2:588-589
+  s_inc = ok ? s_inc : 0.f;
+  if (PCA) acc0 = fma(w, (double)s_inc, acc0); else acc0 += (double)s_inc;
+}
+
 // ------------------------------------------------------------------------------------ tolerance arithmetic (ORD = 2)
 // MI355NDT_OPT_ARITH = 1: the same evaluation -- updateDerivatives with the patterns of computePointDerivatives_AngleAxisd folded in -- priced
 // for north_star's tolerance (trans < 1e-4 m, rot < 1e-5 rad) instead of one separately rounded operation per step of the reference recipe.  What changes against eval_hit:
@@ -180,6 +197,32 @@ __device__ __forceinline__ void eval_hit_fast(const float u[3], const float r[3]
     for (int j = 0; j < 3; j++) a[FA_BASE + 3 * i + j] = fmaf(er, y[j], a[FA_BASE + 3 * i + j]);
   }
 }
+// ... and its score-only prefix (as eval_score for eval_hit): same operations, same f32 sum a[0]
+template <bool PCA>
+__device__ __forceinline__ void eval_score_fast(const float u[3], const float c[6], const float d1f, const float d2f, const float kq,
+                                                const float w, const bool ok_in, float& a0) {
+  const float c00 = c[0], c01 = c[1], c02 = c[2], c11 = c[3], c12 = c[4], c22 = c[5];
+  float y[3];
+  y[0] = fmaf(c02, u[2], fmaf(c01, u[1], c00 * u[0]));
+  y[1] = fmaf(c12, u[2], fmaf(c11, u[1], c01 * u[0]));
+  y[2] = fmaf(c22, u[2], fmaf(c12, u[1], c02 * u[0]));
+  const float q = fmaf(u[2], y[2], fmaf(u[1], y[1], u[0] * y[0]));
+  const float e0 = __builtin_amdgcn_exp2f(kq * q);                               // impl2:581
+  const float e1 = d2f * e0;                                                     // impl2:585
+  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);                  // impl2:588-589
+  float s = -d1f * e0;                                                           // impl2:583
+  if (PCA) s *= w;
+  s = ok ? s : 0.f;
+  a0 += s;
+}
+// A score-only work item's row: the lane sums of the score added with the pairwise tree of the reduce-scatter below (lanes l / l^32, then
+// l^16, ... l^1: the same operand pairs, so the same bits), then the score and the hit count are the only words of the row written.
+__device__ __forceinline__ double score_tree(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // the 37 sums of a lane -> the 43 entries of a partial row (score, g, H row-major), widened
 __device__ __forceinline__ void fast_acc_to_row(const float a[NACC_F], double acc[43]) {
 #pragma unroll
@@ -279,13 +322,15 @@ static inline int sweep_wpe(bool pca, int K, bool fast = false) { (void)pca; ret
 typedef __attribute__((address_space(1))) unsigned int gu32;
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-// ASYNC: the 21 pose words of pair state S (T: 12, Rj: 9), lane k holding word k -- one agent-scope (L1-bypassing) vector load, never the
-// scalar cache: the pair's updater, some other workgroup of the same launch, rewrote them since the pair's previous sweep
+// ASYNC: the 21 pose words of pair state S (T: 12, Rj: 9) and its last_sweep flag (word 21), lane k holding word k -- one agent-scope
+// (L1-bypassing) vector load, never the scalar cache: the pair's updater, some other workgroup of the same launch, rewrote them since the
+// pair's previous sweep
+#define POSE_W_LAST 21
 __device__ __forceinline__ unsigned sweep_pose_words(const PairState* S) {
-  static_assert(offsetof(PairState, T) == 0 && offsetof(PairState, Rj) == 48, "pose words");
+  static_assert(offsetof(PairState, T) == 0 && offsetof(PairState, Rj) == 48 && offsetof(PairState, last_sweep) == 4 * POSE_W_LAST, "pose words");
   const int lane = threadIdx.x & 63;
   unsigned w = 0;
-  if (lane < 21) w = __hip_atomic_load((const gu32*)reinterpret_cast<const unsigned*>(S) + lane, RLX_AGENT);
+  if (lane <= POSE_W_LAST) w = __hip_atomic_load((const gu32*)reinterpret_cast<const unsigned*>(S) + lane, RLX_AGENT);
   return w;
 }
 
@@ -297,11 +342,17 @@ __device__ __forceinline__ void sweep_rows_d1p(const int b, const int rem0, cons
                                                , unsigned long long* tl, unsigned long long& tl_last
 #endif
                                                );
+// The LDS of a work item by purpose (SLOT) and shape, declared outside the item functions: a function's own __shared__ arrays are one set per
+// instantiation, and the score-only and the full item body of one kernel (SO) must share theirs, not each take the workgroup's LDS.
+template <typename T, int SLOT>
+__device__ __forceinline__ T& item_lds() { __shared__ T v; return v; }
 #ifndef FAST_D1_POINT
 #define FAST_D1_POINT 0          // tolerance arithmetic, DIRECT1: 1 = lane = point (sweep_rows_d1p) instead of the hit queue -- built, measured, not faster (below)
 #endif
 
-template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC>
+// SO: score-only item (the pair's last sweep, PairState::last_sweep): the same probe stage, hit queue, 64-hit batches and ndt_pca weights; each
+// hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
+template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false>
 __device__ __forceinline__ void sweep_item(const int b, const int rem, const float* __restrict__ src, const size_t pitch, const PairState* st,
                                            const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                            double* partials, const int rows_per_pair, const SweepConst& sc, const float* __restrict__ cent,
@@ -313,6 +364,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
                                            ) {
   constexpr bool KD = (K == 27);
   constexpr bool FAST = (ORD == 2);                // tolerance arithmetic (eval_hit_fast): `recs` holds VoxelRecF records
+  static_assert(!SO || (ASYNC && !FINE), "score-only items belong to the one-launch align");
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
   typedef SweepTune<PCA, K, ORD> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -326,21 +378,21 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   constexpr int Q_NEED = (IT / TP > 1 ? 64 : 0) + TP * (K < Q_GROUP ? K : Q_GROUP) * 64;
   constexpr int Q_CAP = FAST ? (Q_NEED <= 128 ? 128 : Q_NEED <= 256 ? 256 : Q_NEED <= 512 ? 512 : 1024) : ((K > 1 && K <= Q_GROUP) ? 1024 : 512);
   static_assert(Q_NEED <= Q_CAP, "hit queue");
-  __shared__ unsigned q_ent[WAVES][Q_CAP];
+  auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 0>();
   // ndt_pca weight of a queued hit: the suffix product (f64: up to ~150^7) -- for DIRECT1 just the leaf's own integer weight
   typedef typename std::conditional<K == 1, int, typename std::conditional<FAST, float, double>::type>::type QW;
-  __shared__ QW q_w[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1];
+  auto& q_w = item_lds<QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
   // TP tiles of 64 points are probed together ("super-tile"): their point transforms, then ALL their bitmap loads, then all
   // their ballots -- the probe stage costs a few L2 round trips per super-tile, not per tile.  DIRECT1 has one probe per point
   // and ~0.9 hits, so it is probe-stage bound: 4 tiles at a time; DIRECT7: 2 (14 bitmap words in flight); the 26/27-cell
   // searches already have 7-probe groups inside one tile.
   constexpr int NBUF = (IT / TP > 1) ? 2 : 1;   // a super-tile that is the whole item needs no second buffer
-  __shared__ float stage[WAVES][NBUF * 64 * TP][6];   // (two) super-tiles of staged points: x'(3), R x (3)
+  auto& stage = item_lds<float[WAVES][NBUF * 64 * TP][6], 2>();   // (two) super-tiles of staged points: x'(3), R x (3)
 
   // FINE: the four waves of a block always hold the four rows of ONE chunk (items 4q .. 4q+3: static dealing, four waves per block, a
   // multiple of four items per pair), so the chunk level of k_update's tree -- ((r0 + r1) + r2) + r3 -- is added here through LDS and
   // one row per chunk goes to memory: a quarter of the rows for the update to fetch.
-  __shared__ double red[FINE ? WAVES : 1][FINE ? NACC : 1];
+  auto& red = item_lds<double[FINE ? WAVES : 1][FINE ? NACC : 1], 3>();
   const PairState& S = st[b];
   // ASYNC: T (12 words), Rj (9) and n_src through agent-scope vector loads (never the scalar cache, never a stale L1 line): the
   // updater of this pair -- some other workgroup of this launch -- rewrote them since the pair's previous sweep
@@ -418,10 +470,12 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
       const bool live = lane < m && (PCAQ || KD || B.weight != VOX_DEAD);
       if constexpr (FAST) {
         float u[3] = {(xt0 - B.mh[0]) - B.ml[0], (xt1 - B.mh[1]) - B.ml[1], (xt2 - B.mh[2]) - B.ml[2]};
-        eval_hit_fast<PCA, decltype(mid)>(u, r, B.c, sc.d1f, sc.d2f, sc.kq, B.w, live, acc, mid);
+        if constexpr (SO) { mid(); eval_score_fast<PCA>(u, B.c, sc.d1f, sc.d2f, sc.kq, B.w, live, acc[0]); }
+        else eval_hit_fast<PCA, decltype(mid)>(u, r, B.c, sc.d1f, sc.d2f, sc.kq, B.w, live, acc, mid);
       } else {
         float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
-        eval_hit<PCA, decltype(mid), KD, ORD>(u, r, B.C, sc.d1, sc.d2f, B.w, live, acc, exp_tab, mid);
+        if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, B.w, live, acc[0], exp_tab); }
+        else eval_hit<PCA, decltype(mid), KD, ORD>(u, r, B.C, sc.d1, sc.d2f, B.w, live, acc, exp_tab, mid);
       }
       nhits += PCAQ ? (unsigned)m : (unsigned)__popcll(__ballot(live));
       qhead = (qhead + m) & (Q_CAP - 1);
@@ -587,6 +641,14 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
     // levels use gfx950's v_permlane32_swap / v_permlane16_swap to exchange HALF of the values between lane halves /
     // rows, so 43 -> 22 -> 11 values remain per lane before the in-row butterfly (66 swaps + 88 shuffles + 77 adds
     // instead of 516 shuffles + 258 adds per item).
+    if constexpr (SO) {
+      const double v = score_tree((double)acc[0]);
+      if (lane == 0) {
+        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(partials + ((size_t)b * rows_per_pair + rem) * NACC);
+        __hip_atomic_store(PG, (unsigned long long)__double_as_longlong(v), RLX_AGENT);
+        __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
+      }
+    } else {
     typedef unsigned int u2v __attribute__((ext_vector_type(2)));
     double accd[43];
     if constexpr (FAST) fast_acc_to_row(acc, accd);
@@ -629,6 +691,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
         if (lane == 0) P[43] = (double)nhits;
       }
     }
+    }
     if (FINE) {
       __syncthreads();                              // (uniform: the four waves of a block run the same items loop, see above)
       if (wv == 0 && lane < NACC)
@@ -652,7 +715,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
 // every row -- so the rows carry the same bits (tests/test_gpu_configs.py and tests/test_stream_gpu.py hold this function, which the
 // one-launch align uses, against the round-based kernels, which use sweep_item).
 // The staging area holds one row (four super-tiles); a super-tile's slot is free again when its row has been flushed.
-template <bool PCA, int ORD, int NROWS>
+// SO: score-only rows (the pair's last sweep), as sweep_item's SO.
+template <bool PCA, int ORD, int NROWS, bool SO = false>
 __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const float* __restrict__ src, const size_t pitch,
                                               const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                               double* partials, const int rows_per_pair, const SweepConst& sc, const double* exp_tab,
@@ -664,8 +728,8 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   constexpr int TP = 2, IT = 8, NST = IT / TP, Q_CAP = 512;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  __shared__ unsigned q_ent[WAVES][Q_CAP];
-  __shared__ float stage[WAVES][64 * IT][6];       // one row of staged points: x'(3), R x (3)
+  auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 4>();
+  auto& stage = item_lds<float[WAVES][64 * IT][6], 5>();   // one row of staged points: x'(3), R x (3)
   const GridDesc& g = gd[g_idx];
   const float* X = src + (size_t)b * 3 * pitch;
   const BitWord* W = words + g.word_off;
@@ -706,7 +770,8 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
     float r[3] = {sp[3], sp[4], sp[5]};
     const bool live = lane < m && B.weight != VOX_DEAD;
     float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
-    eval_hit<PCA, decltype(mid), false, ORD>(u, r, B.C, sc.d1, sc.d2f, PCA ? (double)B.weight : 1.0, live, acc, exp_tab, mid);
+    if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, PCA ? (double)B.weight : 1.0, live, acc[0], exp_tab); }
+    else eval_hit<PCA, decltype(mid), false, ORD>(u, r, B.C, sc.d1, sc.d2f, PCA ? (double)B.weight : 1.0, live, acc, exp_tab, mid);
     nhits += (unsigned)__popcll(__ballot(live));
     qhead = (qhead + m) & (Q_CAP - 1);
     qcount -= m;
@@ -801,6 +866,14 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
     if (qcount > 0) { Batch Bt; fetch(0, qcount, Bt); eval_batch(Bt, qcount, NoHook()); }
     TL_STAMP(5);
     if (s + 1 < S_TOTAL) { probe(s + 1); load_points(s + 2); }
+    if constexpr (SO) {
+      const double v = score_tree(acc[0]);
+      if (lane == 0) {
+        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(partials + ((size_t)b * rows_per_pair + rem0 + s / NST) * NACC);
+        __hip_atomic_store(PG, (unsigned long long)__double_as_longlong(v), RLX_AGENT);
+        __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
+      }
+    } else {
     typedef unsigned int u2v __attribute__((ext_vector_type(2)));
     double P1[22], P2[11];
 #pragma unroll
@@ -826,6 +899,7 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
 #pragma unroll
       for (int i = 0; i < 11; i++) if (rb + i < 43) __hip_atomic_store(PG + rb + i, (unsigned long long)__double_as_longlong(P2[i]), RLX_AGENT);
       if (lane == 0) __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
+    }
     }
 #pragma unroll
     for (int a = 0; a < 43; a++) acc[a] = 0.0;

@@ -68,6 +68,10 @@ static_assert(sizeof(VoxelRecF) == sizeof(VoxelRec) && offsetof(VoxelRecF, weigh
 struct PairState {
   float  T[12];                // 3x4 row-major point transform (f32)
   float  Rj[9];                // rotation used for the point Jacobian (f32)
+  // 1: the pending sweep is the pair's last -- the convergence test behind it (newton_update) is decided already -- so its gradient and
+  // Hessian are never read and the one-launch align evaluates the score alone (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP).  Word 21 of the state:
+  // it travels with the 21 pose words a work item fetches (sweep_pose_words), in what was padding in front of p.
+  int    last_sweep;
   double p[6];                 // current tangent [upsilon; omega]
   double dir[6];               // pending step direction
   double a_t;                  // pending step length
@@ -88,6 +92,8 @@ struct PairState {
   float  reb_inc[16];
   long long reb_tag;
 };
+
+static_assert(offsetof(PairState, last_sweep) == 84 && offsetof(PairState, p) == 88, "last_sweep sits in the padding behind the pose words");
 
 struct SweepConst {
   double d1;

@@ -55,7 +55,7 @@ __device__ inline void init_pair_state(PairState& S, const float G[16] /* column
   ndtm::se3_log(ndtm::se3_from_Rt(R, t), S.p);
   float Tdummy[12];
   ndtm::pose_to_f32(S.p, Tdummy, S.Rj);
-  S.it = 0; S.phase = PH_SWEEP0; S.converged = 0; S.sweeps = 1; S.a_t = 0; S.hits = 0; S.score = 0; S.mt_loops = 0;
+  S.it = 0; S.phase = PH_SWEEP0; S.converged = 0; S.sweeps = 1; S.a_t = 0; S.hits = 0; S.score = 0; S.mt_loops = 0; S.last_sweep = 0;
   for (int a = 0; a < 16; a++) S.inc_cm[a] = S.prev_inc_cm[a] = (a % 5 == 0) ? 1.f : 0.f;    // align(): transformation_ = previous_ = I
   S.n_src = n_src;
   S.grid_status = grid_status;
@@ -79,7 +79,7 @@ NDT_KERNEL void k_set_pose(PairState* st, int b, const float* __restrict__ T_cm,
   active_list[0] = b; ctl->n_active = 1;
   for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) S.T[r * 4 + c] = T_cm[c * 4 + r];
   for (int a = 0; a < 9; a++) S.Rj[a] = Rj[a];
-  S.phase = PH_SWEEP0; S.n_src = src_cnt[b]; S.grid_status = gd[b].status; S.it = 0; S.sweeps = 1;
+  S.phase = PH_SWEEP0; S.n_src = src_cnt[b]; S.grid_status = gd[b].status; S.it = 0; S.sweeps = 1; S.last_sweep = 0;
 }
 NDT_KERNEL void k_set_pose_p(PairState* st, int b, const double* __restrict__ p, const int* __restrict__ src_cnt, const GridDesc* __restrict__ gd,
                              int* active_list, SweepCtl* ctl, int for_hessian) {
@@ -88,7 +88,7 @@ NDT_KERNEL void k_set_pose_p(PairState* st, int b, const double* __restrict__ p,
   double pp[6];
   for (int a = 0; a < 6; a++) { pp[a] = p[a]; S.xt[a] = p[a]; }
   ndtm::pose_to_f32(pp, S.T, S.Rj);
-  S.phase = for_hessian ? PH_HESS : PH_SWEEP0; S.n_src = src_cnt[b]; S.grid_status = gd[b].status; S.it = 0; S.sweeps = 1;
+  S.phase = for_hessian ? PH_HESS : PH_SWEEP0; S.n_src = src_cnt[b]; S.grid_status = gd[b].status; S.it = 0; S.sweeps = 1; S.last_sweep = 0;
 }
 
 // ---- More-Thuente pieces (impl2:717-838), live only when step_size <= eps/2 (impl2:888) -------------------------------
@@ -323,9 +323,12 @@ __device__ __forceinline__ void newton_rebase(const double p[6], const double di
   ndtm::se3_log(ndtm::se3_mul(e_dp, e_p), pn);                                   // impl2:166
 }
 
+// score_only_last (one-launch align, MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): mark a scheduled step whose convergence test is decided already
+// (S.last_sweep) -- that test reads S.it and the step length, both fixed here, never the sweep's sums -- so that its sweep evaluates the score alone.
 __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res, double step_max, double eps, int max_iterations, int mt,
                                              volatile double* sol = nullptr /* non-null: the solve comes from newton_solve_side */,
-                                             const bool rebased = false /* S.reb_pn / S.reb_inc hold the re-basing of this step already */) {
+                                             const bool rebased = false /* S.reb_pn / S.reb_inc hold the re-basing of this step already */,
+                                             const bool score_only_last = false) {
   const int lane = threadIdx.x & 63;
   // exp(delta_p) and exp(p) of impl2:163-166, side by side on two lanes (same bits as one after the other on one lane)
   ndtm::SE3 e_dp, e_p;
@@ -381,6 +384,9 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     }
     for (int a = 0; a < 6; a++) S.p[a] = pn[a];
     const bool conv = (S.it > max_iterations) || (S.it && (fabs(S.a_t) < eps));  // impl2:175-179
+#ifdef NDT_DEBUG_LAST_SWEEP
+    if (S.last_sweep && !conv) printf("newton_update: last_sweep set for a step that does not end the pair (it %d, a_t %g)\n", S.it, S.a_t);
+#endif
     S.it++;
     if (conv) { finalize_pair(S, res, 1); return NEWTON_DONE; }
   }
@@ -420,6 +426,9 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     double xt[6];
     for (int a = 0; a < 6; a++) { S.dir[a] = d[a]; xt[a] = S.p[a] + d[a] * a_t; S.xt[a] = xt[a]; }   // impl2:894
     S.a_t = a_t;
+    // the test of impl2:175-179 that follows this step's sweep (above), on the same operands: S.it and a_t are final here.  With the
+    // More-Thuente loop live (mt != 0) the sweep's gradient feeds that loop, so it is never marked.
+    S.last_sweep = (mt == 0 && score_only_last && ((S.it > max_iterations) || (S.it && (fabs(a_t) < eps)))) ? 1 : 0;
     S.phi0 = -S.score;                                                           // impl2:846
     S.dphi0 = dphi0 >= 0 ? -dphi0 : dphi0;                                       // impl2:849, 860
     ndtm::pose_to_f32(xt, S.T, S.Rj);                                            // impl2:900

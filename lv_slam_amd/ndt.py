@@ -57,7 +57,7 @@ class Profile(C.Structure):
                 ("update_launches", C.c_longlong), ("async_fallbacks", C.c_longlong), ("stream_launches", C.c_longlong),
                 ("stream_carried", C.c_longlong), ("stream_redone", C.c_longlong), ("cloud_uploads", C.c_longlong), ("cloud_upload_bytes", C.c_longlong),
                 ("cloud_transfers", C.c_longlong), ("cloud_promotions", C.c_longlong),
-                ("stream_reserved_slots", C.c_longlong), ("stream_launch_slots", C.c_longlong)]
+                ("stream_reserved_slots", C.c_longlong), ("stream_launch_slots", C.c_longlong), ("score_only_sweeps", C.c_longlong)]
 
 
 class SeqParams(C.Structure):
@@ -96,6 +96,7 @@ OPT_STREAM_THRESHOLD = 4       # mi355ndt_option: pairs a stream launch hands ov
 WARN_TOLERANCE_ARITH = 1       # mi355ndt_result.status under OPT_ARITH = 1: fewer than 4,096 hits at the final pose, or stopped at the iteration cap
 OPT_ARITH = 7                  # mi355ndt_option: 0 = the reference recipe's arithmetic, one rounding per operation (default), 1 = tolerance arithmetic (held to 1e-4 m / 1e-5 rad, not to bits)
 OPT_F32_SUM_ORDER = 1          # mi355ndt_option: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
+OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch align's last sweep of a pair evaluates the score alone, 0 = all 43 sums; same bits
 
 _LIB = None
 

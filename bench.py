@@ -9,13 +9,26 @@ Pairs are sharded round-robin over ranks (pair index i -> rank i mod N), no data
   default            : weak scaling, every rank owns `--pairs` pairs (BASELINE config 3 per GPU: 271)
   --total-pairs 4541 : BASELINE config 4 as worded -- a fixed job of T pairs over the N ranks (strong scaling,
                        shards differ by at most one pair; the shorter ones pad their record block with pair_id = -1)
-  (N = 1)            : also reports the drop-in path's rate (host AoS clouds in, PCIe inclusive) as `value_host_clouds`;
-                       --no-host-clouds skips that leg, --host-clouds forces it for N > 1 (rank 0)
+
+A plain run does what the headline needs and no more: generate the inputs, time the job synchronously (the steps it sizes and
+the warm-up the streamed job has always been measured after), check the streamed job against it and time that -- `value`,
+`ms_per_step` -- with the sweep's roofline from the engine's own events in those steps.  `--full` adds everything else the line
+used to carry by default, each leg as before and each with its own off switch:
+  cpu_baseline + parity : the oracle (CPU restatement of ndt_omp) timed on this box's host cores on a bounded sample, in the
+                          reference-shaped arrangement of SURVEY.md 8(d) and as the optimised port, and checked pose by pose
+                          against the GPU results (--cpu-seconds 0 skips it; the reference itself cannot be built here)
+  host_clouds           : (N = 1) the drop-in path's rate, host AoS clouds in, PCIe inclusive, as `value_host_clouds`;
+                          --no-host-clouds skips that leg, --host-clouds forces it for N > 1 (rank 0)
+  sequential            : (N = 1) the latency-mode leg, `value_sequential` (--seq-frames 0 skips it)
+  config4               : BASELINE config 4 strong-scaled over the same ranks (--config4-pairs 0 skips it)
+  tolerance_mode        : the same jobs in the tolerance arithmetic (--no-tolerance-mode skips them)
+  other_configs         : (N = 1) the nodelet's configuration and BASELINE config 5 (--no-other-configs skips them)
+  resident targets      : the align rate against already-built grids and the targets' leaf statistics
+  --prefiltered         : the reference-conditioned row instead of the headline (needs --full)
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel: the derivative
-sweep, algorithmic bytes / HIP-event time, peak 8 TB/s HBM), `roofline_valu` (what actually bounds the sweep) and
-`cpu_baseline` (the oracle = CPU restatement of ndt_omp, timed on this box's host cores on a bounded sample, in the
-reference-shaped arrangement of SURVEY.md 8(d) and as the optimised port; the reference itself cannot be built here).
+sweep, algorithmic bytes / HIP-event time, peak 8 TB/s HBM) and `roofline_valu` (what actually bounds the sweep);
+a plain run's line leaves the --full blocks out the way their own off switches do (null, or no key at all).
 """
 import argparse
 import gc
@@ -53,35 +66,38 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: as many as make the timed region >= 0.5 s, at least 20)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: CPU baseline and oracle parity, host clouds, latency mode, config 4, tolerance "
+                         "arithmetic, other configurations, resident-target rate (a plain run times the headline job only)")
     ap.add_argument("--pairs", type=int, default=271, help="pairs per GPU per step (BASELINE config 3: 271); weak scaling")
     ap.add_argument("--total-pairs", type=int, default=0,
                     help="fixed job of this many pairs over all ranks (BASELINE config 4: 4541); strong scaling; overrides --pairs")
     ap.add_argument("--config4-pairs", type=int, default=4541,
-                    help="size of the BASELINE config 4 job timed beside the default weak-scaling line (strong scaling over the same ranks; 0 = skip)")
+                    help="--full: size of the BASELINE config 4 job timed beside the weak-scaling line (strong scaling over the same ranks; 0 = skip)")
     ap.add_argument("--azimuth", type=int, default=1024, help="firings per revolution; x64 beams = points per cloud")
     ap.add_argument("--mode", default="direct7", choices=sorted(MODES))
     ap.add_argument("--variant", default="omp", choices=["omp", "pca"])
     ap.add_argument("--resolution", type=float, default=1.0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time of the parity/port sample of the cpu_baseline leg (0 = skip the leg)")
-    ap.add_argument("--host-clouds", action="store_true", help="time the drop-in path (host AoS clouds in, PCIe inclusive) also when N > 1")
-    ap.add_argument("--no-host-clouds", action="store_true", help="skip the drop-in path's leg (on by default in the single-GPU run)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU time of the parity/port sample of the cpu_baseline leg (0 = skip the leg)")
+    ap.add_argument("--host-clouds", action="store_true", help="--full: time the drop-in path (host AoS clouds in, PCIe inclusive) also when N > 1")
+    ap.add_argument("--no-host-clouds", action="store_true", help="--full: skip the drop-in path's leg (on by default in the single-GPU --full run)")
     ap.add_argument("--uploaders", type=int, default=0, help="staging threads per engine of the --host-clouds leg (0 = from the CPU quota)")
     ap.add_argument("--prefiltered", action="store_true",
-                    help="the reference-conditioned row instead of the headline: raw scans -> device prefilter (0.5-100 m gate + 0.1 m VoxelGrid, "
+                    help="with --full: the reference-conditioned row instead of the headline: raw scans -> device prefilter (0.5-100 m gate + 0.1 m VoxelGrid, "
                          "launch/dlo_kitti.launch:30-36) -> target / source -> align, one registration at a time (use with --azimuth 2048 --pairs 64)")
-    ap.add_argument("--seq-frames", type=int, default=271, help="frames of the latency-mode leg (value_sequential; 0 = skip; single-GPU run only)")
+    ap.add_argument("--seq-frames", type=int, default=271, help="--full: frames of the latency-mode leg (value_sequential; 0 = skip; single-GPU run only)")
     ap.add_argument("--traffic", type=float, default=None, help="HBM bytes per sweep launch from separate rocprofv3 --pmc passes")
     ap.add_argument("--f32-sum-order", type=int, default=0, choices=[0, 1],
                     help="MI355NDT_OPT_F32_SUM_ORDER of every engine of the run: 0 = (t0 + t1) + t2, the canonical order of the fixtures; 1 = (t0 + t2) + t1, "
                          "the lane pairing of Eigen 3.3's SSE predux -- the parity legs then check against the oracle's matching variant (ORA_VAR_SUM3_02_1)")
     ap.add_argument("--arith", type=int, default=int(os.environ.get("MI355NDT_ARITH", "0") == "1"), choices=[0, 1],
                     help="MI355NDT_OPT_ARITH of every engine of the run: 0 = the exact arithmetic (results equal the oracle's bit for bit; what `value` is measured in), "
-                         "1 = tolerance arithmetic for the whole line (the default line already carries it as the `tolerance_mode` block beside the exact `value`)")
-    ap.add_argument("--no-tolerance-mode", action="store_true", help="skip the `tolerance_mode` blocks (the same jobs again under MI355NDT_OPT_ARITH = 1, compared pair by pair with the exact results)")
+                         "1 = tolerance arithmetic for the whole line (the --full line already carries it as the `tolerance_mode` block beside the exact `value`)")
+    ap.add_argument("--no-tolerance-mode", action="store_true", help="--full: skip the `tolerance_mode` blocks (the same jobs again under MI355NDT_OPT_ARITH = 1, compared pair by pair with the exact results)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` block of the single-GPU line (the nodelet's ndt_pca / DIRECT1 and BASELINE config 5 with DIRECT7 and "
+                    help="--full: skip the `other_configs` block of the single-GPU line (the nodelet's ndt_pca / DIRECT1 and BASELINE config 5 with DIRECT7 and "
                          "DIRECT1, each timed for --other-seconds with its own roofline and oracle parity sample)")
-    ap.add_argument("--other-seconds", type=float, default=0.35, help="timed region of every `other_configs` entry")
+    ap.add_argument("--other-seconds", type=float, default=0.35, help="--full: timed region of every `other_configs` entry")
     ap.add_argument("--no-stream", action="store_true", help="skip the streamed job: `value` is then the synchronous job's rate (as in rounds 1-4)")
     ap.add_argument("--stream-contexts", type=int, default=4, help="batches resident in the engine's stream mode (2..4); four let a launch's stragglers ride through two further launches (config 5 needs that: 20.3 k against 18.9 k with three)")
     ap.add_argument("--stream-batches", type=int, default=4, help="distinct batches the streamed job rotates through")
@@ -100,6 +116,10 @@ def parse():
         ap.error("--steps must be at least 1")
     if a.dump_outputs and a.prefiltered:
         ap.error("--dump-outputs covers the headline job; --prefiltered is a row of its own")
+    if a.prefiltered and not a.full:
+        ap.error("--prefiltered is a row beside the headline: run it with --full")
+    if a.host_clouds and not a.full:
+        ap.error("--host-clouds is a leg of the --full line")
     return a
 
 
@@ -1274,10 +1294,10 @@ def main():
     if total < world:
         raise SystemExit("fewer pairs than ranks")
     # The config-4 block (BASELINE config 4 as worded: ONE fixed job of 4,541 pairs sharded round-robin over the N ranks, strong
-    # scaling) rides along with the default weak-scaling line, so that a driver that only ever passes --gpus N still measures it.
+    # scaling) rides along with the weak-scaling line of a --full run; a plain run generates only the pairs its headline reads.
     # Both jobs give pair i to rank i mod N, so a rank's pairs of either job are a prefix of the same sequence rank, rank + N, ...:
-    # the clouds are generated once, for the longer of the two prefixes.
-    c4_total = 0 if (strong or a.config4_pairs <= 0 or a.config4_pairs < world) else a.config4_pairs
+    # the clouds are generated once, for the longer of the two prefixes (every pair's cloud depends on its index alone).
+    c4_total = 0 if (not a.full or strong or a.config4_pairs <= 0 or a.config4_pairs < world) else a.config4_pairs
     pair_ids = shard.shard_pairs(total, rank, world)           # round-robin shard of the global pair index space
     c4_ids = shard.shard_pairs(c4_total, rank, world) if c4_total else []
     # the streamed job rotates through --stream-batches DISTINCT batches of the same size: more of the same sequence
@@ -1309,18 +1329,20 @@ def main():
     # ---- the headline job
     J = timed_job(ctx, eng, W, B, total, a.steps, a.warmup)
     res, res_np, guesses, dt, steps = J["res"], J["res_np"], J["guesses"], J["dt"], J["steps"]
-    # SURVEY 8(d) asks for the rate with and without setInputTarget: the same pairs again against the now-resident grids
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(steps):
-        eng.batch_align_raw(guesses, res)
-    torch.cuda.synchronize()
-    dt_resident = time.perf_counter() - t1
-    # leaf statistics of the workload's targets (what the derivative sweep's cost depends on besides the point count)
-    lv = [eng.get_voxels(k) for k in range(min(B, 8))]
-    leaf_stats = {"targets_sampled": len(lv), "searchable_leaves_per_target_mean": round(float(np.mean([len(v) for v in lv])), 1),
-                  "points_per_leaf_mean": round(float(np.mean([v["n"][v["n"] > 0].mean() for v in lv])), 2),
-                  "largest_leaf_points": int(max(v["n"].max() for v in lv))}
+    dt_resident, leaf_stats = None, None
+    if a.full:
+        # SURVEY 8(d) asks for the rate with and without setInputTarget: the same pairs again against the now-resident grids
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            eng.batch_align_raw(guesses, res)
+        torch.cuda.synchronize()
+        dt_resident = time.perf_counter() - t1
+        # leaf statistics of the workload's targets (what the derivative sweep's cost depends on besides the point count)
+        lv = [eng.get_voxels(k) for k in range(min(B, 8))]
+        leaf_stats = {"targets_sampled": len(lv), "searchable_leaves_per_target_mean": round(float(np.mean([len(v) for v in lv])), 1),
+                      "points_per_leaf_mean": round(float(np.mean([v["n"][v["n"] > 0].mean() for v in lv])), 2),
+                      "largest_leaf_points": int(max(v["n"].max() for v in lv))}
     head_res = np.frombuffer(res, dtype=np.uint8).copy()       # (the config-4 block below re-binds the engine)
     res_np = np.frombuffer(head_res, dtype=RES_DT)
 
@@ -1333,7 +1355,7 @@ def main():
 
     # ---- the drop-in path: host AoS clouds (pcl::PointXYZI records) in, PCIe inclusive -- rank 0's pairs
     host_path = None
-    if rank == 0 and not a.no_host_clouds and (a.host_clouds or world == 1) and W["data"] == "synthetic":
+    if a.full and rank == 0 and not a.no_host_clouds and (a.host_clouds or world == 1) and W["data"] == "synthetic":
         host_path, hres = host_clouds_leg(a, ndt, prm, local, W["T"][:B], W["S"][:B], guesses, B, N, steps=max(2, min(steps, 40) // 2), uploaders=a.uploaders or None)
         # same bits as the device-resident run of the same pairs
         nh = len(np.frombuffer(hres[0], dtype=RES_DT))      # the leg's pairs: the first min(B, 271) of the batch
@@ -1349,7 +1371,7 @@ def main():
 
     # ---- latency mode: the nodelet's own per-frame loop on a drive (never `value`)
     seq_leg = None
-    if rank == 0 and world == 1 and a.seq_frames > 1 and W["data"] == "synthetic":
+    if a.full and rank == 0 and world == 1 and a.seq_frames > 1 and W["data"] == "synthetic":
         seq_leg = sequential_leg(a, ndt, local, dev, a.seq_frames)
 
     # ---- BASELINE config 4 beside it: the fixed 4,541-pair job, strong-scaled over the same ranks
@@ -1370,7 +1392,7 @@ def main():
 
     # ---- the same jobs in the tolerance arithmetic (never `value`): every rank runs them (they contain the same barriers / gathers)
     tol_head, tol_c4 = None, None
-    tol_ok = a.arith == 0 and not a.no_tolerance_mode and a.mode in ("direct1", "direct7")
+    tol_ok = a.full and a.arith == 0 and not a.no_tolerance_mode and a.mode in ("direct1", "direct7")
     if tol_ok:
         osec = (a.cpu_seconds / 4.0) if (rank == 0 and world == 1) else 0.0
         tol_head = tolerance_block(ctx, a, prm, W, B, total, steps, min(a.warmup, 3), res_np, JS is not None, osec)
@@ -1415,12 +1437,12 @@ def main():
                          "by the whole build -- frac_of_its_slots is the same rate per slot it had, roofline_synchronous.frac the same kernel with the GPU to itself")
 
     cpu, parity = (None, None)
-    if a.cpu_seconds > 0 and world == 1:          # the CPU leg runs on rank 0 of the single-GPU run only
+    if a.full and a.cpu_seconds > 0 and world == 1:          # the CPU leg runs on rank 0 of the single-GPU run only
         cpu, parity = cpu_leg(a, W, G, res_np, B)
 
     # ---- the other BASELINE configurations, in the same line (single-GPU run of the default workload family)
     others = None
-    if world == 1 and not a.no_other_configs and not strong and W["data"] == "synthetic" and a.variant == "omp" and a.mode == "direct7" and a.resolution == 1.0:
+    if a.full and world == 1 and not a.no_other_configs and not strong and W["data"] == "synthetic" and a.variant == "omp" and a.mode == "direct7" and a.resolution == 1.0:
         others = other_configs_block(ctx, a, synth, W)
 
     kind = "KITTI" if W["data"] == "kitti" else "synthetic HDL-64E"
@@ -1449,7 +1471,7 @@ def main():
                    "mean_iterations": round(float(its.mean()), 2), "max_iterations_seen": int(its.max()),
                    "mean_sweeps_per_align": round(float(sweeps.mean()), 2),
                    "converged": int(res_np["conv"].sum()),
-                   "rank0_registrations_per_s_resident_targets": round(B * steps / dt_resident, 1),
+                   "rank0_registrations_per_s_resident_targets": None if dt_resident is None else round(B * steps / dt_resident, 1),
                    "target_leaf_statistics": leaf_stats,
                    "steps_chosen_by": "--steps" if a.steps is not None else "timed region sized to >= 0.5 s",
                    "input_generation_s": round(max(t_gen_ranks), 2), "input_generation_s_per_rank": t_gen_ranks, "pairs_generated_per_rank": len(all_ids), "inputs": W["generated_on"],

@@ -11,12 +11,27 @@ def test_defaults_follow_the_driver_contract(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.gpus == 1 and a.steps is None and a.warmup >= 0 and a.pairs == 271 and a.azimuth * 64 == 65536   # no --steps: timed region sized to >= 0.5 s
-    assert a.config4_pairs == 4541                                       # BASELINE config 4 rides along with the default line
+    assert a.config4_pairs == 4541                                       # BASELINE config 4 rides along with the --full line
     assert a.mode == "direct7" and a.variant == "omp" and a.resolution == 1.0 and a.total_pairs == 0
-    assert a.host_clouds is False and a.no_host_clouds is False          # the leg is on by default at N = 1 (main decides)
+    assert a.host_clouds is False and a.no_host_clouds is False          # the leg is on by default in a --full run at N = 1 (main decides)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2", "--total-pairs", "4541"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup, a.total_pairs) == (8, 5, 2, 4541)
+
+
+def test_full_is_off_by_default_and_its_rows_ask_for_it(monkeypatch):
+    """A plain run times the headline alone; the legs beside it come with --full, and the flags that only make sense there say so."""
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--prefiltered", "--host-clouds"])
+    a = bench.parse()
+    assert a.full and a.prefiltered and a.host_clouds
+    for extra in (["--prefiltered"], ["--host-clouds"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *extra])
+        with pytest.raises(SystemExit):
+            bench.parse()
 
 
 def test_allowed_cpu_set_is_captured_and_reapplied():

@@ -39,7 +39,7 @@ def run_bench(args, nproc=1, env_extra=None):
 
 
 def test_single_gpu_line_contract():
-    d = run_bench(["--pairs", "6", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--config4-pairs", "9", "--seq-frames", "9"])
+    d = run_bench(["--full", "--pairs", "6", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--config4-pairs", "9", "--seq-frames", "9"])
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["unit"] == "registrations/s" and d["value"] > 0 and d["vs_baseline"] is None and d["data"] == "synthetic"
     r = d["roofline"]
@@ -49,7 +49,7 @@ def test_single_gpu_line_contract():
     assert c["value"] >= c["value_reference_shaped"] > 0 and "optimised port" in c["arrangement_of_value"]     # `value` = the fastest CPU arrangement
     p = d["parity"]
     assert p["pairs_checked"] >= 3 and p["iterations_equal"] == p["pairs_checked"] and p["max_dtrans_m"] < 1e-4 and p["max_drot_rad"] < 1e-5
-    # the drop-in path's leg (host AoS clouds in, PCIe inclusive) is part of the default single-GPU line, and never `value`
+    # the drop-in path's leg (host AoS clouds in, PCIe inclusive) is part of the single-GPU --full line, and never `value`
     h = d["host_clouds"]
     assert d["value_host_clouds"] == max(h["registrations_per_s"], h["streamed"]["registrations_per_s"]) > 0 and h["registrations_per_s"] > 0
     assert ("streamed" in d["value_host_clouds_mode"]) == (h["streamed"]["registrations_per_s"] >= h["registrations_per_s"])
@@ -81,9 +81,28 @@ def test_single_gpu_line_contract():
         pp = c["parity"]
         assert pp["pairs_checked"] >= 2 and pp["iterations_equal"] == pp["pairs_checked"] and pp["max_dtrans_m"] < 1e-4 and pp["max_drot_rad"] < 1e-5, name
     assert "DIRECT1" in oc["config5_direct1"]["workload"] and "32768 pts" in oc["config5_direct7"]["workload"]
-    d2 = run_bench(["--pairs", "4", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-host-clouds", "--config4-pairs", "0", "--seq-frames", "0",
+    d2 = run_bench(["--full", "--pairs", "4", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-host-clouds", "--config4-pairs", "0", "--seq-frames", "0",
                     "--no-other-configs"])
     assert "value_host_clouds" not in d2 and d2["config4"] is None and "value_sequential" not in d2 and d2["other_configs"] is None
+
+
+def test_plain_line_is_the_headline_alone():
+    """Without --full the line is the headline job and nothing beside it: the streamed `value` with its synchronous twin, the roofline read
+    from the engine's events in those steps, and no CPU leg, oracle parity, host clouds, latency mode, config 4, tolerance arithmetic, other
+    configurations or resident-target rate.  Only the pairs the headline reads are generated (4 distinct batches of 8, not config 4's job)."""
+    d = run_bench(["--pairs", "8", "--azimuth", "256", "--steps", "3", "--warmup", "1"])
+    assert d["metric"] == "NDT registrations/sec (64k-pt Velodyne pairs)" and d["unit"] == "registrations/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32 terms, f64 accumulation" and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value_mode"] == "streamed" and d["value"] == d["value_streamed"] > 0 and d["value_synchronous"] > 0
+    assert abs(d["ms_per_step"] - 1e3 * 8 / d["value"]) < 1e-2 * d["ms_per_step"]
+    assert d["config"]["stream"]["bit_identical_to_synchronous"] is True and d["config"]["converged"] == 8
+    assert d["roofline"]["bound"] == "hbm" and d["roofline"]["launches"] >= 3
+    for k in ("cpu_baseline", "parity", "config4", "other_configs", "tolerance_mode", "value_tolerance_mode"):
+        assert d[k] is None, k
+    for k in ("host_clouds", "value_host_clouds", "sequential", "value_sequential"):
+        assert k not in d, k
+    assert d["config"]["rank0_registrations_per_s_resident_targets"] is None and d["config"]["target_leaf_statistics"] is None
+    assert d["config"]["pairs_generated_per_rank"] == 32
 
 
 def test_plain_gpus_2_launches_two_ranks_by_itself():
@@ -92,7 +111,7 @@ def test_plain_gpus_2_launches_two_ranks_by_itself():
     two ranks share this box's one GPU; with the default RCCL backend the same command refuses when fewer than two devices are visible.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["LV_SLAM_BENCH_BACKEND"] = "gloo"
-    args = ["--gpus", "2", "--pairs", "3", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "5"]
+    args = ["--gpus", "2", "--full", "--pairs", "3", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "5"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -112,7 +131,7 @@ def test_four_ranks_on_one_device_gloo():
     """The scaling run's N > 2 shape on one device: FOUR ranks (gloo; all on cuda:0; every rank is a process with the GPU open, so the suite
     keeps their number small -- the eight-way sharding and gather are tests/test_dist_cpu.py::test_gather_world8_gloo), the weak-scaling job
     (2 pairs per rank, streamed) and the config-4-style fixed job of 13 pairs (uneven: rank 0 owns 4, three ranks own 3 + a padding row)."""
-    d = run_bench(["--gpus", "4", "--pairs", "2", "--azimuth", "128", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "13"], nproc=4,
+    d = run_bench(["--gpus", "4", "--full", "--pairs", "2", "--azimuth", "128", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "13"], nproc=4,
                   env_extra={"LV_SLAM_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 4 and d["world_size"] == 4 and d["process_group"]["world_size"] == 4 and d["process_group"]["backend"] == "gloo"
     assert d["config"]["pairs_total"] == 8 and d["config"]["pairs_rank0"] == 2
@@ -185,7 +204,7 @@ def test_kitti_directory_as_input(tmp_path):
     for k, sc in enumerate(scans):
         xyz = sc.numpy()
         kitti.write_frame(str(vel / f"{k:06d}.bin"), xyz[: len(xyz) - 1000 * (k == 2)])
-    d = run_bench(["--kitti-dir", str(vel), "--pairs", "4", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--config4-pairs", "0", "--seq-frames", "0"])
+    d = run_bench(["--full", "--kitti-dir", str(vel), "--pairs", "4", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--config4-pairs", "0", "--seq-frames", "0"])
     assert d["data"] == "kitti" and "KITTI seq 04" in d["config"]["workload"] and d["config"]["pairs_total"] == 4
     assert d["config"]["points_per_cloud"] == 16384 and 16384 - 250 - 1 < d["config"]["mean_points_per_source"] < 16384
     p = d["parity"]
@@ -198,7 +217,7 @@ def test_kitti_directory_as_input(tmp_path):
 @pytest.mark.parametrize("extra,total", [(["--pairs", "5"], 10), (["--total-pairs", "11"], 11)])
 def test_two_ranks_on_one_gpu_gather(extra, total):
     """weak scaling (5 pairs per rank) and the config-4-literal mode with uneven shards (11 pairs: 6 + 5)."""
-    d = run_bench(["--gpus", "2", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "13"] + extra, nproc=2,
+    d = run_bench(["--gpus", "2", "--full", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--config4-pairs", "13"] + extra, nproc=2,
                   env_extra={"LV_SLAM_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["config"]["pairs_total"] == total
     assert d["scaling"] == ("strong" if "--total-pairs" in extra else "weak")
@@ -210,7 +229,7 @@ def test_two_ranks_on_one_gpu_gather(extra, total):
     c4 = d["config4"]
     if "--total-pairs" in extra:
         assert c4 is None                              # the line itself is the fixed job
-    else:                                              # the one line a driver that only passes --gpus N gets: weak value + config-4 block
+    else:                                              # the --full line of --gpus N: weak value + config-4 block
         assert c4["pairs_total"] == 13 and c4["pairs_rank0"] == 7 and c4["scaling"] == "strong" and c4["n_gpus"] == 2 and c4["value"] > 0
         g4 = c4["gather_check"]
         assert g4["pairs_gathered"] == 13 and g4["permutation_of_all_pair_ids"] is True and g4["own_records_bit_identical_on_every_rank"] is True
@@ -233,7 +252,7 @@ def test_config4_job_on_one_gpu_parity_over_the_index_range_and_rccl_gather():
     """BASELINE config 4's job -- 4,541 pairs of 65,536 points, ndt_omp, 1 m, DIRECT7 -- as ONE batch on one GPU: the parity leg samples the
     WHOLE index range (every ~16th pair incl. 4540, not the first 271), and the single rank is made to go through RCCL so that the
     gather of 4,541 device-packed 96-byte records is checked too.  Independence of the pairs: scan_matching_odom_nodelet.cpp:240-250."""
-    d = run_bench(["--total-pairs", "4541", "--steps", "3", "--warmup", "1", "--cpu-seconds", "10", "--no-host-clouds", "--seq-frames", "0"],
+    d = run_bench(["--full", "--total-pairs", "4541", "--steps", "3", "--warmup", "1", "--cpu-seconds", "10", "--no-host-clouds", "--seq-frames", "0"],
                   env_extra={"LV_SLAM_BENCH_FORCE_DIST": "1", "MASTER_PORT": str(free_port())})
     assert d["scaling"] == "strong" and d["config"]["pairs_total"] == 4541 and d["config"]["pairs_rank0"] == 4541 and d["config"]["converged"] == 4541
     p = d["parity"]
@@ -251,7 +270,7 @@ def test_default_workload_parity_leg_covers_the_whole_batch(order):
     checks every pair of the batch against the oracle -- same iteration counts, SE(3) inside the north-star tolerance -- and the
     roofline block is internally consistent.  Both evaluation orders of the three-term f32 sums (ndt_omp_impl2.hpp:581, 594-613):
     the canonical one, and the lane pairing of Eigen 3.3's SSE predux against the oracle's matching variant."""
-    d = run_bench(["--steps", "5", "--warmup", "2", "--cpu-seconds", "30", "--config4-pairs", "0", "--seq-frames", "0", "--no-other-configs", "--no-host-clouds",
+    d = run_bench(["--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "30", "--config4-pairs", "0", "--seq-frames", "0", "--no-other-configs", "--no-host-clouds",
                    "--f32-sum-order", str(order)])
     p = d["parity"]
     assert p["f32_sum_order"] == order and d["config"]["f32_sum_order"] == order
@@ -267,7 +286,7 @@ def test_default_workload_parity_leg_covers_the_whole_batch(order):
 def test_prefiltered_row():
     """bench.py --prefiltered: the reference-conditioned row (raw scans -> device prefilter as launch/dlo_kitti.launch:30-36 sets it ->
     target / source -> align), with the oracle's prefilter + align as the checker."""
-    d = run_bench(["--prefiltered", "--azimuth", "512", "--pairs", "4", "--variant", "pca", "--mode", "direct1", "--cpu-seconds", "2"])
+    d = run_bench(["--full", "--prefiltered", "--azimuth", "512", "--pairs", "4", "--variant", "pca", "--mode", "direct1", "--cpu-seconds", "2"])
     assert d["value"] > 0 and d["registrations_per_s_without_prefilter_time"] > d["value"] and d["config"]["converged"] == 4
     c = d["config"]
     assert c["raw_points_per_cloud"] == 32768 and 0 < c["filtered_points_per_target_mean"] < 32768 and c["searchable_leaves_per_target_mean"] > 50
@@ -278,9 +297,9 @@ def test_prefiltered_row():
 
 
 def test_tolerance_mode_block_rides_in_the_line():
-    """The default line carries the same jobs under MI355NDT_OPT_ARITH = 1 beside the exact `value` (which stays the headline): its own rates (streamed and
+    """The --full line carries the same jobs under MI355NDT_OPT_ARITH = 1 beside the exact `value` (which stays the headline): its own rates (streamed and
     synchronous), every pair's result against the exact arithmetic's, a bounded oracle sample -- for the headline, the config-4 job and every other configuration."""
-    d = run_bench(["--pairs", "24", "--azimuth", "512", "--steps", "4", "--warmup", "1", "--cpu-seconds", "4", "--no-host-clouds", "--config4-pairs", "29", "--seq-frames", "0",
+    d = run_bench(["--full", "--pairs", "24", "--azimuth", "512", "--steps", "4", "--warmup", "1", "--cpu-seconds", "4", "--no-host-clouds", "--config4-pairs", "29", "--seq-frames", "0",
                    "--other-seconds", "0.05"])
     assert d["config"]["arith"] == 0 and d["dtype"] == "f32 terms, f64 accumulation" and d["value"] == d["value_streamed"]
     t = d["tolerance_mode"]
@@ -296,7 +315,7 @@ def test_tolerance_mode_block_rides_in_the_line():
         assert c["value_mode"] == "streamed" and c["value"] == c["value_streamed"], name
         assert c["tolerance_mode"]["vs_exact_arithmetic"]["iteration_flips"] == 0 and c["tolerance_mode"]["vs_exact_arithmetic"]["pairs_beyond_tolerance"] == 0, name
     # the whole line in the tolerance arithmetic, on request, says so
-    d1 = run_bench(["--arith", "1", "--pairs", "8", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-host-clouds", "--config4-pairs", "0", "--seq-frames", "0",
+    d1 = run_bench(["--full", "--arith", "1", "--pairs", "8", "--azimuth", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-host-clouds", "--config4-pairs", "0", "--seq-frames", "0",
                     "--no-other-configs"])
     assert d1["config"]["arith"] == 1 and "tolerance arithmetic" in d1["dtype"] and d1["tolerance_mode"] is None
     assert d1["parity"]["arith"] == 1 and d1["parity"]["pairs_beyond_tolerance"] == 0 and d1["parity"]["iterations_equal"] == d1["parity"]["pairs_checked"]

@@ -5,6 +5,6 @@ cd $R
 for rep in 1 2; do
   (cd tools/ab_r04 && timeout 600 python bench.py --cpu-seconds 0 --no-host-clouds --seq-frames 0 --config4-pairs 0 --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('r04', d['value'], r['avg_launch_us'])")
   for L in "$@"; do
-    MI355NDT_LIB=$R/lv_slam_amd/$L timeout 600 python bench.py --no-stream ${BENCH_ARGS} --cpu-seconds 0 --no-host-clouds --seq-frames 0 --config4-pairs 0 --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$L', d['value'], r['avg_launch_us'])"
+    MI355NDT_LIB=$R/lv_slam_amd/$L timeout 600 python bench.py --full --no-stream ${BENCH_ARGS} --cpu-seconds 0 --no-host-clouds --seq-frames 0 --config4-pairs 0 --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$L', d['value'], r['avg_launch_us'])"
   done
 done

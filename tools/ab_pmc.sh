@@ -9,7 +9,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY GRBM_GU
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU" \
            "SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS"; do
   for tree in r04 head; do
-    if [ $tree = r04 ]; then D=$R/tools/ab_r04; X=""; else D=$R; X="--no-stream"; fi
+    if [ $tree = r04 ]; then D=$R/tools/ab_r04; X=""; else D=$R; X="--full --no-stream"; fi
     (cd $D && timeout 300 rocprofv3 --pmc $set --kernel-include-regex 'k_align_async' --output-format csv -d $O/$tree$k -- python $D/bench.py $ARGS $X > $O/$tree$k.log 2>&1)
   done
   k=$((k+1))

@@ -69,18 +69,18 @@ tol)
   ;;
 bench)
   cd $R
-  # bench lines (CPU baseline + pose-by-pose parity legs on); the default line carries the config-4 block and the latency-mode leg
-  timeout 900 python bench.py 2> $O/bench.log | tail -1 > $O/bench.json
-  timeout 400 python bench.py --variant pca --mode direct1 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_pca_d1.json
-  timeout 400 python bench.py --variant pca --mode direct7 --resolution 0.5 --azimuth 2048 --pairs 128 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_cfg5.json
-  timeout 400 python bench.py --variant pca --mode direct1 --resolution 0.5 --azimuth 2048 --pairs 128 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_cfg5_d1.json
-  timeout 400 python bench.py --pairs 1536 --steps 5 --warmup 1 --cpu-seconds 30 --config4-pairs 0 --seq-frames 0 --no-other-configs 2>> $O/bench.log | tail -1 > $O/bench_1536.json
+  # --full bench lines (CPU baseline + pose-by-pose parity legs on); the first one carries the config-4 block and the latency-mode leg
+  timeout 900 python bench.py --full 2> $O/bench.log | tail -1 > $O/bench.json
+  timeout 400 python bench.py --full --variant pca --mode direct1 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_pca_d1.json
+  timeout 400 python bench.py --full --variant pca --mode direct7 --resolution 0.5 --azimuth 2048 --pairs 128 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_cfg5.json
+  timeout 400 python bench.py --full --variant pca --mode direct1 --resolution 0.5 --azimuth 2048 --pairs 128 --config4-pairs 0 --seq-frames 0 2>> $O/bench.log | tail -1 > $O/bench_cfg5_d1.json
+  timeout 400 python bench.py --full --pairs 1536 --steps 5 --warmup 1 --cpu-seconds 30 --config4-pairs 0 --seq-frames 0 --no-other-configs 2>> $O/bench.log | tail -1 > $O/bench_1536.json
   # BASELINE config 4's whole job on one GPU, through the RCCL gather (one forced rank), parity sample spread over pairs 0..4540
-  LV_SLAM_BENCH_FORCE_DIST=1 MASTER_PORT=29541 timeout 600 python bench.py --total-pairs 4541 --steps 5 --warmup 1 --cpu-seconds 16 --no-host-clouds --seq-frames 0 --no-other-configs 2>> $O/bench.log | grep '^{' | tail -1 > $O/bench_cfg4_1gpu.json
-  # the N > 1 branch as two ranks sharing this GPU (gloo), DEFAULT flags = what the driver's scaling runs pass: weak line + config-4 block + gather times
+  LV_SLAM_BENCH_FORCE_DIST=1 MASTER_PORT=29541 timeout 600 python bench.py --full --total-pairs 4541 --steps 5 --warmup 1 --cpu-seconds 16 --no-host-clouds --seq-frames 0 --no-other-configs 2>> $O/bench.log | grep '^{' | tail -1 > $O/bench_cfg4_1gpu.json
+  # the N > 1 branch as two ranks sharing this GPU (gloo), --full: weak line + config-4 block + gather times
   LV_SLAM_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus 2 --steps 5 --warmup 2 2>> $O/bench.log | grep '^{' | tail -1 > $O/bench_2ranks_1gpu_gloo.json
-  timeout 600 python bench.py --prefiltered --azimuth 2048 --pairs 64 --variant pca --mode direct1 --cpu-seconds 10 2>> $O/bench.log | tail -1 > $O/bench_prefiltered.json
+      bench.py --full --gpus 2 --steps 5 --warmup 2 2>> $O/bench.log | grep '^{' | tail -1 > $O/bench_2ranks_1gpu_gloo.json
+  timeout 600 python bench.py --full --prefiltered --azimuth 2048 --pairs 64 --variant pca --mode direct1 --cpu-seconds 10 2>> $O/bench.log | tail -1 > $O/bench_prefiltered.json
   ;;
 extra)
   cd $R

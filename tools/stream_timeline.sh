@@ -7,7 +7,7 @@ TAG=$1; shift
 O=$R/gpurun_out/$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 500 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/kt -- python $R/bench.py --cpu-seconds 0 --no-host-clouds --config4-pairs 0 --seq-frames 0 --no-other-configs --steps 12 --warmup 2 "$@" > $O/bench.json 2> $O/kt.log
+timeout 500 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/kt -- python $R/bench.py --full --cpu-seconds 0 --no-host-clouds --config4-pairs 0 --seq-frames 0 --no-other-configs --steps 12 --warmup 2 "$@" > $O/bench.json 2> $O/kt.log
 python - <<PY > $O/timeline.txt
 import csv, glob, re
 f = glob.glob("$O/kt/**/*_kernel_trace.csv", recursive=True)

@@ -28,6 +28,7 @@
 #include <sched.h>
 #include <fstream>
 #include <chrono>
+#include <memory>
 
 #include "mi355_ndt.h"
 #include "ndt_math.hpp"
@@ -42,6 +43,7 @@
 #include "ndt_prefilter.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
+#include "ndt_hostmem.hpp"
 #ifndef NDT_SINGLE_TU      // the ORD = 1 instantiations come from mi355_ndt_ord1.hip (built side by side with this file)
 #include "ndt_ord1_list.hpp"
 #include "ndt_fast_list.hpp"
@@ -52,11 +54,53 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 
 
 // ------------------------------------------------------------------------------------ host side
+// Ownership: every buffer, pinned block, stream and event the engine allocates lives in an owner of ndt_hostmem.hpp and is released with it.
+// Raw pointers below are views into memory some owner (or the caller) holds; their comments say which.
 struct mi355ndt_handle;
+struct EngineDel { void operator()(mi355ndt_handle* e) const { (void)mi355ndt_destroy(e); } };
+
+// ---- stream mode (mi355ndt_stream_*, the parent handle): n_contexts batches resident, one persistent launch per submitted batch,
+// the stragglers of a launch carried into the next one (ndt_async.hpp).  One StreamState per session: mi355ndt_stream_begin creates it,
+// mi355ndt_stream_end releases it.
+struct StreamCtx {
+  long long batch_id = -1; int n_pairs = 0;
+  bool busy = false;                            // submitted, not yet collected
+  bool redo = false;                            // collect re-runs it synchronously (its launch gave up)
+  bool done_sync = false;                       // processed synchronously inside submit (configuration the one-launch align does not serve)
+  long long launch = -1;                        // the launch that started it
+  // a batch's small inputs -- target counts, source counts, guesses -- travel as ONE copy: pinned staging block -> device block, into which
+  // the context engine's d_tgt_cnt / d_src_cnt / d_guess point
+  DevBuf<int> d_in; PinBuf<int> h_in; unsigned* h_in_dev = nullptr;   // (h_in is mapped: the device reads it itself; h_in_dev views it)
+  // results: MAPPED host memory -- a pair's result record is written there by the updater that finalises it (posted PCIe writes), no copy
+  PinBuf<mi355ndt_result> h_res; mi355ndt_result* d_res_map = nullptr;   // (d_res_map: the device's view of h_res)
+  std::vector<float> guesses;                   // (kept for a synchronous re-run)
+  PoseRecord* d_pose = nullptr; int pose_cap = 0, pose_base = 0, pose_stride = 1;   // mi355ndt_stream_pose_records (this batch's gather block)
+  std::unique_ptr<mi355ndt_handle, EngineDel> e;   // the context's own engine: bound clouds, grids, pair states (runs on the parent's stream)
+};
+struct StreamState {
+  static constexpr int EV = 16;
+  bool sync_only = false, drop_carry = true;
+  int nctx = 0, max_pairs = 0, items = 0, ring_cap = 0, thresh = 0;
+  size_t max_tgt = 0, max_src = 0;              // what mi355ndt_stream_begin was told (mi355ndt_stream_submit_host sizes the contexts' own cloud buffers with it)
+  int plan_cb = 0; size_t plan_words = 0;
+  void* pose_next = nullptr; size_t pose_cap_next = 0; int pose_base_next = 0, pose_stride_next = 1;   // apply to the next submit of this session
+  long long next_id = 0, launches = 0, counted = 0;
+  long long recovered_upto = -1;                // launches up to this one have had their abort handled (stream_recover runs once per aborted launch, not once per collect that walks past its slot)
+  DevBuf<AsyncCtl> d_ctl;                       // two control blocks: a launch reads the hand-over list of the previous one
+  DevBuf<int> d_ring;
+  DevBuf<CtxStat> d_stat;                       // per context: pairs finalised, sizes and verdict of its last planned build
+  // Build under the launch: with reserve_wg > 0 the contexts' engines run their builds on build_stream, the persistent launches leave
+  // that many workgroup slots free, and events order  launch j-2 done -> build of batch j -> launch j
+  HipStream build_stream; int reserve_wg = 0, launch_slots = 0;
+  HipEvent ev_built[ASYNC_MAX_CTX], ev_launched[EV], ev_prepared[EV]; bool prep_first = true;
+  PinBuf<volatile StreamStatus> h_status; StreamStatus* d_status = nullptr;   // mapped ring of per-launch status slots (k_stream_status); d_status: the device's view
+  StreamCtx ctx[ASYNC_MAX_CTX];                 // (last: the contexts' engines are released before the stream they run on)
+};
+
 struct mi355ndt_handle {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = true;
+  HipStream own_stream;                         // the engine's compute stream, unless mi355ndt_set_stream gave it one
+  hipStream_t stream = nullptr;                 // view: own_stream or the caller's stream
   mi355ndt_params prm;
   std::string err;
 
@@ -64,9 +108,10 @@ struct mi355ndt_handle {
   size_t tgt_pitch = 0, src_pitch = 0;          // geometry in use
   size_t own_tgt_pitch = 0, own_src_pitch = 0;  // geometry of the owned buffers
   int own_tgt_pairs = 0, own_src_pairs = 0;
-  float *d_tgt_own = nullptr, *d_src_own = nullptr;
-  const float *d_tgt = nullptr, *d_src = nullptr;
-  int *d_tgt_cnt = nullptr, *d_src_cnt = nullptr;
+  DevBuf<float> d_tgt_own, d_src_own;
+  const float *d_tgt = nullptr, *d_src = nullptr;   // views: d_tgt_own / d_src_own or a device buffer bound by the caller
+  DevBuf<int> d_tgt_cnt_own, d_src_cnt_own;
+  int *d_tgt_cnt = nullptr, *d_src_cnt = nullptr;   // views: d_tgt_cnt_own / d_src_cnt_own or the stream context's input block
   std::vector<int> h_tgt_cnt, h_src_cnt;
   std::vector<int> up_tgt_cnt, up_src_cnt;        // what d_tgt_cnt / d_src_cnt currently hold (uploads are skipped when unchanged)
   bool targets_built = false, have_target = false, have_source = false;
@@ -76,87 +121,87 @@ struct mi355ndt_handle {
   float grid_resolution = 0.f;                    // leaf size the resident grids were built with (setResolution without a source keeps them: ndt_omp.h:126-136)
 
   // build workspace
-  unsigned* d_minmax = nullptr;                  // a slice of d_word_off's allocation (zeroed together before every build)
-  GridDesc* d_grid = nullptr;
-  unsigned *d_nwords = nullptr, *d_word_off = nullptr;
-  unsigned *d_keys_a = nullptr, *d_keys_b = nullptr;      // cell key per target point: unsorted / sorted (segment-local radix sort)
-  unsigned *d_vals_a = nullptr, *d_vals_b = nullptr;
-  size_t keys_cap = 0;
-  BitWord* d_words = nullptr; size_t words_cap = 0;
-  VoxelRec* d_recs = nullptr; int *d_vox_idx = nullptr, *d_vox_n = nullptr;
-  unsigned* d_seg_start = nullptr; double* d_sums = nullptr;
-  unsigned *d_heads = nullptr, *d_head_cnt = nullptr; size_t heads_cap = 0, head_cnt_cap = 0;   // k_mark's run heads per slice
-  float* d_cent = nullptr; double* d_icov64 = nullptr; size_t icov64_cap = 0;
-  int* d_kdw = nullptr; size_t kdw_cap = 0; bool kdw_built = false;   // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
-  float4* d_sorted = nullptr; size_t sorted_cap = 0; bool leaf_sorted = false;   // MI355NDT_LEAF_SORTED: the sorted order as points (k_sorted_points)
-  unsigned* d_rs_hist = nullptr; unsigned* d_rs_offs = nullptr; size_t rs_cap = 0;   // segmented radix sort: tile histograms / offsets
-  unsigned *d_cstart = nullptr, *d_cend = nullptr; size_t cell_cap = 0; bool cells_ready = false; int last_cb = 0;
-  double* d_fit = nullptr; size_t fit_cap = 0;
+  unsigned* d_minmax = nullptr;                  // view: a slice of d_word_off (zeroed together before every build)
+  DevBuf<GridDesc> d_grid;
+  DevBuf<unsigned> d_nwords, d_word_off;
+  DevBuf<unsigned> d_keys_a, d_keys_b;           // cell key per target point: unsorted / sorted (segment-local radix sort)
+  DevBuf<unsigned> d_vals_a, d_vals_b;
+  DevBuf<BitWord> d_words;
+  size_t recs_per_pair = 0;                      // voxel records per target of the records group (d_recs ... d_cent); 0: group not allocated
+  DevBuf<VoxelRec> d_recs; DevBuf<int> d_vox_idx, d_vox_n;
+  DevBuf<unsigned> d_seg_start; DevBuf<double> d_sums;
+  DevBuf<unsigned> d_heads, d_head_cnt;          // k_mark's run heads per slice
+  DevBuf<float> d_cent; DevBuf<double> d_icov64;
+  DevBuf<int> d_kdw; bool kdw_built = false;     // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
+  DevBuf<float4> d_sorted; bool leaf_sorted = false;   // MI355NDT_LEAF_SORTED: the sorted order as points (k_sorted_points)
+  DevBuf<unsigned> d_rs_hist, d_rs_offs;         // segmented radix sort: tile histograms / offsets
+  DevBuf<unsigned> d_cstart, d_cend; bool cells_ready = false; int last_cb = 0;
+  DevBuf<double> d_fit;
   // batched fitness (mi355ndt_batch_fitness_scores): occupied-cell index of every target (ndt_fitness.hpp), built on the first call after a
   // target build; the launch's item table and transforms
-  BitWord* d_fwords = nullptr; size_t fwords_cap = 0; unsigned* d_fruns = nullptr; size_t fruns_cap = 0; bool fit_index_ready = false;
-  int* d_fit_items = nullptr; size_t fit_items_cap = 0; float* d_fit_T = nullptr; size_t fit_T_cap = 0;
+  DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns; bool fit_index_ready = false;
+  DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
   // prefilter workspace
-  float *d_pf_in = nullptr, *d_pf_out = nullptr; unsigned char* d_pf_keep = nullptr; unsigned *d_pf_keys = nullptr, *d_pf_vals = nullptr;
-  int *d_pf_flag = nullptr, *d_pf_pos = nullptr, *d_pf_mm = nullptr; PfGrid* d_pf_grid = nullptr; void* d_pf_tmp = nullptr;
-  size_t pf_cap = 0, pf_tmp_bytes = 0; int pf_count = 0; size_t pf_pitch = 0;
+  DevBuf<float> d_pf_in, d_pf_out; DevBuf<unsigned char> d_pf_keep; DevBuf<unsigned> d_pf_keys, d_pf_vals;
+  DevBuf<int> d_pf_flag, d_pf_pos, d_pf_mm; DevBuf<PfGrid> d_pf_grid; DevBuf<unsigned> d_pf_tmp;
+  int pf_count = 0; size_t pf_pitch = 0;
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
-  size_t recs_per_pair = 0, recs_cap = 0;
-  unsigned* h_pin_u = nullptr;                  // pinned scratch (2 unsigned)
+  PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 
   // align workspace
-  PairState* d_state = nullptr;
-  double* d_partials = nullptr; size_t partials_cap = 0;
+  DevBuf<PairState> d_state;
+  DevBuf<double> d_partials;
   int chunks_per_pair = 0;
   int rows_per_pair = 0, pts_per_chunk = CHUNK_PTS;   // stored partial rows per pair / points covered by one chunk of k_update's tree
   int items_per_pair = 0;                         // sweep work items per pair (= rows_per_pair in batch mode, 4 x rows_per_pair in latency mode)
   bool async_force = false;                       // MI355NDT_OPT_ASYNC_ALIGN = 2 / MI355NDT_ASYNC=2: the one-launch align also for batches smaller than the resident waves (tests, fuzzing)
   bool async_align = true;                        // MI355NDT_OPT_ASYNC_ALIGN: batch aligns as ONE persistent launch (ndt_async.hpp); MI355NDT_ASYNC=0 turns it off
   int score_only_last = 1;                        // MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP: the one-launch align's last sweep of a pair evaluates the score alone
-  int* d_ring = nullptr; size_t ring_cap_total = 0; unsigned* d_arrived = nullptr; size_t arrived_cap = 0; AsyncCtl* d_actl = nullptr;
-  AsyncCtl* h_pin_actl = nullptr;
-  AsyncTab* d_atab = nullptr;                     // the launch's context table (ndt_async.hpp)
+  DevBuf<int> d_ring; DevBuf<unsigned> d_arrived; DevBuf<AsyncCtl> d_actl;
+  PinBuf<AsyncCtl> h_pin_actl;
+  DevBuf<AsyncTab> d_atab;                        // the launch's context table (ndt_async.hpp)
   unsigned debug_abort_pos = 0xFFFFFFFFu;         // MI355NDT_OPT_DEBUG_ASYNC_ABORT (test hook): the wave that claims this position of ring 0 gives up
   unsigned debug_ring_mask = 0xFFu;               // MI355NDT_OPT_DEBUG_ASYNC_RINGS (test hook): rings whose workgroups take part
   int arith = 0;                                  // MI355NDT_OPT_ARITH: 0 = the reference recipe's arithmetic, one rounding per operation; 1 = tolerance arithmetic (ndt_sweep.hpp: eval_hit_fast)
-  VoxelRecF* d_recs_fast = nullptr; size_t recs_fast_cap = 0; bool recs_fast_built = false;   // ... and the records its sweeps read (k_voxels writes them beside d_recs)
+  DevBuf<VoxelRecF> d_recs_fast; bool recs_fast_built = false;   // ... and the records its sweeps read (k_voxels writes them beside d_recs)
   int f32_sum_order = 0;                          // MI355NDT_OPT_F32_SUM_ORDER: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
   double gauss_last[3] = {0, 0, 0};               // gauss_d1_/d2_/d3_ as the constructor / the last computeTransformation left them (calculateScore reads them)
-  float* d_score_pts = nullptr; size_t score_pts_cap = 0; double* d_score_part = nullptr; size_t score_part_cap = 0;   // calculateScore workspace
+  DevBuf<float> d_score_pts; DevBuf<double> d_score_part;   // calculateScore workspace
   bool latency_mode = false;                      // mi355ndt_set_latency_mode
   bool seq_running = false;                       // inside mi355ndt_sequence_run
   int fine_it = 0;                                // 0: batch-mode sweep items (512 points); 1 / 2: fine items of fine_it * 64 points (latency mode)
   int fine_tiles = 2;                             // MI355NDT_FINE_TILES overrides (tuning runs)
-  int* d_grid_of = nullptr; size_t grid_of_cap = 0;   // sequence mode: grid index per pair
-  const int* d_grid_of_use = nullptr;             // what the sweeps are given: d_grid_of inside mi355ndt_sequence_run, else null (pair b -> grid b)
-  SeqState* d_seq = nullptr; mi355ndt_seq_frame* d_seq_out = nullptr; double* d_stamps = nullptr; size_t seq_cap = 0;
-  volatile int* h_seq_flags = nullptr; int* d_seq_flags = nullptr;   // mapped pinned: [0] = run finished, [1] = update launches executed
-  float* d_guess = nullptr;
-  float* h_pin_guess = nullptr;                   // pinned staging copy of the caller's guesses (no sync needed after the upload)
-  mi355ndt_result* d_results = nullptr;
-  int* d_active = nullptr;                      // per-round active counters
-  int* d_active_list = nullptr;                 // pairs taking part in the next sweep (compacted by k_update)
-  SweepCtl* d_ctl = nullptr;                      // two control blocks: the sweep reading one zeroes the other for the next round
+  int dyn_shift = -1;                             // < 0: per search mode (make_sweep_const); MI355NDT_SWEEP_DYN_SHIFT overrides (tuning runs)
+  DevBuf<int> d_grid_of;                          // sequence mode: grid index per pair
+  const int* d_grid_of_use = nullptr;             // what the sweeps are given: view of d_grid_of inside mi355ndt_sequence_run, else null (pair b -> grid b)
+  DevBuf<SeqState> d_seq; DevBuf<mi355ndt_seq_frame> d_seq_out; DevBuf<double> d_stamps;
+  PinBuf<volatile int> h_seq_flags; int* d_seq_flags = nullptr;   // mapped pinned: [0] = run finished, [1] = update launches executed; d_seq_flags: the device's view
+  DevBuf<float> d_guess_own;
+  float* d_guess = nullptr;                       // view: d_guess_own or the stream context's input block
+  PinBuf<float> h_pin_guess;                      // pinned staging copy of the caller's guesses (no sync needed after the upload)
+  DevBuf<mi355ndt_result> d_results;
+  DevBuf<int> d_active;                           // per-round active counters
+  DevBuf<int> d_active_list;                      // pairs taking part in the next sweep (compacted by k_update)
+  DevBuf<SweepCtl> d_ctl;                         // two control blocks: the sweep reading one zeroes the other for the next round
   int ctl_idx = 0;                                // block the NEXT sweep reads (k_init_state / k_update fill it)
   int n_cu = 256;
-  int dyn_shift = -1;                             // < 0: per search mode (make_sweep_const); MI355NDT_SWEEP_DYN_SHIFT overrides (tuning runs)
-  int* h_pin_active = nullptr;
-  hipEvent_t ev_burst[2] = {nullptr, nullptr};   // one per in-flight burst of align rounds
-  unsigned long long* d_hits = nullptr;         // [0] (point,voxel) evaluations, all sweeps; [1] score-only sweeps of the one-launch align
-  float* d_hook = nullptr;                      // 16 + 9 floats, 6 doubles
-  float* d_aligned = nullptr; size_t aligned_cap = 0;
-  float* h_pin_aligned = nullptr; size_t pin_aligned_cap = 0;   // pinned landing buffer of get_aligned
+  PinBuf<int> h_pin_active;
+  HipEvent ev_burst[2];                           // one per in-flight burst of align rounds
+  DevBuf<unsigned long long> d_hits;              // [0] (point,voxel) evaluations, all sweeps; [1] score-only sweeps of the one-launch align
+  DevBuf<float> d_hook;                           // 16 + 9 floats, 6 doubles
+  DevBuf<float> d_aligned;
+  PinBuf<float> h_pin_aligned;                    // pinned landing buffer of get_aligned
   // host-cloud uploads: a ring of pinned staging slots, a copy stream of its own, a device staging buffer per slot.  The caller's
   // records are compacted to x,y,z into a slot (the only CPU work), the slot goes over PCIe asynchronously and a small kernel
   // spreads it into the SoA rows; the next call stages the next cloud while this one is still in flight.
-  struct UpSlot { float* h = nullptr; float* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false, filling = false; };
+  struct UpSlot { PinBuf<float> h; DevBuf<float> d; HipEvent ev; bool used = false, filling = false; };   // h, d: 3 floats per point
   static constexpr int UP_SLOTS = 12;             // (a slot grows to the largest transfer it has carried: up to UP_GROUP_MAX clouds = 12.6 MB of 65,536-point clouds)
   UpSlot up[UP_SLOTS];
   int up_next = 0;
   static constexpr int UP_STREAMS = 4;            // an upload rides copy stream (pair + 2 * side) % UP_STREAMS: per-transfer latencies of the SDMA queues
                                                   // overlap across pairs, uploads into the same rows stay ordered
-  hipStream_t copy_stream[UP_STREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_uploads[UP_STREAMS] = {nullptr, nullptr, nullptr, nullptr}, ev_compute = nullptr;   // copy streams -> compute stream, compute stream -> copy streams
+  HipStream copy_stream[UP_STREAMS];
+  HipEvent ev_uploads[UP_STREAMS], ev_compute;    // copy streams -> compute stream, compute stream -> copy streams
   bool uploads_pending = false;
   std::mutex up_mtx;                              // batch_set_target / batch_set_source may be called from several threads (distinct pairs)
 
@@ -166,49 +211,16 @@ struct mi355ndt_handle {
   // "no grid" (and raises its flag in d_bstat) should the batch not fit the plan -- the parent then re-runs that batch synchronously and learns.
   bool async_build = false;
   int plan_cb = 0; size_t plan_words = 0;
-  unsigned* d_bstat = nullptr;                    // (not owned: the parent's CtxStat of this context) [1] total words, [2] largest grid, [3] plan exceeded
+  unsigned* d_bstat = nullptr;                    // view: the parent's CtxStat of this context -- [1] total words, [2] largest grid, [3] plan exceeded
   bool counts_preloaded = false;                  // the parent has put this batch's point counts (and guesses) on the device already
   bool build_stamped = false;                    // stream mode + profiling: build times come from stamps in the launch's status slot, not from events
   bool word_off_cleared = false;                 // stream mode: k_stream_inputs has cleared d_word_off for the next build (no fill)
   size_t last_total_words = 0;                    // of the last synchronous build
 
-  // ---- stream mode (mi355ndt_stream_*, the parent handle): n_contexts batches resident, one persistent launch per submitted batch,
-  // the stragglers of a launch carried into the next one (ndt_async.hpp)
-  struct StreamCtx {
-    mi355ndt_handle* e = nullptr;                 // the context's own engine: bound clouds, grids, pair states (runs on the parent's stream)
-    long long batch_id = -1; int n_pairs = 0;
-    bool busy = false;                            // submitted, not yet collected
-    bool redo = false;                            // collect re-runs it synchronously (its launch gave up)
-    bool done_sync = false;                       // processed synchronously inside submit (configuration the one-launch align does not serve)
-    long long launch = -1;                        // the launch that started it
-    // a batch's small inputs -- target counts, source counts, guesses -- travel as ONE copy: pinned staging block -> device block, into which
-    // the context engine's d_tgt_cnt / d_src_cnt / d_guess point
-    int* h_in = nullptr; int* d_in = nullptr; size_t in_bytes = 0; unsigned* h_in_dev = nullptr;   // (h_in is mapped: the device reads it itself)
-    void *own_tgt_cnt = nullptr, *own_src_cnt = nullptr, *own_guess = nullptr;   // the engine's own arrays (put back before it is destroyed)
-    // results: MAPPED host memory -- a pair's result record is written there by the updater that finalises it (posted PCIe writes), no copy
-    mi355ndt_result* h_res = nullptr; mi355ndt_result* d_res_map = nullptr;
-    std::vector<float> guesses;                   // (kept for a synchronous re-run)
-    PoseRecord* d_pose = nullptr; int pose_cap = 0, pose_base = 0, pose_stride = 1;   // mi355ndt_stream_pose_records (this batch's gather block)
-  };
-  bool stream_on = false, s_sync_only = false, s_drop_carry = true;
-  int s_nctx = 0, s_max_pairs = 0, s_items = 0, s_ring_cap = 0, s_thresh = 0;
-  size_t s_max_tgt = 0, s_max_src = 0;            // what mi355ndt_stream_begin was told (mi355ndt_stream_submit_host sizes the contexts' own cloud buffers with it)
+  // stream mode: the session (null outside mi355ndt_stream_begin ... mi355ndt_stream_end) and the options it starts with
+  std::unique_ptr<StreamState> ss;
   int s_thresh_opt = -1;                          // MI355NDT_OPT_STREAM_THRESHOLD
   int s_reserve_opt = -1;                         // MI355NDT_OPT_STREAM_RESERVE
-  int s_plan_cb = 0; size_t s_plan_words = 0;
-  void* s_pose_next = nullptr; size_t s_pose_cap_next = 0; int s_pose_base_next = 0, s_pose_stride_next = 1;   // apply to the next submit
-  StreamCtx sctx[ASYNC_MAX_CTX];
-  long long s_next_id = 0, s_launches = 0, s_counted = 0;
-  long long s_recovered_upto = -1;                // launches up to this one have had their abort handled (stream_recover runs once per aborted launch, not once per collect that walks past its slot)
-  AsyncCtl* d_sctl = nullptr;                     // two control blocks: a launch reads the hand-over list of the previous one
-  int* d_sring = nullptr;
-  CtxStat* d_sstat = nullptr;                     // per context: pairs finalised, sizes and verdict of its last planned build
-  static constexpr int S_EV = 16;
-  // Build under the launch: with s_reserve_wg > 0 the contexts' engines run their builds on s_build_stream, the persistent launches leave
-  // that many workgroup slots free, and events order  launch j-2 done -> build of batch j -> launch j
-  hipStream_t s_build_stream = nullptr; int s_reserve_wg = 0, s_launch_slots = 0;
-  hipEvent_t s_ev_built[ASYNC_MAX_CTX] = {}; hipEvent_t s_ev_launched[S_EV] = {}; hipEvent_t s_ev_prepared[S_EV] = {}; bool s_prep_first = true;
-  volatile StreamStatus* h_sstatus = nullptr; StreamStatus* d_sstatus = nullptr;   // mapped ring of per-launch status slots (k_stream_status)
 
   // profiling
   bool prof = false;
@@ -219,6 +231,12 @@ struct mi355ndt_handle {
   bool ev_last_fresh = false;                     // nothing else has been enqueued on the stream since
   std::vector<hipEvent_t> ev_pool;                // idle timing events (filled by mi355ndt_profile_enable)
   size_t ev_pool_target = 4096;
+
+  ~mi355ndt_handle() {                            // (the profiling pool is not held by owners: its events move between the pool and the spans)
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    for (auto* v : {&ev_sweep, &ev_update, &ev_build})
+      for (auto& e : *v) { if (!e.first_shared) (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+  }
 };
 
 #define HIPCHK(h, call)                                                                          \
@@ -238,7 +256,7 @@ struct mi355ndt_handle {
 #define UP_GROUP_MAX   (2 * UP_GROUP_PAIRS)
 static_assert(UP_GROUP_MAX <= (int)(sizeof(DeintTab::e) / sizeof(DeintTab::e[0])), "k_deinterleave_multi's table");
 // between mi355ndt_stream_begin and mi355ndt_stream_end the handle's batches belong to the stream: the other entry points refuse
-#define NOT_IN_STREAM(h) do { if ((h)->stream_on) { (h)->err = "the handle is in stream mode (mi355ndt_stream_begin): call mi355ndt_stream_end first"; return MI355NDT_ERR_STATE; } } while (0)
+#define NOT_IN_STREAM(h) do { if ((h)->ss) { (h)->err = "the handle is in stream mode (mi355ndt_stream_begin): call mi355ndt_stream_end first"; return MI355NDT_ERR_STATE; } } while (0)
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
   __builtin_ia32_pause();
@@ -247,16 +265,6 @@ static inline void cpu_relax() {
 #endif
 }
 static int ceil_log2(unsigned v) { int b = 0; while ((1u << b) < v) b++; return b; }
-
-template <typename T>
-static hipError_t grow(T*& p, size_t& cap, size_t need) {
-  if (need <= cap) return hipSuccess;
-  if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; }
-  hipError_t e = hipMalloc((void**)&p, need * sizeof(T));
-  if (e == hipSuccess) cap = need;
-  else cap = 0;
-  return e;
-}
 
 static void build_offsets(int mode, SweepConst& sc) {
   if (mode == MI355NDT_DIRECT1) { sc.K = 1; sc.table = 0; }
@@ -385,8 +393,7 @@ int mi355ndt_default_params(mi355ndt_params* p) {
   return MI355NDT_OK;
 }
 
-int mi355ndt_destroy(mi355ndt_handle* h);
-
+int mi355ndt_stream_end(mi355ndt_handle* h);
 int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle** out) {
   if (!out) return MI355NDT_ERR_BAD_ARG;
   *out = nullptr;
@@ -398,7 +405,7 @@ int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle**
   if (params) p = *params;
   int rc = check_params(p);
   if (rc) return rc;
-  mi355ndt_handle* h = new mi355ndt_handle();
+  std::unique_ptr<mi355ndt_handle> h(new mi355ndt_handle());   // (a failure below releases whatever was created before it)
   h->device = device;
   h->prm = p;
   gauss_constants3(0.55, 1.0f, h->gauss_last);    // the constructor's gauss_d*_ (impl2:70-76: resolution_ 1.0f, outlier_ratio_ 0.55), whatever the setters say later
@@ -409,61 +416,29 @@ int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle**
   if (const char* e = std::getenv("MI355NDT_ASYNC")) { h->async_align = std::atoi(e) != 0; h->async_force = std::atoi(e) == 2; }
   if (const char* e = std::getenv("MI355NDT_SCORE_ONLY_LAST_SWEEP")) h->score_only_last = std::atoi(e) != 0;   // default of MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP (A/B runs)
   if (const char* e = std::getenv("MI355NDT_SWEEP_DYN_SHIFT")) { const int v = std::atoi(e); if (v >= 0 && v <= 30) h->dyn_shift = v; }
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return MI355NDT_ERR_HIP;
-  }
-  if (hipHostMalloc((void**)&h->h_pin_u, 4 * sizeof(unsigned)) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_pin_active, 128 * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&h->d_active, 128 * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&h->d_ctl, 2 * sizeof(SweepCtl)) != hipSuccess ||
-      hipMalloc((void**)&h->d_hits, 2 * sizeof(unsigned long long)) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || h->own_stream.create() != hipSuccess) return MI355NDT_ERR_HIP;
+  h->stream = h->own_stream;
+  if (h->h_pin_u.realloc_exact(4) != hipSuccess ||
+      h->h_pin_active.realloc_exact(128) != hipSuccess ||
+      h->d_active.realloc_exact(128) != hipSuccess ||
+      h->d_ctl.realloc_exact(2) != hipSuccess ||
+      h->d_hits.realloc_exact(2) != hipSuccess ||
       hipMemsetAsync(h->d_hits, 0, 2 * sizeof(unsigned long long), h->stream) != hipSuccess ||   // (the counters start at zero, not at what the allocation held)
-      hipMalloc((void**)&h->d_hook, 64 * sizeof(double)) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_compute, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_burst[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_burst[1], hipEventDisableTiming) != hipSuccess) {
-    mi355ndt_destroy(h);                          // releases whatever was created before the failure
-    return MI355NDT_ERR_HIP;
-  }
+      h->d_hook.realloc_exact(64 * sizeof(double) / sizeof(float)) != hipSuccess ||
+      h->ev_compute.create() != hipSuccess || h->ev_burst[0].create() != hipSuccess || h->ev_burst[1].create() != hipSuccess) return MI355NDT_ERR_HIP;
   for (int i = 0; i < mi355ndt_handle::UP_STREAMS; i++)
-    if (hipStreamCreateWithFlags(&h->copy_stream[i], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_uploads[i], hipEventDisableTiming) != hipSuccess) { mi355ndt_destroy(h); return MI355NDT_ERR_HIP; }
-  *out = h;
+    if (h->copy_stream[i].create() != hipSuccess || h->ev_uploads[i].create() != hipSuccess) return MI355NDT_ERR_HIP;
+  *out = h.release();
   return MI355NDT_OK;
 }
 
-int mi355ndt_stream_end(mi355ndt_handle* h);
 int mi355ndt_destroy(mi355ndt_handle* h) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  if (h->stream_on) (void)mi355ndt_stream_end(h);
-  void* ptrs[] = {h->d_tgt_own, h->d_src_own, h->d_tgt_cnt, h->d_src_cnt, h->d_grid, h->d_nwords, h->d_word_off,
-                  h->d_keys_a, h->d_keys_b, h->d_vals_a, h->d_vals_b, h->d_words, h->d_recs, h->d_vox_idx, h->d_vox_n,
-                  h->d_state, h->d_partials, h->d_guess, h->d_results, h->d_active, h->d_hook, h->d_aligned, h->d_hits, h->d_seg_start, h->d_heads, h->d_head_cnt, h->d_sums,
-                  h->d_cent, h->d_icov64, h->d_kdw, h->d_rs_hist, h->d_rs_offs, h->d_active_list, h->d_ctl, h->d_cstart, h->d_cend, h->d_fit, h->d_fwords, h->d_fruns, h->d_fit_items, h->d_fit_T, h->d_pf_in, h->d_pf_out, h->d_pf_keep, h->d_pf_keys,
-                  h->d_pf_vals, h->d_pf_flag, h->d_pf_pos, h->d_pf_mm, h->d_pf_grid, h->d_pf_tmp, h->d_score_pts, h->d_score_part,
-                  h->d_ring, h->d_arrived, h->d_actl, h->d_atab, h->d_sorted, h->d_recs_fast};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (void* p : {(void*)h->d_grid_of, (void*)h->d_seq, (void*)h->d_seq_out, (void*)h->d_stamps}) if (p) (void)hipFree(p);
-  if (h->h_seq_flags) (void)hipHostFree((void*)h->h_seq_flags);
+  if (h->ss) (void)mi355ndt_stream_end(h);
   for (hipStream_t cs : h->copy_stream) if (cs) (void)hipStreamSynchronize(cs);
-  for (auto& u : h->up) { if (u.h) (void)hipHostFree(u.h); if (u.d) (void)hipFree(u.d); if (u.ev) (void)hipEventDestroy(u.ev); }
-  if (h->h_pin_aligned) (void)hipHostFree(h->h_pin_aligned);
-  for (hipEvent_t e : h->ev_uploads) if (e) (void)hipEventDestroy(e);
-  if (h->ev_compute) (void)hipEventDestroy(h->ev_compute);
-  for (hipStream_t cs : h->copy_stream) if (cs) (void)hipStreamDestroy(cs);
-  if (h->h_pin_actl) (void)hipHostFree(h->h_pin_actl);
-  if (h->h_pin_u) (void)hipHostFree(h->h_pin_u);
-  if (h->h_pin_active) (void)hipHostFree(h->h_pin_active);
-  if (h->h_pin_guess) (void)hipHostFree(h->h_pin_guess);
-  for (hipEvent_t e : h->ev_burst) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-  for (auto* v : {&h->ev_sweep, &h->ev_update, &h->ev_build})
-    for (auto& e : *v) { if (!e.first_shared) (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                                       // (the owners release every buffer, block, event and stream)
   return MI355NDT_OK;
 }
 
@@ -480,12 +455,11 @@ int mi355ndt_set_stream(mi355ndt_handle* h, void* s) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   if (s) {
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    h->own_stream.reset();
     h->stream = (hipStream_t)s;
-    h->own_stream = false;
   } else if (!h->own_stream) {
-    HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->own_stream = true;
+    HIPCHK(h, h->own_stream.create());
+    h->stream = h->own_stream;
   }
   return MI355NDT_OK;
 }
@@ -511,27 +485,22 @@ static int ensure_pair_arrays(mi355ndt_handle* h, int n_pairs) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   // the arrays are released and re-created one by one: until all of them exist again the engine holds no batch at all
   // (a failure half way must not leave cap_pairs vouching for freed or undersized buffers)
-  h->cap_pairs = 0; h->n_pairs = 0;
+  h->cap_pairs = 0; h->n_pairs = 0; h->d_tgt_cnt = h->d_src_cnt = nullptr; h->d_guess = nullptr;
   h->targets_built = false; h->have_target = false; h->have_source = false; h->aligned_once = false;
-  auto re = [&](void** p, size_t bytes) -> hipError_t {
-    if (*p) { hipError_t e = hipFree(*p); *p = nullptr; if (e != hipSuccess) return e; }
-    return hipMalloc(p, bytes);
-  };
-  HIPCHK(h, re((void**)&h->d_tgt_cnt, n_pairs * sizeof(int)));
-  HIPCHK(h, re((void**)&h->d_src_cnt, n_pairs * sizeof(int)));
+  HIPCHK(h, h->d_tgt_cnt_own.realloc_exact(n_pairs)); h->d_tgt_cnt = h->d_tgt_cnt_own;
+  HIPCHK(h, h->d_src_cnt_own.realloc_exact(n_pairs)); h->d_src_cnt = h->d_src_cnt_own;
   h->up_tgt_cnt.clear(); h->up_src_cnt.clear();       // fresh device arrays: nothing uploaded yet
-  HIPCHK(h, re((void**)&h->d_grid, n_pairs * sizeof(GridDesc)));
-  HIPCHK(h, re((void**)&h->d_nwords, (n_pairs + 2) * sizeof(unsigned)));
+  HIPCHK(h, h->d_grid.realloc_exact(n_pairs));
+  HIPCHK(h, h->d_nwords.realloc_exact(n_pairs + 2));
   // build control words, zeroed by ONE memset per build: [0] total bitmap words, [1] largest grid, then per target six extremes
   // (k_minmax's encoding makes zero "none yet")
-  HIPCHK(h, re((void**)&h->d_word_off, (2 + 6 * (size_t)n_pairs) * sizeof(unsigned)));
+  HIPCHK(h, h->d_word_off.realloc_exact(2 + 6 * (size_t)n_pairs));
   h->d_minmax = h->d_word_off + 2;
-  HIPCHK(h, re((void**)&h->d_state, n_pairs * sizeof(PairState)));
-  HIPCHK(h, re((void**)&h->d_guess, n_pairs * 16 * sizeof(float)));
-  if (h->h_pin_guess) { HIPCHK(h, hipHostFree(h->h_pin_guess)); h->h_pin_guess = nullptr; }
-  HIPCHK(h, hipHostMalloc((void**)&h->h_pin_guess, (size_t)n_pairs * 16 * sizeof(float)));
-  HIPCHK(h, re((void**)&h->d_results, n_pairs * sizeof(mi355ndt_result)));
-  HIPCHK(h, re((void**)&h->d_active_list, n_pairs * sizeof(int)));
+  HIPCHK(h, h->d_state.realloc_exact(n_pairs));
+  HIPCHK(h, h->d_guess_own.realloc_exact((size_t)n_pairs * 16)); h->d_guess = h->d_guess_own;
+  HIPCHK(h, h->h_pin_guess.realloc_exact((size_t)n_pairs * 16));
+  HIPCHK(h, h->d_results.realloc_exact(n_pairs));
+  HIPCHK(h, h->d_active_list.realloc_exact(n_pairs));
   HIPCHK(h, hipMemsetAsync(h->d_grid, 0, n_pairs * sizeof(GridDesc), h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_state, 0, n_pairs * sizeof(PairState), h->stream));
   h->cap_pairs = n_pairs;
@@ -541,14 +510,13 @@ static int ensure_pair_arrays(mi355ndt_handle* h, int n_pairs) {
 }
 
 static int alloc_side(mi355ndt_handle* h, bool tgt, int n_pairs, size_t pitch) {
-  float*& buf = tgt ? h->d_tgt_own : h->d_src_own;
+  DevBuf<float>& buf = tgt ? h->d_tgt_own : h->d_src_own;
   size_t& own_pitch = tgt ? h->own_tgt_pitch : h->own_src_pitch;
   int& own_pairs = tgt ? h->own_tgt_pairs : h->own_src_pairs;
   if (buf && own_pitch == pitch && own_pairs == n_pairs) return MI355NDT_OK;
   for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (buf) { HIPCHK(h, hipFree(buf)); buf = nullptr; }
-  HIPCHK(h, hipMalloc((void**)&buf, (size_t)n_pairs * 3 * pitch * sizeof(float)));
+  HIPCHK(h, buf.realloc_exact((size_t)n_pairs * 3 * pitch));
   own_pitch = pitch; own_pairs = n_pairs;
   std::vector<int>& cnt = tgt ? h->h_tgt_cnt : h->h_src_cnt;
   std::fill(cnt.begin(), cnt.end(), 0);
@@ -628,16 +596,13 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
     std::this_thread::yield();                    // more uploader threads than slots
   }
   hipError_t e = hipSuccess;
-  if (!u->ev) e = hipEventCreateWithFlags(&u->ev, hipEventDisableTiming);
+  if (!u->ev) e = u->ev.create();
   if (e == hipSuccess && u->used) e = hipEventSynchronize(u->ev);      // the slot's previous transfer has to be out of the pinned buffer
-  if (e == hipSuccess && total > u->cap) {
-    if (u->h) { (void)hipHostFree(u->h); u->h = nullptr; }
-    if (u->d) { (void)hipFree(u->d); u->d = nullptr; }
-    u->cap = 0; u->used = false;
-    const size_t cap = std::max(total, (size_t)65536);
-    e = hipHostMalloc((void**)&u->h, cap * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&u->d, cap * 3 * sizeof(float));
-    if (e == hipSuccess) u->cap = cap;
+  if (e == hipSuccess && 3 * total > std::min(u->h.cap, u->d.cap)) {
+    u->used = false;
+    const size_t cap = 3 * std::max(total, (size_t)65536);
+    e = u->h.realloc_exact(cap);
+    if (e == hipSuccess) e = u->d.realloc_exact(cap);
   }
   if (e != hipSuccess) {
     std::lock_guard<std::mutex> lk(h->up_mtx);
@@ -829,7 +794,7 @@ static void ev_collect(mi355ndt_handle* h, std::vector<mi355ndt_handle::EvSpan>&
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   h->prof = on != 0;
-  if (h->stream_on) for (int c = 0; c < h->s_nctx; c++) if (h->sctx[c].e) { h->sctx[c].e->ev_pool_target = 128; (void)mi355ndt_profile_enable(h->sctx[c].e, on); }
+  if (h->ss) for (int c = 0; c < h->ss->nctx; c++) if (h->ss->ctx[c].e) { h->ss->ctx[c].e->ev_pool_target = 128; (void)mi355ndt_profile_enable(h->ss->ctx[c].e.get(), on); }
   if (h->prof) {
     HIPCHK(h, hipSetDevice(h->device));
     while (h->ev_pool.size() < h->ev_pool_target) { // ~40 profiled steps of a 10-round batch align before the pool has to grow
@@ -846,7 +811,7 @@ int mi355ndt_profile_reset(mi355ndt_handle* h) {
   (void)hipStreamSynchronize(h->stream);
   double d; long long n;
   ev_collect(h, h->ev_sweep, d, n); ev_collect(h, h->ev_update, d, n); ev_collect(h, h->ev_build, d, n);
-  if (h->stream_on) for (int c = 0; c < h->s_nctx; c++) if (mi355ndt_handle* e = h->sctx[c].e) {
+  if (h->ss) for (int c = 0; c < h->ss->nctx; c++) if (mi355ndt_handle* e = h->ss->ctx[c].e.get()) {
     ev_collect(e, e->ev_sweep, d, n); ev_collect(e, e->ev_update, d, n); ev_collect(e, e->ev_build, d, n);
     e->P = mi355ndt_profile{};
   }
@@ -863,7 +828,7 @@ int mi355ndt_profile_get(mi355ndt_handle* h, mi355ndt_profile* out) {
   ev_collect(h, h->ev_sweep, h->P.sweep_ms, h->P.sweep_launches);
   ev_collect(h, h->ev_update, h->P.update_ms, h->P.update_launches);
   ev_collect(h, h->ev_build, h->P.build_ms, h->P.build_launches);
-  if (h->stream_on) for (int c = 0; c < h->s_nctx; c++) if (mi355ndt_handle* e = h->sctx[c].e) {   // the contexts' builds (and synchronous re-runs) are this handle's work
+  if (h->ss) for (int c = 0; c < h->ss->nctx; c++) if (mi355ndt_handle* e = h->ss->ctx[c].e.get()) {   // the contexts' builds (and synchronous re-runs) are this handle's work
     ev_collect(e, e->ev_sweep, h->P.sweep_ms, h->P.sweep_launches);
     ev_collect(e, e->ev_update, h->P.update_ms, h->P.update_launches);
     ev_collect(e, e->ev_build, h->P.build_ms, h->P.build_launches);
@@ -875,7 +840,7 @@ int mi355ndt_profile_get(mi355ndt_handle* h, mi355ndt_profile* out) {
   unsigned long long hh[2] = {0, 0};              // (point, voxel) evaluations and score-only sweeps since the last reset, summed on the device
   HIPCHK(h, hipMemcpy(hh, h->d_hits, sizeof hh, hipMemcpyDeviceToHost));
   *out = h->P;
-  if (h->stream_on) { out->stream_reserved_slots = h->s_reserve_wg; out->stream_launch_slots = h->s_launch_slots; }
+  if (h->ss) { out->stream_reserved_slots = h->ss->reserve_wg; out->stream_launch_slots = h->ss->launch_slots; }
   out->sweep_hits += (long long)hh[0];
   out->sweep_alg_bytes += 64.0 * (double)hh[0];
   out->score_only_sweeps = (long long)hh[1];
@@ -909,27 +874,17 @@ static int build_targets_impl(mi355ndt_handle* h) {
   }
 
   // workspace
-  if (total > h->keys_cap) {
-    size_t c1 = h->keys_cap, c2 = h->keys_cap, c3 = h->keys_cap, c4 = h->keys_cap;
-    HIPCHK(h, grow(h->d_keys_a, c1, total)); HIPCHK(h, grow(h->d_keys_b, c2, total));
-    HIPCHK(h, grow(h->d_vals_a, c3, total)); HIPCHK(h, grow(h->d_vals_b, c4, total));
-    h->keys_cap = total;
-  }
+  HIPCHK(h, h->d_keys_a.reserve(total)); HIPCHK(h, h->d_keys_b.reserve(total));
+  HIPCHK(h, h->d_vals_a.reserve(total)); HIPCHK(h, h->d_vals_b.reserve(total));
   const int minpts = h->prm.min_points_per_voxel;
   const size_t rpp = pitch / (size_t)minpts + 1;
   if (rpp > ((size_t)1 << ID_BITS)) { h->err = "target too large: voxel ids would not fit the sweep's queue entries"; return MI355NDT_ERR_BAD_ARG; }
-  if ((size_t)B * rpp > h->recs_cap || rpp != h->recs_per_pair) {
-    size_t need = (size_t)B * rpp, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
-    if (h->d_recs) { HIPCHK(h, hipFree(h->d_recs)); h->d_recs = nullptr; }
-    if (h->d_vox_idx) { HIPCHK(h, hipFree(h->d_vox_idx)); h->d_vox_idx = nullptr; }
-    if (h->d_vox_n) { HIPCHK(h, hipFree(h->d_vox_n)); h->d_vox_n = nullptr; }
-    if (h->d_seg_start) { HIPCHK(h, hipFree(h->d_seg_start)); h->d_seg_start = nullptr; }
-    if (h->d_sums) { HIPCHK(h, hipFree(h->d_sums)); h->d_sums = nullptr; }
-    if (h->d_cent) { HIPCHK(h, hipFree(h->d_cent)); h->d_cent = nullptr; }
-    HIPCHK(h, grow(h->d_recs, c1, need)); HIPCHK(h, grow(h->d_vox_idx, c2, need)); HIPCHK(h, grow(h->d_vox_n, c3, need));
-    HIPCHK(h, grow(h->d_seg_start, c4, need)); HIPCHK(h, grow(h->d_sums, c5, need * 9));
-    { size_t c6 = 0; HIPCHK(h, grow(h->d_cent, c6, need * 3)); }
-    h->recs_cap = need; h->recs_per_pair = rpp;
+  if ((size_t)B * rpp > h->d_recs.cap || rpp != h->recs_per_pair) {
+    const size_t need = (size_t)B * rpp;
+    h->recs_per_pair = 0;                         // (until the whole group exists again: a failure half way is retried by the next build)
+    HIPCHK(h, h->d_recs.realloc_exact(need)); HIPCHK(h, h->d_vox_idx.realloc_exact(need)); HIPCHK(h, h->d_vox_n.realloc_exact(need));
+    HIPCHK(h, h->d_seg_start.realloc_exact(need)); HIPCHK(h, h->d_sums.realloc_exact(need * 9)); HIPCHK(h, h->d_cent.realloc_exact(need * 3));
+    h->recs_per_pair = rpp;
   }
   h->ev_last_fresh = false;
   const bool build_events = h->prof && !(h->build_stamped && h->async_build);   // (the stream's builds are stamped by the kernels around them)
@@ -942,7 +897,7 @@ static int build_targets_impl(mi355ndt_handle* h) {
   k_word_offsets<<<1, 1024, 0, s>>>(h->d_grid, h->d_nwords, B, h->d_word_off);   // d_word_off[0] = total words, [1] = largest grid
   size_t total_words;
   int cb;
-  const bool planned = h->async_build && h->plan_cb > 0 && h->plan_words > 0 && h->plan_words <= h->words_cap && h->d_bstat;
+  const bool planned = h->async_build && h->plan_cb > 0 && h->plan_words > 0 && h->plan_words <= h->d_words.cap && h->d_bstat;
   if (planned) {
     // no wait: the plan's key width and pool size, checked on the device (a batch that does not fit loses its grids and is flagged)
     k_build_check<<<(B + 255) / 256, 256, 0, s>>>(h->d_word_off, h->d_grid, h->d_nwords, B, (unsigned)std::min(h->plan_words, (size_t)0xFFFFFFFFu), h->plan_cb, h->d_bstat + 1);
@@ -957,41 +912,29 @@ static int build_targets_impl(mi355ndt_handle* h) {
     h->last_total_words = total_words;
     if (h->d_bstat) HIPCHK(h, hipMemsetAsync(h->d_bstat + 3, 0, sizeof(unsigned), s));
   }
-  if (total_words > h->words_cap) {
-    size_t c = h->words_cap;
-    HIPCHK(h, grow(h->d_words, c, std::max(total_words, (size_t)1024)));
-    h->words_cap = c;
-  }
+  if (total_words > h->d_words.cap) HIPCHK(h, h->d_words.reserve(std::max(total_words, (size_t)1024)));
   if (total_words) HIPCHK(h, hipMemsetAsync(h->d_words, 0, total_words * sizeof(BitWord), s));
   const bool mt_live = mt_is_live(h->prm);
   const bool want_cent = h->prm.neighbor_mode == MI355NDT_KDTREE || mt_live;   // f32 leaf centroids: KDTREE probe, computeHessian
   h->cent_built = want_cent;
   h->icov64_built = mt_live;
-  if (mt_live) HIPCHK(h, grow(h->d_icov64, h->icov64_cap, h->recs_cap * 9));
+  if (mt_live) HIPCHK(h, h->d_icov64.reserve(h->d_recs.cap * 9));
   // the tolerance arithmetic's records and tree leaf sums only where its sweeps are served (DIRECT1 / DIRECT7, dead More-Thuente loop): every other
   // configuration ignores the option altogether -- ordered sums, the exact records alone, results word for word those of the option off
   const bool want_fast_recs = fast_served(h);
-  if (want_fast_recs) HIPCHK(h, grow(h->d_recs_fast, h->recs_fast_cap, h->recs_cap));
+  if (want_fast_recs) HIPCHK(h, h->d_recs_fast.reserve(h->d_recs.cap));
   h->recs_fast_built = want_fast_recs;
   const bool want_kdw = h->prm.neighbor_mode == MI355NDT_KDTREE && h->prm.variant == MI355NDT_VARIANT_PCA;
   h->kdw_built = want_kdw;
-  if (want_kdw) HIPCHK(h, grow(h->d_kdw, h->kdw_cap, h->recs_cap));
+  if (want_kdw) HIPCHK(h, h->d_kdw.reserve(h->d_recs.cap));
   {
     unsigned *ka = h->d_keys_a, *kb = h->d_keys_b;
     // stable sort by cell inside every target's segment (ndt_segsort.hpp): rs_plan(cb) passes, result in kb / d_vals_b
     const RsPlan plan = rs_plan(cb);
     const int npass = plan.passes;
     const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
-    {
-      const size_t need = ((size_t)B * tiles) << RS_MAX_BITS;
-      if (need > h->rs_cap) {
-        size_t c1 = 0, c2 = 0;
-        if (h->d_rs_hist) { HIPCHK(h, hipFree(h->d_rs_hist)); h->d_rs_hist = nullptr; }
-        if (h->d_rs_offs) { HIPCHK(h, hipFree(h->d_rs_offs)); h->d_rs_offs = nullptr; }
-        HIPCHK(h, grow(h->d_rs_hist, c1, need)); HIPCHK(h, grow(h->d_rs_offs, c2, need));
-        h->rs_cap = need;
-      }
-    }
+    const size_t rs_need = ((size_t)B * tiles) << RS_MAX_BITS;
+    HIPCHK(h, h->d_rs_hist.reserve(rs_need)); HIPCHK(h, h->d_rs_offs.reserve(rs_need));
     unsigned *kin = (npass & 1) ? ka : kb, *kout = (npass & 1) ? kb : ka;      // an odd number of hops must end in kb
     unsigned *vin = (npass & 1) ? h->d_vals_a : h->d_vals_b, *vout = (npass & 1) ? h->d_vals_b : h->d_vals_a;
     // (no key kernel: the first pass's histogram computes the cell indices from the points and writes them, ndt_segsort.hpp)
@@ -1002,8 +945,8 @@ static int build_targets_impl(mi355ndt_handle* h) {
     }
     // k_mark leaves the leaves' run starts in per-wave slices; k_rank strings them together by voxel id (d_seg_start)
     const unsigned nsl = ls_slices(pitch), scap = ls_slice_cap(minpts);
-    HIPCHK(h, grow(h->d_heads, h->heads_cap, (size_t)B * nsl * scap));
-    HIPCHK(h, grow(h->d_head_cnt, h->head_cnt_cap, (size_t)B * nsl));
+    HIPCHK(h, h->d_heads.reserve((size_t)B * nsl * scap));
+    HIPCHK(h, h->d_head_cnt.reserve((size_t)B * nsl));
     k_mark<unsigned><<<dim3((nsl + 3) / 4, B), 256, 0, s>>>(kb, pitch, h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, minpts, cb);
     k_rank<<<B, 1024, 0, s>>>(h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, h->d_seg_start);
     // leaf-sum workgroups per target: 64 keeps ~4 targets (3 MB of points) in flight per XCD, inside its 4 MB L2
@@ -1012,10 +955,10 @@ static int build_targets_impl(mi355ndt_handle* h) {
       k_leafsum_tree<<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, h->d_vals_b, h->d_grid, h->d_seg_start, h->d_sums, h->d_vox_idx, h->d_vox_n, cb, lb, B);
     } else if (h->leaf_sorted) {
       // the sorted order as 16-byte points first (one streaming gather), then leaf sums that read them contiguously
-      HIPCHK(h, grow(h->d_sorted, h->sorted_cap, total));
+      HIPCHK(h, h->d_sorted.reserve(total));
       const int gb = std::max(1, std::min((int)((pitch + 256 * RUN_ILP - 1) / (256 * RUN_ILP)), 64));
       k_sorted_points<<<xcd_grid(gb, B), 256, 0, s>>>(h->d_tgt, pitch, h->d_vals_b, h->d_sorted, gb, B);
-      const unsigned* sp = reinterpret_cast<const unsigned*>(h->d_sorted);
+      const unsigned* sp = reinterpret_cast<const unsigned*>(h->d_sorted.p);
       if (want_cent) k_leafsum<unsigned, true, true><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, sp, h->d_grid, h->d_seg_start,
                                                                                             h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
       else k_leafsum<unsigned, false, true><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, sp, h->d_grid, h->d_seg_start,
@@ -1069,7 +1012,7 @@ static int prep_align_ws(mi355ndt_handle* h) {
     h->pts_per_chunk = CHUNK_PTS;
   }
   size_t need = (size_t)B * std::max(h->rows_per_pair, h->chunks_per_pair * QUARTERS) * NACC;   // (the parity hooks may fall back to batch-mode rows)
-  HIPCHK(h, grow(h->d_partials, h->partials_cap, need));
+  HIPCHK(h, h->d_partials.reserve(need));
   if (h->up_src_cnt.size() != (size_t)B || !std::equal(h->up_src_cnt.begin(), h->up_src_cnt.end(), h->h_src_cnt.begin())) {
     HIPCHK(h, hipMemcpyAsync(h->d_src_cnt, h->h_src_cnt.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1103,11 +1046,11 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
 static bool want_fast(const mi355ndt_handle* h, const SweepConst& sc) { (void)sc; return fast_served(h); }
 static int sweep_ord(const mi355ndt_handle* h, const SweepConst& sc) {
   // (a stream's parent handle owns no grids: its contexts' engines build them, with the option as it stood at mi355ndt_stream_begin)
-  if (want_fast(h, sc) && (h->recs_fast_built || h->stream_on)) return 2;
+  if (want_fast(h, sc) && (h->recs_fast_built || h->ss)) return 2;
   return h->f32_sum_order;
 }
 static const VoxelRec* sweep_recs(const mi355ndt_handle* h, const SweepConst& sc) {
-  return sweep_ord(h, sc) == 2 ? reinterpret_cast<const VoxelRec*>(h->d_recs_fast) : h->d_recs;
+  return sweep_ord(h, sc) == 2 ? reinterpret_cast<const VoxelRec*>(h->d_recs_fast.p) : h->d_recs;
 }
 
 static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs = -1) {
@@ -1183,9 +1126,9 @@ int mi355ndt_batch_align(mi355ndt_handle* h, const float* guesses, mi355ndt_resu
   return rc;
 }
 static int ensure_seq_flags(mi355ndt_handle* h) {
-  if (!h->h_seq_flags) {
-    HIPCHK(h, hipHostMalloc((void**)&h->h_seq_flags, 64, hipHostMallocMapped | hipHostMallocCoherent));   // fine-grained: device writes are visible to the polling host
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->d_seq_flags, (void*)h->h_seq_flags, 0));
+  if (!h->d_seq_flags) {
+    HIPCHK(h, h->h_seq_flags.reserve(16, hipHostMallocMapped | hipHostMallocCoherent));   // fine-grained: device writes are visible to the polling host
+    if (!(h->d_seq_flags = h->h_seq_flags.dev())) { h->err = "hipHostGetDevicePointer failed"; return MI355NDT_ERR_HIP; }
   }
   return MI355NDT_OK;
 }
@@ -1314,11 +1257,11 @@ static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt
   const int ring_cap = async_ring_cap(h, B);
   if (ring_cap == 0) return MI355NDT_ERR_UNSUPPORTED;
   // (a ring that cannot be allocated is no error of the align: the round-based path needs none)
-  if (grow(h->d_ring, h->ring_cap_total, (size_t)8 * ring_cap) != hipSuccess) { (void)hipGetLastError(); return MI355NDT_ERR_UNSUPPORTED; }
-  HIPCHK(h, grow(h->d_arrived, h->arrived_cap, (size_t)B * ASYNC_ARR_STRIDE));
-  if (!h->d_actl) HIPCHK(h, hipMalloc((void**)&h->d_actl, sizeof(AsyncCtl)));
-  if (!h->d_atab) HIPCHK(h, hipMalloc((void**)&h->d_atab, sizeof(AsyncTab)));
-  if (!h->h_pin_actl) HIPCHK(h, hipHostMalloc((void**)&h->h_pin_actl, sizeof(AsyncCtl)));
+  if (h->d_ring.reserve((size_t)8 * ring_cap) != hipSuccess) { (void)hipGetLastError(); return MI355NDT_ERR_UNSUPPORTED; }
+  HIPCHK(h, h->d_arrived.reserve((size_t)B * ASYNC_ARR_STRIDE));
+  HIPCHK(h, h->d_actl.reserve(1));
+  HIPCHK(h, h->d_atab.reserve(1));
+  HIPCHK(h, h->h_pin_actl.reserve(1));
   // everything the launch polls is reset on the stream before it (never inside the kernel, never by a previous launch), together with
   // the pairs' initial states
   AsyncLaunch L;
@@ -1335,7 +1278,7 @@ static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt
   HIPCHK(h, hipMemcpyAsync(out, h->d_results, (size_t)B * sizeof(mi355ndt_result), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
-  if (h->h_pin_actl->abort_ || h->h_pin_actl->fin != (unsigned)B) {
+  if (h->h_pin_actl.p->abort_ || h->h_pin_actl.p->fin != (unsigned)B) {
     // a wave gave up (its ticket never came within the poll budget: a device shared with something that starves the launch, or the
     // test hook): nothing is lost -- the round-based path below produces the same bits from the same guesses
     h->P.async_fallbacks++;
@@ -1571,12 +1514,8 @@ int mi355ndt_get_aligned(mi355ndt_handle* h, void* out_pts, size_t stride) {
   { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
   const int n = h->h_src_cnt[0];
   if (n == 0) return MI355NDT_OK;
-  HIPCHK(h, grow(h->d_aligned, h->aligned_cap, (size_t)3 * n));
-  if ((size_t)3 * n > h->pin_aligned_cap) {
-    if (h->h_pin_aligned) { HIPCHK(h, hipHostFree(h->h_pin_aligned)); h->h_pin_aligned = nullptr; h->pin_aligned_cap = 0; }
-    HIPCHK(h, hipHostMalloc((void**)&h->h_pin_aligned, (size_t)3 * n * sizeof(float)));
-    h->pin_aligned_cap = (size_t)3 * n;
-  }
+  HIPCHK(h, h->d_aligned.reserve((size_t)3 * n));
+  HIPCHK(h, h->h_pin_aligned.reserve((size_t)3 * n));
   // moved cloud as packed x,y,z triples -> pinned memory -> x,y,z of the caller's records (their other fields are left alone)
   k_transform<<<(n + 255) / 256, 256, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, 0, h->d_aligned, n);
   HIPCHK(h, hipMemcpyAsync(h->h_pin_aligned, h->d_aligned, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1637,7 +1576,7 @@ int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, d
   if (!p) return MI355NDT_ERR_BAD_ARG;
   int rc = hook_ready(h);
   if (rc) return rc;
-  double* dp = (double*)h->d_hook;
+  double* dp = (double*)h->d_hook.p;
   HIPCHK(h, hipMemcpyAsync(dp, p, 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
@@ -1659,7 +1598,7 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
     if (rc) return rc;
   }
   h->fine_it = 0; h->rows_per_pair = h->items_per_pair = h->chunks_per_pair * QUARTERS; h->pts_per_chunk = CHUNK_PTS;   // k_hessian writes batch-mode rows
-  double* dp = (double*)h->d_hook;
+  double* dp = (double*)h->d_hook.p;
   HIPCHK(h, hipMemcpyAsync(dp, p, 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
@@ -1753,13 +1692,7 @@ int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], dou
   const bool brute = g.status != GRID_OK;        // no voxel grid (leaf-too-small guard / cell cap): the score does not need one
   if (!brute && !h->cells_ready) {
     const size_t nc = (size_t)g.ncells;
-    if (nc > h->cell_cap) {
-      size_t c1 = 0, c2 = 0;
-      if (h->d_cstart) { HIPCHK(h, hipFree(h->d_cstart)); h->d_cstart = nullptr; }
-      if (h->d_cend) { HIPCHK(h, hipFree(h->d_cend)); h->d_cend = nullptr; }
-      HIPCHK(h, grow(h->d_cstart, c1, nc)); HIPCHK(h, grow(h->d_cend, c2, nc));
-      h->cell_cap = nc;
-    }
+    HIPCHK(h, h->d_cstart.reserve(nc)); HIPCHK(h, h->d_cend.reserve(nc));
     HIPCHK(h, hipMemsetAsync(h->d_cstart, 0, nc * sizeof(unsigned), s));
     HIPCHK(h, hipMemsetAsync(h->d_cend, 0, nc * sizeof(unsigned), s));
     k_cellrange<unsigned><<<(unsigned)((h->tgt_pitch + 255) / 256), 256, 0, s>>>(h->d_keys_b, h->tgt_pitch, h->last_cb,
@@ -1768,7 +1701,7 @@ int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], dou
   }
   const int n = h->h_src_cnt[0];
   const int blocks = (n + 255) / 256;
-  HIPCHK(h, grow(h->d_fit, h->fit_cap, (size_t)2 * blocks));
+  HIPCHK(h, h->d_fit.reserve((size_t)2 * blocks));
   HIPCHK(h, hipMemcpyAsync(h->d_hook, T_colmajor, 16 * sizeof(float), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));
   const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
@@ -1836,8 +1769,8 @@ int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, d
     n_part += nblk[b];
   }
   if (any_ok && !h->fit_index_ready) {
-    HIPCHK(h, grow(h->d_fwords, h->fwords_cap, total_words));
-    HIPCHK(h, grow(h->d_fruns, h->fruns_cap, (size_t)B * (tp + 1)));
+    HIPCHK(h, h->d_fwords.reserve(total_words));
+    HIPCHK(h, h->d_fruns.reserve((size_t)B * (tp + 1)));
     HIPCHK(h, hipMemsetAsync(h->d_fwords, 0, total_words * sizeof(BitWord), s));
     const dim3 pg((unsigned)((tp + 255) / 256), (unsigned)B);
     k_fit_mark<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->last_cb);
@@ -1886,21 +1819,21 @@ int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, d
   if (n_part > 0) {
     static_assert(sizeof(mi355ndt_result) % sizeof(float) == 0 && offsetof(mi355ndt_result, final_colmajor) == 0, "final pose at the head of a result");
     if (T_colmajor) {
-      HIPCHK(h, grow(h->d_fit_T, h->fit_T_cap, (size_t)B * 16));
+      HIPCHK(h, h->d_fit_T.reserve((size_t)B * 16));
       HIPCHK(h, hipMemcpyAsync(h->d_fit_T, T_colmajor, (size_t)B * 16 * sizeof(float), hipMemcpyHostToDevice, s));
       dT = h->d_fit_T;
     } else if (h->aligned_once) {
-      dT = reinterpret_cast<const float*>(h->d_results);
+      dT = reinterpret_cast<const float*>(h->d_results.p);
       Tstride = (int)(sizeof(mi355ndt_result) / sizeof(float));
     } else {
-      HIPCHK(h, grow(h->d_fit_T, h->fit_T_cap, (size_t)16));
+      HIPCHK(h, h->d_fit_T.reserve(16));
       HIPCHK(h, hipMemcpyAsync(h->d_fit_T, ident, sizeof ident, hipMemcpyHostToDevice, s));
       dT = h->d_fit_T;
       Tstride = 0;
     }
-    HIPCHK(h, grow(h->d_fit_items, h->fit_items_cap, tab.size()));
+    HIPCHK(h, h->d_fit_items.reserve(tab.size()));
     HIPCHK(h, hipMemcpyAsync(h->d_fit_items, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(h, grow(h->d_fit, h->fit_cap, (size_t)2 * n_part));
+    HIPCHK(h, h->d_fit.reserve((size_t)2 * n_part));
     static_assert(sizeof(FitItem) == 6 * sizeof(int), "FitItem is six ints");
     const int* t_ok = h->d_fit_items;
     const int* t_brute = h->d_fit_items + brute_at;
@@ -1939,9 +1872,9 @@ int mi355ndt_calculate_score(mi355ndt_handle* h, const void* pts, size_t n, size
     if (rc) return rc;
   }
   const size_t pitch = (n + 63) & ~(size_t)63;
-  HIPCHK(h, grow(h->d_score_pts, h->score_pts_cap, 3 * pitch));
+  HIPCHK(h, h->d_score_pts.reserve(3 * pitch));
   const int blocks = (int)((n + SCORE_THREADS - 1) / SCORE_THREADS);
-  HIPCHK(h, grow(h->d_score_part, h->score_part_cap, (size_t)blocks));
+  HIPCHK(h, h->d_score_part.reserve((size_t)blocks));
   int rc = upload_cloud(h, h->d_score_pts, pitch, 0, pts, n, stride);
   if (rc) return rc;
   rc = uploads_before_compute(h);
@@ -1999,7 +1932,7 @@ int mi355ndt_convert_transform(const double x[6], float out[16]) {
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
-  if (h->stream_on && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
+  if (h->ss && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
                        option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP)) NOT_IN_STREAM(h);
   if (option == MI355NDT_OPT_F32_SUM_ORDER) {
     if (value != 0 && value != 1) return MI355NDT_ERR_BAD_ARG;
@@ -2070,16 +2003,10 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t pitch = (n + 63) & ~(size_t)63;
-  if (pitch > h->pf_cap) {
-    HIPCHK(h, hipStreamSynchronize(s));
-    void** ps[] = {(void**)&h->d_pf_in, (void**)&h->d_pf_out, (void**)&h->d_pf_keep, (void**)&h->d_pf_keys, (void**)&h->d_pf_vals,
-                   (void**)&h->d_pf_flag, (void**)&h->d_pf_pos};
-    const size_t bytes[] = {3 * pitch * 4, 3 * pitch * 4, pitch, 2 * pitch * 4, 2 * pitch * 4, pitch * 4, pitch * 4};
-    for (int i = 0; i < 7; i++) { if (*ps[i]) { HIPCHK(h, hipFree(*ps[i])); *ps[i] = nullptr; } HIPCHK(h, hipMalloc(ps[i], bytes[i])); }
-    if (!h->d_pf_mm) HIPCHK(h, hipMalloc((void**)&h->d_pf_mm, 6 * sizeof(int)));
-    if (!h->d_pf_grid) HIPCHK(h, hipMalloc((void**)&h->d_pf_grid, sizeof(PfGrid)));
-    h->pf_cap = pitch;
-  }
+  if (pitch > h->d_pf_pos.cap) HIPCHK(h, hipStreamSynchronize(s));   // (d_pf_pos grows last: the workspace is re-allocated, nothing may still read it)
+  HIPCHK(h, h->d_pf_in.reserve(3 * pitch)); HIPCHK(h, h->d_pf_out.reserve(3 * pitch)); HIPCHK(h, h->d_pf_keep.reserve(pitch));
+  HIPCHK(h, h->d_pf_keys.reserve(2 * pitch)); HIPCHK(h, h->d_pf_vals.reserve(2 * pitch)); HIPCHK(h, h->d_pf_flag.reserve(pitch)); HIPCHK(h, h->d_pf_pos.reserve(pitch));
+  HIPCHK(h, h->d_pf_mm.reserve(6)); HIPCHK(h, h->d_pf_grid.reserve(1));
   h->pf_pitch = pitch;
   int rc = upload_cloud(h, h->d_pf_in, pitch, 0, pts, n, stride);
   if (rc) return rc;
@@ -2090,22 +2017,8 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
   // workspace of the segment sort (one segment = the whole cloud) and of the emit-position scan
   const int pf_tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
   const int pf_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
-  {
-    const size_t need = (size_t)pf_tiles << RS_MAX_BITS;
-    if (need > h->rs_cap) {
-      size_t c1 = 0, c2 = 0;
-      if (h->d_rs_hist) { HIPCHK(h, hipFree(h->d_rs_hist)); h->d_rs_hist = nullptr; }
-      if (h->d_rs_offs) { HIPCHK(h, hipFree(h->d_rs_offs)); h->d_rs_offs = nullptr; }
-      HIPCHK(h, grow(h->d_rs_hist, c1, need)); HIPCHK(h, grow(h->d_rs_offs, c2, need));
-      h->rs_cap = need;
-    }
-    const size_t nb = (size_t)pf_chunks * sizeof(unsigned);
-    if (nb > h->pf_tmp_bytes) {
-      if (h->d_pf_tmp) { HIPCHK(h, hipFree(h->d_pf_tmp)); h->d_pf_tmp = nullptr; }
-      HIPCHK(h, hipMalloc(&h->d_pf_tmp, nb));
-      h->pf_tmp_bytes = nb;
-    }
-  }
+  HIPCHK(h, h->d_rs_hist.reserve((size_t)pf_tiles << RS_MAX_BITS)); HIPCHK(h, h->d_rs_offs.reserve((size_t)pf_tiles << RS_MAX_BITS));
+  HIPCHK(h, h->d_pf_tmp.reserve((size_t)pf_chunks));
   k_minmax_init<<<1, 64, 0, s>>>(h->d_pf_mm, 1);
   k_pf_flag<<<std::min(gx, 256), 256, 0, s>>>(h->d_pf_in, pitch, (int)n, use_distance_filter, distance_near, distance_far, h->d_pf_keep, h->d_pf_mm);
   int downsample = downsample_resolution > 0.f;
@@ -2132,9 +2045,9 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
     }
   }
   k_pf_heads<<<gx, 256, 0, s>>>(keys_sorted, h->d_pf_keep, (int)n, pitch, downsample, h->d_pf_flag);
-  k_pf_scan_totals<<<pf_chunks, 1024, 0, s>>>(h->d_pf_flag, pitch, (unsigned*)h->d_pf_tmp);
-  k_pf_scan_offsets<<<1, 1024, 0, s>>>((unsigned*)h->d_pf_tmp, pf_chunks);
-  k_pf_scan_apply<<<pf_chunks, 1024, 0, s>>>(h->d_pf_flag, pitch, (const unsigned*)h->d_pf_tmp, h->d_pf_pos);
+  k_pf_scan_totals<<<pf_chunks, 1024, 0, s>>>(h->d_pf_flag, pitch, h->d_pf_tmp);
+  k_pf_scan_offsets<<<1, 1024, 0, s>>>(h->d_pf_tmp, pf_chunks);
+  k_pf_scan_apply<<<pf_chunks, 1024, 0, s>>>(h->d_pf_flag, pitch, h->d_pf_tmp, h->d_pf_pos);
   k_pf_emit<<<gx, 256, 0, s>>>(h->d_pf_in, pitch, keys_sorted, vals_sorted, h->d_pf_flag, h->d_pf_pos, downsample, h->d_pf_out, pitch);
   int last_pos = 0, last_flag = 0;
   HIPCHK(h, hipMemcpyAsync(&last_pos, h->d_pf_pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2212,73 +2125,50 @@ static bool stream_async_ok(const mi355ndt_handle* h) {
   const bool pca_kd = h->prm.neighbor_mode == MI355NDT_KDTREE && h->prm.variant == MI355NDT_VARIANT_PCA;
   return h->async_align && !mt_is_live(h->prm) && !pca_kd;
 }
-static int stream_free(mi355ndt_handle* h) {
-  for (auto& c : h->sctx) {
-    if (c.e) {
-      if (c.d_in) { c.e->d_tgt_cnt = (int*)c.own_tgt_cnt; c.e->d_src_cnt = (int*)c.own_src_cnt; c.e->d_guess = (float*)c.own_guess; }
-      c.e->d_bstat = nullptr;
-      (void)mi355ndt_destroy(c.e);
-    }
-    if (c.d_in) (void)hipFree(c.d_in);
-    if (c.h_in) (void)hipHostFree(c.h_in);
-    if (c.h_res) (void)hipHostFree(c.h_res);
-    c = mi355ndt_handle::StreamCtx();
-  }
-  for (auto& e : h->s_ev_built) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  for (auto& e : h->s_ev_launched) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  for (auto& e : h->s_ev_prepared) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (h->s_build_stream) { (void)hipStreamSynchronize(h->s_build_stream); (void)hipStreamDestroy(h->s_build_stream); h->s_build_stream = nullptr; }
-  if (h->d_sctl) { (void)hipFree(h->d_sctl); h->d_sctl = nullptr; }
-  if (h->d_sring) { (void)hipFree(h->d_sring); h->d_sring = nullptr; }
-  if (h->d_sstat) { (void)hipFree(h->d_sstat); h->d_sstat = nullptr; }
-  if (h->h_sstatus) { (void)hipHostFree((void*)h->h_sstatus); h->h_sstatus = nullptr; h->d_sstatus = nullptr; }
-  h->stream_on = false; h->s_nctx = 0;
-  return MI355NDT_OK;
-}
-
 int mi355ndt_stream_end(mi355ndt_handle* h) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if (!h->stream_on) return MI355NDT_OK;
+  if (!h->ss) return MI355NDT_OK;
   (void)hipSetDevice(h->device);
-  if (h->s_build_stream) (void)hipStreamSynchronize(h->s_build_stream);
+  if (h->ss->build_stream) (void)hipStreamSynchronize(h->ss->build_stream);
   (void)hipStreamSynchronize(h->stream);
   // the contexts' build timings and byte counts belong to this handle's profile
-  for (int c = 0; c < h->s_nctx; c++) {
-    mi355ndt_handle* e = h->sctx[c].e;
+  for (int c = 0; c < h->ss->nctx; c++) {
+    mi355ndt_handle* e = h->ss->ctx[c].e.get();
     if (!e) continue;
     ev_collect(e, e->ev_sweep, h->P.sweep_ms, h->P.sweep_launches);
     ev_collect(e, e->ev_update, h->P.update_ms, h->P.update_launches);
     ev_collect(e, e->ev_build, h->P.build_ms, h->P.build_launches);
     h->P.build_alg_bytes += e->P.build_alg_bytes; e->P.build_alg_bytes = 0;
   }
-  return stream_free(h);
+  h->ss.reset();                                  // (the contexts' engines, the session's buffers, events and build stream, a pending pose-record request)
+  return MI355NDT_OK;
 }
 
 int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, size_t max_tgt, size_t max_src) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (n_contexts < 2 || n_contexts > ASYNC_MAX_CTX || max_pairs < 1 || max_pairs > MAX_PAIRS || max_pairs >= (1 << ASYNC_CTX_SHIFT) ||
       max_tgt == 0 || max_src == 0 || max_tgt >= (1u << 31) || max_src >= (1u << 31)) return MI355NDT_ERR_BAD_ARG;
-  if (h->stream_on) return MI355NDT_ERR_STATE;
+  if (h->ss) return MI355NDT_ERR_STATE;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->s_nctx = n_contexts; h->s_max_pairs = max_pairs; h->s_max_tgt = max_tgt; h->s_max_src = max_src;
-  h->s_items = std::max(1, (int)((max_src + CHUNK_PTS - 1) / CHUNK_PTS)) * QUARTERS;
-  h->s_sync_only = !stream_async_ok(h);
-  h->s_next_id = 0; h->s_launches = 0; h->s_counted = 0; h->s_drop_carry = true; h->s_recovered_upto = -1;
-  h->s_plan_cb = 0; h->s_plan_words = 0;
+  std::unique_ptr<StreamState> session(new StreamState());   // (a failure below releases whatever was created before it)
+  StreamState& ss = *session;
+  ss.nctx = n_contexts; ss.max_pairs = max_pairs; ss.max_tgt = max_tgt; ss.max_src = max_src;
+  ss.items = std::max(1, (int)((max_src + CHUNK_PTS - 1) / CHUNK_PTS)) * QUARTERS;
+  ss.sync_only = !stream_async_ok(h);
   // the grids a streamed launch reads are the contexts' (built at prm.resolution); whatever single-registration grid the parent still holds
   // -- possibly one a setResolution without a source left at another leaf size (ndt_omp.h:126-136) -- is no part of the stream
   h->targets_built = false; h->grid_resolution = 0.f; h->recs_fast_built = false;
   SweepConst sc;
   make_sweep_const(h, sc);
   {
-    const int iu = h->s_items / (sc.K == 1 ? ((want_fast(h, sc) && FAST_D1_POINT) ? FAST_CLAIM1 : 2) : sc.K == 7 ? 2 : 1);   // positions per ticket (stream_launch: two DIRECT7 items per claim when pairs are handed over)
+    const int iu = ss.items / (sc.K == 1 ? ((want_fast(h, sc) && FAST_D1_POINT) ? FAST_CLAIM1 : 2) : sc.K == 7 ? 2 : 1);   // positions per ticket (stream_launch: two DIRECT7 items per claim when pairs are handed over)
     const int waves = h->n_cu * sweep_wpe(sc.pca != 0, sc.K, want_fast(h, sc)) * WAVES;
     // automatic: four sweeps' worth of positions per resident wave -- `tools/gpu_job.sh thresh_sweep`: config 5 gains up to T = 32-64 (DIRECT7 19.1 / 19.4 / 19.5 k,
     // DIRECT1 39.4 / 40.1 / 40.9 / 41.1 k registrations/s at T = 8 / 16 / 32 / 64), the 65,536-point configurations do not care -- capped at a quarter of the batch (stream_launch)
     int t = h->s_thresh_opt >= 0 ? h->s_thresh_opt : 4 * ((waves + iu - 1) / std::max(1, iu));
     if (const char* e = std::getenv("MI355NDT_STREAM_THRESH")) t = std::atoi(e);
-    h->s_thresh = std::max(0, std::min(t, ASYNC_MAX_CARRY));
+    ss.thresh = std::max(0, std::min(t, ASYNC_MAX_CARRY));
   }
   {
     // MI355NDT_STREAM_RESERVE (workgroups, rounded to a multiple of 8; 0 = the build runs between the launches, on the same stream).  Defaults
@@ -2303,57 +2193,56 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
     if (h->s_reserve_opt >= 0) r = h->s_reserve_opt;
     r = std::max(0, std::min(r, h->n_cu * sweep_wpe(sc.pca != 0, sc.K, want_fast(h, sc)) / 2)) & ~7;
     if (n_contexts < 3) r = 0;                       // (the overlapped build needs its context free one launch earlier: at least three contexts)
-    h->s_reserve_wg = r;
-    h->s_launch_slots = std::max(8, h->n_cu * sweep_wpe(sc.pca != 0, sc.K, want_fast(h, sc)) - r);
+    ss.reserve_wg = r;
+    ss.launch_slots = std::max(8, h->n_cu * sweep_wpe(sc.pca != 0, sc.K, want_fast(h, sc)) - r);
   }
-  h->s_ring_cap = async_ring_cap(h, (long long)max_pairs + ASYNC_MAX_CARRY);
-  if (h->s_ring_cap == 0) h->s_sync_only = true;
-  auto fail = [&](int rc) { (void)stream_free(h); return rc; };
-  if (hipMalloc((void**)&h->d_sstat, ASYNC_MAX_CTX * sizeof(CtxStat)) != hipSuccess ||
-      hipMemsetAsync(h->d_sstat, 0, ASYNC_MAX_CTX * sizeof(CtxStat), h->stream) != hipSuccess) return fail(MI355NDT_ERR_HIP);
+  ss.ring_cap = async_ring_cap(h, (long long)max_pairs + ASYNC_MAX_CARRY);
+  if (ss.ring_cap == 0) ss.sync_only = true;
+  if (ss.d_stat.realloc_exact(ASYNC_MAX_CTX) != hipSuccess ||
+      hipMemsetAsync(ss.d_stat, 0, ASYNC_MAX_CTX * sizeof(CtxStat), h->stream) != hipSuccess) return MI355NDT_ERR_HIP;
   for (int c = 0; c < n_contexts; c++) {
-    mi355ndt_handle::StreamCtx& S = h->sctx[c];
-    int rc = mi355ndt_create(&h->prm, h->device, &S.e);
-    if (rc) return fail(rc);
-    mi355ndt_handle* e = S.e;
-    if (h->s_reserve_wg > 0 && !h->s_build_stream) {
-      if (hipStreamCreateWithFlags(&h->s_build_stream, hipStreamNonBlocking) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-      for (auto& ev : h->s_ev_built) if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-      for (auto& ev : h->s_ev_launched) if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-      for (auto& ev : h->s_ev_prepared) if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-      if (const char* pf = std::getenv("MI355NDT_STREAM_PREP_FIRST")) h->s_prep_first = std::atoi(pf) != 0;
+    StreamCtx& S = ss.ctx[c];
+    mi355ndt_handle* e = nullptr;
+    int rc = mi355ndt_create(&h->prm, h->device, &e);
+    S.e.reset(e);
+    if (rc) return rc;
+    if (ss.reserve_wg > 0 && !ss.build_stream) {
+      if (ss.build_stream.create() != hipSuccess) return MI355NDT_ERR_HIP;
+      for (auto& ev : ss.ev_built) if (ev.create() != hipSuccess) return MI355NDT_ERR_HIP;
+      for (auto& ev : ss.ev_launched) if (ev.create() != hipSuccess) return MI355NDT_ERR_HIP;
+      for (auto& ev : ss.ev_prepared) if (ev.create() != hipSuccess) return MI355NDT_ERR_HIP;
+      if (const char* pf = std::getenv("MI355NDT_STREAM_PREP_FIRST")) ss.prep_first = std::atoi(pf) != 0;
     }
-    rc = mi355ndt_set_stream(e, h->s_reserve_wg > 0 ? h->s_build_stream : h->stream);
-    if (rc) return fail(rc);
+    rc = mi355ndt_set_stream(e, ss.reserve_wg > 0 ? ss.build_stream : h->stream);
+    if (rc) return rc;
     e->f32_sum_order = h->f32_sum_order; e->arith = h->arith; e->async_align = h->async_align; e->dyn_shift = h->dyn_shift; e->score_only_last = h->score_only_last;
     e->async_build = true;
     e->ev_pool_target = 128;
     rc = ensure_pair_arrays(e, max_pairs);          // every per-pair array at its final size: no allocation, no wait inside submit
-    if (rc) { h->err = e->err; return fail(rc); }
+    if (rc) { h->err = e->err; return rc; }
     // the input block: [target counts | source counts | guesses]
-    S.in_bytes = (size_t)max_pairs * (2 * sizeof(int) + 16 * sizeof(float));
-    if (hipMalloc((void**)&S.d_in, S.in_bytes) != hipSuccess || hipHostMalloc((void**)&S.h_in, S.in_bytes, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&S.h_in_dev, S.h_in, 0) != hipSuccess ||
-        hipHostMalloc((void**)&S.h_res, (size_t)max_pairs * sizeof(mi355ndt_result), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&S.d_res_map, S.h_res, 0) != hipSuccess) { h->err = "stream_begin: allocation failed"; return fail(MI355NDT_ERR_HIP); }
-    S.own_tgt_cnt = e->d_tgt_cnt; S.own_src_cnt = e->d_src_cnt; S.own_guess = e->d_guess;
+    static_assert(sizeof(float) == sizeof(int), "the input block holds ints and floats");
+    const size_t in_words = (size_t)max_pairs * (2 + 16);
+    if (S.d_in.realloc_exact(in_words) != hipSuccess || S.h_in.realloc_exact(in_words, hipHostMallocMapped) != hipSuccess ||
+        !(S.h_in_dev = (unsigned*)S.h_in.dev()) ||
+        S.h_res.realloc_exact(max_pairs, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        !(S.d_res_map = S.h_res.dev())) { h->err = "stream_begin: allocation failed"; return MI355NDT_ERR_HIP; }
     e->d_tgt_cnt = S.d_in; e->d_src_cnt = S.d_in + max_pairs; e->d_guess = (float*)(S.d_in + 2 * (size_t)max_pairs);
-    e->d_bstat = reinterpret_cast<unsigned*>(h->d_sstat + c);
-    size_t need = (size_t)max_pairs * h->s_items * NACC;
-    if (grow(e->d_partials, e->partials_cap, need) != hipSuccess || grow(e->d_arrived, e->arrived_cap, (size_t)max_pairs * ASYNC_ARR_STRIDE) != hipSuccess)
-      { h->err = "stream_begin: allocation failed"; return fail(MI355NDT_ERR_HIP); }
+    e->d_bstat = reinterpret_cast<unsigned*>(ss.d_stat + c);
+    size_t need = (size_t)max_pairs * ss.items * NACC;
+    if (e->d_partials.reserve(need) != hipSuccess || e->d_arrived.reserve((size_t)max_pairs * ASYNC_ARR_STRIDE) != hipSuccess)
+      { h->err = "stream_begin: allocation failed"; return MI355NDT_ERR_HIP; }
     if (h->prof) (void)mi355ndt_profile_enable(e, 1);
   }
-  if (hipMalloc((void**)&h->d_sctl, 2 * sizeof(AsyncCtl)) != hipSuccess || hipMemsetAsync(h->d_sctl, 0, 2 * sizeof(AsyncCtl), h->stream) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_sstatus, mi355ndt_handle::S_EV * sizeof(StreamStatus), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->d_sstatus, (void*)h->h_sstatus, 0) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-  memset((void*)h->h_sstatus, 0, mi355ndt_handle::S_EV * sizeof(StreamStatus));
-  if (!h->d_atab && hipMalloc((void**)&h->d_atab, sizeof(AsyncTab)) != hipSuccess) return fail(MI355NDT_ERR_HIP);
-  if (!h->s_sync_only && hipMalloc((void**)&h->d_sring, (size_t)8 * h->s_ring_cap * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->s_sync_only = true; }
-  if (h->s_build_stream) HIPCHK(h, hipStreamSynchronize(h->s_build_stream));
+  if (ss.d_ctl.realloc_exact(2) != hipSuccess || hipMemsetAsync(ss.d_ctl, 0, 2 * sizeof(AsyncCtl), h->stream) != hipSuccess ||
+      ss.h_status.realloc_exact(StreamState::EV, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+      !(ss.d_status = ss.h_status.dev())) return MI355NDT_ERR_HIP;
+  memset((void*)ss.h_status.p, 0, StreamState::EV * sizeof(StreamStatus));
+  if (h->d_atab.reserve(1) != hipSuccess) return MI355NDT_ERR_HIP;
+  if (!ss.sync_only && ss.d_ring.realloc_exact((size_t)8 * ss.ring_cap) != hipSuccess) { (void)hipGetLastError(); ss.sync_only = true; }
+  if (ss.build_stream) HIPCHK(h, hipStreamSynchronize(ss.build_stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  (void)max_tgt;
-  h->stream_on = true;
+  h->ss = std::move(session);
   return MI355NDT_OK;
 }
 
@@ -2366,59 +2255,59 @@ static int stream_launch(mi355ndt_handle* h, int new_ci, int n_new) {
   AsyncLaunch L;
   memset(&L.tab, 0, sizeof L.tab);
   const bool flush = new_ci < 0;
-  for (int c = 0; c < h->s_nctx; c++) {
-    mi355ndt_handle* e = h->sctx[c].e;
+  for (int c = 0; c < h->ss->nctx; c++) {
+    mi355ndt_handle* e = h->ss->ctx[c].e.get();
     if (!e->d_src) continue;                         // never bound: no ticket can name it
     fill_async_ctx(e, L.tab.c[c]);
-    L.tab.c[c].results = h->sctx[c].d_res_map;
-    L.tab.c[c].n_done = &h->d_sstat[c].done;
-    L.tab.c[c].pose = h->sctx[c].busy ? h->sctx[c].d_pose : nullptr; L.tab.c[c].pose_base = h->sctx[c].pose_base; L.tab.c[c].pose_stride = h->sctx[c].pose_stride;
+    L.tab.c[c].results = h->ss->ctx[c].d_res_map;
+    L.tab.c[c].n_done = &h->ss->d_stat[c].done;
+    L.tab.c[c].pose = h->ss->ctx[c].busy ? h->ss->ctx[c].d_pose : nullptr; L.tab.c[c].pose_base = h->ss->ctx[c].pose_base; L.tab.c[c].pose_stride = h->ss->ctx[c].pose_stride;
     // The context the NEXT submit recycles must be finished by this launch; the others may hand their last pairs over.  With three or more
     // contexts the context after that one must finish too: its batch is then complete one launch BEFORE the submit that recycles it, so the
     // host collects it and enqueues the next build while a launch is still running -- otherwise every collect returns at the very end of a
     // launch and the GPU idles for as long as the host takes to notice, collect and enqueue (~0.1-0.2 ms per batch, measured as the
     // difference between a streamed step and its kernels).  (The build under the launch -- s_reserve_wg -- needs the same.)
-    const int ahead = (h->s_reserve_wg > 0 || h->s_nctx >= 3) ? 2 : 1;
+    const int ahead = (h->ss->reserve_wg > 0 || h->ss->nctx >= 3) ? 2 : 1;
     bool mf = flush;
-    for (int a = 1; a <= ahead; a++) mf = mf || c == (new_ci + a) % h->s_nctx;
+    for (int a = 1; a <= ahead; a++) mf = mf || c == (new_ci + a) % h->ss->nctx;
     L.tab.c[c].must_finish = mf ? 1 : 0;
   }
-  const long long j = h->s_launches;
+  const long long j = h->ss->launches;
   L.new_ci = flush ? 0 : new_ci; L.n_new = flush ? 0 : n_new;
   if (!flush) {
-    mi355ndt_handle* e = h->sctx[new_ci].e;
+    mi355ndt_handle* e = h->ss->ctx[new_ci].e.get();
     L.st_new = e->d_state; L.guess_new = e->d_guess; L.src_cnt_new = e->d_src_cnt; L.gd_new = e->d_grid; L.arrived_new = e->d_arrived;
-    L.active_list = e->d_active_list; L.sweep_ctl = nullptr; L.done_new = &h->d_sstat[new_ci].done;
-    L.pose_new = h->sctx[new_ci].d_pose; L.pose_cap = h->sctx[new_ci].pose_cap;
+    L.active_list = e->d_active_list; L.sweep_ctl = nullptr; L.done_new = &h->ss->d_stat[new_ci].done;
+    L.pose_new = h->ss->ctx[new_ci].d_pose; L.pose_cap = h->ss->ctx[new_ci].pose_cap;
   }
-  L.tab_dev = h->d_atab; L.ring = h->d_sring; L.ring_cap = h->s_ring_cap;
-  L.ctl = h->d_sctl + (j & 1); L.prev = h->s_drop_carry ? nullptr : h->d_sctl + ((j + 1) & 1);
+  L.tab_dev = h->d_atab; L.ring = h->ss->d_ring; L.ring_cap = h->ss->ring_cap;
+  L.ctl = h->ss->d_ctl + (j & 1); L.prev = h->ss->drop_carry ? nullptr : h->ss->d_ctl + ((j + 1) & 1);
   // (the automatic threshold never hands over more than a quarter of the batch: a batch too small to fill the GPU has no bulk to hide stragglers under)
   const bool thresh_given = h->s_thresh_opt >= 0 || std::getenv("MI355NDT_STREAM_THRESH");
-  L.items_per_pair = h->s_items; L.stop_thresh = flush ? 0 : (thresh_given ? h->s_thresh : std::min(h->s_thresh, n_new / 4)); L.debug_abort_pos = h->debug_abort_pos; L.debug_ring_mask = h->debug_ring_mask;
-  L.reserve_wg = flush ? 0 : h->s_reserve_wg;
-  L.ev_prepared = (h->s_reserve_wg > 0 && h->s_prep_first) ? h->s_ev_prepared[j % mi355ndt_handle::S_EV] : nullptr;
+  L.items_per_pair = h->ss->items; L.stop_thresh = flush ? 0 : (thresh_given ? h->ss->thresh : std::min(h->ss->thresh, n_new / 4)); L.debug_abort_pos = h->debug_abort_pos; L.debug_ring_mask = h->debug_ring_mask;
+  L.reserve_wg = flush ? 0 : h->ss->reserve_wg;
+  L.ev_prepared = (h->ss->reserve_wg > 0 && h->ss->prep_first) ? h->ss->ev_prepared[j % StreamState::EV] : nullptr;
   // two DIRECT7 items per claim halve the hand-overs between items (+1.4-2 %); the coarser positions lengthen a launch's own tail, so only
   // where the tail is handed on (docs/experiments.md 10d)
   L.claim_items = (sc.K == 7 && L.stop_thresh > 0) ? 2 : 1;
   h->ev_last_fresh = false;                          // (the contexts' builds sit between two launches on this stream)
-  if (!flush && h->s_reserve_wg > 0) HIPCHK(h, hipStreamWaitEvent(s, h->s_ev_built[new_ci], 0));   // this batch's grids (built on the other stream)
-  L.stamp_end = (!flush && h->prof) ? &h->d_sstatus[j % mi355ndt_handle::S_EV].build_t1 : nullptr;
+  if (!flush && h->ss->reserve_wg > 0) HIPCHK(h, hipStreamWaitEvent(s, h->ss->ev_built[new_ci], 0));   // this batch's grids (built on the other stream)
+  L.stamp_end = (!flush && h->prof) ? &h->ss->d_status[j % StreamState::EV].build_t1 : nullptr;
   int rc = launch_async(h, sc, L);
   if (rc) return rc;
-  h->s_drop_carry = false;
-  const int slot = (int)(j % mi355ndt_handle::S_EV);
-  k_stream_status<<<1, 64, 0, s>>>(L.ctl, h->d_sstat, reinterpret_cast<volatile unsigned*>(h->d_sstatus + slot), (unsigned)(j + 1));
+  h->ss->drop_carry = false;
+  const int slot = (int)(j % StreamState::EV);
+  k_stream_status<<<1, 64, 0, s>>>(L.ctl, h->ss->d_stat, reinterpret_cast<volatile unsigned*>(h->ss->d_status + slot), (unsigned)(j + 1));
   HIPCHK(h, hipGetLastError());
-  if (h->s_reserve_wg > 0) HIPCHK(h, hipEventRecord(h->s_ev_launched[slot], s));
-  h->s_launches++;
+  if (h->ss->reserve_wg > 0) HIPCHK(h, hipEventRecord(h->ss->ev_launched[slot], s));
+  h->ss->launches++;
   h->P.stream_launches++;
   return MI355NDT_OK;
 }
 
 // wait until launch j has reported (its status slot carries sequence number j + 1): the host polls mapped memory
 static int stream_wait_launch(mi355ndt_handle* h, long long j) {
-  volatile StreamStatus* st = h->h_sstatus + (j % mi355ndt_handle::S_EV);
+  volatile StreamStatus* st = h->ss->h_status + (j % StreamState::EV);
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0; st->seq != (unsigned)(j + 1); spins++) {
     if ((spins & 1023) == 1023) {
@@ -2427,8 +2316,8 @@ static int stream_wait_launch(mi355ndt_handle* h, long long j) {
     } else cpu_relax();
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  for (; h->s_counted <= j; h->s_counted++) {       // (launches finish in order)
-    volatile StreamStatus* c = h->h_sstatus + (h->s_counted % mi355ndt_handle::S_EV);
+  for (; h->ss->counted <= j; h->ss->counted++) {       // (launches finish in order)
+    volatile StreamStatus* c = h->ss->h_status + (h->ss->counted % StreamState::EV);
     h->P.stream_carried += c->susp;
     const unsigned long long b0 = c->build_t0, b1 = c->build_t1;
     if (b0 && b1 > b0) { h->P.build_ms += (double)(b1 - b0) * 1e-5; h->P.build_launches++; }   // wall_clock64: 100 MHz
@@ -2440,22 +2329,22 @@ static int stream_wait_launch(mi355ndt_handle* h, long long j) {
 int mi355ndt_stream_submit(mi355ndt_handle* h, int n_pairs, const float* d_t, const int* tc, size_t tp, const float* d_s, const int* scnt, size_t sp,
                            const float* guesses, long long* batch_id) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if (!h->stream_on) return MI355NDT_ERR_STATE;
-  if (n_pairs < 1 || n_pairs > h->s_max_pairs || !guesses || !batch_id || !tc || !scnt) return MI355NDT_ERR_BAD_ARG;
+  if (!h->ss) return MI355NDT_ERR_STATE;
+  if (n_pairs < 1 || n_pairs > h->ss->max_pairs || !guesses || !batch_id || !tc || !scnt) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  const long long id = h->s_next_id;
-  const int ci = (int)(id % h->s_nctx);
-  mi355ndt_handle::StreamCtx& S = h->sctx[ci];
+  const long long id = h->ss->next_id;
+  const int ci = (int)(id % h->ss->nctx);
+  StreamCtx& S = h->ss->ctx[ci];
   if (S.busy) { h->err = "stream_submit: collect batch " + std::to_string(S.batch_id) + " first (its context is the one this batch needs)"; return MI355NDT_ERR_STATE; }
-  mi355ndt_handle* e = S.e;
-  for (int b = 0; b < n_pairs; b++) if ((size_t)scnt[b] > (size_t)(h->s_items / QUARTERS) * CHUNK_PTS) return MI355NDT_ERR_BAD_ARG;   // more source points than stream_begin was told
+  mi355ndt_handle* e = S.e.get();
+  for (int b = 0; b < n_pairs; b++) if ((size_t)scnt[b] > (size_t)(h->ss->items / QUARTERS) * CHUNK_PTS) return MI355NDT_ERR_BAD_ARG;   // more source points than stream_begin was told
   int rc = mi355ndt_batch_bind_device(e, n_pairs, d_t, tc, tp, d_s, scnt, sp);
   if (rc) { h->err = e->err; return rc; }
   e->prm = h->prm;
   S.batch_id = id; S.n_pairs = n_pairs; S.redo = false; S.done_sync = false; S.launch = -1;
   S.guesses.assign(guesses, guesses + (size_t)n_pairs * 16);
-  S.d_pose = (PoseRecord*)h->s_pose_next; S.pose_cap = (int)h->s_pose_cap_next; S.pose_base = h->s_pose_base_next; S.pose_stride = h->s_pose_stride_next;
-  h->s_pose_next = nullptr; h->s_pose_cap_next = 0;
+  S.d_pose = (PoseRecord*)h->ss->pose_next; S.pose_cap = (int)h->ss->pose_cap_next; S.pose_base = h->ss->pose_base_next; S.pose_stride = h->ss->pose_stride_next;
+  h->ss->pose_next = nullptr; h->ss->pose_cap_next = 0;
   if (S.d_pose && (size_t)n_pairs > (size_t)S.pose_cap) return MI355NDT_ERR_BAD_ARG;
   auto run_sync = [&]() -> int {                     // build + align this batch here and now, results into the context's host buffer
     e->async_build = false; e->counts_preloaded = false;
@@ -2466,62 +2355,58 @@ int mi355ndt_stream_submit(mi355ndt_handle* h, int n_pairs, const float* d_t, co
     if (r) h->err = e->err;
     return r;
   };
-  if (h->s_sync_only) {                              // a configuration the one-launch align does not serve: processed here and now
+  if (h->ss->sync_only) {                              // a configuration the one-launch align does not serve: processed here and now
     rc = run_sync();
     if (rc) return rc;
     S.done_sync = true; S.busy = true;
-    *batch_id = id; h->s_next_id++;
+    *batch_id = id; h->ss->next_id++;
     return MI355NDT_OK;
   }
   // the batch's small inputs in one copy: point counts of both sides, guesses
   memcpy(S.h_in, tc, (size_t)n_pairs * sizeof(int));
-  memcpy(S.h_in + h->s_max_pairs, scnt, (size_t)n_pairs * sizeof(int));
-  memcpy(S.h_in + 2 * (size_t)h->s_max_pairs, guesses, (size_t)n_pairs * 16 * sizeof(float));
+  memcpy(S.h_in + h->ss->max_pairs, scnt, (size_t)n_pairs * sizeof(int));
+  memcpy(S.h_in + 2 * (size_t)h->ss->max_pairs, guesses, (size_t)n_pairs * 16 * sizeof(float));
   // this context's previous batch was finished by the launch before the last one (must_finish): the build may start when that launch has ended -- and
   // a moment later still, when the LAST launch's prepare kernel is through (it follows that end on the stream): the build's first kernels stream the
   // whole batch through HBM and would otherwise run against the one short kernel every launch waits for (k_async_prepare: 50 us beside k_minmax, 17 alone)
-  if (h->s_reserve_wg > 0 && h->s_prep_first && h->s_launches >= 1)
-    HIPCHK(h, hipStreamWaitEvent(e->stream, h->s_ev_prepared[(h->s_launches - 1) % mi355ndt_handle::S_EV], 0));
-  else if (h->s_reserve_wg > 0 && h->s_launches >= 2)
-    HIPCHK(h, hipStreamWaitEvent(e->stream, h->s_ev_launched[(h->s_launches - 2) % mi355ndt_handle::S_EV], 0));
+  if (h->ss->reserve_wg > 0 && h->ss->prep_first && h->ss->launches >= 1)
+    HIPCHK(h, hipStreamWaitEvent(e->stream, h->ss->ev_prepared[(h->ss->launches - 1) % StreamState::EV], 0));
+  else if (h->ss->reserve_wg > 0 && h->ss->launches >= 2)
+    HIPCHK(h, hipStreamWaitEvent(e->stream, h->ss->ev_launched[(h->ss->launches - 2) % StreamState::EV], 0));
   // (one workgroup reads the block from mapped host memory and clears the build's word block: no copy, no fill -- k_stream_inputs)
-  k_stream_inputs<<<1, 1024, 0, e->stream>>>(S.h_in_dev, reinterpret_cast<unsigned*>(S.d_in), (unsigned)(2 * (size_t)h->s_max_pairs + (size_t)n_pairs * 16),
+  k_stream_inputs<<<1, 1024, 0, e->stream>>>(S.h_in_dev, reinterpret_cast<unsigned*>(S.d_in.p), (unsigned)(2 * (size_t)h->ss->max_pairs + (size_t)n_pairs * 16),
                                             e->d_word_off, (unsigned)(2 + 6 * (size_t)e->cap_pairs),
-                                            h->prof ? &h->d_sstatus[h->s_launches % mi355ndt_handle::S_EV].build_t0 : nullptr);
+                                            h->prof ? &h->ss->d_status[h->ss->launches % StreamState::EV].build_t0 : nullptr);
   e->word_off_cleared = true;
   e->build_stamped = h->prof;
   e->counts_preloaded = true; e->up_src_cnt.clear(); e->up_tgt_cnt.clear();
   // target build: against the stream's plan when there is one (no wait), else synchronously -- which makes the plan
   e->async_build = true;
-  e->plan_cb = h->s_plan_cb; e->plan_words = h->s_plan_words;
-  if (e->plan_words > e->words_cap) {
-    size_t c = e->words_cap;
-    HIPCHK(h, grow(e->d_words, c, e->plan_words));
-    e->words_cap = c;
-  }
+  e->plan_cb = h->ss->plan_cb; e->plan_words = h->ss->plan_words;
+  HIPCHK(h, e->d_words.reserve(e->plan_words));
   rc = mi355ndt_batch_build_targets(e);
   if (rc) { h->err = e->err; return rc; }
   if (!(e->plan_cb > 0 && e->plan_words > 0)) {      // that build waited for its sizes: learn from it (with headroom: scans of one drive vary by a few per cent)
-    h->s_plan_cb = std::max(h->s_plan_cb, e->last_cb);
-    h->s_plan_words = std::max(h->s_plan_words, e->last_total_words + e->last_total_words / 4 + 1024);
+    h->ss->plan_cb = std::max(h->ss->plan_cb, e->last_cb);
+    h->ss->plan_words = std::max(h->ss->plan_words, e->last_total_words + e->last_total_words / 4 + 1024);
   }
-  if (h->s_reserve_wg > 0) HIPCHK(h, hipEventRecord(h->s_ev_built[ci], e->stream));
+  if (h->ss->reserve_wg > 0) HIPCHK(h, hipEventRecord(h->ss->ev_built[ci], e->stream));
   // align workspace of this context: fixed row geometry for the whole stream (a pair's rows do not depend on it)
-  e->chunks_per_pair = h->s_items / QUARTERS; e->rows_per_pair = e->items_per_pair = h->s_items; e->pts_per_chunk = CHUNK_PTS; e->fine_it = 0;
+  e->chunks_per_pair = h->ss->items / QUARTERS; e->rows_per_pair = e->items_per_pair = h->ss->items; e->pts_per_chunk = CHUNK_PTS; e->fine_it = 0;
   gauss_constants3(h->prm.outlier_ratio, h->prm.resolution, h->gauss_last);
   S.busy = true;
-  S.launch = h->s_launches;
+  S.launch = h->ss->launches;
   rc = stream_launch(h, ci, n_pairs);
   if (rc) {                                          // the launch cannot be made (not resident): this and every later batch synchronously
-    h->s_sync_only = true;
-    if (h->s_build_stream) HIPCHK(h, hipStreamSynchronize(h->s_build_stream));
+    h->ss->sync_only = true;
+    if (h->ss->build_stream) HIPCHK(h, hipStreamSynchronize(h->ss->build_stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     rc = run_sync();
     if (rc) { S.busy = false; return rc; }
     S.done_sync = true;
   }
   e->aligned_once = true;
-  *batch_id = id; h->s_next_id++;
+  *batch_id = id; h->ss->next_id++;
   return MI355NDT_OK;
 }
 
@@ -2532,22 +2417,22 @@ int mi355ndt_stream_submit(mi355ndt_handle* h, int n_pairs, const float* d_t, co
 int mi355ndt_stream_submit_host(mi355ndt_handle* h, int n_pairs, const void* const* targets, const size_t* target_counts, const void* const* sources,
                                 const size_t* source_counts, size_t stride, const float* guesses, int n_threads, long long* batch_id) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if (!h->stream_on) return MI355NDT_ERR_STATE;
-  if (n_pairs < 1 || n_pairs > h->s_max_pairs || !targets || !target_counts || !sources || !source_counts || stride < 12 || !guesses || !batch_id) return MI355NDT_ERR_BAD_ARG;
+  if (!h->ss) return MI355NDT_ERR_STATE;
+  if (n_pairs < 1 || n_pairs > h->ss->max_pairs || !targets || !target_counts || !sources || !source_counts || stride < 12 || !guesses || !batch_id) return MI355NDT_ERR_BAD_ARG;
   for (int b = 0; b < n_pairs; b++)
-    if (target_counts[b] > h->s_max_tgt || source_counts[b] > h->s_max_src || (!targets[b] && target_counts[b]) || (!sources[b] && source_counts[b])) return MI355NDT_ERR_BAD_ARG;
+    if (target_counts[b] > h->ss->max_tgt || source_counts[b] > h->ss->max_src || (!targets[b] && target_counts[b]) || (!sources[b] && source_counts[b])) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  const int ci = (int)(h->s_next_id % h->s_nctx);
-  mi355ndt_handle::StreamCtx& S = h->sctx[ci];
+  const int ci = (int)(h->ss->next_id % h->ss->nctx);
+  StreamCtx& S = h->ss->ctx[ci];
   if (S.busy) { h->err = "stream_submit_host: collect batch " + std::to_string(S.batch_id) + " first (its context is the one this batch needs)"; return MI355NDT_ERR_STATE; }
-  mi355ndt_handle* e = S.e;
-  const size_t tp = (h->s_max_tgt + 63) & ~(size_t)63, sp = (h->s_max_src + 63) & ~(size_t)63;
-  if (!e->d_tgt_own || !e->d_src_own || e->own_tgt_pairs < h->s_max_pairs || e->own_src_pairs < h->s_max_pairs || e->own_tgt_pitch != tp || e->own_src_pitch != sp) {
-    int rc = mi355ndt_batch_reserve(e, h->s_max_pairs, h->s_max_tgt, h->s_max_src);      // (once per context: the stream's sizes never change)
+  mi355ndt_handle* e = S.e.get();
+  const size_t tp = (h->ss->max_tgt + 63) & ~(size_t)63, sp = (h->ss->max_src + 63) & ~(size_t)63;
+  if (!e->d_tgt_own || !e->d_src_own || e->own_tgt_pairs < h->ss->max_pairs || e->own_src_pairs < h->ss->max_pairs || e->own_tgt_pitch != tp || e->own_src_pitch != sp) {
+    int rc = mi355ndt_batch_reserve(e, h->ss->max_pairs, h->ss->max_tgt, h->ss->max_src);      // (once per context: the stream's sizes never change)
     if (rc) { h->err = e->err; return rc; }
   }
   // (the context's previous batch has been collected -- S.busy is false --, so no kernel still reads these rows)
-  e->n_pairs = h->s_max_pairs; e->d_tgt = e->d_tgt_own; e->d_src = e->d_src_own; e->tgt_pitch = tp; e->src_pitch = sp;
+  e->n_pairs = h->ss->max_pairs; e->d_tgt = e->d_tgt_own; e->d_src = e->d_src_own; e->tgt_pitch = tp; e->src_pitch = sp;
   int rc = mi355ndt_batch_set_clouds(e, 0, n_pairs, targets, target_counts, sources, source_counts, stride, n_threads);
   if (rc) { h->err = e->err; return rc; }
   std::vector<int> tc((size_t)n_pairs), sc((size_t)n_pairs);
@@ -2558,37 +2443,37 @@ int mi355ndt_stream_submit_host(mi355ndt_handle* h, int n_pairs, const void* con
 
 int mi355ndt_stream_pose_records(mi355ndt_handle* h, void* d_records, size_t capacity, int id_base, int id_stride) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if (!h->stream_on) return MI355NDT_ERR_STATE;
+  if (!h->ss) return MI355NDT_ERR_STATE;
   if ((d_records && capacity == 0) || capacity > (size_t)MAX_PAIRS) return MI355NDT_ERR_BAD_ARG;
-  h->s_pose_next = d_records; h->s_pose_cap_next = d_records ? capacity : 0; h->s_pose_base_next = id_base; h->s_pose_stride_next = id_stride;
+  h->ss->pose_next = d_records; h->ss->pose_cap_next = d_records ? capacity : 0; h->ss->pose_base_next = id_base; h->ss->pose_stride_next = id_stride;
   return MI355NDT_OK;
 }
 
 // a launch gave up (ctl->abort_): nothing it left behind can be trusted to continue from -- every unfinished batch is re-run synchronously
 // by its collect, and the next launch starts without a hand-over list
 static void stream_recover(mi355ndt_handle* h) {
-  if (h->s_build_stream) (void)hipStreamSynchronize(h->s_build_stream);
+  if (h->ss->build_stream) (void)hipStreamSynchronize(h->ss->build_stream);
   (void)hipStreamSynchronize(h->stream);
   CtxStat st[ASYNC_MAX_CTX];
-  if (hipMemcpy(st, h->d_sstat, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) memset(st, 0, sizeof st);
-  for (int c = 0; c < h->s_nctx; c++) {
-    mi355ndt_handle::StreamCtx& S = h->sctx[c];
+  if (hipMemcpy(st, h->ss->d_stat, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) memset(st, 0, sizeof st);
+  for (int c = 0; c < h->ss->nctx; c++) {
+    StreamCtx& S = h->ss->ctx[c];
     if (S.busy && !S.done_sync && st[c].done != (unsigned)S.n_pairs) S.redo = true;
   }
-  h->s_drop_carry = true;
-  h->s_recovered_upto = h->s_launches - 1;       // everything enqueued so far has drained and been marked: a later collect that reads this launch's abort flag again has nothing to do
+  h->ss->drop_carry = true;
+  h->ss->recovered_upto = h->ss->launches - 1;       // everything enqueued so far has drained and been marked: a later collect that reads this launch's abort flag again has nothing to do
   h->P.async_fallbacks++;
 }
 
 int mi355ndt_stream_collect(mi355ndt_handle* h, long long batch_id, mi355ndt_result* out) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if (!h->stream_on) return MI355NDT_ERR_STATE;
-  if (batch_id < 0 || batch_id >= h->s_next_id || !out) return MI355NDT_ERR_BAD_ARG;
+  if (!h->ss) return MI355NDT_ERR_STATE;
+  if (batch_id < 0 || batch_id >= h->ss->next_id || !out) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  const int ci = (int)(batch_id % h->s_nctx);
-  mi355ndt_handle::StreamCtx& S = h->sctx[ci];
+  const int ci = (int)(batch_id % h->ss->nctx);
+  StreamCtx& S = h->ss->ctx[ci];
   if (!S.busy || S.batch_id != batch_id) return MI355NDT_ERR_BAD_ARG;       // collected already (or its context has been recycled)
-  mi355ndt_handle* e = S.e;
+  mi355ndt_handle* e = S.e.get();
   bool reran = S.done_sync;                          // went through the synchronous path (then the pose records come from the engine's packer)
   if (!S.done_sync) {
     long long j = S.launch;
@@ -2596,30 +2481,30 @@ int mi355ndt_stream_collect(mi355ndt_handle* h, long long batch_id, mi355ndt_res
     for (;;) {
       int rc = stream_wait_launch(h, j);
       if (rc) return rc;
-      const StreamStatus st = *const_cast<const StreamStatus*>(h->h_sstatus + (j % mi355ndt_handle::S_EV));
-      if (st.abort_ && !S.redo && j > h->s_recovered_upto) stream_recover(h);
+      const StreamStatus st = *const_cast<const StreamStatus*>(h->ss->h_status + (j % StreamState::EV));
+      if (st.abort_ && !S.redo && j > h->ss->recovered_upto) stream_recover(h);
       plan_exceeded = st.ctx[ci].plan_exceeded != 0;
       if (S.redo || plan_exceeded) break;
       if (st.ctx[ci].done == (unsigned)S.n_pairs) break;
-      if (j + 1 < h->s_launches) { j++; continue; }  // its stragglers ride in a later launch that is already queued
+      if (j + 1 < h->ss->launches) { j++; continue; }  // its stragglers ride in a later launch that is already queued
       rc = stream_launch(h, -1, 0);                  // nothing newer: flush them
       if (rc) { stream_recover(h); S.redo = true; break; }
-      j = h->s_launches - 1;
+      j = h->ss->launches - 1;
     }
     if (S.redo || plan_exceeded) {
       // the batch did not fit the build plan (its grids were withheld), or its launch gave up: the synchronous path, which also re-makes the plan
-      if (h->s_build_stream) HIPCHK(h, hipStreamSynchronize(h->s_build_stream));
+      if (h->ss->build_stream) HIPCHK(h, hipStreamSynchronize(h->ss->build_stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
       e->async_build = false; e->counts_preloaded = false; e->up_tgt_cnt.clear(); e->up_src_cnt.clear();
       int rc = mi355ndt_batch_build_targets(e);
       if (rc == MI355NDT_OK) rc = mi355ndt_batch_align(e, S.guesses.data(), S.h_res);
       e->async_build = true;
       if (rc) { h->err = e->err; S.busy = false; return rc; }
-      h->s_plan_cb = std::max(h->s_plan_cb, e->last_cb);
-      h->s_plan_words = std::max(h->s_plan_words, e->last_total_words + e->last_total_words / 4 + 1024);
+      h->ss->plan_cb = std::max(h->ss->plan_cb, e->last_cb);
+      h->ss->plan_words = std::max(h->ss->plan_words, e->last_total_words + e->last_total_words / 4 + 1024);
       // the synchronous align re-computed its own row geometry: back to the stream's for this context's next batch
-      e->chunks_per_pair = h->s_items / QUARTERS; e->rows_per_pair = e->items_per_pair = h->s_items; e->pts_per_chunk = CHUNK_PTS; e->fine_it = 0;
-      if (grow(e->d_partials, e->partials_cap, (size_t)h->s_max_pairs * h->s_items * NACC) != hipSuccess) return MI355NDT_ERR_HIP;
+      e->chunks_per_pair = h->ss->items / QUARTERS; e->rows_per_pair = e->items_per_pair = h->ss->items; e->pts_per_chunk = CHUNK_PTS; e->fine_it = 0;
+      if (e->d_partials.reserve((size_t)h->ss->max_pairs * h->ss->items * NACC) != hipSuccess) return MI355NDT_ERR_HIP;
       h->P.stream_redone++;
       reran = true;
     }
@@ -2698,9 +2583,8 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
   const bool keep_prof = h->prof;
   struct ProfBack { mi355ndt_handle* h; bool v; ~ProfBack() { h->prof = v; } } profback{h, keep_prof};   // (every exit restores it)
   h->prof = false;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  struct EvFree { hipEvent_t* e; ~EvFree() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evfree{ev};
-  for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
+  HipEvent ev[3];
+  for (auto& e : ev) HIPCHK(h, e.create(hipEventDefault));
   hipStream_t s = h->stream;
   HIPCHK(h, hipEventRecord(ev[0], s));
   rc = mi355ndt_batch_build_targets(h);
@@ -2713,15 +2597,8 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
   if (rc == MI355NDT_OK && !h->fine_it) { h->err = "sequence run: the fine-grained sweep does not serve this configuration"; rc = MI355NDT_ERR_UNSUPPORTED; }
   if (rc) { h->prof = keep_prof; return rc; }
   // one pair is in flight at a time: the fine grid is sized for one pair
-  if ((size_t)n_frames > h->seq_cap) {
-    for (void** p : {(void**)&h->d_grid_of, (void**)&h->d_seq_out, (void**)&h->d_stamps}) if (*p) { HIPCHK(h, hipFree(*p)); *p = nullptr; }
-    h->seq_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&h->d_grid_of, (size_t)n_frames * sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&h->d_seq_out, (size_t)n_frames * sizeof(mi355ndt_seq_frame)));
-    HIPCHK(h, hipMalloc((void**)&h->d_stamps, (size_t)n_frames * sizeof(double)));
-    h->seq_cap = (size_t)n_frames;
-  }
-  if (!h->d_seq) HIPCHK(h, hipMalloc((void**)&h->d_seq, sizeof(SeqState)));
+  HIPCHK(h, h->d_grid_of.reserve(n_frames)); HIPCHK(h, h->d_seq_out.reserve(n_frames)); HIPCHK(h, h->d_stamps.reserve(n_frames));
+  HIPCHK(h, h->d_seq.reserve(1));
   rc = ensure_seq_flags(h);
   if (rc) { h->prof = keep_prof; return rc; }
   h->h_seq_flags[0] = 0; h->h_seq_flags[1] = 0;

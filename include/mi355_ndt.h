@@ -105,7 +105,7 @@ typedef struct mi355ndt_profile {
   long long stream_launches; /* stream mode: persistent launches (one per submitted batch + flushes) */
   long long stream_carried;  /* stream mode: pairs handed over from one launch to the next (stragglers that finished under a later batch) */
   long long stream_redone;   /* stream mode: batches re-run synchronously (build plan exceeded, or a launch gave up) */
-  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter), counted always */
+  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter / map_cloud: its non-empty keyframes), counted always */
   long long cloud_upload_bytes;
   long long cloud_transfers;  /* host-to-device transfers those clouds travelled in (mi355ndt_batch_set_clouds / stream_submit_host send up to eight clouds per transfer) */
   long long cloud_promotions; /* mi355ndt_promote_source_to_target calls (device-to-device instead of an upload) */
@@ -410,6 +410,23 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
                        void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
 /* install the last prefilter result as the registration source (role 1) or target (role 2) without a host round trip */
 int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
+
+/* ---- map cloud: the global graph's map (MapCloudGenerator::generate) ------------------------------------ */
+/* replaces MapCloudGenerator::generate(keyframes, resolution) (src/global_graph/map_cloud_generator.cpp:17-55), which
+ * GlobalGraphNodelet::optimization_timer_callback (global_graph_nodelet.cpp:725-745) and save_map_service (:1036-1046) call
+ * over every keyframe: keyframe k's clouds[k] (counts[k] records of stride_bytes, x,y,z f32 first) moved by poses[16k..16k+15]
+ * (KeyFrameSnapshot::pose.matrix(), column-major f64; cast to f32 as the reference does), all points fed in keyframe order into
+ * pcl::octree::OctreePointCloud(resolution), and the occupied voxel centres written to out_pts as x,y,z f32 records (may be
+ * NULL) in the order getOccupiedVoxelCenters returns them.  The input order matters: the first finite point anchors the
+ * octree's lattice.  *n_out always gets the count; if it exceeds out_capacity the call returns MI355NDT_ERR_BAD_ARG and
+ * writes nothing.  n_keyframes == 0 (the reference returns nullptr) and clouds without a finite point give *n_out = 0.
+ * MI355NDT_ERR_BAD_ARG also for resolution <= 0, NaN or infinite, 2^30 points or more in all, and for points that would
+ * need an octree deeper than 21 levels (2^21 voxels per axis: 105 km at 0.05 m; mi355ndt_last_error says so).  Intensity is
+ * not carried (the reference's centres carry 0).  Synchronous; MI355NDT_ERR_STATE in stream mode.  Uses buffers of its
+ * own: the batch, grids, prefilter result and stream state of the handle are left as they were. */
+int mi355ndt_map_cloud(mi355ndt_handle* h, int n_keyframes, const void* const* clouds, const size_t* counts, size_t stride_bytes,
+                       const double* poses, double resolution, void* out_pts, size_t out_capacity,
+                       size_t out_stride_bytes, size_t* n_out);
 
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);

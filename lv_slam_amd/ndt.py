@@ -87,6 +87,7 @@ SYMBOLS = [
     "mi355ndt_set_latency_mode", "mi355ndt_sequence_run",
     "mi355ndt_calculate_score", "mi355ndt_convert_transform", "mi355ndt_set_option", "mi355ndt_get_option",
     "mi355ndt_stream_begin", "mi355ndt_stream_submit", "mi355ndt_stream_submit_host", "mi355ndt_stream_collect", "mi355ndt_stream_end", "mi355ndt_stream_pose_records", "mi355ndt_pack_pose_records",
+    "mi355ndt_map_cloud",
 ]
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
@@ -131,6 +132,7 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_fitness_score_T.argtypes = [vp, vp, C.c_double, vp, vp]
     L.mi355ndt_prefilter.argtypes = [vp, vp, sz, sz, i, C.c_double, C.c_double, C.c_float, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
+    L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_derivatives.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mi355ndt_derivatives_T.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi355ndt_compute_hessian.argtypes = [vp, vp, vp]
@@ -307,6 +309,30 @@ class Engine:
         self._chk(self.lib.mi355ndt_use_prefiltered(self.h, 2 if as_target else 1), "use_prefiltered")
         if not as_target:
             self._n_src = self._pf_count
+
+    def map_cloud(self, clouds, poses, resolution, fetch=True):
+        """MapCloudGenerator::generate(keyframes, resolution): keyframe k's cloud ([N_k,>=3], x,y,z first) moved by poses[k] (4x4, f64;
+        cast to f32 as the reference does), every point fed in keyframe order into an OctreePointCloud(resolution), the occupied voxel
+        centres returned as [M,3] float32 in getOccupiedVoxelCenters' order (M alone with fetch=False).  None for an empty keyframe list
+        (the reference returns nullptr).  tools/map_cloud_ref.py is the CPU restatement it equals bit for bit."""
+        clouds = [np.ascontiguousarray(_as_points(c)[:, :3]) for c in clouds]
+        P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        if P.shape[0] != len(clouds):
+            raise ValueError("one 4x4 pose per cloud")
+        if not clouds:
+            self._chk(self.lib.mi355ndt_map_cloud(self.h, 0, None, None, 12, None, float(resolution), None, 0, 12, C.byref(C.c_size_t())),
+                      "map_cloud")
+            return None
+        K = len(clouds)
+        ptrs = (C.c_void_p * K)(*[c.ctypes.data for c in clouds])
+        counts = (C.c_size_t * K)(*[c.shape[0] for c in clouds])
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(K, 16)        # column-major per keyframe
+        n = sum(c.shape[0] for c in clouds)
+        out = np.empty((max(n, 1), 3), np.float32) if fetch else None
+        n_out = C.c_size_t()
+        self._chk(self.lib.mi355ndt_map_cloud(self.h, K, ptrs, counts, 12, pcm.ctypes.data_as(C.c_void_p), float(resolution),
+                                              out.ctypes.data_as(C.c_void_p) if fetch else None, n, 12, C.byref(n_out)), "map_cloud")
+        return out[: n_out.value].copy() if fetch else n_out.value
 
     # -- parity hooks
     def derivatives(self, p):

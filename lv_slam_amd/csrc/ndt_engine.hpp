@@ -1,0 +1,271 @@
+// ndt_engine.hpp -- the engine behind a handle: StreamCtx / StreamState / mi355ndt_handle, the error and state macros, the constants, and the
+// one home of every decision about a configuration that more than one surface takes (neighbor_K, is_pca_kd, async_served, launch_slots, ...).
+#pragma once
+
+// ------------------------------------------------------------------------------------ host side
+// Ownership: every buffer, pinned block, stream and event the engine allocates lives in an owner of ndt_hostmem.hpp and is released with it.
+// Raw pointers below are views into memory some owner (or the caller) holds; their comments say which.
+struct mi355ndt_handle;
+struct EngineDel { void operator()(mi355ndt_handle* e) const { (void)mi355ndt_destroy(e); } };
+
+// ---- stream mode (mi355ndt_stream_*, the parent handle): n_contexts batches resident, one persistent launch per submitted batch,
+// the stragglers of a launch carried into the next one (ndt_async.hpp).  One StreamState per session: mi355ndt_stream_begin creates it,
+// mi355ndt_stream_end releases it.
+struct StreamCtx {
+  long long batch_id = -1; int n_pairs = 0;
+  bool busy = false;                            // submitted, not yet collected
+  bool redo = false;                            // collect re-runs it synchronously (its launch gave up)
+  bool done_sync = false;                       // processed synchronously inside submit (configuration the one-launch align does not serve)
+  long long launch = -1;                        // the launch that started it
+  // a batch's small inputs -- target counts, source counts, guesses -- travel as ONE copy: pinned staging block -> device block, into which
+  // the context engine's d_tgt_cnt / d_src_cnt / d_guess point
+  DevBuf<int> d_in; PinBuf<int> h_in; unsigned* h_in_dev = nullptr;   // (h_in is mapped: the device reads it itself; h_in_dev views it)
+  // results: MAPPED host memory -- a pair's result record is written there by the updater that finalises it (posted PCIe writes), no copy
+  PinBuf<mi355ndt_result> h_res; mi355ndt_result* d_res_map = nullptr;   // (d_res_map: the device's view of h_res)
+  std::vector<float> guesses;                   // (kept for a synchronous re-run)
+  PoseRecord* d_pose = nullptr; int pose_cap = 0, pose_base = 0, pose_stride = 1;   // mi355ndt_stream_pose_records (this batch's gather block)
+  std::unique_ptr<mi355ndt_handle, EngineDel> e;   // the context's own engine: bound clouds, grids, pair states (runs on the parent's stream)
+};
+struct StreamState {
+  static constexpr int EV = 16;
+  bool sync_only = false, drop_carry = true;
+  int nctx = 0, max_pairs = 0, items = 0, ring_cap = 0, thresh = 0;
+  bool thresh_given = false;                    // MI355NDT_OPT_STREAM_THRESHOLD or MI355NDT_STREAM_THRESH named the threshold (else automatic: capped per batch, stream_launch)
+  size_t max_tgt = 0, max_src = 0;              // what mi355ndt_stream_begin was told (mi355ndt_stream_submit_host sizes the contexts' own cloud buffers with it)
+  int plan_cb = 0; size_t plan_words = 0;
+  void* pose_next = nullptr; size_t pose_cap_next = 0; int pose_base_next = 0, pose_stride_next = 1;   // apply to the next submit of this session
+  long long next_id = 0, launches = 0, counted = 0;
+  long long recovered_upto = -1;                // launches up to this one have had their abort handled (stream_recover runs once per aborted launch, not once per collect that walks past its slot)
+  DevBuf<AsyncCtl> d_ctl;                       // two control blocks: a launch reads the hand-over list of the previous one
+  DevBuf<int> d_ring;
+  DevBuf<CtxStat> d_stat;                       // per context: pairs finalised, sizes and verdict of its last planned build
+  // Build under the launch: with reserve_wg > 0 the contexts' engines run their builds on build_stream, the persistent launches leave
+  // that many workgroup slots free, and events order  launch j-2 done -> build of batch j -> launch j
+  HipStream build_stream; int reserve_wg = 0, launch_slots = 0;
+  HipEvent ev_built[ASYNC_MAX_CTX], ev_launched[EV], ev_prepared[EV]; bool prep_first = true;
+  PinBuf<volatile StreamStatus> h_status; StreamStatus* d_status = nullptr;   // mapped ring of per-launch status slots (k_stream_status); d_status: the device's view
+  StreamCtx ctx[ASYNC_MAX_CTX];                 // (last: the contexts' engines are released before the stream they run on)
+};
+
+struct mi355ndt_handle {
+  int device = 0;
+  HipStream own_stream;                         // the engine's compute stream, unless mi355ndt_set_stream gave it one
+  hipStream_t stream = nullptr;                 // view: own_stream or the caller's stream
+  mi355ndt_params prm;
+  std::string err;
+
+  int n_pairs = 0, cap_pairs = 0;
+  size_t tgt_pitch = 0, src_pitch = 0;          // geometry in use
+  size_t own_tgt_pitch = 0, own_src_pitch = 0;  // geometry of the owned buffers
+  int own_tgt_pairs = 0, own_src_pairs = 0;
+  DevBuf<float> d_tgt_own, d_src_own;
+  const float *d_tgt = nullptr, *d_src = nullptr;   // views: d_tgt_own / d_src_own or a device buffer bound by the caller
+  DevBuf<int> d_tgt_cnt_own, d_src_cnt_own;
+  int *d_tgt_cnt = nullptr, *d_src_cnt = nullptr;   // views: d_tgt_cnt_own / d_src_cnt_own or the stream context's input block
+  std::vector<int> h_tgt_cnt, h_src_cnt;
+  std::vector<int> up_tgt_cnt, up_src_cnt;        // what d_tgt_cnt / d_src_cnt currently hold (uploads are skipped when unchanged)
+  bool targets_built = false, have_target = false, have_source = false;
+  bool aligned_once = false;                      // d_state / d_results hold the outcome of an align of the CURRENT batch
+  bool icov64_built = false;                      // ... and the f64 inverse covariances computeHessian reads (live More-Thuente)
+  bool cent_built = false;                        // last target build also produced the f32 leaf centroids (KDTREE mode)
+  float grid_resolution = 0.f;                    // leaf size the resident grids were built with (setResolution without a source keeps them: ndt_omp.h:126-136)
+
+  // build workspace
+  unsigned* d_minmax = nullptr;                  // view: a slice of d_word_off (zeroed together before every build)
+  DevBuf<GridDesc> d_grid;
+  DevBuf<unsigned> d_nwords, d_word_off;
+  DevBuf<unsigned> d_keys_a, d_keys_b;           // cell key per target point: unsorted / sorted (segment-local radix sort)
+  DevBuf<unsigned> d_vals_a, d_vals_b;
+  DevBuf<BitWord> d_words;
+  size_t recs_per_pair = 0;                      // voxel records per target of the records group (d_recs ... d_cent); 0: group not allocated
+  DevBuf<VoxelRec> d_recs; DevBuf<int> d_vox_idx, d_vox_n;
+  DevBuf<unsigned> d_seg_start; DevBuf<double> d_sums;
+  DevBuf<unsigned> d_heads, d_head_cnt;          // k_mark's run heads per slice
+  DevBuf<float> d_cent; DevBuf<double> d_icov64;
+  DevBuf<int> d_kdw; bool kdw_built = false;     // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
+  DevBuf<float4> d_sorted; bool leaf_sorted = false;   // MI355NDT_LEAF_SORTED: the sorted order as points (k_sorted_points)
+  DevBuf<unsigned> d_rs_hist, d_rs_offs;         // segmented radix sort: tile histograms / offsets
+  DevBuf<unsigned> d_cstart, d_cend; bool cells_ready = false; int last_cb = 0;
+  DevBuf<double> d_fit;
+  // batched fitness (mi355ndt_batch_fitness_scores): occupied-cell index of every target (ndt_fitness.hpp), built on the first call after a
+  // target build; the launch's item table and transforms
+  DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns; bool fit_index_ready = false;
+  DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
+  // prefilter workspace
+  DevBuf<float> d_pf_in, d_pf_out; DevBuf<unsigned char> d_pf_keep; DevBuf<unsigned> d_pf_keys, d_pf_vals;
+  DevBuf<int> d_pf_flag, d_pf_pos, d_pf_mm; DevBuf<PfGrid> d_pf_grid; DevBuf<unsigned> d_pf_tmp;
+  int pf_count = 0; size_t pf_pitch = 0;
+  // map cloud workspace (mi355ndt_map_cloud; touches nothing of the batch, grid, prefilter or stream state)
+  DevBuf<float> d_mc_in, d_mc_x, d_mc_out; DevBuf<unsigned char> d_mc_fin; DevBuf<int> d_mc_aabb, d_mc_flag, d_mc_pos;
+  DevBuf<unsigned> d_mc_keys, d_mc_hist, d_mc_offs, d_mc_tmp;   // d_mc_keys: low / high words of the codes, two of each (sort ping-pong)
+  DevBuf<McKf> d_mc_kf; DevBuf<float> d_mc_T; DevBuf<McBox> d_mc_box;
+  PinBuf<unsigned char> h_mc_tab;                 // pinned staging of the keyframe table and the f32 poses
+  PinBuf<int> h_mc_ret;                           // pinned landing words: status, depth, last scan position, last head flag
+  bool mc_pending = false;                        // a map cloud call returned before its final synchronisation (h_mc_tab may still be read)
+  float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
+  PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
+
+  // align workspace
+  DevBuf<PairState> d_state;
+  DevBuf<double> d_partials;
+  int chunks_per_pair = 0;
+  int rows_per_pair = 0, pts_per_chunk = CHUNK_PTS;   // stored partial rows per pair / points covered by one chunk of k_update's tree
+  int items_per_pair = 0;                         // sweep work items per pair (= rows_per_pair in batch mode, 4 x rows_per_pair in latency mode)
+  bool async_force = false;                       // MI355NDT_OPT_ASYNC_ALIGN = 2 / MI355NDT_ASYNC=2: the one-launch align also for batches smaller than the resident waves (tests, fuzzing)
+  bool async_align = true;                        // MI355NDT_OPT_ASYNC_ALIGN: batch aligns as ONE persistent launch (ndt_async.hpp); MI355NDT_ASYNC=0 turns it off
+  int score_only_last = 1;                        // MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP: the one-launch align's last sweep of a pair evaluates the score alone
+  DevBuf<int> d_ring; DevBuf<unsigned> d_arrived; DevBuf<AsyncCtl> d_actl;
+  PinBuf<AsyncCtl> h_pin_actl;
+  DevBuf<AsyncTab> d_atab;                        // the launch's context table (ndt_async.hpp)
+  unsigned debug_abort_pos = 0xFFFFFFFFu;         // MI355NDT_OPT_DEBUG_ASYNC_ABORT (test hook): the wave that claims this position of ring 0 gives up
+  unsigned debug_ring_mask = 0xFFu;               // MI355NDT_OPT_DEBUG_ASYNC_RINGS (test hook): rings whose workgroups take part
+  int arith = 0;                                  // MI355NDT_OPT_ARITH: 0 = the reference recipe's arithmetic, one rounding per operation; 1 = tolerance arithmetic (ndt_sweep.hpp: eval_hit_fast)
+  DevBuf<VoxelRecF> d_recs_fast; bool recs_fast_built = false;   // ... and the records its sweeps read (k_voxels writes them beside d_recs)
+  int f32_sum_order = 0;                          // MI355NDT_OPT_F32_SUM_ORDER: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
+  double gauss_last[3] = {0, 0, 0};               // gauss_d1_/d2_/d3_ as the constructor / the last computeTransformation left them (calculateScore reads them)
+  DevBuf<float> d_score_pts; DevBuf<double> d_score_part;   // calculateScore workspace
+  bool latency_mode = false;                      // mi355ndt_set_latency_mode
+  bool seq_running = false;                       // inside mi355ndt_sequence_run
+  int fine_it = 0;                                // 0: batch-mode sweep items (512 points); 1 / 2: fine items of fine_it * 64 points (latency mode)
+  int fine_tiles = 2;                             // MI355NDT_FINE_TILES overrides (tuning runs)
+  int dyn_shift = -1;                             // < 0: per search mode (make_sweep_const); MI355NDT_SWEEP_DYN_SHIFT overrides (tuning runs)
+  DevBuf<int> d_grid_of;                          // sequence mode: grid index per pair
+  const int* d_grid_of_use = nullptr;             // what the sweeps are given: view of d_grid_of inside mi355ndt_sequence_run, else null (pair b -> grid b)
+  DevBuf<SeqState> d_seq; DevBuf<mi355ndt_seq_frame> d_seq_out; DevBuf<double> d_stamps;
+  PinBuf<volatile int> h_seq_flags; int* d_seq_flags = nullptr;   // mapped pinned: [0] = run finished, [1] = update launches executed; d_seq_flags: the device's view
+  DevBuf<float> d_guess_own;
+  float* d_guess = nullptr;                       // view: d_guess_own or the stream context's input block
+  PinBuf<float> h_pin_guess;                      // pinned staging copy of the caller's guesses (no sync needed after the upload)
+  DevBuf<mi355ndt_result> d_results;
+  DevBuf<int> d_active;                           // per-round active counters
+  DevBuf<int> d_active_list;                      // pairs taking part in the next sweep (compacted by k_update)
+  DevBuf<SweepCtl> d_ctl;                         // two control blocks: the sweep reading one zeroes the other for the next round
+  int ctl_idx = 0;                                // block the NEXT sweep reads (k_init_state / k_update fill it)
+  int n_cu = 256;
+  PinBuf<int> h_pin_active;
+  HipEvent ev_burst[2];                           // one per in-flight burst of align rounds
+  DevBuf<unsigned long long> d_hits;              // [0] (point,voxel) evaluations, all sweeps; [1] score-only sweeps of the one-launch align
+  DevBuf<float> d_hook;                           // 16 + 9 floats, 6 doubles
+  DevBuf<float> d_aligned;
+  PinBuf<float> h_pin_aligned;                    // pinned landing buffer of get_aligned
+  // host-cloud uploads: a ring of pinned staging slots, a copy stream of its own, a device staging buffer per slot.  The caller's
+  // records are compacted to x,y,z into a slot (the only CPU work), the slot goes over PCIe asynchronously and a small kernel
+  // spreads it into the SoA rows; the next call stages the next cloud while this one is still in flight.
+  struct UpSlot { PinBuf<float> h; DevBuf<float> d; HipEvent ev; bool used = false, filling = false; };   // h, d: 3 floats per point
+  static constexpr int UP_SLOTS = 12;             // (a slot grows to the largest transfer it has carried: up to UP_GROUP_MAX clouds = 12.6 MB of 65,536-point clouds)
+  UpSlot up[UP_SLOTS];
+  int up_next = 0;
+  static constexpr int UP_STREAMS = 4;            // an upload rides copy stream (pair + 2 * side) % UP_STREAMS: per-transfer latencies of the SDMA queues
+                                                  // overlap across pairs, uploads into the same rows stay ordered
+  HipStream copy_stream[UP_STREAMS];
+  HipEvent ev_uploads[UP_STREAMS], ev_compute;    // copy streams -> compute stream, compute stream -> copy streams
+  bool uploads_pending = false;
+  std::mutex up_mtx;                              // batch_set_target / batch_set_source may be called from several threads (distinct pairs)
+
+  // asynchronous target build (stream mode: the engine is one batch context of a parent handle).  A build normally waits for two words
+  // from the device -- the bitmap words of all grids (pool size) and the largest grid (sort key width); with a PLAN from earlier builds of
+  // the stream it does not: it sorts plan_cb key bits, clears plan_words pool words, and k_build_check turns every grid of the batch into
+  // "no grid" (and raises its flag in d_bstat) should the batch not fit the plan -- the parent then re-runs that batch synchronously and learns.
+  bool async_build = false;
+  int plan_cb = 0; size_t plan_words = 0;
+  unsigned* d_bstat = nullptr;                    // view: the parent's CtxStat of this context -- [1] total words, [2] largest grid, [3] plan exceeded
+  bool counts_preloaded = false;                  // the parent has put this batch's point counts (and guesses) on the device already
+  bool build_stamped = false;                    // stream mode + profiling: build times come from stamps in the launch's status slot, not from events
+  bool word_off_cleared = false;                 // stream mode: k_stream_inputs has cleared d_word_off for the next build (no fill)
+  size_t last_total_words = 0;                    // of the last synchronous build
+
+  // stream mode: the session (null outside mi355ndt_stream_begin ... mi355ndt_stream_end) and the options it starts with
+  std::unique_ptr<StreamState> ss;
+  int s_thresh_opt = -1;                          // MI355NDT_OPT_STREAM_THRESHOLD
+  int s_reserve_opt = -1;                         // MI355NDT_OPT_STREAM_RESERVE
+
+  // profiling
+  bool prof = false;
+  mi355ndt_profile P{};
+  struct EvSpan { hipEvent_t first, second; bool first_shared; };   // first_shared: `first` is the previous span's `second`
+  std::vector<EvSpan> ev_sweep, ev_update, ev_build;
+  hipEvent_t ev_last = nullptr;                   // end event of the span just closed, reusable as the next span's begin while
+  bool ev_last_fresh = false;                     // nothing else has been enqueued on the stream since
+  std::vector<hipEvent_t> ev_pool;                // idle timing events (filled by mi355ndt_profile_enable)
+  size_t ev_pool_target = 4096;
+
+  ~mi355ndt_handle() {                            // (the profiling pool is not held by owners: its events move between the pool and the spans)
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    for (auto* v : {&ev_sweep, &ev_update, &ev_build})
+      for (auto& e : *v) { if (!e.first_shared) (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+  }
+};
+
+#define HIPCHK(h, call)                                                                          \
+  do {                                                                                           \
+    hipError_t e_ = (call);                                                                      \
+    if (e_ != hipSuccess) {                                                                      \
+      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                              \
+      return MI355NDT_ERR_HIP;                                                                   \
+    }                                                                                            \
+  } while (0)
+
+// several kernels carry the pair index in grid.y (HIP limit 65535)
+#define MAX_PAIRS 65535
+#ifndef UP_GROUP_PAIRS
+#define UP_GROUP_PAIRS 8          // pair slots per upload group of mi355ndt_batch_set_clouds: their targets and sources travel as ONE transfer (measured, 271-pair
+#endif                            // batches of 32-byte records streamed: 2 / 4 / 8 pairs per transfer = 20.2 / 21.4 / 22.2 k registrations/s; one cloud per transfer: 15.4 k)
+#define UP_GROUP_MAX   (2 * UP_GROUP_PAIRS)
+static_assert(UP_GROUP_MAX <= (int)(sizeof(DeintTab::e) / sizeof(DeintTab::e[0])), "k_deinterleave_multi's table");
+// between mi355ndt_stream_begin and mi355ndt_stream_end the handle's batches belong to the stream: the other entry points refuse
+#define NOT_IN_STREAM(h) do { if ((h)->ss) { (h)->err = "the handle is in stream mode (mi355ndt_stream_begin): call mi355ndt_stream_end first"; return MI355NDT_ERR_STATE; } } while (0)
+static inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#elif defined(__aarch64__)
+  asm volatile("yield");
+#endif
+}
+static int ceil_log2(unsigned v) { int b = 0; while ((1u << b) < v) b++; return b; }
+
+// neighbour search mode -> cells probed per point (KDTREE: the 27-cell block + centroid radius test)
+static int neighbor_K(int mode) { return mode == MI355NDT_DIRECT1 ? 1 : mode == MI355NDT_DIRECT7 ? 7 : mode == MI355NDT_DIRECT26 ? 26 : 27; }
+static void build_offsets(int mode, SweepConst& sc) {
+  sc.K = neighbor_K(mode);
+  sc.table = sc.K == 1 ? 0 : sc.K == 7 ? 1 : 2;
+}
+
+static void gauss_constants3(double outlier_ratio, float resolution, double d[3]) {
+  // ndt_omp_impl2.hpp:93-100 (and the constructor, impl2:70-76)
+  double c1 = 10 * (1 - outlier_ratio);
+  double c2 = outlier_ratio / pow((double)resolution, 3);
+  d[2] = -log(c2);
+  d[0] = -log(c1 + c2) - d[2];
+  d[1] = -2 * log((-log(c1 * exp(-0.5) + c2) - d[2]) / d[0]);
+}
+static void gauss_constants(const mi355ndt_params& p, double& d1, double& d2) {
+  double d[3];
+  gauss_constants3(p.outlier_ratio, p.resolution, d);
+  d1 = d[0]; d2 = d[1];
+}
+
+static int check_params(const mi355ndt_params& p) {
+  if (!(p.resolution > 0) || !std::isfinite(p.resolution)) return MI355NDT_ERR_BAD_ARG;
+  if (p.neighbor_mode < 0 || p.neighbor_mode > 3) return MI355NDT_ERR_BAD_ARG;
+  if (p.variant < 0 || p.variant > 1) return MI355NDT_ERR_BAD_ARG;
+  if (p.min_points_per_voxel < 1) return MI355NDT_ERR_BAD_ARG;
+  if (p.max_iterations < 0) return MI355NDT_ERR_BAD_ARG;
+  return MI355NDT_OK;
+}
+
+// impl2:888: the More-Thuente loop (and computeHessian after it) runs iff !(step_max - step_min > 0), step_min = eps/2
+static bool mt_is_live(const mi355ndt_params& p) { return !((p.step_size - p.trans_epsilon / 2) > 0); }
+// MI355NDT_OPT_ARITH = 1 is served for DIRECT1 / DIRECT7 with the dead More-Thuente loop (every configuration lv_slam ships); every other configuration
+// ignores the option altogether: exact kernels, ordered leaf sums, the exact records alone
+static bool fast_served(const mi355ndt_handle* h) {
+  return h->arith == 1 && (h->prm.neighbor_mode == MI355NDT_DIRECT1 || h->prm.neighbor_mode == MI355NDT_DIRECT7) && !mt_is_live(h->prm);
+}
+// ndt_pca + KDTREE: order-dependent weights -- its own per-leaf weights from the build (d_kdw), its own sweep kernel (ndt_sweep_kd.hpp)
+static bool is_pca_kd(const mi355ndt_params& p) { return p.neighbor_mode == MI355NDT_KDTREE && p.variant == MI355NDT_VARIANT_PCA; }
+// May an align of this configuration be ONE persistent launch (ndt_async.hpp)?  Asked by mi355ndt_batch_align and by mi355ndt_stream_begin.
+static bool async_served(const mi355ndt_handle* h) { return h->async_align && !mt_is_live(h->prm) && !is_pca_kd(h->prm); }
+// algorithmic bytes of sweeping `points` points: every point is streamed (12 B) and probes K table words
+static double sweep_alg_bytes(double points, int K) { return points * (12.0 + 4.0 * K); }
+// resident workgroup slots of a sweep launch or a persistent launch; `fast`: the tolerance arithmetic's kernels serve it.  (Callers decide
+// `fast` by sweep_ord(...) == 2 or by fast_served(h); the two differ before the fast records are built: ndt_host_sweep.hpp, sweep_ord.)
+static int launch_slots(const mi355ndt_handle* h, const SweepConst& sc, bool fast) { return h->n_cu * sweep_wpe(sc.pca != 0, sc.K, fast); }

@@ -1,0 +1,125 @@
+// ndt_host_sequence.hpp -- latency mode's switch and the sequence run: a whole scan-to-keyframe sequence pumped without a host decision per frame.
+#pragma once
+
+// ---- latency mode ---------------------------------------------------------------------------------------------------------
+int mi355ndt_set_latency_mode(mi355ndt_handle* h, int on) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  h->latency_mode = on != 0;
+  return MI355NDT_OK;
+}
+
+int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
+                          const double* stamps, const mi355ndt_seq_params* policy,
+                          mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (n_frames < 1 || n_frames > MAX_PAIRS || !clouds || !counts || !stamps || !out_frames || stride < 12) return MI355NDT_ERR_BAD_ARG;
+  if (mt_is_live(h->prm) || (h->prm.neighbor_mode != MI355NDT_DIRECT1 && h->prm.neighbor_mode != MI355NDT_DIRECT7)) {
+    h->err = "sequence mode serves DIRECT1 / DIRECT7 with step_size > transformation_epsilon / 2 (every configuration lv_slam ships)";
+    return MI355NDT_ERR_UNSUPPORTED;
+  }
+  size_t maxn = 0;
+  for (int k = 0; k < n_frames; k++) { if (counts[k] == 0 || counts[k] >= (1u << 31) || !clouds[k]) return MI355NDT_ERR_BAD_ARG; maxn = std::max(maxn, counts[k]); }
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_up0 = std::chrono::steady_clock::now();
+  // every frame is a TARGET slot (its voxel grid is built: it may become a keyframe) and, through the same rows, the SOURCE of its own
+  // align: one cloud buffer serves both sides
+  int rc = mi355ndt_batch_reserve(h, n_frames, maxn, 64);
+  if (rc) return rc;
+  rc = mi355ndt_batch_set_clouds(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, 0);
+  if (rc) return rc;
+  h->d_src = h->d_tgt_own; h->src_pitch = h->tgt_pitch;
+  for (int k = 0; k < n_frames; k++) h->h_src_cnt[k] = h->h_tgt_cnt[k];
+  h->have_source = true;
+  struct Unalias { mi355ndt_handle* h; ~Unalias() { h->d_src = h->d_src_own; h->src_pitch = h->own_src_pitch; std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0);
+                                                     h->have_source = false; h->d_grid_of_use = nullptr; h->aligned_once = false;
+                                                     if (h->ev_compute) (void)compute_enqueued(h); } } unalias{h};   // (error exits too: later uploads wait for what was enqueued)
+  for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));     // (upload time is reported on its own)
+  const auto t_up1 = std::chrono::steady_clock::now();
+  const bool keep_prof = h->prof;
+  struct ProfBack { mi355ndt_handle* h; bool v; ~ProfBack() { h->prof = v; } } profback{h, keep_prof};   // (every exit restores it)
+  h->prof = false;
+  HipEvent ev[3];
+  for (auto& e : ev) HIPCHK(h, e.create(hipEventDefault));
+  hipStream_t s = h->stream;
+  HIPCHK(h, hipEventRecord(ev[0], s));
+  rc = mi355ndt_batch_build_targets(h);
+  if (rc) { h->prof = keep_prof; return rc; }
+  HIPCHK(h, hipEventRecord(ev[1], s));
+  const bool lat = h->latency_mode;
+  h->latency_mode = true; h->seq_running = true;
+  rc = prep_align_ws(h);
+  h->latency_mode = lat; h->seq_running = false;
+  if (rc == MI355NDT_OK && !h->fine_it) { h->err = "sequence run: the fine-grained sweep does not serve this configuration"; rc = MI355NDT_ERR_UNSUPPORTED; }
+  if (rc) { h->prof = keep_prof; return rc; }
+  // one pair is in flight at a time: the fine grid is sized for one pair
+  HIPCHK(h, h->d_grid_of.reserve(n_frames)); HIPCHK(h, h->d_seq_out.reserve(n_frames)); HIPCHK(h, h->d_stamps.reserve(n_frames));
+  HIPCHK(h, h->d_seq.reserve(1));
+  rc = ensure_seq_flags(h);
+  if (rc) { h->prof = keep_prof; return rc; }
+  h->h_seq_flags[0] = 0; h->h_seq_flags[1] = 0;
+  SeqState q0;
+  memset(&q0, 0, sizeof q0);
+  q0.n_frames = n_frames;
+  q0.d_trans = policy ? policy->keyframe_delta_trans : 5.0;                       // scan_matching_odom_nodelet.cpp:67-76
+  q0.d_angle = policy ? policy->keyframe_delta_angle : 0.17;
+  q0.d_time = policy ? policy->keyframe_delta_time : 1.0;
+  HIPCHK(h, hipMemcpyAsync(h->d_seq, &q0, sizeof q0, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->d_stamps, stamps, (size_t)n_frames * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemsetAsync(h->d_grid_of, 0, (size_t)n_frames * sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->d_results, 0, (size_t)n_frames * sizeof(mi355ndt_result), s));
+  HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), s));
+  HIPCHK(h, hipStreamSynchronize(s));            // q0 / stamps are pageable: they must be out of the caller's memory before the pump starts
+  h->ctl_idx = 0;
+  h->d_grid_of_use = h->d_grid_of;
+  SweepConst sc;
+  make_sweep_const(h, sc);
+  sc.rebase_block = 1;                           // every fine sweep also prepares the next update's re-basing (its extra workgroup)
+  gauss_constants3(h->prm.outlier_ratio, h->prm.resolution, h->gauss_last);
+  k_seq_begin<<<1, 64, 0, s>>>(h->d_seq, h->d_state, h->d_grid, h->d_src_cnt, h->d_stamps, h->d_seq_out, h->d_active_list, h->d_ctl, h->d_grid_of, h->d_seq_flags);
+  bool stuck = false;
+  rc = launch_sweep(h, sc, 1);
+  // The pump: (update, sweep), (update, sweep), ... enqueued blindly, at most `depth` rounds ahead of what the device has executed;
+  // whether a launch continues a frame's Newton loop, closes the frame and opens the next, or has nothing left to do is decided
+  // on the device.  The host never waits for a result -- it only reads two words the device writes into mapped memory.
+  const int depth = 12;
+  long long enq = 0;
+  const long long max_launches = (long long)n_frames * (h->prm.max_iterations + 6) + 64;
+  auto t_progress = std::chrono::steady_clock::now();
+  long long seen_last = -1;
+  while (rc == MI355NDT_OK && !h->h_seq_flags[0] && enq < max_launches) {
+    const long long seen = h->h_seq_flags[1];
+    if (seen != seen_last) { seen_last = seen; t_progress = std::chrono::steady_clock::now(); }
+    if (enq - seen >= depth) {
+      // (a device that stops answering -- a faulted kernel -- must not leave the host spinning here)
+      if (std::chrono::steady_clock::now() - t_progress > std::chrono::seconds(20)) { stuck = true; break; }
+      std::this_thread::yield();
+      continue;
+    }
+    k_seq_update<<<1, UPD_THREADS, 0, s>>>(h->d_seq, h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->d_results, h->d_grid, h->d_src_cnt,
+                                           h->d_stamps, h->d_seq_out, h->d_active_list, h->d_ctl + h->ctl_idx, h->d_grid_of, h->d_seq_flags,
+                                           h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations);
+    rc = launch_sweep(h, sc, 1);
+    enq++;
+  }
+  hipError_t e = hipEventRecord(ev[2], s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  h->prof = keep_prof;
+  if (e != hipSuccess) { h->err = std::string("sequence run: ") + hipGetErrorString(e); return MI355NDT_ERR_HIP; }
+  if (rc) return rc;
+  HIPCHK(h, hipGetLastError());
+  if (stuck || !h->h_seq_flags[0]) { h->err = stuck ? "sequence run: the device stopped making progress" : "sequence run did not finish within its launch budget"; return MI355NDT_ERR_STATE; }
+  HIPCHK(h, hipMemcpy(out_frames, h->d_seq_out, (size_t)n_frames * sizeof(mi355ndt_seq_frame), hipMemcpyDeviceToHost));
+  if (out_results) HIPCHK(h, hipMemcpy(out_results, h->d_results, (size_t)n_frames * sizeof(mi355ndt_result), hipMemcpyDeviceToHost));
+  if (stats) {
+    float b_ms = 0, t_ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&b_ms, ev[0], ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&t_ms, ev[1], ev[2]));
+    stats->upload_ms = std::chrono::duration<double, std::milli>(t_up1 - t_up0).count();
+    stats->build_ms = b_ms;
+    stats->track_ms = t_ms;
+    stats->aligns = n_frames > 1 ? n_frames : 0;
+    stats->update_launches = h->h_seq_flags[1];
+  }
+  return compute_enqueued(h);
+}

@@ -105,7 +105,7 @@ typedef struct mi355ndt_profile {
   long long stream_launches; /* stream mode: persistent launches (one per submitted batch + flushes) */
   long long stream_carried;  /* stream mode: pairs handed over from one launch to the next (stragglers that finished under a later batch) */
   long long stream_redone;   /* stream mode: batches re-run synchronously (build plan exceeded, or a launch gave up) */
-  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter / map_cloud: its non-empty keyframes), counted always */
+  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter / map_cloud: its non-empty keyframes / window_keyframe: its non-empty scans / keyframe_add), counted always */
   long long cloud_upload_bytes;
   long long cloud_transfers;  /* host-to-device transfers those clouds travelled in (mi355ndt_batch_set_clouds / stream_submit_host send up to eight clouds per transfer) */
   long long cloud_promotions; /* mi355ndt_promote_source_to_target calls (device-to-device instead of an upload) */
@@ -427,6 +427,42 @@ int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
 int mi355ndt_map_cloud(mi355ndt_handle* h, int n_keyframes, const void* const* clouds, const size_t* counts, size_t stride_bytes,
                        const double* poses, double resolution, void* out_pts, size_t out_capacity,
                        size_t out_stride_bytes, size_t* n_out);
+
+/* ---- keyframes that stay on the device: window map, keyframe store, consumers by id ---------------------- */
+/* replaces the window accumulation and down-sampling of GlobalGraphNodelet::cloud_callback (global_graph_nodelet.cpp:202-244):
+ * scan 0 as it is (:206, :232 `w_cloud = *cloud`), scan k > 0 moved by rel_poses[16k..] = (w_odom.inverse() * odom_k).matrix(),
+ * column-major f64, the way PCL 1.8's transformPointCloud<PointT, double> moves it (:241: x, y, z widened to f64, one rounding
+ * to f32 per coordinate), appended in scan order (:242), then pcl::VoxelGrid(leaf) over the whole window (:214-218: centroids
+ * of x, y, z and -- with intensity_offset_bytes >= 0, the byte offset of an f32 in every record -- of the intensity; f32 sums in
+ * input order; output in ascending voxel index).  rel_poses of scan 0 is ignored (rel_poses may be NULL for one scan).  Points
+ * with a non-finite coordinate are dropped.  leaf <= 0: no down-sampling, the finite points of the window in order; a leaf too
+ * small for the window's extent (PCL's "Leaf size is too small") does the same and says so in mi355ndt_last_error.  The
+ * result stays on the device as keyframe *id; *n_out gets its point count.  MI355NDT_ERR_BAD_ARG for n_scans <= 0, a NaN
+ * leaf, 2^30 points or more in all.  MI355NDT_ERR_STATE in stream mode.  Uses buffers of its own: the batch, grids, prefilter
+ * result and map-cloud workspace of the handle are left as they were. */
+int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const* scans, const size_t* counts, size_t stride_bytes,
+                             int intensity_offset_bytes /* < 0: no intensity */, const double* rel_poses, float leaf,
+                             int* id, size_t* n_out);
+/* The keyframe store.  A keyframe owns [3 or 4][pitch] f32 rows on the device (x, y, z, and the intensity when it carries
+ * one; pitch = count rounded up to 64, the tail zeroed).  Ids count up from 0 and are never reused within a handle; an
+ * unknown or released id is MI355NDT_ERR_BAD_ARG with a message.  mi355ndt_keyframe_add stores a host cloud as it is (no
+ * filtering, non-finite points included).  mi355ndt_keyframe_get writes x, y, z (and, with out_intensity_offset_bytes >= 0,
+ * the intensity, 0 for a keyframe without one) into records of out_stride_bytes; out_pts NULL: the count only; a count above
+ * out_capacity is MI355NDT_ERR_BAD_ARG with *n set.  All are MI355NDT_ERR_STATE in stream mode and leave the rest of the
+ * handle as it was; mi355ndt_destroy frees the keyframes that are left. */
+int mi355ndt_keyframe_add(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes, int intensity_offset_bytes, int* id);
+int mi355ndt_keyframe_get(mi355ndt_handle* h, int id, void* out_pts, size_t out_capacity, size_t out_stride_bytes,
+                          int out_intensity_offset_bytes, size_t* n);
+int mi355ndt_keyframe_release(mi355ndt_handle* h, int id);
+int mi355ndt_keyframe_count(const mi355ndt_handle* h);
+/* mi355ndt_map_cloud over resident keyframes: the same result, word for word, as mi355ndt_map_cloud over the same clouds,
+ * with nothing crossing PCIe on the way in (cloud_uploads does not move).  A keyframe may appear more than once. */
+int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int* ids, const double* poses, double resolution,
+                                 void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
+/* mi355ndt_batch_set_target / _source with a resident keyframe, device to device, after mi355ndt_batch_reserve (the keyframe
+ * must fit the reserved points; the intensity is not carried).  Everything downstream is as after the host-cloud setters. */
+int mi355ndt_batch_set_target_keyframe(mi355ndt_handle* h, int pair, int id);
+int mi355ndt_batch_set_source_keyframe(mi355ndt_handle* h, int pair, int id);
 
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);

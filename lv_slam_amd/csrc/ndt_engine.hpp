@@ -102,6 +102,17 @@ struct mi355ndt_handle {
   PinBuf<unsigned char> h_mc_tab;                 // pinned staging of the keyframe table and the f32 poses
   PinBuf<int> h_mc_ret;                           // pinned landing words: status, depth, last scan position, last head flag
   bool mc_pending = false;                        // a map cloud call returned before its final synchronisation (h_mc_tab may still be read)
+  // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
+  // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice
+  struct Keyframe { DevBuf<float> rows; size_t n = 0, pitch = 0; int ch = 3; };
+  std::map<int, Keyframe> keyframes;
+  int kf_next_id = 0;
+  // window map workspace (mi355ndt_window_keyframe; touches nothing of the batch, grid, prefilter, map cloud or stream state)
+  DevBuf<float> d_kf_in, d_kf_x; DevBuf<unsigned char> d_kf_keep; DevBuf<unsigned> d_kf_keys, d_kf_vals, d_kf_hist, d_kf_offs, d_kf_tmp;
+  DevBuf<int> d_kf_flag, d_kf_pos, d_kf_mm; DevBuf<PfGrid> d_kf_grid; DevBuf<KfScan> d_kf_scans; DevBuf<double> d_kf_T;
+  PinBuf<unsigned char> h_kf_tab;                 // pinned staging of the scan table and the f64 poses
+  PinBuf<int> h_kf_ret;                           // pinned landing words: last scan position, last head flag
+  bool kf_pending = false;                        // a window call returned before its synchronisation (h_kf_tab may still be read)
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 

@@ -1,0 +1,284 @@
+// ndt_host_keyframe.hpp -- keyframes that stay on the device: mi355ndt_window_keyframe (the window map -> keyframe cloud), the keyframe store
+// (mi355ndt_keyframe_add / _get / _release / _count) and the consumers that take ids (mi355ndt_map_cloud_keyframes,
+// mi355ndt_batch_set_target_keyframe / _source_keyframe).  Buffers of their own throughout: the batch, grids, prefilter result and map-cloud
+// workspace of the handle are left as they were.
+#pragma once
+
+static mi355ndt_handle::Keyframe* kf_find(mi355ndt_handle* h, int id, const char* where) {
+  auto it = h->keyframes.find(id);
+  if (it == h->keyframes.end()) {
+    h->err = std::string(where) + ": no keyframe with id " + std::to_string(id) + (id >= 0 && id < h->kf_next_id ? " (released)" : " (never given out)");
+    return nullptr;
+  }
+  return &it->second;
+}
+
+// rows for a keyframe of m points with `ch` channels; an empty keyframe owns nothing
+static int kf_alloc(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, size_t m, int ch) {
+  kf.n = m; kf.ch = ch; kf.pitch = (m + 63) & ~(size_t)63;
+  if (kf.pitch) HIPCHK(h, kf.rows.realloc_exact((size_t)ch * kf.pitch));
+  return MI355NDT_OK;
+}
+
+// ---- window map -> keyframe ------------------------------------------------------------------------
+// replaces the window accumulation and down-sampling of GlobalGraphNodelet::cloud_callback (global_graph_nodelet.cpp:202-244).  The scans go
+// up through the engine's staging as the map cloud's keyframes do; the call waits for the device twice -- the grid's status, as the
+// prefilter does, and the count, which sizes the keyframe's rows -- and returns with the emit kernel enqueued.
+int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const* scans, const size_t* counts, size_t stride_bytes,
+                             int intensity_offset_bytes, const double* rel_poses, float leaf, int* id, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!id || !n_out || n_scans <= 0 || !scans || !counts || (n_scans > 1 && !rel_poses) || std::isnan(leaf)) return MI355NDT_ERR_BAD_ARG;
+  *id = -1; *n_out = 0;
+  const int K = n_scans, ioff = intensity_offset_bytes, ch = ioff >= 0 ? 4 : 3;
+  size_t n = 0, in_total = 0;
+  for (int k = 0; k < K; k++) {
+    if (counts[k] && (!scans[k] || stride_bytes < 12 || (ioff >= 0 && (size_t)ioff + 4 > stride_bytes))) return MI355NDT_ERR_BAD_ARG;
+    n += counts[k];
+    in_total += (size_t)ch * ((counts[k] + 63) & ~(size_t)63);
+    if (n >= (1u << 30)) return MI355NDT_ERR_BAD_ARG;   // (the prefilter's limit: int positions, 32-bit scan)
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  mi355ndt_handle::Keyframe kf;
+  if (n == 0) {                                   // a window without a point: an empty keyframe
+    kf_alloc(h, kf, 0, ch);
+    *id = h->kf_next_id++;
+    h->keyframes.emplace(*id, std::move(kf));
+    return MI355NDT_OK;
+  }
+  hipStream_t s = h->stream;
+  if (h->kf_pending) { HIPCHK(h, hipStreamSynchronize(s)); h->kf_pending = false; }
+  const size_t pitch = (n + 63) & ~(size_t)63;
+  const int nblk = (int)((pitch + KF_CHUNK - 1) / KF_CHUNK);
+  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
+  const int scan_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
+  const size_t tab_bytes = (size_t)K * 12 * sizeof(double) + (size_t)K * sizeof(KfScan);
+  if (in_total > h->d_kf_in.cap || pitch > h->d_kf_pos.cap || (size_t)ch * pitch > h->d_kf_x.cap) {   // re-allocation: nothing of an earlier call may still run (its emit kernel, uploads)
+    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  HIPCHK(h, h->d_kf_in.reserve(in_total)); HIPCHK(h, h->d_kf_x.reserve((size_t)ch * pitch)); HIPCHK(h, h->d_kf_keep.reserve(pitch));
+  HIPCHK(h, h->d_kf_keys.reserve(2 * pitch)); HIPCHK(h, h->d_kf_vals.reserve(2 * pitch)); HIPCHK(h, h->d_kf_flag.reserve(pitch));
+  HIPCHK(h, h->d_kf_hist.reserve((size_t)tiles << RS_MAX_BITS)); HIPCHK(h, h->d_kf_offs.reserve((size_t)tiles << RS_MAX_BITS));
+  HIPCHK(h, h->d_kf_tmp.reserve((size_t)scan_chunks)); HIPCHK(h, h->d_kf_mm.reserve(6)); HIPCHK(h, h->d_kf_grid.reserve(1));
+  HIPCHK(h, h->d_kf_scans.reserve((size_t)K)); HIPCHK(h, h->d_kf_T.reserve((size_t)K * 12));
+  HIPCHK(h, h->h_kf_tab.reserve(tab_bytes)); HIPCHK(h, h->h_kf_ret.reserve(2));
+  HIPCHK(h, h->d_kf_pos.reserve(pitch));          // (last: its capacity vouches for the whole workspace above)
+
+  // scan table and poses ((w_odom.inverse() * odom_k).matrix(), column-major f64 -> row-major rows 0..2), one pinned block
+  double* T = (double*)(unsigned char*)h->h_kf_tab;
+  KfScan* tab = (KfScan*)((unsigned char*)h->h_kf_tab + (size_t)K * 12 * sizeof(double));
+  std::vector<UpItem> items;
+  items.reserve((size_t)K);
+  size_t start = 0, base = 0;
+  for (int k = 0; k < K; k++) {
+    const size_t kp = (counts[k] + 63) & ~(size_t)63;
+    tab[k].rows = h->d_kf_in + base; tab[k].start = (unsigned)start; tab[k].pitch = (unsigned)kp;
+    for (int a = 0; a < 3; a++)
+      for (int j = 0; j < 4; j++) T[12 * k + 4 * a + j] = k == 0 ? (a == j ? 1.0 : 0.0) : rel_poses[16 * k + 4 * j + a];   // (scan 0 is not moved)
+    if (counts[k]) items.push_back(UpItem{h->d_kf_in + base, kp, 0, scans[k], counts[k], stride_bytes, ioff});
+    start += counts[k]; base += (size_t)ch * kp;
+  }
+  h->kf_pending = true;
+  HIPCHK(h, hipMemcpyAsync(h->d_kf_scans, tab, (size_t)K * sizeof(KfScan), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->d_kf_T, T, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+  // the scans: groups of up to UP_GROUP_MAX, one transfer each, staged by up to eight threads (the caller's among them)
+  const int n_groups = (int)((items.size() + UP_GROUP_MAX - 1) / UP_GROUP_MAX);
+  const int nt = std::max(1, std::min(8, n_groups));
+  std::vector<int> rcs((size_t)nt, MI355NDT_OK);
+  std::atomic<int> next_group{0};
+  auto work = [&](int t) {
+    (void)hipSetDevice(h->device);
+    for (int g = next_group.fetch_add(1); g < n_groups; g = next_group.fetch_add(1)) {
+      const size_t i0 = (size_t)g * UP_GROUP_MAX, i1 = std::min(items.size(), i0 + UP_GROUP_MAX);
+      const int rc = upload_items(h, items.data() + i0, (int)(i1 - i0));
+      if (rc != MI355NDT_OK) { rcs[(size_t)t] = rc; return; }
+    }
+  };
+  std::vector<std::thread> th;
+  try {
+    th.reserve((size_t)nt);
+    for (int t = 1; t < nt; t++) th.emplace_back(work, t);
+  } catch (...) {}
+  work(0);
+  for (auto& x : th) x.join();
+  for (int r : rcs) if (r != MI355NDT_OK) return r;
+  int rc = uploads_before_compute(h);
+  if (rc) return rc;
+
+  float* X = h->d_kf_x;
+  const int gx = (int)((pitch + 255) / 256);
+  unsigned *ka = h->d_kf_keys, *kb = ka + pitch, *va = h->d_kf_vals, *vb = va + pitch;
+  k_minmax_init<<<1, 64, 0, s>>>(h->d_kf_mm, 1);
+  k_kf_window<<<nblk, KF_THREADS, 0, s>>>(h->d_kf_scans, K, h->d_kf_T, (int)n, pitch, ch, X, h->d_kf_keep, h->d_kf_mm);
+  int downsample = leaf > 0.f;
+  const unsigned *keys_sorted = ka, *vals_sorted = va;
+  if (downsample) {
+    k_pf_grid<<<1, 1, 0, s>>>(h->d_kf_mm, leaf, h->d_kf_grid);
+    PfGrid g;
+    HIPCHK(h, hipMemcpyAsync(&g, h->d_kf_grid, sizeof g, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    h->kf_pending = false;
+    if (g.status == 2) {                          // PCL: "Leaf size is too small for the input dataset" -> output = input
+      h->err = "window_keyframe: leaf size too small for the window's extent, voxel indices would overflow; window not down-sampled";
+      downsample = 0;
+    } else {
+      k_pf_keys<<<gx, 256, 0, s>>>(X, pitch, (int)n, h->d_kf_keep, h->d_kf_grid, ka, va);
+      const RsPlan plan = rs_plan(31);            // stable sort by voxel index, the whole window one segment (the prefilter's)
+      unsigned *kin = ka, *kout = kb, *vin = va, *vout = vb;
+      for (int p = 0; p < plan.passes; p++) {
+        rs_pass(s, plan.bits, kin, vin, kout, vout, pitch, p * plan.bits, h->d_kf_hist, h->d_kf_offs, tiles, 1, false);
+        std::swap(kin, kout); std::swap(vin, vout);
+      }
+      keys_sorted = kin; vals_sorted = vin;
+    }
+  }
+  k_pf_heads<<<gx, 256, 0, s>>>(keys_sorted, h->d_kf_keep, (int)n, pitch, downsample, h->d_kf_flag);
+  k_pf_scan_totals<<<scan_chunks, 1024, 0, s>>>(h->d_kf_flag, pitch, h->d_kf_tmp);
+  k_pf_scan_offsets<<<1, 1024, 0, s>>>(h->d_kf_tmp, scan_chunks);
+  k_pf_scan_apply<<<scan_chunks, 1024, 0, s>>>(h->d_kf_flag, pitch, h->d_kf_tmp, h->d_kf_pos);
+  HIPCHK(h, hipGetLastError());
+  int* ret = h->h_kf_ret;
+  HIPCHK(h, hipMemcpyAsync(ret, h->d_kf_pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(ret + 1, h->d_kf_flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  h->kf_pending = false;
+  const size_t m = (size_t)ret[0] + (size_t)ret[1];
+  rc = kf_alloc(h, kf, m, ch);
+  if (rc) return rc;
+  if (m) {
+    k_kf_emit<<<gx, 256, 0, s>>>(X, pitch, keys_sorted, vals_sorted, h->d_kf_flag, h->d_kf_pos, downsample, ch, kf.rows, kf.pitch, m);
+    HIPCHK(h, hipGetLastError());
+  }
+  *id = h->kf_next_id++;
+  *n_out = m;
+  h->keyframes.emplace(*id, std::move(kf));
+  return MI355NDT_OK;
+}
+
+// ---- keyframe store ---------------------------------------------------------------------------------
+// a host cloud as it is (x, y, z and, with intensity_offset_bytes >= 0, the f32 at that offset of every record)
+int mi355ndt_keyframe_add(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes, int intensity_offset_bytes, int* id) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  const int ioff = intensity_offset_bytes, ch = ioff >= 0 ? 4 : 3;
+  if (!id || (n && (!pts || stride_bytes < 12 || (ioff >= 0 && (size_t)ioff + 4 > stride_bytes))) || n >= (1u << 30)) return MI355NDT_ERR_BAD_ARG;
+  *id = -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  mi355ndt_handle::Keyframe kf;
+  int rc = kf_alloc(h, kf, n, ch);
+  if (rc) return rc;
+  if (n) {
+    const UpItem it = {kf.rows, kf.pitch, 0, pts, n, stride_bytes, ioff};
+    rc = upload_items(h, &it, 1);
+    if (rc) {                                     // (the rows go away with kf: nothing of a transfer may still be under way into them)
+      for (hipStream_t cs : h->copy_stream) (void)hipStreamSynchronize(cs);
+      return rc;
+    }
+  }
+  *id = h->kf_next_id++;
+  h->keyframes.emplace(*id, std::move(kf));
+  return MI355NDT_OK;
+}
+
+int mi355ndt_keyframe_get(mi355ndt_handle* h, int id, void* out_pts, size_t out_capacity, size_t out_stride_bytes, int out_intensity_offset_bytes,
+                          size_t* n) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!n) return MI355NDT_ERR_BAD_ARG;
+  *n = 0;
+  const mi355ndt_handle::Keyframe* kf = kf_find(h, id, "keyframe_get");
+  if (!kf) return MI355NDT_ERR_BAD_ARG;
+  *n = kf->n;
+  if (!out_pts || kf->n == 0) return MI355NDT_OK;
+  const int ioff = out_intensity_offset_bytes;
+  if (out_stride_bytes < 12 || (ioff >= 0 && (size_t)ioff + 4 > out_stride_bytes) || kf->n > out_capacity) return MI355NDT_ERR_BAD_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = uploads_before_compute(h);             // (a keyframe_add's transfer may still be on its way)
+  if (rc) return rc;
+  std::vector<float> tmp((size_t)kf->ch * kf->pitch);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), kf->rows, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned char* o = (unsigned char*)out_pts;
+  const size_t p = kf->pitch;
+  for (size_t i = 0; i < kf->n; i++) {
+    const float v[3] = {tmp[i], tmp[p + i], tmp[2 * p + i]};
+    memcpy(o + i * out_stride_bytes, v, 12);
+    if (ioff >= 0) { const float w = kf->ch == 4 ? tmp[3 * p + i] : 0.f; memcpy(o + i * out_stride_bytes + ioff, &w, 4); }
+  }
+  return MI355NDT_OK;
+}
+
+int mi355ndt_keyframe_release(mi355ndt_handle* h, int id) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!kf_find(h, id, "keyframe_release")) return MI355NDT_ERR_BAD_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));   // nothing enqueued may still read or fill the rows
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->mc_pending = false;
+  h->keyframes.erase(id);
+  return MI355NDT_OK;
+}
+
+int mi355ndt_keyframe_count(const mi355ndt_handle* h) { return !h ? MI355NDT_ERR_BAD_HANDLE : h->ss ? MI355NDT_ERR_STATE : (int)h->keyframes.size(); }
+
+// ---- consumers by id -------------------------------------------------------------------------------
+// mi355ndt_map_cloud over resident keyframes: the McKf table points into the store, nothing is staged
+int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int* ids, const double* poses, double resolution,
+                                 void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!n_out || n_keyframes < 0 || (out_pts && out_stride_bytes < 12)) return MI355NDT_ERR_BAD_ARG;
+  *n_out = 0;
+  if (n_keyframes == 0) return MI355NDT_OK;
+  if (!(resolution > 0) || !std::isfinite(resolution) || !ids || !poses) return MI355NDT_ERR_BAD_ARG;
+  const int K = n_keyframes;
+  size_t n = 0;
+  for (int k = 0; k < K; k++) {
+    const mi355ndt_handle::Keyframe* kf = kf_find(h, ids[k], "map_cloud_keyframes");
+    if (!kf) return MI355NDT_ERR_BAD_ARG;
+    n += kf->n;
+    if (n >= (1u << 30)) return MI355NDT_ERR_BAD_ARG;
+  }
+  if (n == 0) return MI355NDT_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = mc_reserve(h, K, n, 0);
+  if (rc) return rc;
+  McKf* tab = (McKf*)(unsigned char*)h->h_mc_tab;
+  size_t start = 0;
+  for (int k = 0; k < K; k++) {
+    const mi355ndt_handle::Keyframe& kf = h->keyframes.find(ids[k])->second;
+    tab[k].rows = kf.rows; tab[k].start = (unsigned)start; tab[k].pitch = (unsigned)kf.pitch;
+    start += kf.n;
+  }
+  return mc_generate(h, K, n, poses, resolution, out_pts, out_capacity, out_stride_bytes, n_out);
+}
+
+// A resident keyframe into a slot of the engine's own batch rows, device to device: what mi355ndt_batch_set_target / _source do with a host
+// cloud (the slot's rows zero-filled up to the pitch), with the bookkeeping of mi355ndt_use_prefiltered.
+static int batch_set_side_keyframe(mi355ndt_handle* h, bool tgt, int pair, int id) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (pair < 0 || pair >= h->n_pairs || (tgt ? h->d_tgt != h->d_tgt_own : h->d_src != h->d_src_own)) return MI355NDT_ERR_BAD_ARG;
+  const mi355ndt_handle::Keyframe* kf = kf_find(h, id, tgt ? "batch_set_target_keyframe" : "batch_set_source_keyframe");
+  if (!kf) return MI355NDT_ERR_BAD_ARG;
+  const size_t dp = tgt ? h->tgt_pitch : h->src_pitch;
+  if (kf->n > dp) { h->err = "batch_set_*_keyframe: the keyframe has more points than mi355ndt_batch_reserve made room for"; return MI355NDT_ERR_BAD_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = uploads_before_compute(h);             // an earlier upload into the same rows must not land after these copies
+  if (rc) return rc;
+  float* dst = (tgt ? h->d_tgt_own : h->d_src_own) + (size_t)pair * 3 * dp;
+  HIPCHK(h, hipMemsetAsync(dst, 0, 3 * dp * sizeof(float), h->stream));
+  for (int a = 0; a < 3; a++)
+    if (kf->n) HIPCHK(h, hipMemcpyAsync(dst + a * dp, kf->rows + a * kf->pitch, kf->n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  {
+    std::lock_guard<std::mutex> lk(h->up_mtx);
+    (tgt ? h->h_tgt_cnt : h->h_src_cnt)[(size_t)pair] = (int)kf->n;
+    if (tgt) h->targets_built = false;
+    (tgt ? h->have_target : h->have_source) = true;
+  }
+  return compute_enqueued(h);                     // a later upload into these rows waits for the copies
+}
+int mi355ndt_batch_set_target_keyframe(mi355ndt_handle* h, int pair, int id) { return batch_set_side_keyframe(h, true, pair, id); }
+int mi355ndt_batch_set_source_keyframe(mi355ndt_handle* h, int pair, int id) { return batch_set_side_keyframe(h, false, pair, id); }

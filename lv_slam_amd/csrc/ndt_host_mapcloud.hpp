@@ -2,6 +2,35 @@
 #pragma once
 
 // ---- map cloud ----------------------------------------------------------------------------------
+// The map cloud has two routes to its keyframes and one way on from there: mi355ndt_map_cloud stages host clouds into d_mc_in,
+// mi355ndt_map_cloud_keyframes (ndt_host_keyframe.hpp) reads the keyframe store.  Both size the workspace with mc_reserve, fill the McKf
+// table in h_mc_tab (an address per keyframe) and hand over to mc_generate, which runs from the transform kernel to the output.
+static int mc_reserve(mi355ndt_handle* h, int K, size_t n, size_t in_total) {
+  hipStream_t s = h->stream;
+  if (h->mc_pending) { HIPCHK(h, hipStreamSynchronize(s)); h->mc_pending = false; }
+  const size_t pitch = (n + 63) & ~(size_t)63;
+  const int nchunks = (int)((pitch + MC_CHUNK - 1) / MC_CHUNK);
+  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
+  const int scan_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
+  const size_t tab_bytes = (size_t)K * sizeof(McKf) + (size_t)K * 12 * sizeof(float);
+  if (in_total > h->d_mc_in.cap || pitch > h->d_mc_pos.cap) {   // re-allocation: nothing of an earlier call may still run (uploads included)
+    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  HIPCHK(h, h->d_mc_in.reserve(in_total)); HIPCHK(h, h->d_mc_x.reserve(3 * pitch)); HIPCHK(h, h->d_mc_out.reserve(3 * pitch));
+  HIPCHK(h, h->d_mc_fin.reserve(pitch)); HIPCHK(h, h->d_mc_aabb.reserve(6 * (size_t)nchunks));
+  HIPCHK(h, h->d_mc_keys.reserve(4 * pitch)); HIPCHK(h, h->d_mc_flag.reserve(pitch));
+  HIPCHK(h, h->d_mc_hist.reserve((size_t)tiles << RS_MAX_BITS)); HIPCHK(h, h->d_mc_offs.reserve((size_t)tiles << RS_MAX_BITS));
+  HIPCHK(h, h->d_mc_tmp.reserve((size_t)scan_chunks));
+  HIPCHK(h, h->d_mc_kf.reserve((size_t)K)); HIPCHK(h, h->d_mc_T.reserve((size_t)K * 12)); HIPCHK(h, h->d_mc_box.reserve(1));
+  HIPCHK(h, h->h_mc_tab.reserve(tab_bytes)); HIPCHK(h, h->h_mc_ret.reserve(4));
+  HIPCHK(h, h->d_mc_pos.reserve(pitch));          // (last: its capacity vouches for the whole workspace above)
+  return MI355NDT_OK;
+}
+
+static int mc_generate(mi355ndt_handle* h, int K, size_t n, const double* poses, double resolution, void* out_pts, size_t out_capacity,
+                       size_t out_stride_bytes, size_t* n_out);
+
 // replaces MapCloudGenerator::generate (src/global_graph/map_cloud_generator.cpp:17-55; global_graph_nodelet.cpp:725-745, 1036-1046): the
 // keyframes' clouds go up through the engine's staging (up to UP_GROUP_MAX clouds per transfer, a few staging threads), one SoA row set per
 // keyframe in a buffer of the map cloud's own; every kernel runs on the engine's stream and the call synchronises once, for the count.
@@ -23,43 +52,19 @@ int mi355ndt_map_cloud(mi355ndt_handle* h, int n_keyframes, const void* const* c
   }
   if (n == 0) return MI355NDT_OK;                 // no point at all: no octree leaf
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  if (h->mc_pending) { HIPCHK(h, hipStreamSynchronize(s)); h->mc_pending = false; }
-  const size_t pitch = (n + 63) & ~(size_t)63;
-  const int nchunks = (int)((pitch + MC_CHUNK - 1) / MC_CHUNK);
-  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
-  const int scan_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
-  const size_t tab_bytes = (size_t)K * sizeof(McKf) + (size_t)K * 12 * sizeof(float);
-  if (in_total > h->d_mc_in.cap || pitch > h->d_mc_pos.cap) {   // re-allocation: nothing of an earlier call may still run (uploads included)
-    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
-    HIPCHK(h, hipStreamSynchronize(s));
-  }
-  HIPCHK(h, h->d_mc_in.reserve(in_total)); HIPCHK(h, h->d_mc_x.reserve(3 * pitch)); HIPCHK(h, h->d_mc_out.reserve(3 * pitch));
-  HIPCHK(h, h->d_mc_fin.reserve(pitch)); HIPCHK(h, h->d_mc_aabb.reserve(6 * (size_t)nchunks));
-  HIPCHK(h, h->d_mc_keys.reserve(4 * pitch)); HIPCHK(h, h->d_mc_flag.reserve(pitch));
-  HIPCHK(h, h->d_mc_hist.reserve((size_t)tiles << RS_MAX_BITS)); HIPCHK(h, h->d_mc_offs.reserve((size_t)tiles << RS_MAX_BITS));
-  HIPCHK(h, h->d_mc_tmp.reserve((size_t)scan_chunks));
-  HIPCHK(h, h->d_mc_kf.reserve((size_t)K)); HIPCHK(h, h->d_mc_T.reserve((size_t)K * 12)); HIPCHK(h, h->d_mc_box.reserve(1));
-  HIPCHK(h, h->h_mc_tab.reserve(tab_bytes)); HIPCHK(h, h->h_mc_ret.reserve(4));
-  HIPCHK(h, h->d_mc_pos.reserve(pitch));          // (last: its capacity vouches for the whole workspace above)
+  int rc = mc_reserve(h, K, n, in_total);
+  if (rc) return rc;
 
-  // keyframe table and poses (Matrix4f pose = keyframe->pose.matrix().cast<float>(), map_cloud_generator.cpp:31), one pinned block
   McKf* kf = (McKf*)(unsigned char*)h->h_mc_tab;
-  float* T = (float*)((unsigned char*)h->h_mc_tab + (size_t)K * sizeof(McKf));
   std::vector<UpItem> items;
   items.reserve((size_t)K);
   size_t start = 0, base = 0;
   for (int k = 0; k < K; k++) {
     const size_t kp = (counts[k] + 63) & ~(size_t)63;
-    kf[k].base = base; kf[k].start = (unsigned)start; kf[k].pitch = (unsigned)kp;
-    for (int a = 0; a < 3; a++)
-      for (int j = 0; j < 4; j++) T[12 * k + 4 * a + j] = (float)poses[16 * k + 4 * j + a];   // column-major f64 -> row-major f32 rows 0..2
+    kf[k].rows = h->d_mc_in + base; kf[k].start = (unsigned)start; kf[k].pitch = (unsigned)kp;
     if (counts[k]) items.push_back(UpItem{h->d_mc_in + base, kp, 0, clouds[k], counts[k], stride_bytes});
     start += counts[k]; base += 3 * kp;
   }
-  h->mc_pending = true;
-  HIPCHK(h, hipMemcpyAsync(h->d_mc_kf, kf, (size_t)K * sizeof(McKf), hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(h->d_mc_T, T, (size_t)K * 12 * sizeof(float), hipMemcpyHostToDevice, s));
   // the clouds: groups of up to UP_GROUP_MAX keyframes, one transfer each, staged by up to eight threads (the caller's among them)
   const int n_groups = (int)((items.size() + UP_GROUP_MAX - 1) / UP_GROUP_MAX);
   const int nt = std::max(1, std::min(8, n_groups));
@@ -80,14 +85,34 @@ int mi355ndt_map_cloud(mi355ndt_handle* h, int n_keyframes, const void* const* c
   } catch (...) {}
   work(0);
   for (auto& x : th) x.join();
-  for (int rc : rcs) if (rc != MI355NDT_OK) return rc;
+  for (int r : rcs) if (r != MI355NDT_OK) return r;
+  return mc_generate(h, K, n, poses, resolution, out_pts, out_capacity, out_stride_bytes, n_out);
+}
+
+// From the transform kernel on.  h_mc_tab holds the McKf table of the K keyframes (n points in all); the poses become the f32 rows behind
+// it (Matrix4f pose = keyframe->pose.matrix().cast<float>(), map_cloud_generator.cpp:31), one pinned block, two copies.
+static int mc_generate(mi355ndt_handle* h, int K, size_t n, const double* poses, double resolution, void* out_pts, size_t out_capacity,
+                       size_t out_stride_bytes, size_t* n_out) {
+  hipStream_t s = h->stream;
+  const size_t pitch = (n + 63) & ~(size_t)63;
+  const int nchunks = (int)((pitch + MC_CHUNK - 1) / MC_CHUNK);
+  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
+  const int scan_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
+  McKf* kf = (McKf*)(unsigned char*)h->h_mc_tab;
+  float* T = (float*)((unsigned char*)h->h_mc_tab + (size_t)K * sizeof(McKf));
+  for (int k = 0; k < K; k++)
+    for (int a = 0; a < 3; a++)
+      for (int j = 0; j < 4; j++) T[12 * k + 4 * a + j] = (float)poses[16 * k + 4 * j + a];   // column-major f64 -> row-major f32 rows 0..2
+  h->mc_pending = true;
+  HIPCHK(h, hipMemcpyAsync(h->d_mc_kf, kf, (size_t)K * sizeof(McKf), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->d_mc_T, T, (size_t)K * 12 * sizeof(float), hipMemcpyHostToDevice, s));
   int rc = uploads_before_compute(h);
   if (rc) return rc;
 
   float* X = h->d_mc_x;
   unsigned *lo_a = h->d_mc_keys, *lo_b = lo_a + pitch, *hi_a = lo_b + pitch, *hi_b = hi_a + pitch;
   const int gx = (int)((pitch + 255) / 256);
-  k_mc_transform<<<nchunks, MC_THREADS, 0, s>>>(h->d_mc_in, h->d_mc_kf, K, h->d_mc_T, (int)n, pitch, X, h->d_mc_fin, h->d_mc_aabb);
+  k_mc_transform<<<nchunks, MC_THREADS, 0, s>>>(h->d_mc_kf, K, h->d_mc_T, (int)n, pitch, X, h->d_mc_fin, h->d_mc_aabb);
   k_mc_box<<<1, MC_THREADS, 0, s>>>(X, pitch, h->d_mc_fin, h->d_mc_aabb, (int)n, resolution, h->d_mc_box);
   k_mc_keys<<<gx, 256, 0, s>>>(X, pitch, h->d_mc_fin, h->d_mc_box, resolution, lo_a, hi_a);
   // Stable LSD sort of the 64-bit codes with ndt_segsort.hpp's passes: the low words carrying the high words, then the high words carrying the

@@ -98,14 +98,17 @@ static int compute_enqueued(mi355ndt_handle* h) {       // call after enqueueing
 // hipMemcpyAsync + one k_deinterleave_multi launch + one event, whatever the number of clouds in it: with one cloud per transfer the ~50 us of
 // HIP calls per cloud, serialised under the engine's lock, held the staging of a 271-pair batch to 60 GB/s of records read whatever the number
 // of staging threads (round 6, tools/host_stage_probe.cpp: the same compaction alone reaches 180-195 GB/s at eight threads on the same host).
-struct UpItem { float* d_base; size_t pitch; int pair; const void* pts; size_t n, stride; };
+// ioff >= 0: the record's f32 at that byte offset (its intensity) travels as a fourth word and lands in a fourth row behind x, y, z
+struct UpItem { float* d_base; size_t pitch; int pair; const void* pts; size_t n, stride; int ioff = -1; };
 static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
   if (cnt < 1 || cnt > UP_GROUP_MAX) return MI355NDT_ERR_BAD_ARG;
-  size_t total = 0;
+  size_t total = 0;                               // words staged: 3 per point (4 with the intensity, each such cloud starting on a 16-byte boundary)
   for (int k = 0; k < cnt; k++) {
     if (!it[k].pts && it[k].n) return MI355NDT_ERR_BAD_ARG;
     if ((it[k].n && it[k].stride < 12) || it[k].n > it[k].pitch) return MI355NDT_ERR_BAD_ARG;
-    total += it[k].n;
+    if (it[k].n && it[k].ioff >= 0 && (size_t)it[k].ioff + 4 > it[k].stride) return MI355NDT_ERR_BAD_ARG;
+    if (it[k].ioff >= 0) total = (total + 3) & ~(size_t)3;
+    total += (it[k].ioff >= 0 ? 4 : 3) * it[k].n;
   }
   mi355ndt_handle::UpSlot* u = nullptr;
   for (;;) {                                      // a slot no other thread is filling right now
@@ -122,9 +125,9 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
   hipError_t e = hipSuccess;
   if (!u->ev) e = u->ev.create();
   if (e == hipSuccess && u->used) e = hipEventSynchronize(u->ev);      // the slot's previous transfer has to be out of the pinned buffer
-  if (e == hipSuccess && 3 * total > std::min(u->h.cap, u->d.cap)) {
+  if (e == hipSuccess && total > std::min(u->h.cap, u->d.cap)) {
     u->used = false;
-    const size_t cap = 3 * std::max(total, (size_t)65536);
+    const size_t cap = std::max(total, (size_t)3 * 65536);
     e = u->h.realloc_exact(cap);
     if (e == hipSuccess) e = u->d.realloc_exact(cap);
   }
@@ -134,18 +137,23 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
     u->filling = false;
     return MI355NDT_ERR_HIP;
   }
-  // the CPU part, outside the lock: x,y,z of every record into the pinned slot, cloud after cloud
+  // the CPU part, outside the lock: x,y,z (and the intensity, where asked for) of every record into the pinned slot, cloud after cloud
   DeintTab tab;
   tab.cnt = cnt;
-  size_t off = 0, max_pitch = 0;
+  size_t off = 0, max_pitch = 0;                  // off: words
   for (int k = 0; k < cnt; k++) {
     const unsigned char* p = (const unsigned char*)it[k].pts;
-    float* dst = u->h + 3 * off;
     const size_t n = it[k].n, stride = it[k].stride;
-    if (stride == 12) { if (n) memcpy(dst, p, n * 12); }
+    const int ioff = it[k].ioff;
+    if (ioff >= 0) off = (off + 3) & ~(size_t)3;
+    float* dst = u->h + off;
+    if (ioff >= 0) {
+      if (stride == 16 && ioff == 12) { if (n) memcpy(dst, p, n * 16); }
+      else for (size_t i = 0; i < n; i++) { memcpy(dst + 4 * i, p + i * stride, 12); memcpy(dst + 4 * i + 3, p + i * stride + ioff, 4); }
+    } else if (stride == 12) { if (n) memcpy(dst, p, n * 12); }
     else for (size_t i = 0; i < n; i++) memcpy(dst + 3 * i, p + i * stride, 12);
-    tab.e[k].src_off = 3 * off; tab.e[k].n = (int)n; tab.e[k].rows = it[k].d_base + (size_t)it[k].pair * 3 * it[k].pitch; tab.e[k].pitch = it[k].pitch;
-    off += n;
+    tab.e[k].src_off = off; tab.e[k].n = (int)n; tab.e[k].w4 = ioff >= 0; tab.e[k].rows = it[k].d_base + (size_t)it[k].pair * 3 * it[k].pitch; tab.e[k].pitch = it[k].pitch;
+    off += (ioff >= 0 ? 4 : 3) * n;
     max_pitch = std::max(max_pitch, it[k].pitch);
   }
   {
@@ -154,7 +162,7 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
     // then set_source(B) with no build / align in between -- ride one stream and land in call order (a group never spans two stream classes:
     // mi355ndt_batch_set_clouds groups pairs by pair / UP_GROUP_PAIRS)
     hipStream_t cs = h->copy_stream[(it[0].pair / UP_GROUP_PAIRS) % mi355ndt_handle::UP_STREAMS];
-    if (total) e = hipMemcpyAsync(u->d, u->h, total * 3 * sizeof(float), hipMemcpyHostToDevice, cs);
+    if (total) e = hipMemcpyAsync(u->d, u->h, total * sizeof(float), hipMemcpyHostToDevice, cs);
     if (e == hipSuccess) {
       k_deinterleave_multi<<<dim3((unsigned)((max_pitch + 255) / 256), (unsigned)cnt), 256, 0, cs>>>(u->d, tab);
       e = hipEventRecord(u->ev, cs);
@@ -163,7 +171,7 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
     u->filling = false;
     h->uploads_pending = true;
     h->P.cloud_uploads += cnt;                     // (counted whether or not event profiling is on: tests/test_adaptor.py holds the drop-in to one per frame)
-    h->P.cloud_upload_bytes += (long long)(total * 3 * sizeof(float));
+    h->P.cloud_upload_bytes += (long long)(total * sizeof(float));
     h->P.cloud_transfers++;
     if (e != hipSuccess) { h->err = std::string("upload: ") + hipGetErrorString(e); return MI355NDT_ERR_HIP; }
   }

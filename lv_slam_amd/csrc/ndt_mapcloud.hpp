@@ -18,7 +18,7 @@
 
 enum { MC_OK = 0, MC_EMPTY = 1, MC_DEPTH = 2, MC_ITERS = 3 };
 
-struct McKf { unsigned long long base; unsigned start, pitch; };   // keyframe k: x,y,z rows of `pitch` at in + base; global index of its first point
+struct McKf { const float* rows; unsigned start, pitch; };   // keyframe k: its x,y,z rows of `pitch` floats (staged or resident); global index of its first point
 // The box after each point that changed it (the first finite point, then every point that grew it).  A point is keyed in the box of the
 // last event at or before it, as addPointIdx keys it right after adoptBoundingBoxToPoint; `shift` = what the later growth levels add to
 // that key (the old root hung below a new one as child (!upX << 2 | !upY << 1 | !upZ): +2^depth on every axis that grew downwards).
@@ -50,7 +50,7 @@ __device__ __forceinline__ unsigned mc_compact3(unsigned long long x) {
 // Vector4f with w = 1 (map_cloud_generator.cpp:31-35): ((M[a][0] x + M[a][1] y) + M[a][2] z) + M[a][3], every f32 step rounded (-ffp-contract=off).
 // T: per keyframe the three upper rows of pose.cast<float>(), row-major.  aabb: per chunk the ordered-int extremes of its finite points
 // (INT_MAX / INT_MIN: none).
-__global__ void __launch_bounds__(MC_THREADS) k_mc_transform(const float* __restrict__ in, const McKf* __restrict__ kf, int n_kf,
+__global__ void __launch_bounds__(MC_THREADS) k_mc_transform(const McKf* __restrict__ kf, int n_kf,
                                                              const float* __restrict__ T, int n, size_t pitch, float* X, unsigned char* fin, int* aabb) {
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
   const int g0 = blockIdx.x * MC_CHUNK + threadIdx.x;
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_transform(const float* __rest
     if (g < n) {
       while (k + 1 < n_kf && (int)kf[k + 1].start <= g) k++;
       const McKf e = kf[k];
-      const float* R = in + e.base;
+      const float* R = e.rows;
       const int j = g - (int)e.start;
       const float x = R[j], y = R[e.pitch + j], z = R[2 * (size_t)e.pitch + j];
       const float* M = T + 12 * (size_t)k;

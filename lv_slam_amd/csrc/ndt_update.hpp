@@ -516,17 +516,22 @@ NDT_KERNEL void __launch_bounds__(256) k_deinterleave(const float* __restrict__ 
 }
 
 
-// ... and several clouds of one transfer at once (grid.y = cloud): mi355_ndt.hip, upload_items
-struct DeintTab { int cnt, pad_; struct { unsigned long long src_off; float* rows; unsigned long long pitch; int n, pad_; } e[16]; };
+// ... and several clouds of one transfer at once (grid.y = cloud): mi355_ndt.hip, upload_items.  A cloud staged with its intensity (w4: four
+// words per record) fills a fourth row; the others are read and written exactly as before.
+struct DeintTab { int cnt, pad_; struct { unsigned long long src_off; float* rows; unsigned long long pitch; int n, w4; } e[16]; };
 NDT_KERNEL void __launch_bounds__(256) k_deinterleave_multi(const float* __restrict__ packed, const DeintTab tab) {
   const int c = blockIdx.y;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t pitch = tab.e[c].pitch;
   if (i >= pitch) return;
   const float* xyz = packed + tab.e[c].src_off;
-  float x = 0.f, y = 0.f, z = 0.f;
-  if (i < (size_t)tab.e[c].n) { x = xyz[3 * i]; y = xyz[3 * i + 1]; z = xyz[3 * i + 2]; }
   float* rows = tab.e[c].rows;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (tab.e[c].w4) {
+    float w = 0.f;
+    if (i < (size_t)tab.e[c].n) { const float4 r = *(const float4*)(xyz + 4 * i); x = r.x; y = r.y; z = r.z; w = r.w; }
+    rows[3 * pitch + i] = w;
+  } else if (i < (size_t)tab.e[c].n) { x = xyz[3 * i]; y = xyz[3 * i + 1]; z = xyz[3 * i + 2]; }
   rows[i] = x; rows[pitch + i] = y; rows[2 * pitch + i] = z;
 }
 

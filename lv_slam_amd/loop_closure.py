@@ -77,7 +77,7 @@ def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range
     """Verify loop candidates against one new keyframe on the batch surface: the target in every slot, candidate k as the source of
     slot k, ONE batch_align from `guesses` ([K,4,4], e.g. loop_guess per candidate), ONE batch_fitness_scores(max_range), then
     select_matching (bow=None) or select_matching_and_bow (bow = [(bow_score, candidate index), ...] in query order; only the candidates
-    it names are aligned).  The engine's parameters are the registration's (resolution, epsilon, iterations, search method).
+    it names are aligned).  `target` and every candidate is a host cloud or the id of a resident keyframe.  The engine's parameters are the registration's (resolution, epsilon, iterations, search method).
     Returns select_*'s tuple: (candidate index or None, relative pose, best score, aligns the sequential reference would have run)."""
     K = len(candidates)
     if K == 0:
@@ -88,12 +88,16 @@ def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range
     slots = list(range(K)) if bow is None else list(dict.fromkeys(int(c) for _, c in bow))
     if not slots:
         return None, None, DBL_MAX, 0
-    tgt = ndt._as_points(target)
-    srcs = [ndt._as_points(candidates[c]) for c in slots]
-    engine.batch_reserve(len(slots), max(len(tgt), 1), max(max(len(s) for s in srcs), 1))
+    # a keyframe is a host cloud ([N,>=3] array) or the id (int) of a keyframe resident in the engine's store (Engine.window_keyframe /
+    # keyframe_add): ids go into the batch rows device to device, arrays are uploaded as before
+    is_id = lambda c: isinstance(c, (int, np.integer))
+    size = lambda c: engine.keyframe_get(c, fetch=False) if is_id(c) else len(c)
+    tgt = target if is_id(target) else ndt._as_points(target)
+    srcs = [candidates[c] if is_id(candidates[c]) else ndt._as_points(candidates[c]) for c in slots]
+    engine.batch_reserve(len(slots), max(size(tgt), 1), max(max(size(s) for s in srcs), 1))
     for k, s in enumerate(srcs):
-        engine.batch_set_target(k, tgt)
-        engine.batch_set_source(k, s)
+        (engine.batch_set_target_keyframe if is_id(tgt) else engine.batch_set_target)(k, tgt)
+        (engine.batch_set_source_keyframe if is_id(s) else engine.batch_set_source)(k, s)
     res = engine.batch_align(G[slots])
     sc, _ = engine.batch_fitness_scores(max_range)
     converged, scores, finals = [False] * K, [DBL_MAX] * K, [None] * K

@@ -88,6 +88,8 @@ SYMBOLS = [
     "mi355ndt_calculate_score", "mi355ndt_convert_transform", "mi355ndt_set_option", "mi355ndt_get_option",
     "mi355ndt_stream_begin", "mi355ndt_stream_submit", "mi355ndt_stream_submit_host", "mi355ndt_stream_collect", "mi355ndt_stream_end", "mi355ndt_stream_pose_records", "mi355ndt_pack_pose_records",
     "mi355ndt_map_cloud",
+    "mi355ndt_window_keyframe", "mi355ndt_keyframe_add", "mi355ndt_keyframe_get", "mi355ndt_keyframe_release", "mi355ndt_keyframe_count",
+    "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
 ]
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
@@ -133,6 +135,14 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_prefilter.argtypes = [vp, vp, sz, sz, i, C.c_double, C.c_double, C.c_float, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
+    L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
+    L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
+    L.mi355ndt_keyframe_get.argtypes = [vp, i, vp, sz, sz, i, C.POINTER(sz)]
+    L.mi355ndt_keyframe_release.argtypes = [vp, i]
+    L.mi355ndt_keyframe_count.argtypes = [vp]
+    L.mi355ndt_map_cloud_keyframes.argtypes = [vp, i, vp, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
+    L.mi355ndt_batch_set_target_keyframe.argtypes = [vp, i, i]
+    L.mi355ndt_batch_set_source_keyframe.argtypes = [vp, i, i]
     L.mi355ndt_derivatives.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mi355ndt_derivatives_T.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi355ndt_compute_hessian.argtypes = [vp, vp, vp]
@@ -334,6 +344,87 @@ class Engine:
                                               out.ctypes.data_as(C.c_void_p) if fetch else None, n, 12, C.byref(n_out)), "map_cloud")
         return out[: n_out.value].copy() if fetch else n_out.value
 
+    # -- keyframes that stay on the device
+    @staticmethod
+    def _records(cloud, intensity: bool) -> np.ndarray:
+        """C-contiguous f32 records, x, y, z first and -- with `intensity` -- the intensity in column 3."""
+        a = _as_points(cloud)
+        if intensity and a.shape[1] < 4:
+            raise ValueError("intensity=True needs [N,>=4] records (x, y, z, intensity)")
+        return a
+
+    def window_keyframe(self, scans, rel_poses, leaf: float = 0.1, intensity: bool = False):
+        """The window map of GlobalGraphNodelet::cloud_callback (global_graph_nodelet.cpp:202-244) as one keyframe on the device: scan 0 as it
+        is, scan k moved by rel_poses[k] (4x4 f64, w_odom.inverse() * odom_k; rel_poses[0] is ignored), appended in order, VoxelGrid(leaf).
+        scans: [N_k,>=3] float arrays sharing one record layout (column 3 = intensity with intensity=True).  Returns (keyframe id, points);
+        the cloud stays on the device (keyframe_get fetches it).  tools/window_map_ref.py is the CPU restatement it equals bit for bit."""
+        recs = [self._records(c, intensity) for c in scans]
+        K = len(recs)
+        if K == 0:
+            raise ValueError("a window has at least one scan")
+        widths = {r.shape[1] for r in recs}
+        if len(widths) != 1:
+            raise ValueError("all scans of a window must share one record layout")
+        P = np.ascontiguousarray(np.asarray(rel_poses, np.float64).reshape(-1, 4, 4))
+        if P.shape[0] != K:
+            raise ValueError("one 4x4 relative pose per scan")
+        ptrs = (C.c_void_p * K)(*[r.ctypes.data for r in recs])
+        counts = (C.c_size_t * K)(*[r.shape[0] for r in recs])
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(K, 16)        # column-major per scan
+        kid, n_out = C.c_int(-1), C.c_size_t()
+        self._chk(self.lib.mi355ndt_window_keyframe(self.h, K, ptrs, counts, 4 * widths.pop(), 12 if intensity else -1,
+                                                    pcm.ctypes.data_as(C.c_void_p), float(leaf), C.byref(kid), C.byref(n_out)), "window_keyframe")
+        return kid.value, n_out.value
+
+    def keyframe_add(self, cloud, intensity: bool = False) -> int:
+        """A host cloud as it is becomes a resident keyframe; returns its id."""
+        a = self._records(cloud, intensity)
+        kid = C.c_int(-1)
+        self._chk(self.lib.mi355ndt_keyframe_add(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], 4 * a.shape[1], 12 if intensity else -1,
+                                                 C.byref(kid)), "keyframe_add")
+        return kid.value
+
+    def keyframe_get(self, kid: int, intensity: bool = False, fetch: bool = True):
+        """The keyframe's cloud as [N,3] (or [N,4] with the intensity; zeros for a keyframe without one) float32; fetch=False: N alone."""
+        n = C.c_size_t()
+        self._chk(self.lib.mi355ndt_keyframe_get(self.h, int(kid), None, 0, 12, -1, C.byref(n)), "keyframe_get")
+        if not fetch:
+            return n.value
+        w = 4 if intensity else 3
+        out = np.zeros((n.value, w), np.float32)
+        if n.value:
+            self._chk(self.lib.mi355ndt_keyframe_get(self.h, int(kid), out.ctypes.data_as(C.c_void_p), n.value, 4 * w, 12 if intensity else -1,
+                                                     C.byref(n)), "keyframe_get")
+        return out
+
+    def keyframe_release(self, kid: int):
+        self._chk(self.lib.mi355ndt_keyframe_release(self.h, int(kid)), "keyframe_release")
+
+    def keyframe_count(self) -> int:
+        n = self.lib.mi355ndt_keyframe_count(self.h)
+        if n < 0:
+            raise NDTError(n, "keyframe_count")
+        return n
+
+    def map_cloud_keyframes(self, ids, poses, resolution, fetch=True):
+        """map_cloud over resident keyframes (ids from window_keyframe / keyframe_add): the same centres, word for word, with no upload."""
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        K = len(ids)
+        P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        if P.shape[0] != K:
+            raise ValueError("one 4x4 pose per keyframe")
+        if K == 0:
+            self._chk(self.lib.mi355ndt_map_cloud_keyframes(self.h, 0, None, None, float(resolution), None, 0, 12, C.byref(C.c_size_t())),
+                      "map_cloud_keyframes")
+            return None
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(K, 16)
+        n = sum(self.keyframe_get(k, fetch=False) for k in ids) if fetch else 0       # an upper bound of the centres: the points
+        out = np.empty((max(n, 1), 3), np.float32) if fetch else None
+        n_out = C.c_size_t()
+        self._chk(self.lib.mi355ndt_map_cloud_keyframes(self.h, K, ids.ctypes.data_as(C.c_void_p), pcm.ctypes.data_as(C.c_void_p), float(resolution),
+                                                        out.ctypes.data_as(C.c_void_p) if fetch else None, n, 12, C.byref(n_out)), "map_cloud_keyframes")
+        return out[: n_out.value].copy() if fetch else n_out.value
+
     # -- parity hooks
     def derivatives(self, p):
         p = np.ascontiguousarray(p, np.float64)
@@ -385,6 +476,13 @@ class Engine:
     def batch_set_source(self, pair, cloud):
         a = _as_points(cloud)
         self._chk(self.lib.mi355ndt_batch_set_source(self.h, pair, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0]), "batch_set_source")
+
+    def batch_set_target_keyframe(self, pair: int, kid: int):
+        """batch_set_target with a resident keyframe, device to device."""
+        self._chk(self.lib.mi355ndt_batch_set_target_keyframe(self.h, pair, int(kid)), "batch_set_target_keyframe")
+
+    def batch_set_source_keyframe(self, pair: int, kid: int):
+        self._chk(self.lib.mi355ndt_batch_set_source_keyframe(self.h, pair, int(kid)), "batch_set_source_keyframe")
 
     def batch_set_target_raw(self, pair: int, ptr: int, n: int, stride: int):
         """batch_set_target on a raw host pointer (records `stride` bytes apart); thread-safe across different pairs."""

@@ -240,7 +240,12 @@ enum mi355ndt_option {
    * Hessian are never read.  0: every sweep evaluates all 43 sums.  Same results bit for bit; mi355ndt_profile.score_only_sweeps counts the
    * score-only sweeps.  The environment variable MI355NDT_SCORE_ONLY_LAST_SWEEP sets the default for engines created afterwards.  Not changed
    * in stream mode. */
-  MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP = 8
+  MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP = 8,
+  /* Cell size, in millimetres, of the spatial index mi355ndt_keyframe_fitness_scores builds over a searched keyframe (default 100).  The cell is
+   * doubled until the keyframe's lattice has at most min(2^21, 64 x points) cells; a keyframe that does not get there within six doublings (a
+   * stray point at 1e12 m) is searched exhaustively.  The search is exact for any cell: no result bit depends on the option, only the time.
+   * Indexes that exist keep the cell they were built with. */
+  MI355NDT_OPT_KF_FITNESS_CELL_MM = 9
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);
@@ -463,6 +468,40 @@ int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int*
  * must fit the reserved points; the intensity is not carried).  Everything downstream is as after the host-cloud setters. */
 int mi355ndt_batch_set_target_keyframe(mi355ndt_handle* h, int pair, int id);
 int mi355ndt_batch_set_source_keyframe(mi355ndt_handle* h, int pair, int id);
+
+/* ---- graph edges between resident keyframes: fitness scores and information matrices ------------------------ */
+/* replaces InformationMatrixCalculator::calc_fitness_score(cloud1, cloud2, relpose, max_range)
+ * (src/global_graph/information_matrix_calculator.cpp:53-87) for E graph edges at once, over resident keyframes -- the odometry edge of
+ * every new keyframe (global_graph_nodelet.cpp:298) and every accepted loop (:697).  Per edge e: keyframe ids1[e] is the searched cloud
+ * (the kd-tree side), keyframe ids2[e] is moved by relposes[16e..] (column-major f64, cast entry-wise to f32 as relpose.cast<float>()
+ * does, applied in the PCL 1.8 scalar form); each moved point takes its exact nearest point of cloud1; scores[e] is the mean of the
+ * SQUARED distances that are <= max_range (squared distance vs max_range, as the reference compares them), DBL_MAX with 0 inliers when
+ * nothing is in range or either keyframe is empty.  Points with a non-finite coordinate take no part, on either side.  scores[e] and
+ * n_inliers[e] (may be NULL) are word for word what mi355ndt_fitness_score_T returns on a one-pair engine with cloud1 as target, cloud2 as
+ * source and the f32-cast pose as T.  A keyframe may appear in any number of edges and on either side; ids1[e] == ids2[e] is allowed.
+ * The first call that searches a keyframe builds a spatial index over it, which stays with the keyframe until it is released (about
+ * 16 + 16 B per point beside the keyframe's own 12; MI355NDT_OPT_KF_FITNESS_CELL_MM); later calls find it.  n_edges == 0 is MI355NDT_OK;
+ * an unknown or released id is MI355NDT_ERR_BAD_ARG with a message and nothing is written; MI355NDT_ERR_STATE in stream mode.  Nothing
+ * crosses PCIe on the way in (cloud_uploads does not move); synchronous, one wait for the device per call.  Uses buffers of its own: the
+ * batch, grids, prefilter result, map-cloud and window workspaces of the handle are left as they were. */
+int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int* ids1, const int* ids2,
+                                     const double* relposes /* 16 per edge, column-major f64 */, double max_range,
+                                     double* scores, long long* n_inliers /* may be NULL */);
+
+/* The weighting half of InformationMatrixCalculator::calc_information_matrix (information_matrix_calculator.cpp:27-51,
+ * include/global_graph/information_matrix_calculator.hpp:40-44), as written, quirks included: the variance bounds are the stddev
+ * bounds squared; weight = min + (max - min) * (1 - exp(-a x)) / (1 - exp(-a thresh)) with NO clamp (a DBL_MAX score gives a weight
+ * slightly above max); the weight is stored in a float before every entry of the 3x3 block of Identity(6,6) is divided by it; with
+ * use_const_inf_matrix the blocks are divided by the STDDEV, not the variance (:32-33), and the score is not read.  inf: 6x6, row-major
+ * (the matrix is diagonal).  Plain host arithmetic: no handle, no device.
+ * mi355ndt_inf_params_default gives the constructor's defaults (:11-20; fitness_score_thresh 0.5).  Note that the reference's other
+ * initialiser, load() (information_matrix_calculator.hpp:32), defaults the threshold to 2.5. */
+typedef struct mi355ndt_inf_params {
+  int    use_const_inf_matrix;
+  double const_stddev_x, const_stddev_q, var_gain_a, min_stddev_x, max_stddev_x, min_stddev_q, max_stddev_q, fitness_score_thresh;
+} mi355ndt_inf_params;
+void mi355ndt_inf_params_default(mi355ndt_inf_params* p);
+int  mi355ndt_information_matrix(const mi355ndt_inf_params* p, double fitness_score, double inf[36]);
 
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);

@@ -10,7 +10,7 @@
 // Build: __graft_entry__.build() compiles three translation units side by side and links them: this file, mi355_ndt_ord1.hip (the kernel
 // instantiations of the second f32 sum order) and mi355_ndt_fast.hip (those of the tolerance arithmetic); -DNDT_SINGLE_TU builds everything
 // from this file alone.
-// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp / ndt_hessian.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_keyframe.hpp / ...; the host side of the
+// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp / ndt_hessian.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
 // C-ABI lives in ndt_engine.hpp and the ndt_host_*.hpp headers listed at the end of this file, one per surface.  It stays ONE translation unit
 // (the non-template kernels of the headers would collide across units).  Data layout in HBM: DESIGN.md.  Built with -ffp-contract=off: every
 // f32/f64 step of the reference recipe is a separately rounded operation.
@@ -47,6 +47,7 @@
 #include "ndt_prefilter.hpp"
 #include "ndt_mapcloud.hpp"
 #include "ndt_keyframe.hpp"
+#include "ndt_kffitness.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
@@ -72,5 +73,6 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_prefilter.hpp"  // prefilter
 #include "ndt_host_mapcloud.hpp"   // map cloud
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id
+#include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
 #include "ndt_host_sequence.hpp"   // latency mode, sequence run
 #include "ndt_host_stream.hpp"     // stream mode

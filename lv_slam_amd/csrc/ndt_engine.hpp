@@ -104,7 +104,14 @@ struct mi355ndt_handle {
   bool mc_pending = false;                        // a map cloud call returned before its final synchronisation (h_mc_tab may still be read)
   // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
   // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice
-  struct Keyframe { DevBuf<float> rows; size_t n = 0, pitch = 0; int ch = 3; };
+  // ... and, once it has been the searched side of mi355ndt_keyframe_fitness_scores, its spatial index (ndt_kffitness.hpp: lattice, occupancy
+  // words, run starts, the points in cell order -- one block), kept until the keyframe is released.  index_status: NO_INDEX, else the
+  // lattice's GRID_* status as the host learned it at the end of the call that built the index.
+  struct Keyframe {
+    static constexpr int NO_INDEX = -1;
+    DevBuf<float> rows; size_t n = 0, pitch = 0; int ch = 3;
+    DevBuf<unsigned char> index; int index_status = NO_INDEX;
+  };
   std::map<int, Keyframe> keyframes;
   int kf_next_id = 0;
   // window map workspace (mi355ndt_window_keyframe; touches nothing of the batch, grid, prefilter, map cloud or stream state)
@@ -113,6 +120,12 @@ struct mi355ndt_handle {
   PinBuf<unsigned char> h_kf_tab;                 // pinned staging of the scan table and the f64 poses
   PinBuf<int> h_kf_ret;                           // pinned landing words: last scan position, last head flag
   bool kf_pending = false;                        // a window call returned before its synchronisation (h_kf_tab may still be read)
+  // keyframe fitness workspace (mi355ndt_keyframe_fitness_scores; touches nothing of the batch, grid, prefilter, map cloud, window or stream state):
+  // the index build's sort and extremes, the call's edge / item tables and block partials with their pinned twins
+  DevBuf<unsigned> d_kfi_keys, d_kfi_vals, d_kfi_hist, d_kfi_offs, d_kfi_mm; DevBuf<int> d_kfi_cnt, d_kfi_stat;
+  DevBuf<unsigned char> d_kff_tab; DevBuf<double> d_kff_part;
+  PinBuf<unsigned char> h_kff_tab; PinBuf<double> h_kff_part; PinBuf<int> h_kff_stat;
+  int kff_cell_mm = 100;                          // MI355NDT_OPT_KF_FITNESS_CELL_MM
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 

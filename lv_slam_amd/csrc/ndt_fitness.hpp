@@ -243,6 +243,60 @@ __device__ __forceinline__ bool fit_item(const FitItem* __restrict__ items, cons
   return bx * 256 < it.n_src;
 }
 
+// The ring walk of the batched score over an occupied-cell index: the query's cell, the rings r_first .. r_last around it, the stopping
+// rule of k_fitness.  visit(j0, j1) takes the sorted positions j0 .. j1 - 1 of one row's (or one cell's) points and lowers `best`, the
+// squared distance of the nearest point so far, which the walk reads to stop.  Shared by k_fitness_batch (batch rows, points by id) and
+// k_kf_fitness (ndt_kffitness.hpp: a keyframe's own index, points in cell order).
+template <typename Visit>
+__device__ __forceinline__ void fit_rings(const float (&q)[3], const GridDesc& g, const BitWord* __restrict__ W, const unsigned* __restrict__ R,
+                                          const int ring_max, const float max_range, const float& best, Visit visit) {
+  int cq[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float cf = floorf(q[a] * g.inv_leaf);
+    const long long ci = cf >= 1.0e9f ? 1000000000ll : (cf <= -1.0e9f ? -1000000000ll : (long long)cf);
+    const long long cl = ci - (long long)g.min_b[a];
+    cq[a] = (int)(cl > (1ll << 29) ? (1ll << 29) : (cl < -(1ll << 29) ? -(1ll << 29) : cl));
+  }
+  const int c0 = cq[0], c1 = cq[1], c2 = cq[2];
+  const int o0 = c0 < 0 ? -c0 : (c0 >= g.div_b[0] ? c0 - g.div_b[0] + 1 : 0);
+  const int o1 = c1 < 0 ? -c1 : (c1 >= g.div_b[1] ? c1 - g.div_b[1] + 1 : 0);
+  const int o2 = c2 < 0 ? -c2 : (c2 >= g.div_b[2] ? c2 - g.div_b[2] + 1 : 0);
+  const int r_first = max(o0, max(o1, o2));
+  const int r_last = min(ring_max, r_first + max(g.div_b[0], max(g.div_b[1], g.div_b[2])) + 1);
+  for (int r = r_first; r <= r_last; r++) {
+    const float reach = ((float)(r - 1) - 1e-3f) * g.leaf;
+    if (r > 1 && (best <= reach * reach || reach * reach > max_range)) break;
+    const int z0 = max(c2 - r, 0), z1 = min(c2 + r, g.div_b[2] - 1);
+    const int y0 = max(c1 - r, 0), y1 = min(c1 + r, g.div_b[1] - 1);
+    const int x0 = max(c0 - r, 0), x1 = min(c0 + r, g.div_b[0] - 1);
+    if (x0 > x1) continue;                    // (the ring misses the grid's x extent: k_fitness visits no cell of it either)
+    for (int z = z0; z <= z1; z++) {
+      const bool zface = (z == c2 - r || z == c2 + r);
+      for (int y = y0; y <= y1; y++) {
+        const bool yface = (y == c1 - r || y == c1 + r);
+        const unsigned row = (unsigned)(y * g.mul1 + z * g.mul2);
+        if (zface || yface) {                 // the whole row x0 .. x1: its occupied cells are one rank interval
+          const unsigned k0 = fit_rank(W, row + (unsigned)x0), k1 = fit_rank(W, row + (unsigned)x1 + 1u);
+          if (k0 != k1) visit(R[k0], R[k1]);
+        } else {                              // interior row: the two x faces only
+#pragma unroll
+          for (int f = 0; f < 2; f++) {
+            const int x = f ? c0 + r : c0 - r;
+            if (x < x0 || x > x1) continue;
+            const unsigned c = row + (unsigned)x;
+            const BitWord w = W[c >> 6];
+            if ((w.bits >> (c & 63)) & 1ull) {
+              const unsigned k = w.prefix + (unsigned)__popcll(w.bits & ((1ull << (c & 63)) - 1ull));
+              visit(R[k], R[k + 1]);
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
 // k_fitness for every pair with a grid: the same transform, the same rings, the same stopping rule, the same distance arithmetic and
 // block reduction; only the way a ring finds its occupied cells differs (rows of the z / y faces by rank, the x faces of the other rows by
 // one bit each).  The nearest distance is a minimum over the same set of points, so it does not depend on the order they are visited in.
@@ -271,60 +325,15 @@ __global__ void __launch_bounds__(256) k_fitness_batch(const FitItem* __restrict
 #pragma unroll
     for (int a = 0; a < 3; a++) q[a] = ((Tb[0 * 4 + a] * px + Tb[1 * 4 + a] * py) + Tb[2 * 4 + a] * pz) + Tb[3 * 4 + a];   // PCL 1.8 scalar form
     if (finite3(q[0], q[1], q[2])) {
-      int cq[3];
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        const float cf = floorf(q[a] * g.inv_leaf);
-        const long long ci = cf >= 1.0e9f ? 1000000000ll : (cf <= -1.0e9f ? -1000000000ll : (long long)cf);
-        const long long cl = ci - (long long)g.min_b[a];
-        cq[a] = (int)(cl > (1ll << 29) ? (1ll << 29) : (cl < -(1ll << 29) ? -(1ll << 29) : cl));
-      }
-      const int c0 = cq[0], c1 = cq[1], c2 = cq[2];
-      const int o0 = c0 < 0 ? -c0 : (c0 >= g.div_b[0] ? c0 - g.div_b[0] + 1 : 0);
-      const int o1 = c1 < 0 ? -c1 : (c1 >= g.div_b[1] ? c1 - g.div_b[1] + 1 : 0);
-      const int o2 = c2 < 0 ? -c2 : (c2 >= g.div_b[2] ? c2 - g.div_b[2] + 1 : 0);
-      const int r_first = max(o0, max(o1, o2));
-      const int r_last = min(it.ring_max, r_first + max(g.div_b[0], max(g.div_b[1], g.div_b[2])) + 1);
       float best = __int_as_float(0x7f800000);
-      auto visit = [&](unsigned j0, unsigned j1) {
+      fit_rings(q, g, W, R, it.ring_max, max_range, best, [&](unsigned j0, unsigned j1) {
         for (unsigned j = j0; j < j1; j++) {
           const unsigned pi = V[j];
           const float dx = q[0] - X[pi], dy = q[1] - X[tpitch + pi], dz = q[2] - X[2 * tpitch + pi];
           const float d2 = (dx * dx + dy * dy) + dz * dz;          // FLANN L2_Simple accumulation order
           best = d2 < best ? d2 : best;
         }
-      };
-      for (int r = r_first; r <= r_last; r++) {
-        const float reach = ((float)(r - 1) - 1e-3f) * g.leaf;
-        if (r > 1 && (best <= reach * reach || reach * reach > max_range)) break;
-        const int z0 = max(c2 - r, 0), z1 = min(c2 + r, g.div_b[2] - 1);
-        const int y0 = max(c1 - r, 0), y1 = min(c1 + r, g.div_b[1] - 1);
-        const int x0 = max(c0 - r, 0), x1 = min(c0 + r, g.div_b[0] - 1);
-        if (x0 > x1) continue;                    // (the ring misses the grid's x extent: k_fitness visits no cell of it either)
-        for (int z = z0; z <= z1; z++) {
-          const bool zface = (z == c2 - r || z == c2 + r);
-          for (int y = y0; y <= y1; y++) {
-            const bool yface = (y == c1 - r || y == c1 + r);
-            const unsigned row = (unsigned)(y * g.mul1 + z * g.mul2);
-            if (zface || yface) {                 // the whole row x0 .. x1: its occupied cells are one rank interval
-              const unsigned k0 = fit_rank(W, row + (unsigned)x0), k1 = fit_rank(W, row + (unsigned)x1 + 1u);
-              if (k0 != k1) visit(R[k0], R[k1]);
-            } else {                              // interior row: the two x faces only
-#pragma unroll
-              for (int f = 0; f < 2; f++) {
-                const int x = f ? c0 + r : c0 - r;
-                if (x < x0 || x > x1) continue;
-                const unsigned c = row + (unsigned)x;
-                const BitWord w = W[c >> 6];
-                if ((w.bits >> (c & 63)) & 1ull) {
-                  const unsigned k = w.prefix + (unsigned)__popcll(w.bits & ((1ull << (c & 63)) - 1ull));
-                  visit(R[k], R[k + 1]);
-                }
-              }
-            }
-          }
-        }
-      }
+      });
       if (best <= max_range) { sum = (double)best; cnt = 1; }
     }
   }

@@ -1,0 +1,225 @@
+// ndt_host_kffitness.hpp -- mi355ndt_keyframe_fitness_scores (graph edges between resident keyframes, ndt_kffitness.hpp) and the host
+// arithmetic of InformationMatrixCalculator::calc_information_matrix (mi355ndt_information_matrix).  Buffers of their own throughout: the
+// batch, grids, prefilter result, map-cloud and window workspaces of the handle are left as they were.
+#pragma once
+
+// ---- a keyframe's spatial index ----------------------------------------------------------------------
+// one block: GridDesc (128 B) | BitWord words[nw] | unsigned runs[pitch + 1] (to 16 B) | float sorted[3][pitch]
+struct KfiLayout { size_t words, runs, sorted, bytes; int max_cells; };
+static KfiLayout kfi_layout(size_t pitch) {
+  KfiLayout L;
+  L.max_cells = (int)std::min((size_t)KFI_MAX_CELLS, std::max((size_t)4096, 64 * pitch));   // at most 16 B of bitmap per point
+  const size_t nw = (size_t)L.max_cells / 64 + 2;
+  static_assert(sizeof(GridDesc) <= 128, "the index block's header");
+  L.words = 128;
+  L.runs = L.words + nw * sizeof(BitWord);
+  L.sorted = L.runs + (((pitch + 1) * sizeof(unsigned) + 15) & ~(size_t)15);
+  L.bytes = L.sorted + 3 * pitch * sizeof(float);
+  return L;
+}
+
+// enqueue the build of kf's index (kf.n > 0); the status lands in d_kfi_stat[slot].  The workspace (d_kfi_*) is sized by the caller.
+static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot) {
+  hipStream_t s = h->stream;
+  const size_t pitch = kf.pitch;
+  const KfiLayout L = kfi_layout(pitch);
+  kf.index_status = mi355ndt_handle::Keyframe::NO_INDEX;
+  HIPCHK(h, kf.index.realloc_exact(L.bytes));
+  unsigned char* blob = kf.index;
+  GridDesc* gd = reinterpret_cast<GridDesc*>(blob);
+  BitWord* words = reinterpret_cast<BitWord*>(blob + L.words);
+  unsigned* runs = reinterpret_cast<unsigned*>(blob + L.runs);
+  float* sorted = reinterpret_cast<float*>(blob + L.sorted);
+  HIPCHK(h, hipMemsetAsync(blob, 0, L.runs, s));   // header and bitmap (k_fit_mark ORs into it)
+  const int gx = (int)((pitch + 255) / 256);
+  const int cb = KFI_CELL_BITS;
+  k_kfi_begin<<<1, 64, 0, s>>>(h->d_kfi_mm, h->d_kfi_cnt, (int)kf.n);
+  k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(kf.rows, pitch, h->d_kfi_cnt, h->d_kfi_mm);
+  k_kfi_grid<<<1, 1, 0, s>>>(h->d_kfi_mm, (float)h->kff_cell_mm * 1e-3f, L.max_cells, gd, h->d_kfi_stat + slot);
+  // stable sort by cell, the first pass computing the keys from the points (ndt_segsort.hpp); one segment
+  const RsPlan plan = rs_plan(cb);
+  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
+  unsigned *kin = h->d_kfi_keys, *kout = kin + pitch, *vin = h->d_kfi_vals, *vout = vin + pitch;
+  const RsPoints points = {kf.rows, h->d_kfi_cnt, gd, cb, kin};
+  for (int p = 0; p < plan.passes; p++) {
+    rs_pass(s, plan.bits, kin, vin, kout, vout, pitch, p * plan.bits, h->d_kfi_hist, h->d_kfi_offs, tiles, 1, p == 0, p == 0 ? &points : nullptr);
+    std::swap(kin, kout); std::swap(vin, vout);
+  }
+  const dim3 pg((unsigned)gx, 1u);
+  k_fit_mark<<<pg, 256, 0, s>>>(kin, pitch, gd, words, cb);
+  k_fit_rank<<<1, 1024, 0, s>>>(gd, words);
+  k_fit_runs<<<pg, 256, 0, s>>>(kin, pitch, gd, words, runs, cb);
+  k_kfi_gather<<<gx, 256, 0, s>>>(kf.rows, pitch, vin, sorted);
+  HIPCHK(h, hipGetLastError());
+  return MI355NDT_OK;
+}
+
+// replaces InformationMatrixCalculator::calc_fitness_score (information_matrix_calculator.cpp:53-87) for E graph edges at once
+int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int* ids1, const int* ids2, const double* relposes, double max_range,
+                                     double* scores, long long* n_inliers) {
+  using Keyframe = mi355ndt_handle::Keyframe;
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (n_edges < 0) return MI355NDT_ERR_BAD_ARG;
+  if (n_edges == 0) return MI355NDT_OK;
+  if (!ids1 || !ids2 || !relposes || !scores) return MI355NDT_ERR_BAD_ARG;
+  const int E = n_edges;
+  std::vector<Keyframe*> k1((size_t)E), k2((size_t)E);
+  long long n_blocks = 0;
+  for (int e = 0; e < E; e++) {
+    k1[(size_t)e] = kf_find(h, ids1[e], "keyframe_fitness_scores");
+    k2[(size_t)e] = k1[(size_t)e] ? kf_find(h, ids2[e], "keyframe_fitness_scores") : nullptr;
+    if (!k2[(size_t)e]) return MI355NDT_ERR_BAD_ARG;
+    n_blocks += (long long)((k2[(size_t)e]->n + 255) / 256);
+  }
+  if (n_blocks >= (1ll << 28)) { h->err = "keyframe_fitness_scores: too many points in all the edges of one call"; return MI355NDT_ERR_BAD_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = uploads_before_compute(h);             // (a keyframe_add's transfer may still be on its way)
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+
+  // the indexes this call needs and does not find: every searched keyframe once, however many edges name it.  (An empty side costs nothing.)
+  std::map<Keyframe*, int> todo;
+  size_t ws_pitch = 0;
+  for (int e = 0; e < E; e++) {
+    Keyframe* kf = k1[(size_t)e];
+    if (kf->n == 0 || k2[(size_t)e]->n == 0 || kf->index_status != Keyframe::NO_INDEX || todo.count(kf)) continue;
+    const int slot = (int)todo.size();
+    todo.emplace(kf, slot);
+    ws_pitch = std::max(ws_pitch, kf->pitch);
+  }
+  if (!todo.empty()) {
+    const size_t tiles = (ws_pitch + RS_TILE - 1) / RS_TILE;
+    HIPCHK(h, h->d_kfi_keys.reserve(2 * ws_pitch)); HIPCHK(h, h->d_kfi_vals.reserve(2 * ws_pitch));
+    HIPCHK(h, h->d_kfi_hist.reserve(tiles << RS_MAX_BITS)); HIPCHK(h, h->d_kfi_offs.reserve(tiles << RS_MAX_BITS));
+    HIPCHK(h, h->d_kfi_mm.reserve(6)); HIPCHK(h, h->d_kfi_cnt.reserve(1));
+    HIPCHK(h, h->d_kfi_stat.reserve(todo.size())); HIPCHK(h, h->h_kff_stat.reserve(todo.size()));
+    for (auto& t : todo) { rc = kfi_build(h, *t.first, t.second); if (rc) return rc; }
+  }
+
+  // which edges go where.  known[e]: the host has the status of the searched keyframe's index (built by an earlier call); an index built
+  // by this call is in both tables and the kernels decide by its status -- the call waits for the device once, at its end
+  const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+  std::vector<int> part0((size_t)E, 0), nblk((size_t)E, 0), st((size_t)E, GRID_EMPTY);
+  int n_part = 0;
+  for (int e = 0; e < E; e++) {
+    const Keyframe *a = k1[(size_t)e], *b = k2[(size_t)e];
+    if (a->n == 0 || b->n == 0 || a->index_status == GRID_EMPTY) continue;   // DBL_MAX, 0 without a launch
+    st[(size_t)e] = a->index_status;
+    nblk[(size_t)e] = (int)((b->n + 255) / 256);
+    part0[(size_t)e] = n_part;
+    n_part += nblk[(size_t)e];
+  }
+  // item tables of the two launches (FitItem, ndt_fitness.hpp): 16 ints of group starts, then the items group by group.  An edge goes to
+  // the least loaded of the eight groups, in edge order.
+  auto make_table = [&](bool with_grid, std::vector<int>& t, int& group_max) {
+    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int> eg((size_t)E, -1);
+    for (int e = 0; e < E; e++) {
+      const int v = st[(size_t)e];
+      if (nblk[(size_t)e] == 0 || !(v == Keyframe::NO_INDEX || (v == GRID_OK) == with_grid)) continue;
+      int g = 0;
+      for (int k = 1; k < 8; k++) if (load[k] < load[g]) g = k;
+      eg[(size_t)e] = g;
+      load[g] += nblk[(size_t)e];
+    }
+    t.assign(16, 0);
+    for (int g = 0; g < 8; g++) {
+      t[(size_t)g] = (int)((t.size() - 16) / 6);
+      for (int e = 0, blk = 0; e < E; e++) {
+        if (eg[(size_t)e] != g) continue;
+        t.insert(t.end(), {e, blk, part0[(size_t)e], (int)k2[(size_t)e]->n, (int)k1[(size_t)e]->n, 0});
+        blk += nblk[(size_t)e];
+      }
+    }
+    t[8] = (int)((t.size() - 16) / 6);
+    group_max = *std::max_element(load, load + 8);
+  };
+  std::vector<double> part((size_t)2 * n_part);
+  if (n_part > 0) {
+    std::vector<int> tab, tab_brute;
+    int gmax = 0, gmax_brute = 0;
+    make_table(true, tab, gmax);
+    make_table(false, tab_brute, gmax_brute);
+    static_assert(sizeof(FitItem) == 6 * sizeof(int) && sizeof(KfEdge) % 8 == 0, "the tables' layout");
+    const size_t at_ok = (size_t)E * sizeof(KfEdge), at_brute = at_ok + tab.size() * sizeof(int), bytes = at_brute + tab_brute.size() * sizeof(int);
+    HIPCHK(h, h->h_kff_tab.reserve(bytes)); HIPCHK(h, h->d_kff_tab.reserve(bytes));
+    HIPCHK(h, h->d_kff_part.reserve((size_t)2 * n_part)); HIPCHK(h, h->h_kff_part.reserve((size_t)2 * n_part));
+    unsigned char* ht = h->h_kff_tab;
+    KfEdge* he = reinterpret_cast<KfEdge*>(ht);
+    for (int e = 0; e < E; e++) {
+      const Keyframe *a = k1[(size_t)e], *b = k2[(size_t)e];
+      KfEdge& x = he[e];
+      memset(&x, 0, sizeof x);
+      if (nblk[(size_t)e]) {
+        const KfiLayout L = kfi_layout(a->pitch);
+        const unsigned char* blob = a->index;
+        x.src = b->rows; x.tgt = a->rows; x.sorted = reinterpret_cast<const float*>(blob + L.sorted);
+        x.gd = reinterpret_cast<const GridDesc*>(blob); x.words = reinterpret_cast<const BitWord*>(blob + L.words);
+        x.runs = reinterpret_cast<const unsigned*>(blob + L.runs);
+        x.spitch = (unsigned)b->pitch; x.tpitch = (unsigned)a->pitch;
+      }
+      for (int k = 0; k < 16; k++) x.T[k] = (float)relposes[16 * (size_t)e + k];   // relpose.cast<float>() (:62)
+    }
+    memcpy(ht + at_ok, tab.data(), tab.size() * sizeof(int));
+    memcpy(ht + at_brute, tab_brute.data(), tab_brute.size() * sizeof(int));
+    HIPCHK(h, hipMemcpyAsync(h->d_kff_tab, ht, bytes, hipMemcpyHostToDevice, s));
+    const unsigned char* dt = h->d_kff_tab;
+    const KfEdge* de = reinterpret_cast<const KfEdge*>(dt);
+    const int* t_ok = reinterpret_cast<const int*>(dt + at_ok);
+    const int* t_brute = reinterpret_cast<const int*>(dt + at_brute);
+    if (gmax) k_kf_fitness<<<8u * (unsigned)gmax, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_ok + 16), t_ok, de, mr, max_range, h->d_kff_part);
+    if (gmax_brute) k_kf_fitness_brute<<<8u * (unsigned)gmax_brute, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_brute + 16), t_brute, de, mr, h->d_kff_part);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->h_kff_part, h->d_kff_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (!todo.empty()) HIPCHK(h, hipMemcpyAsync(h->h_kff_stat, h->d_kfi_stat, todo.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));             // the call's one wait
+  HIPCHK(h, hipGetLastError());
+  for (auto& t : todo) t.first->index_status = h->h_kff_stat[t.second];
+  if (n_part > 0) memcpy(part.data(), h->h_kff_part, part.size() * sizeof(double));
+  for (int e = 0; e < E; e++) {
+    double sum = 0, cnt = 0;
+    for (int k = 0; k < nblk[(size_t)e]; k++) { sum += part[2 * ((size_t)part0[(size_t)e] + k)]; cnt += part[2 * ((size_t)part0[(size_t)e] + k) + 1]; }
+    scores[e] = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
+    if (n_inliers) n_inliers[e] = (long long)cnt;
+  }
+  return MI355NDT_OK;
+}
+
+// ---- the weighting half of calc_information_matrix: plain host arithmetic ------------------------------
+void mi355ndt_inf_params_default(mi355ndt_inf_params* p) {
+  if (!p) return;
+  p->use_const_inf_matrix = 0;                    // information_matrix_calculator.cpp:11-20
+  p->const_stddev_x = 0.5; p->const_stddev_q = 0.1;
+  p->var_gain_a = 20.0;
+  p->min_stddev_x = 0.1; p->max_stddev_x = 5.0;
+  p->min_stddev_q = 0.05; p->max_stddev_q = 0.2;
+  p->fitness_score_thresh = 0.5;
+}
+
+// information_matrix_calculator.hpp:40-44
+static double inf_weight(double a, double max_x, double min_y, double max_y, double x) {
+  const double y = (1.0 - std::exp(-a * x)) / (1.0 - std::exp(-a * max_x));
+  return min_y + (max_y - min_y) * y;
+}
+
+int mi355ndt_information_matrix(const mi355ndt_inf_params* p, double fitness_score, double inf[36]) {
+  if (!p || !inf) return MI355NDT_ERR_BAD_ARG;
+  double dx, dq;
+  if (p->use_const_inf_matrix) {                  // (:32-33: the stddev, not the variance)
+    dx = p->const_stddev_x; dq = p->const_stddev_q;
+  } else {
+    const double min_var_x = std::pow(p->min_stddev_x, 2), max_var_x = std::pow(p->max_stddev_x, 2);
+    const double min_var_q = std::pow(p->min_stddev_q, 2), max_var_q = std::pow(p->max_stddev_q, 2);
+    const float w_x = (float)inf_weight(p->var_gain_a, p->fitness_score_thresh, min_var_x, max_var_x, fitness_score);   // (:44-45: a float)
+    const float w_q = (float)inf_weight(p->var_gain_a, p->fitness_score_thresh, min_var_q, max_var_q, fitness_score);
+    dx = (double)w_x; dq = (double)w_q;
+  }
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) {
+      const double id = r == c ? 1.0 : 0.0;
+      inf[6 * r + c] = (r < 3 && c < 3) ? id / dx : ((r >= 3 && c >= 3) ? id / dq : id);   // every entry of the two 3x3 blocks is divided
+    }
+  return MI355NDT_OK;
+}

@@ -1,0 +1,139 @@
+// ndt_kffitness.hpp -- fitness scores of graph edges between resident keyframes (mi355ndt_keyframe_fitness_scores):
+// InformationMatrixCalculator::calc_fitness_score (src/global_graph/information_matrix_calculator.cpp:53-87) for E edges in one launch.
+//
+// The searched keyframe of an edge (cloud1, the kd-tree side of the reference) owns a spatial index, built the first time it is searched and
+// kept until the keyframe is released: one block of device memory holding
+//   GridDesc           the cell lattice over the keyframe's finite points (k_kfi_grid: the cell rule below); status != GRID_OK = no lattice
+//   BitWord words[]    occupancy of 64 cells + rank of the first, the layout k_fit_mark / k_fit_rank write and fit_rank reads (ndt_fitness.hpp)
+//   unsigned runs[]    sorted position of the first point of the k-th occupied cell; runs[n_occ] = number of binned points
+//   float sorted[3][pitch]  x, y, z of the points IN CELL ORDER: a row of a ring face is one contiguous run of floats per coordinate, where
+//                      the batch surface gathers every point through its id (the index lives as long as the keyframe; the copy pays once)
+// No NDT leaves: no sums, no eigen decomposition, no inverse covariances.  The build reuses the engine's kernels as they are -- k_minmax
+// (ordered-int extremes), the segmented radix sort whose first pass computes the cell keys from the points (rs_pass), k_fit_mark / k_fit_rank /
+// k_fit_runs -- on a one-target "batch".
+//
+// The search is exact for any cell size (fit_rings: ring by ring, stop when no unvisited ring can beat the best or be within max_range), so
+// the cell rule is about speed only: start from MI355NDT_OPT_KF_FITNESS_CELL_MM and double the cell until the lattice has at most
+// `max_cells` cells; a keyframe that does not get there within KFI_MAX_DOUBLINGS doublings (a stray point at 1e12 m) has no lattice and is
+// scored by the exhaustive block kernel (fitness_brute_block) over its unsorted rows.
+#pragma once
+#include "ndt_types.hpp"
+#include "ndt_build.hpp"
+#include "ndt_fitness.hpp"
+
+#define KFI_CELL_BITS      22            // key field of the index build's sort: every cell index + the all-ones "not binned" value
+#define KFI_MAX_CELLS      (1 << 21)     // cap of a keyframe's lattice (32,770 BitWords = 512 KB at the cap)
+#define KFI_MAX_DOUBLINGS  6             // the cell is coarsened up to 64 x the option's size before the keyframe counts as not indexable
+static_assert(KFI_MAX_CELLS < (1 << KFI_CELL_BITS) - 1, "the all-ones key is no cell");
+
+// extremes cleared (k_minmax's all-zero "no finite point yet"), the point count where k_minmax and the sort's key pass read it
+__global__ void k_kfi_begin(unsigned* mm, int* cnt, int n) {
+  if (threadIdx.x < 6) mm[threadIdx.x] = 0u;
+  if (threadIdx.x == 6) *cnt = n;
+}
+
+// the cell rule; *stat_out = the status, for the host (one word per index built in a call, fetched with the call's partials)
+__global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max_cells, GridDesc* gd, int* stat_out) {
+  GridDesc g;
+  memset(&g, 0, sizeof g);
+  g.leaf = cell0;
+  g.inv_leaf = 1.0f / cell0;
+  if (mm[0] == 0u) {
+    g.status = GRID_EMPTY;
+  } else {
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; a++) { mn[a] = ord2f(mm_dec_min(mm[a])); mx[a] = ord2f(mm_dec_max(mm[3 + a])); }
+    g.status = GRID_CAP;
+    float leaf = cell0;
+    for (int k = 0; k <= KFI_MAX_DOUBLINGS; k++, leaf *= 2.0f) {
+      const float inv = 1.0f / leaf;
+      if (grid_too_big((mx[0] - mn[0]) * inv, (mx[1] - mn[1]) * inv, (mx[2] - mn[2]) * inv)) continue;
+      int lo[3], hi[3];
+      for (int a = 0; a < 3; a++) { lo[a] = (int)floorf(mn[a] * inv); hi[a] = (int)floorf(mx[a] * inv); }
+      const long long nc = (long long)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
+      if (nc > (long long)max_cells) continue;
+      for (int a = 0; a < 3; a++) { g.min_b[a] = lo[a]; g.max_b[a] = hi[a]; g.div_b[a] = hi[a] - lo[a] + 1; }
+      g.leaf = leaf; g.inv_leaf = inv;
+      g.mul1 = g.div_b[0];
+      g.mul2 = g.div_b[0] * g.div_b[1];
+      g.ncells = (int)nc;
+      g.nwords = (int)((nc + 63) >> 6) + 1;       // + one all-zero word, as the target grids have (k_fit_rank leaves n_occ in it)
+      g.status = GRID_OK;
+      break;
+    }
+  }
+  *gd = g;
+  *stat_out = g.status;
+}
+
+// the points in cell order (positions past the binned points hold the not-binned points and the padding: never read, runs[n_occ] ends the last run)
+__global__ void __launch_bounds__(256) k_kfi_gather(const float* __restrict__ rows, size_t pitch, const unsigned* __restrict__ vals, float* __restrict__ sorted) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pitch) return;
+  const unsigned v = vals[i];
+  sorted[i] = rows[v]; sorted[pitch + i] = rows[pitch + v]; sorted[2 * pitch + i] = rows[2 * pitch + v];
+}
+
+// One scored edge.  src: the rows of keyframe ids2[e] (moved by T); tgt: the rows of keyframe ids1[e] as they are (exhaustive search);
+// gd / words / runs / sorted: the index of keyframe ids1[e].
+struct KfEdge {
+  const float* src; const float* tgt; const float* sorted;
+  const GridDesc* gd; const BitWord* words; const unsigned* runs;
+  unsigned spitch, tpitch;
+  float T[16];                                    // relpose.cast<float>(), column-major
+};
+
+// The launch is k_fitness_batch's: a flat grid over (edge, 256-point block) items, workgroup L serving group L % 8 -- the workgroups of one
+// XCD -- so that an edge's blocks share one L2 with its index and its cloud1 points (FitItem / fit_item, ndt_fitness.hpp; .pair = the edge).
+// Same transform, same rings and stopping rule (fit_rings), same distance arithmetic, same block reduction: an edge's partials are those of
+// k_fitness on a one-pair engine, because the nearest distance is a minimum over the same points whatever the lattice and the visiting order.
+// An edge whose searched keyframe has no lattice leaves its partials to k_kf_fitness_brute.
+__global__ void __launch_bounds__(256) k_kf_fitness(const FitItem* __restrict__ items, const int* __restrict__ gstart, const KfEdge* __restrict__ edges,
+                                                    float max_range, double max_range_d, double* partial) {
+  FitItem it;
+  int bx;
+  if (!fit_item(items, gstart, it, bx)) return;
+  const KfEdge& e = edges[it.pair];
+  const GridDesc& g = *e.gd;
+  if (g.status != GRID_OK) return;
+  // rings needed to cover sqrt(max_range) (+1 cell of slack), as mi355ndt_fitness_score_T computes them
+  const double rr = sqrt(fmin(max_range_d, 1e30)) / (double)g.leaf + 2.0;
+  const int ring_max = rr > (double)(1 << 30) ? (1 << 30) : (int)rr;
+  const float* S = e.src;
+  const float* X = e.sorted;
+  const size_t spitch = e.spitch, tpitch = e.tpitch;
+  double sum = 0.0;
+  unsigned long long cnt = 0;
+  const int i = bx * 256 + threadIdx.x;
+  if (i < it.n_src) {
+    const float px = S[i], py = S[spitch + i], pz = S[2 * spitch + i];
+    float q[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) q[a] = ((e.T[0 * 4 + a] * px + e.T[1 * 4 + a] * py) + e.T[2 * 4 + a] * pz) + e.T[3 * 4 + a];   // PCL 1.8 scalar form
+    if (finite3(q[0], q[1], q[2])) {
+      float best = __int_as_float(0x7f800000);
+      fit_rings(q, g, e.words, e.runs, ring_max, max_range, best, [&](unsigned j0, unsigned j1) {
+        for (unsigned j = j0; j < j1; j++) {
+          const float dx = q[0] - X[j], dy = q[1] - X[tpitch + j], dz = q[2] - X[2 * tpitch + j];
+          const float d2 = (dx * dx + dy * dy) + dz * dz;          // FLANN L2_Simple accumulation order
+          best = d2 < best ? d2 : best;
+        }
+      });
+      if (best <= max_range) { sum = (double)best; cnt = 1; }
+    }
+  }
+  fit_block_reduce(sum, cnt, partial + 2 * ((size_t)it.part0 + bx));
+}
+
+// the edges whose searched keyframe has no lattice, in a launch of their own (a keyframe without a finite point: no target point at all)
+__global__ void __launch_bounds__(256) k_kf_fitness_brute(const FitItem* __restrict__ items, const int* __restrict__ gstart, const KfEdge* __restrict__ edges,
+                                                          float max_range, double* partial) {
+  FitItem it;
+  int bx;
+  if (!fit_item(items, gstart, it, bx)) return;
+  const KfEdge& e = edges[it.pair];
+  const int status = e.gd->status;
+  if (status == GRID_OK) return;
+  fitness_brute_block(e.src, e.spitch, it.n_src, e.tgt, e.tpitch, status == GRID_EMPTY ? 0 : it.n_tgt, e.T, max_range, bx,
+                      partial + 2 * ((size_t)it.part0 + bx));
+}

@@ -60,6 +60,13 @@ class Profile(C.Structure):
                 ("stream_reserved_slots", C.c_longlong), ("stream_launch_slots", C.c_longlong), ("score_only_sweeps", C.c_longlong)]
 
 
+class InfParams(C.Structure):
+    """mi355ndt_inf_params: the parameters of InformationMatrixCalculator (information_matrix_calculator.cpp:11-20)."""
+    _fields_ = [("use_const_inf_matrix", C.c_int), ("const_stddev_x", C.c_double), ("const_stddev_q", C.c_double), ("var_gain_a", C.c_double),
+                ("min_stddev_x", C.c_double), ("max_stddev_x", C.c_double), ("min_stddev_q", C.c_double), ("max_stddev_q", C.c_double),
+                ("fitness_score_thresh", C.c_double)]
+
+
 class SeqParams(C.Structure):
     _fields_ = [("keyframe_delta_trans", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double)]
 
@@ -90,6 +97,7 @@ SYMBOLS = [
     "mi355ndt_map_cloud",
     "mi355ndt_window_keyframe", "mi355ndt_keyframe_add", "mi355ndt_keyframe_get", "mi355ndt_keyframe_release", "mi355ndt_keyframe_count",
     "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
+    "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
 ]
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
@@ -100,6 +108,7 @@ WARN_TOLERANCE_ARITH = 1       # mi355ndt_result.status under OPT_ARITH = 1: few
 OPT_ARITH = 7                  # mi355ndt_option: 0 = the reference recipe's arithmetic, one rounding per operation (default), 1 = tolerance arithmetic (held to 1e-4 m / 1e-5 rad, not to bits)
 OPT_F32_SUM_ORDER = 1          # mi355ndt_option: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
 OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch align's last sweep of a pair evaluates the score alone, 0 = all 43 sums; same bits
+OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
 
 _LIB = None
 
@@ -143,6 +152,10 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_map_cloud_keyframes.argtypes = [vp, i, vp, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_batch_set_target_keyframe.argtypes = [vp, i, i]
     L.mi355ndt_batch_set_source_keyframe.argtypes = [vp, i, i]
+    L.mi355ndt_keyframe_fitness_scores.argtypes = [vp, i, vp, vp, vp, C.c_double, vp, vp]
+    L.mi355ndt_inf_params_default.argtypes = [C.POINTER(InfParams)]
+    L.mi355ndt_inf_params_default.restype = None
+    L.mi355ndt_information_matrix.argtypes = [C.POINTER(InfParams), C.c_double, vp]
     L.mi355ndt_derivatives.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mi355ndt_derivatives_T.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi355ndt_compute_hessian.argtypes = [vp, vp, vp]
@@ -185,6 +198,31 @@ def default_params(**kw) -> Params:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_inf_params(**kw) -> InfParams:
+    """The defaults of InformationMatrixCalculator's constructor (fitness_score_thresh 0.5; the reference's load() says 2.5)."""
+    p = InfParams()
+    load_library().mi355ndt_inf_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"no information matrix parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def information_matrix(fitness: float, params: InfParams | None = None, **kw) -> np.ndarray:
+    """The weighting half of InformationMatrixCalculator::calc_information_matrix (information_matrix_calculator.cpp:27-51) for one fitness
+    score: the 6x6 f64 information matrix, quirks of the reference included (mi355ndt_information_matrix).  Parameters: an InfParams, or
+    the constructor's defaults with `kw` overriding fields.  Host arithmetic: no engine, no GPU."""
+    p = params if params is not None else default_inf_params(**kw)
+    if params is not None and kw:
+        raise TypeError("give either params or keyword overrides")
+    out = np.zeros(36, np.float64)
+    rc = load_library().mi355ndt_information_matrix(C.byref(p), float(fitness), out.ctypes.data_as(C.c_void_p))
+    if rc != OK:
+        raise NDTError(rc, "information_matrix")
+    return out.reshape(6, 6)
 
 
 def _as_points(cloud) -> np.ndarray:
@@ -424,6 +462,27 @@ class Engine:
         self._chk(self.lib.mi355ndt_map_cloud_keyframes(self.h, K, ids.ctypes.data_as(C.c_void_p), pcm.ctypes.data_as(C.c_void_p), float(resolution),
                                                         out.ctypes.data_as(C.c_void_p) if fetch else None, n, 12, C.byref(n_out)), "map_cloud_keyframes")
         return out[: n_out.value].copy() if fetch else n_out.value
+
+    def keyframe_fitness_scores(self, ids1, ids2, relposes, max_range: float = float("inf")):
+        """InformationMatrixCalculator::calc_fitness_score for E graph edges between resident keyframes in one call: keyframe ids1[e] is
+        searched, keyframe ids2[e] is moved by relposes[e] (4x4 f64, cast to f32 as the reference does).  Returns (scores float64[E],
+        inliers int64[E]): word for word fitness_score(T=relposes[e]) of a one-pair engine with cloud1 as target and cloud2 as source;
+        (DBL_MAX, 0) where nothing is in range or a keyframe is empty.  Nothing is uploaded; the first call that searches a keyframe
+        builds its index, which stays with it."""
+        a = np.ascontiguousarray(ids1, np.int32).ravel()
+        b = np.ascontiguousarray(ids2, np.int32).ravel()
+        E = len(a)
+        P = np.asarray(relposes, np.float64).reshape(-1, 4, 4)
+        if len(b) != E or P.shape[0] != E:
+            raise ValueError("one id of each side and one 4x4 relative pose per edge")
+        mr = 1.7976931348623157e308 if max_range == float("inf") else float(max_range)
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(E, 16)        # column-major per edge
+        scores = np.zeros(max(E, 1), np.float64)
+        inliers = np.zeros(max(E, 1), np.int64)
+        self._chk(self.lib.mi355ndt_keyframe_fitness_scores(self.h, E, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                                            pcm.ctypes.data_as(C.c_void_p), mr, scores.ctypes.data_as(C.c_void_p),
+                                                            inliers.ctypes.data_as(C.c_void_p)), "keyframe_fitness_scores")
+        return scores[:E], inliers[:E]
 
     # -- parity hooks
     def derivatives(self, p):

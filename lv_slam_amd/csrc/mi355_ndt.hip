@@ -32,6 +32,7 @@
 #include <chrono>
 #include <memory>
 #include <map>
+#include <array>
 #include <type_traits>
 
 #include "mi355_ndt.h"
@@ -70,6 +71,7 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_align.hpp"      // batch align, single-registration surface
 #include "ndt_host_hooks.hpp"      // parity hooks and getters
 #include "ndt_host_fitness.hpp"    // fitness scores, calculateScore
+#include "ndt_host_voxel.hpp"      // the scratch and the steps shared by the four voxel surfaces below
 #include "ndt_host_prefilter.hpp"  // prefilter
 #include "ndt_host_mapcloud.hpp"   // map cloud
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id

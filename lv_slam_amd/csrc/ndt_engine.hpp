@@ -47,6 +47,33 @@ struct StreamState {
   StreamCtx ctx[ASYNC_MAX_CTX];                 // (last: the contexts' engines are released before the stream they run on)
 };
 
+// ---- scratch of the sort-and-compact chain: stage clouds -> extremes -> grid -> keys -> one-segment radix sort -> run heads -> exclusive
+// scan -> emit -> count.  The prefilter, the map cloud (both routes), the window map and the keyframe index builds of
+// mi355ndt_keyframe_fitness_scores share this one instance; results (d_pf_out, the keyframe store and its indexes) are not in it.
+// Sharing is safe because
+//   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;
+//   * every user waits for the stream before it returns, except mi355ndt_window_keyframe, whose trailing k_kf_emit still reads x, keys, vals,
+//     flag and pos: only kernels on h->stream write those, so stream order covers it as well;
+//   * `in` alone is written from the copy streams: its readers (k_pf_*, k_mc_transform, k_kf_window) have finished when their call returns,
+//     and uploads_before_compute / compute_enqueued order the uploads against the compute stream as they do for the batch rows;
+//   * the pinned blocks are written by the host only at the start of a call, after vs_reserve has waited out a copy that may still read
+//     them (`pending`), and read by the host only after the call's own wait.
+// Growth: vs_reserve (ndt_host_voxel.hpp), the one place that re-allocates a member.
+struct VoxelScratch {
+  DevBuf<float> in, x, out;                       // staged SoA rows (upload_items) / moved points / the map cloud's centres
+  DevBuf<unsigned char> keep;                     // per point: kept (the map cloud: finite)
+  DevBuf<unsigned> keys, vals;                    // two of each per point (sort ping-pong); the map cloud: low / high words of its codes
+  DevBuf<unsigned> hist, offs, tmp;               // radix sort tile histograms / offsets, scan chunk totals
+  DevBuf<int> flag, pos;                          // run heads, their exclusive scan.  pos grows last: its capacity vouches for every per-point member
+  DevBuf<int> mm, cnt, aabb, stat;                // six extreme words (k_minmax / k_kfi_begin take them as unsigned), a point count, the map
+                                                  // cloud's per-chunk boxes, the index builds' status words
+  DevBuf<PfGrid> grid; DevBuf<McBox> box;
+  DevBuf<unsigned char> tab; PinBuf<unsigned char> h_tab;   // per-call tables (scan / keyframe table + poses; edges + item tables) and their pinned twin
+  DevBuf<double> part; PinBuf<double> h_part;     // block partials of the keyframe fitness kernels
+  PinBuf<int> h_ret;                              // pinned landing words (counts, statuses)
+  bool pending = false;                           // a copy out of h_tab is enqueued and the stream has not been waited for since
+};
+
 struct mi355ndt_handle {
   int device = 0;
   HipStream own_stream;                         // the engine's compute stream, unless mi355ndt_set_stream gave it one
@@ -91,17 +118,9 @@ struct mi355ndt_handle {
   // target build; the launch's item table and transforms
   DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns; bool fit_index_ready = false;
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
-  // prefilter workspace
-  DevBuf<float> d_pf_in, d_pf_out; DevBuf<unsigned char> d_pf_keep; DevBuf<unsigned> d_pf_keys, d_pf_vals;
-  DevBuf<int> d_pf_flag, d_pf_pos, d_pf_mm; DevBuf<PfGrid> d_pf_grid; DevBuf<unsigned> d_pf_tmp;
-  int pf_count = 0; size_t pf_pitch = 0;
-  // map cloud workspace (mi355ndt_map_cloud; touches nothing of the batch, grid, prefilter or stream state)
-  DevBuf<float> d_mc_in, d_mc_x, d_mc_out; DevBuf<unsigned char> d_mc_fin; DevBuf<int> d_mc_aabb, d_mc_flag, d_mc_pos;
-  DevBuf<unsigned> d_mc_keys, d_mc_hist, d_mc_offs, d_mc_tmp;   // d_mc_keys: low / high words of the codes, two of each (sort ping-pong)
-  DevBuf<McKf> d_mc_kf; DevBuf<float> d_mc_T; DevBuf<McBox> d_mc_box;
-  PinBuf<unsigned char> h_mc_tab;                 // pinned staging of the keyframe table and the f32 poses
-  PinBuf<int> h_mc_ret;                           // pinned landing words: status, depth, last scan position, last head flag
-  bool mc_pending = false;                        // a map cloud call returned before its final synchronisation (h_mc_tab may still be read)
+  // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)
+  DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0;
+  VoxelScratch vs;                                // scratch of the prefilter, the map cloud, the window map and the keyframe index builds
   // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
   // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice
   // ... and, once it has been the searched side of mi355ndt_keyframe_fitness_scores, its spatial index (ndt_kffitness.hpp: lattice, occupancy
@@ -114,17 +133,6 @@ struct mi355ndt_handle {
   };
   std::map<int, Keyframe> keyframes;
   int kf_next_id = 0;
-  // window map workspace (mi355ndt_window_keyframe; touches nothing of the batch, grid, prefilter, map cloud or stream state)
-  DevBuf<float> d_kf_in, d_kf_x; DevBuf<unsigned char> d_kf_keep; DevBuf<unsigned> d_kf_keys, d_kf_vals, d_kf_hist, d_kf_offs, d_kf_tmp;
-  DevBuf<int> d_kf_flag, d_kf_pos, d_kf_mm; DevBuf<PfGrid> d_kf_grid; DevBuf<KfScan> d_kf_scans; DevBuf<double> d_kf_T;
-  PinBuf<unsigned char> h_kf_tab;                 // pinned staging of the scan table and the f64 poses
-  PinBuf<int> h_kf_ret;                           // pinned landing words: last scan position, last head flag
-  bool kf_pending = false;                        // a window call returned before its synchronisation (h_kf_tab may still be read)
-  // keyframe fitness workspace (mi355ndt_keyframe_fitness_scores; touches nothing of the batch, grid, prefilter, map cloud, window or stream state):
-  // the index build's sort and extremes, the call's edge / item tables and block partials with their pinned twins
-  DevBuf<unsigned> d_kfi_keys, d_kfi_vals, d_kfi_hist, d_kfi_offs, d_kfi_mm; DevBuf<int> d_kfi_cnt, d_kfi_stat;
-  DevBuf<unsigned char> d_kff_tab; DevBuf<double> d_kff_part;
-  PinBuf<unsigned char> h_kff_tab; PinBuf<double> h_kff_part; PinBuf<int> h_kff_stat;
   int kff_cell_mm = 100;                          // MI355NDT_OPT_KF_FITNESS_CELL_MM
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)

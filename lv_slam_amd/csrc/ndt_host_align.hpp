@@ -290,12 +290,8 @@ int mi355ndt_promote_source_to_target(mi355ndt_handle* h) {
   const size_t m = (size_t)h->h_src_cnt[0];
   int rc = ensure_single(h, true, m);
   if (rc) return rc;
-  rc = uploads_before_compute(h);                 // the source's upload has to have landed; an earlier target upload must not land after these copies
+  rc = rows_into_slot(h, true, 0, h->d_src_own, h->src_pitch, m);
   if (rc) return rc;
-  const size_t dp = h->tgt_pitch, sp = h->src_pitch;
-  HIPCHK(h, hipMemsetAsync(h->d_tgt_own, 0, 3 * dp * sizeof(float), h->stream));
-  for (int a = 0; a < 3; a++)
-    if (m) HIPCHK(h, hipMemcpyAsync(h->d_tgt_own + a * dp, h->d_src_own + a * sp, m * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->h_tgt_cnt[0] = (int)m; h->have_target = true; h->targets_built = false;
   h->P.cloud_promotions++;
   return mi355ndt_batch_build_targets(h);

@@ -1,6 +1,46 @@
 // ndt_host_fitness.hpp -- getFitnessScore for one pair and for every batch slot, calculateScore.
 #pragma once
 
+// ---- shared by the single, the batch and the keyframe fitness calls ---------------------------------------
+// max_range as the kernels take it
+static float fit_range_f32(double max_range) { return max_range >= 3.0e38 ? 3.0e38f : (float)max_range; }
+
+// the block partials (sum, count) of one pair or edge, added on the host in block order from 0.0
+static void fit_reduce(const double* part, int nblk, double* score, long long* n_inliers) {
+  double sum = 0, cnt = 0;
+  for (int k = 0; k < nblk; k++) { sum += part[2 * (size_t)k]; cnt += part[2 * (size_t)k + 1]; }
+  *score = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
+  if (n_inliers) *n_inliers = (long long)cnt;
+}
+
+// Item table of one launch (FitItem, ndt_fitness.hpp): 16 ints of group starts, then the items group by group.  Item i of N (a pair, an
+// edge; nblk[i] blocks of 256 points) takes part iff takes(i), and goes to the least loaded of the eight groups, in index order;
+// tail(i) gives the three ints behind {i, first block in its group, part0[i]}.  The order decides which block partial lands where.
+template <typename Takes, typename Tail>
+static void fit_item_table(int N, const std::vector<int>& nblk, const std::vector<int>& part0, Takes takes, Tail tail, std::vector<int>& t, int& group_max) {
+  int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<int> group((size_t)N, -1);
+  for (int i = 0; i < N; i++) {
+    if (nblk[(size_t)i] == 0 || !takes(i)) continue;
+    int g = 0;
+    for (int k = 1; k < 8; k++) if (load[k] < load[g]) g = k;
+    group[(size_t)i] = g;
+    load[g] += nblk[(size_t)i];
+  }
+  t.assign(16, 0);
+  for (int g = 0; g < 8; g++) {
+    t[(size_t)g] = (int)((t.size() - 16) / 6);
+    for (int i = 0, blk = 0; i < N; i++) {
+      if (group[(size_t)i] != g) continue;
+      const std::array<int, 3> x = tail(i);
+      t.insert(t.end(), {i, blk, part0[(size_t)i], x[0], x[1], x[2]});
+      blk += nblk[(size_t)i];
+    }
+  }
+  t[8] = (int)((t.size() - 16) / 6);
+  group_max = *std::max_element(load, load + 8);
+}
+
 // replaces pcl::Registration::getFitnessScore(max_range) for the loop-closure caller (loop_detector.hpp:249-262)
 int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], double max_range, double* score, long long* n_inliers) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
@@ -30,7 +70,7 @@ int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], dou
   HIPCHK(h, h->d_fit.reserve((size_t)2 * blocks));
   HIPCHK(h, hipMemcpyAsync(h->d_hook, T_colmajor, 16 * sizeof(float), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+  const float mr = fit_range_f32(max_range);
   // rings needed to cover sqrt(max_range) (+1 cell of slack)
   double rr = brute ? 0.0 : std::sqrt(std::min(max_range, 1e30)) / (double)g.leaf + 2.0;   // (a target without a grid has no leaf size to divide by)
   // (a query outside the grid may sit further away than the grid is wide: the kernel clamps its cell to 2^29 cells from the grid's
@@ -43,10 +83,7 @@ int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], dou
   HIPCHK(h, hipMemcpyAsync(part.data(), h->d_fit, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
-  double sum = 0, cnt = 0;
-  for (int b = 0; b < blocks; b++) { sum += part[2 * b]; cnt += part[2 * b + 1]; }
-  *score = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
-  if (n_inliers) *n_inliers = (long long)cnt;
+  fit_reduce(part.data(), blocks, score, n_inliers);
   return MI355NDT_OK;
 }
 
@@ -73,7 +110,7 @@ int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, d
   HIPCHK(h, hipMemcpyAsync(gd.data(), h->d_grid, (size_t)B * sizeof(GridDesc), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   // which pairs go where: an empty target or source scores DBL_MAX with no launch, a grid -> k_fitness_batch, no grid -> k_fitness_brute_batch
-  const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+  const float mr = fit_range_f32(max_range);
   std::vector<int> part0(B, 0), nblk(B, 0);
   int n_part = 0;
   // the index covers EVERY pair with a grid, whatever its source holds now (k_fit_* index every GRID_OK pair, and a source set later
@@ -103,37 +140,16 @@ int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, d
     HIPCHK(h, hipGetLastError());
     h->fit_index_ready = true;
   }
-  // item tables of the two launches (FitItem, ndt_fitness.hpp): 16 ints of group starts, then the items group by group.  A pair goes to
-  // the least loaded of the eight groups, in pair order.
-  auto make_table = [&](bool with_grid, std::vector<int>& t, int& group_max) {
-    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<int> pg(B, -1);
-    for (int b = 0; b < B; b++) {
-      if (nblk[b] == 0 || (gd[b].status == GRID_OK) != with_grid) continue;
-      int g = 0;
-      for (int k = 1; k < 8; k++) if (load[k] < load[g]) g = k;
-      pg[b] = g;
-      load[g] += nblk[b];
-    }
-    t.assign(16, 0);
-    for (int g = 0; g < 8; g++) {
-      t[g] = (int)((t.size() - 16) / 6);
-      for (int b = 0, blk = 0; b < B; b++) {
-        if (pg[b] != g) continue;
-        // rings needed to cover sqrt(max_range) (+1 cell of slack), as mi355ndt_fitness_score_T computes them
-        const double rr = with_grid ? std::sqrt(std::min(max_range, 1e30)) / (double)gd[b].leaf + 2.0 : 0.0;
-        const int ring_max = rr > (double)(1 << 30) ? (1 << 30) : (int)rr;
-        t.insert(t.end(), {b, blk, part0[b], h->h_src_cnt[b], h->h_tgt_cnt[b], ring_max});
-        blk += nblk[b];
-      }
-    }
-    t[8] = (int)((t.size() - 16) / 6);
-    group_max = *std::max_element(load, load + 8);
-  };
+  // item tables of the two launches: a grid -> k_fitness_batch, no grid -> k_fitness_brute_batch
   std::vector<int> tab, tab_brute;
   int gmax = 0, gmax_brute = 0;
-  make_table(true, tab, gmax);
-  make_table(false, tab_brute, gmax_brute);
+  for (const bool with_grid : {true, false})
+    fit_item_table(B, nblk, part0, [&](int b) { return (gd[b].status == GRID_OK) == with_grid; },
+                   [&](int b) {
+                     // rings needed to cover sqrt(max_range) (+1 cell of slack), as mi355ndt_fitness_score_T computes them
+                     const double rr = with_grid ? std::sqrt(std::min(max_range, 1e30)) / (double)gd[b].leaf + 2.0 : 0.0;
+                     return std::array<int, 3>{h->h_src_cnt[b], h->h_tgt_cnt[b], rr > (double)(1 << 30) ? (1 << 30) : (int)rr};
+                   }, with_grid ? tab : tab_brute, with_grid ? gmax : gmax_brute);
   const size_t brute_at = tab.size();
   tab.insert(tab.end(), tab_brute.begin(), tab_brute.end());
   // transforms: the caller's, the final poses the last align left in d_results (read there, no host round trip), or the identity
@@ -171,12 +187,7 @@ int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, d
   if (n_part > 0) HIPCHK(h, hipMemcpyAsync(part.data(), h->d_fit, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
-  for (int b = 0; b < B; b++) {
-    double sum = 0, cnt = 0;
-    for (int k = 0; k < nblk[b]; k++) { sum += part[2 * ((size_t)part0[b] + k)]; cnt += part[2 * ((size_t)part0[b] + k) + 1]; }
-    scores[b] = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
-    if (n_inliers) n_inliers[b] = (long long)cnt;
-  }
+  for (int b = 0; b < B; b++) fit_reduce(part.data() + 2 * (size_t)part0[b], nblk[b], scores + b, n_inliers ? n_inliers + b : nullptr);
   return MI355NDT_OK;
 }
 

@@ -1,7 +1,7 @@
 // ndt_host_keyframe.hpp -- keyframes that stay on the device: mi355ndt_window_keyframe (the window map -> keyframe cloud), the keyframe store
 // (mi355ndt_keyframe_add / _get / _release / _count) and the consumers that take ids (mi355ndt_map_cloud_keyframes,
-// mi355ndt_batch_set_target_keyframe / _source_keyframe).  Buffers of their own throughout: the batch, grids, prefilter result and map-cloud
-// workspace of the handle are left as they were.
+// mi355ndt_batch_set_target_keyframe / _source_keyframe).  The batch, the grids, the prefilter result and the store's other keyframes are left
+// as they were; the window map's scratch is the shared one (h->vs).
 #pragma once
 
 static mi355ndt_handle::Keyframe* kf_find(mi355ndt_handle* h, int id, const char* where) {
@@ -47,107 +47,54 @@ int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const*
     return MI355NDT_OK;
   }
   hipStream_t s = h->stream;
-  if (h->kf_pending) { HIPCHK(h, hipStreamSynchronize(s)); h->kf_pending = false; }
+  VoxelScratch& w = h->vs;
   const size_t pitch = (n + 63) & ~(size_t)63;
   const int nblk = (int)((pitch + KF_CHUNK - 1) / KF_CHUNK);
-  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
-  const int scan_chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
-  const size_t tab_bytes = (size_t)K * 12 * sizeof(double) + (size_t)K * sizeof(KfScan);
-  if (in_total > h->d_kf_in.cap || pitch > h->d_kf_pos.cap || (size_t)ch * pitch > h->d_kf_x.cap) {   // re-allocation: nothing of an earlier call may still run (its emit kernel, uploads)
-    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
-    HIPCHK(h, hipStreamSynchronize(s));
-  }
-  HIPCHK(h, h->d_kf_in.reserve(in_total)); HIPCHK(h, h->d_kf_x.reserve((size_t)ch * pitch)); HIPCHK(h, h->d_kf_keep.reserve(pitch));
-  HIPCHK(h, h->d_kf_keys.reserve(2 * pitch)); HIPCHK(h, h->d_kf_vals.reserve(2 * pitch)); HIPCHK(h, h->d_kf_flag.reserve(pitch));
-  HIPCHK(h, h->d_kf_hist.reserve((size_t)tiles << RS_MAX_BITS)); HIPCHK(h, h->d_kf_offs.reserve((size_t)tiles << RS_MAX_BITS));
-  HIPCHK(h, h->d_kf_tmp.reserve((size_t)scan_chunks)); HIPCHK(h, h->d_kf_mm.reserve(6)); HIPCHK(h, h->d_kf_grid.reserve(1));
-  HIPCHK(h, h->d_kf_scans.reserve((size_t)K)); HIPCHK(h, h->d_kf_T.reserve((size_t)K * 12));
-  HIPCHK(h, h->h_kf_tab.reserve(tab_bytes)); HIPCHK(h, h->h_kf_ret.reserve(2));
-  HIPCHK(h, h->d_kf_pos.reserve(pitch));          // (last: its capacity vouches for the whole workspace above)
+  const size_t at_tab = (size_t)K * 12 * sizeof(double);
+  VsNeed need;
+  need.pitch = pitch; need.in = in_total; need.x = (size_t)ch * pitch; need.tab = at_tab + (size_t)K * sizeof(KfScan);
+  int rc = vs_reserve(h, need);                   // (an earlier window's emit kernel may still run: it is waited for if anything grows)
+  if (rc) return rc;
 
-  // scan table and poses ((w_odom.inverse() * odom_k).matrix(), column-major f64 -> row-major rows 0..2), one pinned block
-  double* T = (double*)(unsigned char*)h->h_kf_tab;
-  KfScan* tab = (KfScan*)((unsigned char*)h->h_kf_tab + (size_t)K * 12 * sizeof(double));
+  // poses ((w_odom.inverse() * odom_k).matrix(), column-major f64 -> row-major rows 0..2) and scan table, one pinned block, one copy
+  double* T = (double*)(unsigned char*)w.h_tab;
+  KfScan* tab = (KfScan*)((unsigned char*)w.h_tab + at_tab);
   std::vector<UpItem> items;
   items.reserve((size_t)K);
   size_t start = 0, base = 0;
   for (int k = 0; k < K; k++) {
     const size_t kp = (counts[k] + 63) & ~(size_t)63;
-    tab[k].rows = h->d_kf_in + base; tab[k].start = (unsigned)start; tab[k].pitch = (unsigned)kp;
+    tab[k].rows = w.in + base; tab[k].start = (unsigned)start; tab[k].pitch = (unsigned)kp;
     for (int a = 0; a < 3; a++)
       for (int j = 0; j < 4; j++) T[12 * k + 4 * a + j] = k == 0 ? (a == j ? 1.0 : 0.0) : rel_poses[16 * k + 4 * j + a];   // (scan 0 is not moved)
-    if (counts[k]) items.push_back(UpItem{h->d_kf_in + base, kp, 0, scans[k], counts[k], stride_bytes, ioff});
+    if (counts[k]) items.push_back(UpItem{w.in + base, kp, 0, scans[k], counts[k], stride_bytes, ioff});
     start += counts[k]; base += (size_t)ch * kp;
   }
-  h->kf_pending = true;
-  HIPCHK(h, hipMemcpyAsync(h->d_kf_scans, tab, (size_t)K * sizeof(KfScan), hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(h->d_kf_T, T, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-  // the scans: groups of up to UP_GROUP_MAX, one transfer each, staged by up to eight threads (the caller's among them)
-  const int n_groups = (int)((items.size() + UP_GROUP_MAX - 1) / UP_GROUP_MAX);
-  const int nt = std::max(1, std::min(8, n_groups));
-  std::vector<int> rcs((size_t)nt, MI355NDT_OK);
-  std::atomic<int> next_group{0};
-  auto work = [&](int t) {
-    (void)hipSetDevice(h->device);
-    for (int g = next_group.fetch_add(1); g < n_groups; g = next_group.fetch_add(1)) {
-      const size_t i0 = (size_t)g * UP_GROUP_MAX, i1 = std::min(items.size(), i0 + UP_GROUP_MAX);
-      const int rc = upload_items(h, items.data() + i0, (int)(i1 - i0));
-      if (rc != MI355NDT_OK) { rcs[(size_t)t] = rc; return; }
-    }
-  };
-  std::vector<std::thread> th;
-  try {
-    th.reserve((size_t)nt);
-    for (int t = 1; t < nt; t++) th.emplace_back(work, t);
-  } catch (...) {}
-  work(0);
-  for (auto& x : th) x.join();
-  for (int r : rcs) if (r != MI355NDT_OK) return r;
-  int rc = uploads_before_compute(h);
+  w.pending = true;
+  HIPCHK(h, hipMemcpyAsync(w.tab, w.h_tab, need.tab, hipMemcpyHostToDevice, s));
+  rc = upload_items_grouped(h, items);
+  if (rc) return rc;
+  rc = uploads_before_compute(h);
   if (rc) return rc;
 
-  float* X = h->d_kf_x;
+  float* X = w.x;
   const int gx = (int)((pitch + 255) / 256);
-  unsigned *ka = h->d_kf_keys, *kb = ka + pitch, *va = h->d_kf_vals, *vb = va + pitch;
-  k_minmax_init<<<1, 64, 0, s>>>(h->d_kf_mm, 1);
-  k_kf_window<<<nblk, KF_THREADS, 0, s>>>(h->d_kf_scans, K, h->d_kf_T, (int)n, pitch, ch, X, h->d_kf_keep, h->d_kf_mm);
-  int downsample = leaf > 0.f;
-  const unsigned *keys_sorted = ka, *vals_sorted = va;
-  if (downsample) {
-    k_pf_grid<<<1, 1, 0, s>>>(h->d_kf_mm, leaf, h->d_kf_grid);
-    PfGrid g;
-    HIPCHK(h, hipMemcpyAsync(&g, h->d_kf_grid, sizeof g, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    h->kf_pending = false;
-    if (g.status == 2) {                          // PCL: "Leaf size is too small for the input dataset" -> output = input
-      h->err = "window_keyframe: leaf size too small for the window's extent, voxel indices would overflow; window not down-sampled";
-      downsample = 0;
-    } else {
-      k_pf_keys<<<gx, 256, 0, s>>>(X, pitch, (int)n, h->d_kf_keep, h->d_kf_grid, ka, va);
-      const RsPlan plan = rs_plan(31);            // stable sort by voxel index, the whole window one segment (the prefilter's)
-      unsigned *kin = ka, *kout = kb, *vin = va, *vout = vb;
-      for (int p = 0; p < plan.passes; p++) {
-        rs_pass(s, plan.bits, kin, vin, kout, vout, pitch, p * plan.bits, h->d_kf_hist, h->d_kf_offs, tiles, 1, false);
-        std::swap(kin, kout); std::swap(vin, vout);
-      }
-      keys_sorted = kin; vals_sorted = vin;
-    }
-  }
-  k_pf_heads<<<gx, 256, 0, s>>>(keys_sorted, h->d_kf_keep, (int)n, pitch, downsample, h->d_kf_flag);
-  k_pf_scan_totals<<<scan_chunks, 1024, 0, s>>>(h->d_kf_flag, pitch, h->d_kf_tmp);
-  k_pf_scan_offsets<<<1, 1024, 0, s>>>(h->d_kf_tmp, scan_chunks);
-  k_pf_scan_apply<<<scan_chunks, 1024, 0, s>>>(h->d_kf_flag, pitch, h->d_kf_tmp, h->d_kf_pos);
+  k_minmax_init<<<1, 64, 0, s>>>(w.mm, 1);
+  k_kf_window<<<nblk, KF_THREADS, 0, s>>>((const KfScan*)((unsigned char*)w.tab + at_tab), K, (const double*)(unsigned char*)w.tab, (int)n, pitch, ch, X, w.keep, w.mm);
+  VgHeads v;
+  rc = voxel_grid_heads(h, "window_keyframe", "window", X, pitch, n, leaf, &v);
+  if (rc) return rc;
   HIPCHK(h, hipGetLastError());
-  int* ret = h->h_kf_ret;
-  HIPCHK(h, hipMemcpyAsync(ret, h->d_kf_pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(ret + 1, h->d_kf_flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  int* ret = w.h_ret;                             // last scan position, last head flag
+  HIPCHK(h, hipMemcpyAsync(ret, w.pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(ret + 1, w.flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  h->kf_pending = false;
+  w.pending = false;
   const size_t m = (size_t)ret[0] + (size_t)ret[1];
   rc = kf_alloc(h, kf, m, ch);
   if (rc) return rc;
   if (m) {
-    k_kf_emit<<<gx, 256, 0, s>>>(X, pitch, keys_sorted, vals_sorted, h->d_kf_flag, h->d_kf_pos, downsample, ch, kf.rows, kf.pitch, m);
+    k_kf_emit<<<gx, 256, 0, s>>>(X, pitch, v.keys, v.vals, w.flag, w.pos, v.downsample, ch, kf.rows, kf.pitch, m);
     HIPCHK(h, hipGetLastError());
   }
   *id = h->kf_next_id++;
@@ -199,13 +146,7 @@ int mi355ndt_keyframe_get(mi355ndt_handle* h, int id, void* out_pts, size_t out_
   std::vector<float> tmp((size_t)kf->ch * kf->pitch);
   HIPCHK(h, hipMemcpyAsync(tmp.data(), kf->rows, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  unsigned char* o = (unsigned char*)out_pts;
-  const size_t p = kf->pitch;
-  for (size_t i = 0; i < kf->n; i++) {
-    const float v[3] = {tmp[i], tmp[p + i], tmp[2 * p + i]};
-    memcpy(o + i * out_stride_bytes, v, 12);
-    if (ioff >= 0) { const float w = kf->ch == 4 ? tmp[3 * p + i] : 0.f; memcpy(o + i * out_stride_bytes + ioff, &w, 4); }
-  }
+  rows_to_records(tmp.data(), kf->pitch, kf->ch, kf->n, out_pts, out_stride_bytes, ioff);
   return MI355NDT_OK;
 }
 
@@ -216,7 +157,7 @@ int mi355ndt_keyframe_release(mi355ndt_handle* h, int id) {
   HIPCHK(h, hipSetDevice(h->device));
   for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));   // nothing enqueued may still read or fill the rows
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->mc_pending = false;
+  h->vs.pending = false;
   h->keyframes.erase(id);
   return MI355NDT_OK;
 }
@@ -245,7 +186,7 @@ int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int*
   HIPCHK(h, hipSetDevice(h->device));
   int rc = mc_reserve(h, K, n, 0);
   if (rc) return rc;
-  McKf* tab = (McKf*)(unsigned char*)h->h_mc_tab;
+  McKf* tab = (McKf*)(unsigned char*)h->vs.h_tab;
   size_t start = 0;
   for (int k = 0; k < K; k++) {
     const mi355ndt_handle::Keyframe& kf = h->keyframes.find(ids[k])->second;
@@ -266,12 +207,8 @@ static int batch_set_side_keyframe(mi355ndt_handle* h, bool tgt, int pair, int i
   const size_t dp = tgt ? h->tgt_pitch : h->src_pitch;
   if (kf->n > dp) { h->err = "batch_set_*_keyframe: the keyframe has more points than mi355ndt_batch_reserve made room for"; return MI355NDT_ERR_BAD_ARG; }
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = uploads_before_compute(h);             // an earlier upload into the same rows must not land after these copies
+  int rc = rows_into_slot(h, tgt, pair, kf->rows, kf->pitch, kf->n);
   if (rc) return rc;
-  float* dst = (tgt ? h->d_tgt_own : h->d_src_own) + (size_t)pair * 3 * dp;
-  HIPCHK(h, hipMemsetAsync(dst, 0, 3 * dp * sizeof(float), h->stream));
-  for (int a = 0; a < 3; a++)
-    if (kf->n) HIPCHK(h, hipMemcpyAsync(dst + a * dp, kf->rows + a * kf->pitch, kf->n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   {
     std::lock_guard<std::mutex> lk(h->up_mtx);
     (tgt ? h->h_tgt_cnt : h->h_src_cnt)[(size_t)pair] = (int)kf->n;

@@ -1,6 +1,6 @@
 // ndt_host_kffitness.hpp -- mi355ndt_keyframe_fitness_scores (graph edges between resident keyframes, ndt_kffitness.hpp) and the host
-// arithmetic of InformationMatrixCalculator::calc_information_matrix (mi355ndt_information_matrix).  Buffers of their own throughout: the
-// batch, grids, prefilter result, map-cloud and window workspaces of the handle are left as they were.
+// arithmetic of InformationMatrixCalculator::calc_information_matrix (mi355ndt_information_matrix).  The batch, the grids, the prefilter result
+// and the keyframes' rows are left as they were; the index builds' sort and the call's tables use the shared scratch (h->vs).
 #pragma once
 
 // ---- a keyframe's spatial index ----------------------------------------------------------------------
@@ -18,7 +18,7 @@ static KfiLayout kfi_layout(size_t pitch) {
   return L;
 }
 
-// enqueue the build of kf's index (kf.n > 0); the status lands in d_kfi_stat[slot].  The workspace (d_kfi_*) is sized by the caller.
+// enqueue the build of kf's index (kf.n > 0); the status lands in vs.stat[slot].  The scratch is sized by the caller.
 static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot) {
   hipStream_t s = h->stream;
   const size_t pitch = kf.pitch;
@@ -33,18 +33,15 @@ static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot
   HIPCHK(h, hipMemsetAsync(blob, 0, L.runs, s));   // header and bitmap (k_fit_mark ORs into it)
   const int gx = (int)((pitch + 255) / 256);
   const int cb = KFI_CELL_BITS;
-  k_kfi_begin<<<1, 64, 0, s>>>(h->d_kfi_mm, h->d_kfi_cnt, (int)kf.n);
-  k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(kf.rows, pitch, h->d_kfi_cnt, h->d_kfi_mm);
-  k_kfi_grid<<<1, 1, 0, s>>>(h->d_kfi_mm, (float)h->kff_cell_mm * 1e-3f, L.max_cells, gd, h->d_kfi_stat + slot);
+  VoxelScratch& w = h->vs;
+  unsigned* mm = reinterpret_cast<unsigned*>(w.mm.p);
+  k_kfi_begin<<<1, 64, 0, s>>>(mm, w.cnt, (int)kf.n);
+  k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(kf.rows, pitch, w.cnt, mm);
+  k_kfi_grid<<<1, 1, 0, s>>>(mm, (float)h->kff_cell_mm * 1e-3f, L.max_cells, gd, w.stat + slot);
   // stable sort by cell, the first pass computing the keys from the points (ndt_segsort.hpp); one segment
-  const RsPlan plan = rs_plan(cb);
-  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
-  unsigned *kin = h->d_kfi_keys, *kout = kin + pitch, *vin = h->d_kfi_vals, *vout = vin + pitch;
-  const RsPoints points = {kf.rows, h->d_kfi_cnt, gd, cb, kin};
-  for (int p = 0; p < plan.passes; p++) {
-    rs_pass(s, plan.bits, kin, vin, kout, vout, pitch, p * plan.bits, h->d_kfi_hist, h->d_kfi_offs, tiles, 1, p == 0, p == 0 ? &points : nullptr);
-    std::swap(kin, kout); std::swap(vin, vout);
-  }
+  const RsPoints points = {kf.rows, w.cnt, gd, cb, w.keys};
+  const RsSorted r = rs_sort_one_segment(s, cb, w.keys, w.vals, w.keys + pitch, w.vals + pitch, pitch, w.hist, w.offs, &points);
+  unsigned *kin = r.keys, *vin = r.vals;
   const dim3 pg((unsigned)gx, 1u);
   k_fit_mark<<<pg, 256, 0, s>>>(kin, pitch, gd, words, cb);
   k_fit_rank<<<1, 1024, 0, s>>>(gd, words);
@@ -88,18 +85,9 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
     todo.emplace(kf, slot);
     ws_pitch = std::max(ws_pitch, kf->pitch);
   }
-  if (!todo.empty()) {
-    const size_t tiles = (ws_pitch + RS_TILE - 1) / RS_TILE;
-    HIPCHK(h, h->d_kfi_keys.reserve(2 * ws_pitch)); HIPCHK(h, h->d_kfi_vals.reserve(2 * ws_pitch));
-    HIPCHK(h, h->d_kfi_hist.reserve(tiles << RS_MAX_BITS)); HIPCHK(h, h->d_kfi_offs.reserve(tiles << RS_MAX_BITS));
-    HIPCHK(h, h->d_kfi_mm.reserve(6)); HIPCHK(h, h->d_kfi_cnt.reserve(1));
-    HIPCHK(h, h->d_kfi_stat.reserve(todo.size())); HIPCHK(h, h->h_kff_stat.reserve(todo.size()));
-    for (auto& t : todo) { rc = kfi_build(h, *t.first, t.second); if (rc) return rc; }
-  }
-
   // which edges go where.  known[e]: the host has the status of the searched keyframe's index (built by an earlier call); an index built
   // by this call is in both tables and the kernels decide by its status -- the call waits for the device once, at its end
-  const float mr = max_range >= 3.0e38 ? 3.0e38f : (float)max_range;
+  const float mr = fit_range_f32(max_range);
   std::vector<int> part0((size_t)E, 0), nblk((size_t)E, 0), st((size_t)E, GRID_EMPTY);
   int n_part = 0;
   for (int e = 0; e < E; e++) {
@@ -110,42 +98,24 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
     part0[(size_t)e] = n_part;
     n_part += nblk[(size_t)e];
   }
-  // item tables of the two launches (FitItem, ndt_fitness.hpp): 16 ints of group starts, then the items group by group.  An edge goes to
-  // the least loaded of the eight groups, in edge order.
-  auto make_table = [&](bool with_grid, std::vector<int>& t, int& group_max) {
-    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<int> eg((size_t)E, -1);
-    for (int e = 0; e < E; e++) {
-      const int v = st[(size_t)e];
-      if (nblk[(size_t)e] == 0 || !(v == Keyframe::NO_INDEX || (v == GRID_OK) == with_grid)) continue;
-      int g = 0;
-      for (int k = 1; k < 8; k++) if (load[k] < load[g]) g = k;
-      eg[(size_t)e] = g;
-      load[g] += nblk[(size_t)e];
-    }
-    t.assign(16, 0);
-    for (int g = 0; g < 8; g++) {
-      t[(size_t)g] = (int)((t.size() - 16) / 6);
-      for (int e = 0, blk = 0; e < E; e++) {
-        if (eg[(size_t)e] != g) continue;
-        t.insert(t.end(), {e, blk, part0[(size_t)e], (int)k2[(size_t)e]->n, (int)k1[(size_t)e]->n, 0});
-        blk += nblk[(size_t)e];
-      }
-    }
-    t[8] = (int)((t.size() - 16) / 6);
-    group_max = *std::max_element(load, load + 8);
-  };
-  std::vector<double> part((size_t)2 * n_part);
+  // item tables of the two launches: an edge whose searched keyframe has a lattice -> k_kf_fitness, none -> k_kf_fitness_brute, an index
+  // this call builds -> both (the kernels decide by its status)
+  std::vector<int> tab, tab_brute;
+  int gmax = 0, gmax_brute = 0;
+  for (const bool with_grid : {true, false})
+    fit_item_table(E, nblk, part0, [&](int e) { return st[(size_t)e] == Keyframe::NO_INDEX || (st[(size_t)e] == GRID_OK) == with_grid; },
+                   [&](int e) { return std::array<int, 3>{(int)k2[(size_t)e]->n, (int)k1[(size_t)e]->n, 0}; },
+                   with_grid ? tab : tab_brute, with_grid ? gmax : gmax_brute);
+  static_assert(sizeof(FitItem) == 6 * sizeof(int) && sizeof(KfEdge) % 8 == 0, "the tables' layout");
+  const size_t at_ok = (size_t)E * sizeof(KfEdge), at_brute = at_ok + tab.size() * sizeof(int), bytes = at_brute + tab_brute.size() * sizeof(int);
+  VoxelScratch& w = h->vs;
+  VsNeed need;
+  need.pitch = ws_pitch; need.tab = n_part > 0 ? bytes : 0; need.part = (size_t)2 * n_part; need.stat = todo.size();
+  rc = vs_reserve(h, need);
+  if (rc) return rc;
+  for (auto& t : todo) { rc = kfi_build(h, *t.first, t.second); if (rc) return rc; }
   if (n_part > 0) {
-    std::vector<int> tab, tab_brute;
-    int gmax = 0, gmax_brute = 0;
-    make_table(true, tab, gmax);
-    make_table(false, tab_brute, gmax_brute);
-    static_assert(sizeof(FitItem) == 6 * sizeof(int) && sizeof(KfEdge) % 8 == 0, "the tables' layout");
-    const size_t at_ok = (size_t)E * sizeof(KfEdge), at_brute = at_ok + tab.size() * sizeof(int), bytes = at_brute + tab_brute.size() * sizeof(int);
-    HIPCHK(h, h->h_kff_tab.reserve(bytes)); HIPCHK(h, h->d_kff_tab.reserve(bytes));
-    HIPCHK(h, h->d_kff_part.reserve((size_t)2 * n_part)); HIPCHK(h, h->h_kff_part.reserve((size_t)2 * n_part));
-    unsigned char* ht = h->h_kff_tab;
+    unsigned char* ht = w.h_tab;
     KfEdge* he = reinterpret_cast<KfEdge*>(ht);
     for (int e = 0; e < E; e++) {
       const Keyframe *a = k1[(size_t)e], *b = k2[(size_t)e];
@@ -163,27 +133,23 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
     }
     memcpy(ht + at_ok, tab.data(), tab.size() * sizeof(int));
     memcpy(ht + at_brute, tab_brute.data(), tab_brute.size() * sizeof(int));
-    HIPCHK(h, hipMemcpyAsync(h->d_kff_tab, ht, bytes, hipMemcpyHostToDevice, s));
-    const unsigned char* dt = h->d_kff_tab;
+    w.pending = true;
+    HIPCHK(h, hipMemcpyAsync(w.tab, ht, bytes, hipMemcpyHostToDevice, s));
+    const unsigned char* dt = w.tab;
     const KfEdge* de = reinterpret_cast<const KfEdge*>(dt);
     const int* t_ok = reinterpret_cast<const int*>(dt + at_ok);
     const int* t_brute = reinterpret_cast<const int*>(dt + at_brute);
-    if (gmax) k_kf_fitness<<<8u * (unsigned)gmax, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_ok + 16), t_ok, de, mr, max_range, h->d_kff_part);
-    if (gmax_brute) k_kf_fitness_brute<<<8u * (unsigned)gmax_brute, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_brute + 16), t_brute, de, mr, h->d_kff_part);
+    if (gmax) k_kf_fitness<<<8u * (unsigned)gmax, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_ok + 16), t_ok, de, mr, max_range, w.part);
+    if (gmax_brute) k_kf_fitness_brute<<<8u * (unsigned)gmax_brute, 256, 0, s>>>(reinterpret_cast<const FitItem*>(t_brute + 16), t_brute, de, mr, w.part);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->h_kff_part, h->d_kff_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(w.h_part, w.part, (size_t)2 * n_part * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  if (!todo.empty()) HIPCHK(h, hipMemcpyAsync(h->h_kff_stat, h->d_kfi_stat, todo.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!todo.empty()) HIPCHK(h, hipMemcpyAsync(w.h_ret, w.stat, todo.size() * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));             // the call's one wait
+  w.pending = false;
   HIPCHK(h, hipGetLastError());
-  for (auto& t : todo) t.first->index_status = h->h_kff_stat[t.second];
-  if (n_part > 0) memcpy(part.data(), h->h_kff_part, part.size() * sizeof(double));
-  for (int e = 0; e < E; e++) {
-    double sum = 0, cnt = 0;
-    for (int k = 0; k < nblk[(size_t)e]; k++) { sum += part[2 * ((size_t)part0[(size_t)e] + k)]; cnt += part[2 * ((size_t)part0[(size_t)e] + k) + 1]; }
-    scores[e] = cnt > 0 ? sum / cnt : 1.7976931348623157e308;     // std::numeric_limits<double>::max()
-    if (n_inliers) n_inliers[e] = (long long)cnt;
-  }
+  for (auto& t : todo) t.first->index_status = w.h_ret[t.second];
+  for (int e = 0; e < E; e++) fit_reduce(w.h_part + 2 * (size_t)part0[(size_t)e], nblk[(size_t)e], scores + e, n_inliers ? n_inliers + e : nullptr);
   return MI355NDT_OK;
 }
 

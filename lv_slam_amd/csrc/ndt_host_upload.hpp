@@ -1,5 +1,6 @@
-// ndt_host_upload.hpp -- capacity management (reserve, bind) and the host-cloud uploads: pinned staging ring, copy streams, upload_items,
-// mi355ndt_batch_set_* / mi355ndt_batch_set_clouds, and the two events that order uploads against compute.
+// ndt_host_upload.hpp -- capacity management (reserve, bind) and the host-cloud uploads: pinned staging ring, copy streams, upload_items and its
+// staging threads, mi355ndt_batch_set_* / mi355ndt_batch_set_clouds, the two events that order uploads against compute, and the device-to-device
+// copy of rows into a batch slot.
 #pragma once
 
 // ---- capacity management ----------------------------------------------------------------------
@@ -182,6 +183,52 @@ static int upload_cloud(mi355ndt_handle* h, float* d_base, size_t pitch, int pai
   return upload_items(h, &it, 1);
 }
 
+// nt staging threads, the caller's among them (t = 0), each running work(t) -> status; the first status that is not OK is returned.  Nothing
+// may be thrown across the C boundary: a thread that cannot be created (std::system_error) just means the others -- at least the caller's --
+// do its share.
+template <typename Work>
+static int staging_threads(int nt, Work work) {
+  std::vector<int> rcs((size_t)nt, MI355NDT_OK);
+  std::vector<std::thread> th;
+  try {
+    th.reserve((size_t)nt);
+    for (int t = 1; t < nt; t++) th.emplace_back([&rcs, &work, t] { rcs[(size_t)t] = work(t); });
+  } catch (...) {}
+  rcs[0] = work(0);
+  for (auto& x : th) x.join();
+  for (int rc : rcs) if (rc != MI355NDT_OK) return rc;
+  return MI355NDT_OK;
+}
+
+// many clouds into rows of one buffer (the map cloud's keyframes, the window's scans): groups of up to UP_GROUP_MAX items, one transfer
+// each, staged by up to eight threads
+static int upload_items_grouped(mi355ndt_handle* h, const std::vector<UpItem>& items) {
+  const int n_groups = (int)((items.size() + UP_GROUP_MAX - 1) / UP_GROUP_MAX);
+  std::atomic<int> next_group{0};
+  return staging_threads(std::max(1, std::min(8, n_groups)), [&](int) {
+    (void)hipSetDevice(h->device);
+    for (int g = next_group.fetch_add(1); g < n_groups; g = next_group.fetch_add(1)) {
+      const size_t i0 = (size_t)g * UP_GROUP_MAX, i1 = std::min(items.size(), i0 + UP_GROUP_MAX);
+      const int rc = upload_items(h, items.data() + i0, (int)(i1 - i0));
+      if (rc != MI355NDT_OK) return rc;
+    }
+    return (int)MI355NDT_OK;
+  });
+}
+
+// m points of device SoA rows (pitch src_pitch) into a pair slot of the engine's own batch rows, device to device, the slot's rows
+// zero-filled up to their pitch as an upload leaves them.  The caller does the bookkeeping (counts, flags, compute_enqueued or a build).
+static int rows_into_slot(mi355ndt_handle* h, bool tgt, int pair, const float* rows, size_t src_pitch, size_t m) {
+  int rc = uploads_before_compute(h);             // an earlier upload into these rows must not land after the copies (and one into `rows` has to have landed)
+  if (rc) return rc;
+  const size_t dp = tgt ? h->tgt_pitch : h->src_pitch;
+  float* dst = (tgt ? h->d_tgt_own : h->d_src_own) + (size_t)pair * 3 * dp;
+  HIPCHK(h, hipMemsetAsync(dst, 0, 3 * dp * sizeof(float), h->stream));
+  for (int a = 0; a < 3; a++)
+    if (m) HIPCHK(h, hipMemcpyAsync(dst + a * dp, rows + a * src_pitch, m * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  return MI355NDT_OK;
+}
+
 // one host cloud into its pair slot, target or source side (may be called from several threads, distinct pairs)
 static int batch_set_side(mi355ndt_handle* h, bool tgt, int pair, const void* pts, size_t n, size_t stride) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
@@ -208,7 +255,6 @@ int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const v
   if (h->d_tgt != h->d_tgt_own || h->d_src != h->d_src_own) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
   const int nt = std::max(1, std::min(n_threads > 0 ? n_threads : 8, n));
-  std::vector<int> rcs((size_t)nt, MI355NDT_OK);
   // the engine's own threads stage next to the GPU -- but only on CPUs the CALLER may use: the NUMA node's CPUs intersected with the
   // calling thread's affinity mask (a taskset / cgroup-restricted process keeps its restriction); an empty intersection = no pinning
   cpu_set_t near, mine;
@@ -222,7 +268,7 @@ int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const v
   // (the caller's, t = 0, may sit on a narrowed CPU set) simply takes fewer groups
   const int g_first = first_pair / UP_GROUP_PAIRS, g_last = (first_pair + n - 1) / UP_GROUP_PAIRS;
   std::atomic<int> next_group{g_first};
-  auto work = [&](int t) {
+  auto work = [&](int t) -> int {
     (void)hipSetDevice(h->device);
     if (pin && t > 0) (void)sched_setaffinity(0, sizeof near, &near);   // (t = 0 is the caller's thread: left alone)
     for (int g = next_group.fetch_add(1); g <= g_last; g = next_group.fetch_add(1)) {
@@ -234,17 +280,12 @@ int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const v
         if (sources) it[cnt++] = UpItem{h->d_src_own, h->src_pitch, pr, sources[k], source_counts[k], stride};
       }
       const int rc = upload_items(h, it, cnt);
-      if (rc != MI355NDT_OK) { rcs[(size_t)t] = rc; return; }
+      if (rc != MI355NDT_OK) return rc;
     }
+    return (int)MI355NDT_OK;
   };
-  std::vector<std::thread> th;
-  try {                                          // nothing may be thrown across the C boundary: a thread that cannot be created
-    th.reserve((size_t)nt);                      // (std::system_error) just means the others -- at least the caller's -- do its share
-    for (int t = 1; t < nt; t++) th.emplace_back(work, t);
-  } catch (...) {}
-  work(0);
-  for (auto& x : th) x.join();
-  for (int rc : rcs) if (rc != MI355NDT_OK) return rc;
+  const int rc = staging_threads(nt, work);
+  if (rc) return rc;
   {
     std::lock_guard<std::mutex> lk(h->up_mtx);
     for (int k = 0; k < n; k++) {

@@ -1,0 +1,78 @@
+// ndt_host_voxel.hpp -- what the prefilter, the map cloud, the window map and the keyframe index builds share on the host: growth of their one
+// scratch (VoxelScratch, ndt_engine.hpp), the exclusive scan, the VoxelGrid chain and the scatter of SoA rows into the caller's records.
+#pragma once
+
+// what a call needs of the scratch: points (a multiple of 64: every per-point member follows from it), floats of in / x / out, bytes of the
+// tables, doubles of the partials, status ints
+struct VsNeed { size_t pitch = 0, in = 0, x = 0, out = 0, tab = 0, part = 0, stat = 0; };
+
+// The growth rule, once: a member that grows is freed first, so nothing enqueued -- on the copy streams or the compute stream -- may still
+// use the scratch.  pos is reserved last: a failed allocation leaves its capacity vouching for nothing that was freed.
+static int vs_reserve(mi355ndt_handle* h, const VsNeed& n) {
+  VoxelScratch& w = h->vs;
+  hipStream_t s = h->stream;
+  if (w.pending) { HIPCHK(h, hipStreamSynchronize(s)); w.pending = false; }   // (the host is about to write h_tab)
+  if (n.pitch > w.pos.cap || n.in > w.in.cap || n.x > w.x.cap || n.out > w.out.cap || n.tab > w.tab.cap || n.part > w.part.cap || n.stat > w.stat.cap) {
+    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  const size_t tiles = (n.pitch + RS_TILE - 1) / RS_TILE;
+  HIPCHK(h, w.in.reserve(n.in)); HIPCHK(h, w.x.reserve(n.x)); HIPCHK(h, w.out.reserve(n.out)); HIPCHK(h, w.keep.reserve(n.pitch));
+  HIPCHK(h, w.keys.reserve(2 * n.pitch)); HIPCHK(h, w.vals.reserve(2 * n.pitch)); HIPCHK(h, w.flag.reserve(n.pitch));
+  HIPCHK(h, w.hist.reserve(tiles << RS_MAX_BITS)); HIPCHK(h, w.offs.reserve(tiles << RS_MAX_BITS));
+  HIPCHK(h, w.tmp.reserve((n.pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK)); HIPCHK(h, w.aabb.reserve(6 * ((n.pitch + MC_CHUNK - 1) / MC_CHUNK)));
+  HIPCHK(h, w.mm.reserve(6)); HIPCHK(h, w.cnt.reserve(1)); HIPCHK(h, w.grid.reserve(1)); HIPCHK(h, w.box.reserve(1));
+  HIPCHK(h, w.tab.reserve(n.tab)); HIPCHK(h, w.h_tab.reserve(n.tab)); HIPCHK(h, w.part.reserve(n.part)); HIPCHK(h, w.h_part.reserve(n.part));
+  HIPCHK(h, w.stat.reserve(n.stat)); HIPCHK(h, w.h_ret.reserve(std::max((size_t)4, n.stat)));
+  HIPCHK(h, w.pos.reserve(n.pitch));
+  return MI355NDT_OK;
+}
+
+// exclusive scan of `pitch` ints (ndt_prefilter.hpp); tmp: one word per PF_SCAN_CHUNK
+static void exscan_ints(hipStream_t s, const int* flag, size_t pitch, unsigned* tmp, int* pos) {
+  const int chunks = (int)((pitch + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK);
+  k_pf_scan_totals<<<chunks, 1024, 0, s>>>(flag, pitch, tmp);
+  k_pf_scan_offsets<<<1, 1024, 0, s>>>(tmp, chunks);
+  k_pf_scan_apply<<<chunks, 1024, 0, s>>>(flag, pitch, tmp, pos);
+}
+
+// The VoxelGrid chain between the caller's flag kernel (vs.keep and vs.mm filled from the n points of X) and its emit kernel: grid, keys,
+// stable sort by voxel index (the whole cloud one segment, 31 key bits), run heads, emit positions in vs.pos.  It waits for the device once,
+// for the grid's status; a leaf too small for the extent (PCL: "Leaf size is too small for the input dataset") leaves the cloud as it is:
+// `who`'s `what` is not down-sampled, and h->err says so.  leaf <= 0: no down-sampling, no wait.
+struct VgHeads { const unsigned *keys, *vals; int downsample; };   // the sorted keys and point ids; 0: the kept points in input order
+static int voxel_grid_heads(mi355ndt_handle* h, const char* who, const char* what, const float* X, size_t pitch, size_t n, float leaf, VgHeads* out) {
+  VoxelScratch& w = h->vs;
+  hipStream_t s = h->stream;
+  const int gx = (int)((pitch + 255) / 256);
+  *out = VgHeads{w.keys, w.vals, leaf > 0.f};
+  if (out->downsample) {
+    k_pf_grid<<<1, 1, 0, s>>>(w.mm, leaf, w.grid);
+    PfGrid g;
+    HIPCHK(h, hipMemcpyAsync(&g, w.grid, sizeof g, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    w.pending = false;
+    if (g.status == 2) {
+      h->err = std::string(who) + ": leaf size too small for the " + what + "'s extent, voxel indices would overflow; " + what + " not down-sampled";
+      out->downsample = 0;
+    } else {
+      k_pf_keys<<<gx, 256, 0, s>>>(X, pitch, (int)n, w.keep, w.grid, w.keys, w.vals);
+      const RsSorted r = rs_sort_one_segment(s, 31, w.keys, w.vals, w.keys + pitch, w.vals + pitch, pitch, w.hist, w.offs);
+      out->keys = r.keys; out->vals = r.vals;
+    }
+  }
+  k_pf_heads<<<gx, 256, 0, s>>>(out->keys, w.keep, (int)n, pitch, out->downsample, w.flag);
+  exscan_ints(s, w.flag, pitch, w.tmp, w.pos);
+  return MI355NDT_OK;
+}
+
+// n points of host SoA rows (`ch` rows of `pitch` floats: x, y, z and, with ch = 4, the intensity) into the caller's records; ioff >= 0: the
+// record's f32 at that byte offset receives the intensity (0 where the rows carry none)
+static void rows_to_records(const float* rows, size_t pitch, int ch, size_t n, void* out_pts, size_t out_stride, int ioff) {
+  unsigned char* o = (unsigned char*)out_pts;
+  for (size_t i = 0; i < n; i++) {
+    const float v[3] = {rows[i], rows[pitch + i], rows[2 * pitch + i]};
+    memcpy(o + i * out_stride, v, 12);
+    if (ioff >= 0) { const float w = ch == 4 ? rows[3 * pitch + i] : 0.f; memcpy(o + i * out_stride + ioff, &w, 4); }
+  }
+}

@@ -241,3 +241,19 @@ static inline void rs_pass(hipStream_t s, int bits, const unsigned* kin, const u
   else if (bits == 10) rs_pass_bits<10>(s, kin, vin, kout, vout, pitch, shift, hist, offs, tiles, n_segments, first, points);
   else rs_pass_bits<11>(s, kin, vin, kout, vout, pitch, shift, hist, offs, tiles, n_segments, first, points);
 }
+
+// The whole sort of ONE segment of `pitch` positions over `field_bits` key bits: rs_plan(field_bits).passes passes hopping between (ka, va)
+// and (kb, vb).  Returns where the sorted keys and values ended up, and the other pair (free again; the map cloud's second sort hops through
+// it).  `points`: the first pass computes the keys from the points (into ka) and takes position i as point id i; else ka / va hold both.
+struct RsSorted { unsigned *keys, *vals, *keys_free, *vals_free; };
+static inline RsSorted rs_sort_one_segment(hipStream_t s, int field_bits, unsigned* ka, unsigned* va, unsigned* kb, unsigned* vb, size_t pitch,
+                                           unsigned* hist, unsigned* offs, const RsPoints* points = nullptr) {
+  const RsPlan plan = rs_plan(field_bits);
+  const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
+  RsSorted r = {ka, va, kb, vb};
+  for (int p = 0; p < plan.passes; p++) {
+    rs_pass(s, plan.bits, r.keys, r.vals, r.keys_free, r.vals_free, pitch, p * plan.bits, hist, offs, tiles, 1, points && p == 0, p == 0 ? points : nullptr);
+    std::swap(r.keys, r.keys_free); std::swap(r.vals, r.vals_free);
+  }
+  return r;
+}

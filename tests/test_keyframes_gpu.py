@@ -233,3 +233,63 @@ def test_window_keyframer_to_map_cloud_end_to_end():
         exp = MR.map_cloud([ref.clouds[r.id] for r in exp_kf], [r.odom for r in exp_kf], res)
         assert got.shape == exp.shape and same_words(got, exp)
     e.close()
+
+
+def test_interleaved_surfaces_equal_fresh_engines():
+    """The prefilter, both routes of the map cloud, the window map and the keyframe fitness scores (whose first look at a keyframe builds its
+    index) share one scratch on the engine.  One engine runs them interleaved, every surface once right after a larger call and once right
+    after a smaller one; every output equals, word for word, that of the same call alone on a fresh engine.  use_prefiltered then still
+    hands over the prefilter result made before all of that -- and, after a second prefilter that follows a larger call, that one."""
+    scans, poses = synth.make_sequence(6, 128, n_beams=48)        # 6,144 points per scan
+    big = [c.numpy().astype(np.float32) for c in scans]
+    small = [np.ascontiguousarray(c[::4]) for c in big]            # 1,536
+    t, s, _ = synth.make_pair(210, 256, n_beams=16)                # 4,096
+    t, s, s2 = t.numpy(), s.numpy(), np.ascontiguousarray(s.numpy()[::2])
+    G = synth.default_guess()
+
+    def pf(e, cloud):
+        return e.prefilter(cloud, 0.5, 100.0, 0.2).tobytes()
+
+    def mc(e, clouds, k0):
+        return e.map_cloud(clouds[k0:k0 + 3], poses[k0:k0 + 3], 0.5).tobytes()
+
+    def mk(e, clouds, k0):
+        return e.map_cloud_keyframes([e.keyframe_add(c) for c in clouds[k0:k0 + 3]], poses[k0:k0 + 3], 0.5).tobytes()
+
+    def wk(e, clouds, k0):
+        kid, n = e.window_keyframe(clouds[k0:k0 + 2], [np.linalg.inv(poses[k0]) @ P for P in poses[k0:k0 + 2]], 0.1)
+        return n, e.keyframe_get(kid).tobytes()
+
+    def kff(e, clouds, k0):
+        ids = [e.keyframe_add(c) for c in clouds[k0:k0 + 3]]
+        rel = np.stack([np.linalg.inv(poses[k0 + i]) @ poses[k0 + i + 1] for i in range(2)])
+        sc, inl = e.keyframe_fitness_scores(ids[:2], ids[1:], rel, 1.0)
+        return np.float64(sc).tobytes(), np.int64(inl).tobytes()
+
+    def handed(e):                                                 # the prefilter result as the target of a registration
+        e.set_source(s)
+        e.use_prefiltered(as_target=True)
+        return _res_words(e.align(G)), e.fitness_score()
+
+    def fresh(f, *a, then=None):
+        e = ndt.Engine(ndt.default_params(**PRM))
+        out = f(e, *a) if then is None else (f(e, *a), then(e))[1]
+        e.close()
+        return out
+
+    # (call, arguments, points the call's scratch is sized for)
+    order = [(wk, (small, 0), 3072), (pf, (t,), 4096), (mc, (big, 0), 18432), (wk, (small, 2), 3072), (mk, (big, 1), 18432),
+             (kff, (small, 0), 1536), (wk, (big, 0), 12288), (mc, (small, 1), 4608), (kff, (big, 0), 6144), (mk, (small, 3), 4608)]
+    tail = [(mc, (big, 3), 18432), (pf, (s2,), 2048)]
+    for f in (pf, mc, mk, wk, kff):                                # every surface follows a larger and a smaller call
+        seq = order + tail
+        after = [seq[i - 1][2] - seq[i][2] for i in range(1, len(seq)) if seq[i][0] is f]
+        assert min(after) < 0 < max(after), f.__name__
+    e = ndt.Engine(ndt.default_params(**PRM))
+    for i, (f, a, _) in enumerate(order):
+        assert f(e, *a) == fresh(f, *a), (i, f.__name__)
+    assert handed(e) == fresh(pf, t, then=handed)                  # the first prefilter's result, nine other calls later
+    for i, (f, a, _) in enumerate(tail):
+        assert f(e, *a) == fresh(f, *a), ("tail", i, f.__name__)
+    assert handed(e) == fresh(pf, s2, then=handed)
+    e.close()

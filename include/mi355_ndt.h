@@ -245,7 +245,11 @@ enum mi355ndt_option {
    * doubled until the keyframe's lattice has at most min(2^21, 64 x points) cells; a keyframe that does not get there within six doublings (a
    * stray point at 1e12 m) is searched exhaustively.  The search is exact for any cell: no result bit depends on the option, only the time.
    * Indexes that exist keep the cell they were built with. */
-  MI355NDT_OPT_KF_FITNESS_CELL_MM = 9
+  MI355NDT_OPT_KF_FITNESS_CELL_MM = 9,
+  /* Cell size, in millimetres, of the spatial index mi355ndt_prefilter_outliers builds over the prefilter result in every call (default 100,
+   * the keyframe option's default until the timing tool's sweep has been run on a GPU: DESIGN.md 8), doubled by the keyframe option's rule.
+   * The search is exact for any cell: no result bit depends on the option, only the time. */
+  MI355NDT_OPT_OUTLIER_CELL_MM = 10
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);
@@ -415,6 +419,41 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
                        void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
 /* install the last prefilter result as the registration source (role 1) or target (role 2) without a host round trip */
 int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
+
+/* replaces PrefilteringNodelet::outlier_removal (prefiltering_nodelet.cpp:128, 150-161), the nodelet's last stage, over the RESIDENT
+ * prefilter result, in place: the survivors keep their order, the result's count and rows are updated, and mi355ndt_use_prefiltered
+ * installs the filtered cloud.  (A cloud that needs only this stage goes through mi355ndt_prefilter first, distance filter off and
+ * resolution <= 0.)  Searchable points are those with three finite coordinates; squared distances are f32, (dx*dx + dy*dy) + dz*dz.
+ *   STATISTICAL (pcl::StatisticalOutlierRemoval, the nodelet's in-code default, :61-70): per point, the mean_k + 1 smallest squared
+ *     distances over the searchable points, itself included; sorted ascending, the first dropped; dist = (float)(sum of
+ *     (double)sqrtf(d2) in ascending order / mean_k).  A non-finite point, or any point of a cloud with fewer than mean_k + 1
+ *     searchable points, has dist = 0 and is not valid.  f64, in index order over every dist (zeros included): sum, sq;
+ *     mean = sum / n_valid; var = (sq - sum * sum / n_valid) / (n_valid - 1); threshold = mean + stddev_mul * sqrt(var).  A point is
+ *     removed iff (double)dist > threshold: non-valid points survive, and with n_valid of 0 or 1 the threshold is NaN and all survive.
+ *   RADIUS (pcl::RadiusOutlierRemoval): kept iff at least min_neighbors searchable points other than itself have d2 < (float)(radius *
+ *     radius), strictly; coincident points count; non-finite points are removed.  NOTE: the reference never runs this branch -- it
+ *     builds the filter and does not assign it (:71-78), so under its launch files, which all ask for RADIUS, nothing is removed.  A
+ *     host that wants the reference's behaviour under those launch files must not call this function.
+ * mean_distances (may be NULL): dist of the n_in input points, input order (zeros for RADIUS).  out_pts / out_capacity /
+ * out_stride_bytes / n_out as in mi355ndt_prefilter.  stats (may be NULL): STATISTICAL only, zeros for RADIUS.  The rules are PCL 1.8's
+ * and FLANN's as restated in tools/outlier_ref.py, unpinned.  MI355NDT_ERR_STATE when no prefilter result is resident
+ * or in stream mode; MI355NDT_ERR_BAD_ARG with a mi355ndt_last_error text for an unknown method, mean_k outside 1..64, min_neighbors
+ * outside 0..64, a NaN or negative radius, a NaN stddev_mul.  An empty resident cloud gives *n_out = 0.  Synchronous, two waits for
+ * the device (dist comes back once: the index-order sums are the host's).  The batch, the grids, the keyframes and their indexes, the
+ * map-cloud and window workspaces of the handle are left as they were.  MI355NDT_OPT_OUTLIER_CELL_MM. */
+enum { MI355NDT_OUTLIER_STATISTICAL = 1, MI355NDT_OUTLIER_RADIUS = 2 };
+typedef struct mi355ndt_outlier_params {
+  int method; int mean_k; double stddev_mul;      /* STATISTICAL: 20, 1.0  (prefiltering_nodelet.cpp:63-64) */
+  double radius; int min_neighbors;               /* RADIUS: 0.8, 2        (:72-73) */
+} mi355ndt_outlier_params;
+typedef struct mi355ndt_outlier_stats {           /* STATISTICAL only; zeros for RADIUS */
+  long long n_in, n_valid; double mean, stddev, threshold;
+} mi355ndt_outlier_stats;
+int mi355ndt_outlier_params_default(mi355ndt_outlier_params* p);   /* method STATISTICAL and the five defaults above */
+int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_params* p,
+                                float* mean_distances /* may be NULL; n_in floats, input order */,
+                                void* out_pts, size_t out_capacity, size_t out_stride_bytes,
+                                size_t* n_out, mi355ndt_outlier_stats* stats /* may be NULL */);
 
 /* ---- map cloud: the global graph's map (MapCloudGenerator::generate) ------------------------------------ */
 /* replaces MapCloudGenerator::generate(keyframes, resolution) (src/global_graph/map_cloud_generator.cpp:17-55), which

@@ -49,6 +49,7 @@
 #include "ndt_mapcloud.hpp"
 #include "ndt_keyframe.hpp"
 #include "ndt_kffitness.hpp"
+#include "ndt_outlier.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
@@ -76,5 +77,6 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_mapcloud.hpp"   // map cloud
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id
 #include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
+#include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result
 #include "ndt_host_sequence.hpp"   // latency mode, sequence run
 #include "ndt_host_stream.hpp"     // stream mode

@@ -48,7 +48,7 @@ struct StreamState {
 };
 
 // ---- scratch of the sort-and-compact chain: stage clouds -> extremes -> grid -> keys -> one-segment radix sort -> run heads -> exclusive
-// scan -> emit -> count.  The prefilter, the map cloud (both routes), the window map and the keyframe index builds of
+// scan -> emit -> count.  The prefilter, its outlier removal, the map cloud (both routes), the window map and the keyframe index builds of
 // mi355ndt_keyframe_fitness_scores share this one instance; results (d_pf_out, the keyframe store and its indexes) are not in it.
 // Sharing is safe because
 //   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;
@@ -120,6 +120,9 @@ struct mi355ndt_handle {
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
   // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)
   DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0;
+  // outlier removal over it (mi355ndt_prefilter_outliers): the index block rebuilt by every call, dist[] and its pinned twin
+  DevBuf<unsigned char> d_ol_index; DevBuf<float> d_ol_dist; PinBuf<float> h_ol_dist;
+  int ol_cell_mm = 100;                           // MI355NDT_OPT_OUTLIER_CELL_MM
   VoxelScratch vs;                                // scratch of the prefilter, the map cloud, the window map and the keyframe index builds
   // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
   // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice

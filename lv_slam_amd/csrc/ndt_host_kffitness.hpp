@@ -18,14 +18,13 @@ static KfiLayout kfi_layout(size_t pitch) {
   return L;
 }
 
-// enqueue the build of kf's index (kf.n > 0); the status lands in vs.stat[slot].  The scratch is sized by the caller.
-static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot) {
+// enqueue the build of an index over `n` points of SoA rows (n > 0) into `blob` (kfi_layout(pitch).bytes, the caller's), the lattice starting
+// from cells of `cell_mm`; the status lands in vs.stat[slot], the point ids in cell order in *ids (scratch: valid until the scratch is used
+// again).  The scratch is sized by the caller.  Shared by the keyframe indexes and the outlier removal (ndt_host_outlier.hpp).
+static int kfi_build_rows(mi355ndt_handle* h, const float* rows, size_t pitch, size_t n, int cell_mm, unsigned char* blob, int slot,
+                          const unsigned** ids = nullptr) {
   hipStream_t s = h->stream;
-  const size_t pitch = kf.pitch;
   const KfiLayout L = kfi_layout(pitch);
-  kf.index_status = mi355ndt_handle::Keyframe::NO_INDEX;
-  HIPCHK(h, kf.index.realloc_exact(L.bytes));
-  unsigned char* blob = kf.index;
   GridDesc* gd = reinterpret_cast<GridDesc*>(blob);
   BitWord* words = reinterpret_cast<BitWord*>(blob + L.words);
   unsigned* runs = reinterpret_cast<unsigned*>(blob + L.runs);
@@ -35,20 +34,28 @@ static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot
   const int cb = KFI_CELL_BITS;
   VoxelScratch& w = h->vs;
   unsigned* mm = reinterpret_cast<unsigned*>(w.mm.p);
-  k_kfi_begin<<<1, 64, 0, s>>>(mm, w.cnt, (int)kf.n);
-  k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(kf.rows, pitch, w.cnt, mm);
-  k_kfi_grid<<<1, 1, 0, s>>>(mm, (float)h->kff_cell_mm * 1e-3f, L.max_cells, gd, w.stat + slot);
+  k_kfi_begin<<<1, 64, 0, s>>>(mm, w.cnt, (int)n);
+  k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(rows, pitch, w.cnt, mm);
+  k_kfi_grid<<<1, 1, 0, s>>>(mm, (float)cell_mm * 1e-3f, L.max_cells, gd, w.stat + slot);
   // stable sort by cell, the first pass computing the keys from the points (ndt_segsort.hpp); one segment
-  const RsPoints points = {kf.rows, w.cnt, gd, cb, w.keys};
+  const RsPoints points = {rows, w.cnt, gd, cb, w.keys};
   const RsSorted r = rs_sort_one_segment(s, cb, w.keys, w.vals, w.keys + pitch, w.vals + pitch, pitch, w.hist, w.offs, &points);
   unsigned *kin = r.keys, *vin = r.vals;
   const dim3 pg((unsigned)gx, 1u);
   k_fit_mark<<<pg, 256, 0, s>>>(kin, pitch, gd, words, cb);
   k_fit_rank<<<1, 1024, 0, s>>>(gd, words);
   k_fit_runs<<<pg, 256, 0, s>>>(kin, pitch, gd, words, runs, cb);
-  k_kfi_gather<<<gx, 256, 0, s>>>(kf.rows, pitch, vin, sorted);
+  k_kfi_gather<<<gx, 256, 0, s>>>(rows, pitch, vin, sorted);
   HIPCHK(h, hipGetLastError());
+  if (ids) *ids = vin;
   return MI355NDT_OK;
+}
+
+// enqueue the build of kf's index (kf.n > 0); the status lands in vs.stat[slot].  The scratch is sized by the caller.
+static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot) {
+  kf.index_status = mi355ndt_handle::Keyframe::NO_INDEX;
+  HIPCHK(h, kf.index.realloc_exact(kfi_layout(kf.pitch).bytes));
+  return kfi_build_rows(h, kf.rows, kf.pitch, kf.n, h->kff_cell_mm, kf.index, slot);
 }
 
 // replaces InformationMatrixCalculator::calc_fitness_score (information_matrix_calculator.cpp:53-87) for E graph edges at once

@@ -252,6 +252,11 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
     h->kff_cell_mm = value;                      // (indexes that exist keep the cell they were built with)
     return MI355NDT_OK;
   }
+  if (option == MI355NDT_OPT_OUTLIER_CELL_MM) {
+    if (value < 1 || value > 1000000) return MI355NDT_ERR_BAD_ARG;
+    h->ol_cell_mm = value;
+    return MI355NDT_OK;
+  }
   return MI355NDT_ERR_BAD_ARG;
 }
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
@@ -266,5 +271,6 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (option == MI355NDT_OPT_STREAM_THRESHOLD) { *value = h->s_thresh_opt; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_STREAM_RESERVE) { *value = h->s_reserve_opt; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_KF_FITNESS_CELL_MM) { *value = h->kff_cell_mm; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_OUTLIER_CELL_MM) { *value = h->ol_cell_mm; return MI355NDT_OK; }
   return MI355NDT_ERR_BAD_ARG;
 }

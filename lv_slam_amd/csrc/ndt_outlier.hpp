@@ -1,0 +1,160 @@
+// ndt_outlier.hpp -- outlier removal over the resident prefilter result (mi355ndt_prefilter_outliers): the last stage of
+// PrefilteringNodelet::filter (src/lidar_odometry/prefiltering_nodelet.cpp:128, 150-161) -- pcl::StatisticalOutlierRemoval (the in-code
+// default, :61-70) and pcl::RadiusOutlierRemoval (:71-78, built by the reference and never assigned: it does not run there).
+//
+// Both filters ask one question per point: the K smallest squared distances to the OTHER searchable points (three finite coordinates).
+//   STATISTICAL  nearestKSearch(mean_k + 1) returns the point itself first (d2 = 0, the smallest there is) and the filter drops it: what is
+//                left is the mean_k smallest distances to the others, K = mean_k.  dist = (float)(sum of (double)sqrtf(d2), ascending / mean_k).
+//   RADIUS       kept iff at least min_neighbors others have d2 < r2 (strict): the K-th smallest distance to the others, K = min_neighbors, is < r2.
+// The multiset of the K smallest does not depend on the visiting order or on how ties are broken, so the search is exact word for word.
+//
+// The index is the keyframe index (ndt_kffitness.hpp: lattice, rank words, run starts, points in cell order), built per call into a block of
+// this surface's own.  k_ol_knn takes its queries in cell order -- a wave's lanes sit in neighbouring cells and walk similar rings -- and
+// scatters the results by point id; fit_rings drives it with the list's worst entry as `best` once the list is full.  Each lane's list lives in
+// LDS, [slot][lane]: a wave's access to one slot touches 64 consecutive words (no bank conflict), and no lane needs scratch memory for it.
+// A cloud without a lattice (GRID_CAP: a stray point at 1e12 m) goes through k_ol_knn_brute, exhaustive over LDS tiles of the rows.
+#pragma once
+#include "ndt_types.hpp"
+#include "ndt_fitness.hpp"
+#include "ndt_kffitness.hpp"
+
+#define OL_LANES 64                      // one wave per workgroup: a wave whose lanes walk far gives its LDS back on its own
+#define OL_MAX_K 64
+#define OL_STATISTICAL 1
+#define OL_RADIUS 2
+
+// the K smallest squared distances a lane has seen, unsorted, with the largest of them (`worst`, at `wslot`) tracked: a candidate that does
+// not beat it costs one compare.  worst = +inf until the list is full -- what fit_rings reads as `best`.
+template <int CAP>
+struct OlList {
+  float* L;                              // this lane's column: slot s at L[s * OL_LANES]
+  int K, cnt, wslot;
+  float worst;
+  __device__ __forceinline__ void init(float (*lst)[OL_LANES], int k) {
+    L = &lst[0][threadIdx.x]; K = k; cnt = 0; wslot = 0; worst = __int_as_float(0x7f800000);
+  }
+  __device__ __forceinline__ void rescan() {
+    float w = L[0];
+    int ws = 0;
+    for (int s = 1; s < K; s++) { const float v = L[s * OL_LANES]; if (v > w) { w = v; ws = s; } }
+    worst = w; wslot = ws;
+  }
+  __device__ __forceinline__ void insert(float d2) {
+    if (cnt < K) {
+      L[cnt * OL_LANES] = d2;
+      if (++cnt == K) rescan();
+    } else if (d2 < worst) {
+      L[wslot * OL_LANES] = d2;
+      rescan();
+    }
+  }
+  // STATISTICAL: selection sort, ascending; s += (double)sqrtf(d2) in that order; (float)(s / mean_k).  sqrtf, correctly rounded under
+  // the build's -fhip-fp32-correctly-rounded-divide-sqrt -- not __fsqrt_rn, which this toolchain maps to the native approximate
+  // square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined (one ulp off in some terms, which reaches dist[] now and then).
+  __device__ __forceinline__ float mean_distance() {
+    double s = 0.0;
+    for (int m = 0; m < K; m++) {
+      float v = L[m * OL_LANES];
+      int at = m;
+      for (int t = m + 1; t < K; t++) { const float u = L[t * OL_LANES]; if (u < v) { v = u; at = t; } }
+      L[at * OL_LANES] = L[m * OL_LANES];
+      s += (double)sqrtf(v);
+    }
+    return (float)(s / (double)K);
+  }
+  __device__ __forceinline__ bool full() const { return cnt == K; }
+};
+
+// searchable points: *n_fin += their number; keep (may be null): 1 for each of them (RADIUS with min_neighbors = 0)
+__global__ void __launch_bounds__(256) k_ol_finite(const float* __restrict__ rows, size_t pitch, int n, int* n_fin, int* keep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool f = i < n && finite3(rows[i], rows[pitch + i], rows[2 * pitch + i]);
+  if (keep && i < n) keep[i] = f ? 1 : 0;
+  const unsigned long long b = __ballot(f);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_fin, __popcll(b));
+}
+
+// One lane per searchable point, in cell order (sorted position j, point id vals[j]).  method STATISTICAL: dist[id]; RADIUS: keep[id].
+// The caller has zeroed both; non-searchable points keep their zero.
+template <int CAP>
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn(const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const unsigned* __restrict__ runs,
+                                                     const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ vals,
+                                                     const int* __restrict__ n_fin, int method, int K, float r2, float* dist, int* keep) {
+  __shared__ float lst[CAP][OL_LANES];
+  const GridDesc& g = *gd;
+  if (g.status != GRID_OK) return;
+  const int nf = *n_fin;                           // (a lattice bins every searchable point: sorted positions 0 .. nf - 1)
+  if (method == OL_STATISTICAL && nf < K + 1) return;   // nearestKSearch(mean_k + 1) comes back short: dist = 0, not valid
+  const unsigned j = blockIdx.x * OL_LANES + threadIdx.x;
+  if (j >= (unsigned)nf) return;
+  const float q[3] = {X[j], X[pitch + j], X[2 * pitch + j]};
+  OlList<CAP> list;
+  list.init(lst, K);
+  const float inf = __int_as_float(0x7f800000);
+  fit_rings(q, g, words, runs, 1 << 30, method == OL_RADIUS ? r2 : inf, list.worst, [&](unsigned j0, unsigned j1) {
+    for (unsigned t = j0; t < j1; t++) {
+      if (t == j) continue;                       // the point itself
+      const float dx = q[0] - X[t], dy = q[1] - X[pitch + t], dz = q[2] - X[2 * pitch + t];
+      list.insert((dx * dx + dy * dy) + dz * dz);                // FLANN L2_Simple accumulation order
+    }
+  });
+  const unsigned id = vals[j];
+  if (method == OL_STATISTICAL) dist[id] = list.mean_distance();
+  else keep[id] = (list.full() && list.worst < r2) ? 1 : 0;
+}
+
+// the same lists for a cloud without a lattice: queries in input order, the rows staged through LDS 256 points at a time
+template <int CAP>
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn_brute(const GridDesc* __restrict__ gd, const float* __restrict__ rows, size_t pitch, int n,
+                                                           const int* __restrict__ n_fin, int method, int K, float r2, float* dist, int* keep) {
+  __shared__ float lst[CAP][OL_LANES];
+  __shared__ float tx[256], ty[256], tz[256];
+  if (gd->status != GRID_CAP) return;
+  if (method == OL_STATISTICAL && *n_fin < K + 1) return;
+  const int i = blockIdx.x * OL_LANES + threadIdx.x;
+  float q[3] = {0.f, 0.f, 0.f};
+  bool live = false;
+  if (i < n) {
+    q[0] = rows[i]; q[1] = rows[pitch + i]; q[2] = rows[2 * pitch + i];
+    live = finite3(q[0], q[1], q[2]);
+  }
+  OlList<CAP> list;
+  list.init(lst, K);
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 256 / OL_LANES; u++) {
+      const int k = u * OL_LANES + threadIdx.x, j = j0 + k;
+      float x = __int_as_float(0x7fc00000), y = x, z = x;                        // past the end: NaN, skipped below
+      if (j < n) { x = rows[j]; y = rows[pitch + j]; z = rows[2 * pitch + j]; }
+      tx[k] = x; ty[k] = y; tz[k] = z;
+    }
+    __syncthreads();
+    if (live) {
+      for (int k = 0; k < 256; k++) {
+        if (j0 + k == i || !finite3(tx[k], ty[k], tz[k])) continue;              // itself; non-finite points are in no tree
+        const float dx = q[0] - tx[k], dy = q[1] - ty[k], dz = q[2] - tz[k];
+        list.insert((dx * dx + dy * dy) + dz * dz);
+      }
+    }
+  }
+  if (!live) return;
+  if (method == OL_STATISTICAL) dist[i] = list.mean_distance();
+  else keep[i] = (list.full() && list.worst < r2) ? 1 : 0;
+}
+
+// STATISTICAL: removed iff (double)dist > threshold (a NaN threshold removes nothing); positions past n: 0
+__global__ void __launch_bounds__(256) k_ol_flag(const float* __restrict__ dist, int n, size_t pitch, double threshold, int* flag) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pitch) return;
+  flag[i] = (i < (size_t)n && !((double)dist[i] > threshold)) ? 1 : 0;
+}
+
+// the survivors, in order, into rows of the same pitch (the caller has zeroed `out`: the tail stays zero to the pitch)
+__global__ void __launch_bounds__(256) k_ol_compact(const float* __restrict__ rows, size_t pitch, const int* __restrict__ flag,
+                                                    const int* __restrict__ pos, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pitch || !flag[i]) return;
+  const int o = pos[i];
+  out[o] = rows[i]; out[pitch + o] = rows[pitch + i]; out[2 * pitch + o] = rows[2 * pitch + i];
+}

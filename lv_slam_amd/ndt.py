@@ -67,6 +67,14 @@ class InfParams(C.Structure):
                 ("fitness_score_thresh", C.c_double)]
 
 
+class OutlierParams(C.Structure):
+    _fields_ = [("method", C.c_int), ("mean_k", C.c_int), ("stddev_mul", C.c_double), ("radius", C.c_double), ("min_neighbors", C.c_int)]
+
+
+class OutlierStats(C.Structure):
+    _fields_ = [("n_in", C.c_longlong), ("n_valid", C.c_longlong), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
 class SeqParams(C.Structure):
     _fields_ = [("keyframe_delta_trans", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double)]
 
@@ -98,6 +106,7 @@ SYMBOLS = [
     "mi355ndt_window_keyframe", "mi355ndt_keyframe_add", "mi355ndt_keyframe_get", "mi355ndt_keyframe_release", "mi355ndt_keyframe_count",
     "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
     "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
+    "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers",
 ]
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
@@ -109,6 +118,9 @@ OPT_ARITH = 7                  # mi355ndt_option: 0 = the reference recipe's ari
 OPT_F32_SUM_ORDER = 1          # mi355ndt_option: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
 OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch align's last sweep of a pair evaluates the score alone, 0 = all 43 sums; same bits
 OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
+OPT_OUTLIER_CELL_MM = 10       # mi355ndt_option: cell size [mm] of the index prefilter_outliers builds over the prefilter result in every call (default 100); no result bit depends on it
+OUTLIER_STATISTICAL = 1        # pcl::StatisticalOutlierRemoval, the prefiltering nodelet's in-code default
+OUTLIER_RADIUS = 2             # pcl::RadiusOutlierRemoval (the reference builds it and never runs it)
 
 _LIB = None
 
@@ -143,6 +155,8 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_fitness_score_T.argtypes = [vp, vp, C.c_double, vp, vp]
     L.mi355ndt_prefilter.argtypes = [vp, vp, sz, sz, i, C.c_double, C.c_double, C.c_float, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
+    L.mi355ndt_outlier_params_default.argtypes = [C.POINTER(OutlierParams)]
+    L.mi355ndt_prefilter_outliers.argtypes = [vp, C.POINTER(OutlierParams), vp, vp, sz, sz, C.POINTER(sz), C.POINTER(OutlierStats)]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
@@ -339,11 +353,16 @@ class Engine:
         return v.value
 
     def prefilter(self, cloud, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True,
-                  fetch=True):
+                  fetch=True, outlier=None):
         """PrefilteringNodelet distance_filter + VoxelGrid downsample (defaults of launch/dlo_kitti.launch:30-36).
-        Returns the filtered [M,3] cloud (or just M when fetch=False; the result stays on the GPU for use_prefiltered)."""
+        Returns the filtered [M,3] cloud (or just M when fetch=False; the result stays on the GPU for use_prefiltered).
+        outlier: a dict of prefilter_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the nodelet's third stage runs on
+        the resident result before anything is fetched, and what is returned is what prefilter_outliers returns."""
         a = _as_points(cloud)
         n_out = C.c_size_t()
+        if outlier is not None:
+            self.prefilter(a, distance_near, distance_far, downsample_resolution, use_distance_filter, fetch=False)
+            return self.prefilter_outliers(**{"fetch": fetch, **outlier})
         out = np.zeros((a.shape[0], 3), np.float32) if fetch else None
         self._chk(self.lib.mi355ndt_prefilter(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0] if a.shape[0] else 12,
                                               int(use_distance_filter), float(distance_near), float(distance_far),
@@ -351,6 +370,27 @@ class Engine:
                                               a.shape[0], 12, C.byref(n_out)), "prefilter")
         self._pf_count = n_out.value
         return out[: n_out.value].copy() if fetch else n_out.value
+
+    def prefilter_outliers(self, method="STATISTICAL", mean_k=20, stddev_mul=1.0, radius=0.8, min_neighbors=2, fetch=True, return_stats=False):
+        """PrefilteringNodelet::outlier_removal over the resident prefilter result, in place (mi355ndt_prefilter_outliers): "STATISTICAL"
+        (pcl::StatisticalOutlierRemoval, the nodelet's in-code default) or "RADIUS" (pcl::RadiusOutlierRemoval -- which the reference never
+        runs: prefiltering_nodelet.cpp:71-78).  Returns the surviving [M,3] cloud (or just M when fetch=False); with return_stats also a
+        dict: dist (f32 per input point, input order), n_in, n_valid, mean, stddev, threshold (zeros for RADIUS)."""
+        if isinstance(method, str):                # (an unknown name becomes 0, which the library refuses with its own message)
+            method = {"STATISTICAL": OUTLIER_STATISTICAL, "RADIUS": OUTLIER_RADIUS}.get(method.upper(), 0)
+        prm = OutlierParams(int(method), int(mean_k), float(stddev_mul), float(radius), int(min_neighbors))
+        n_in = getattr(self, "_pf_count", 0)
+        n_out, st = C.c_size_t(), OutlierStats()
+        out = np.zeros((n_in, 3), np.float32) if fetch else None
+        dist = np.zeros(n_in, np.float32) if return_stats else None
+        self._chk(self.lib.mi355ndt_prefilter_outliers(self.h, C.byref(prm), dist.ctypes.data_as(C.c_void_p) if return_stats else None,
+                                                       out.ctypes.data_as(C.c_void_p) if fetch else None, n_in, 12, C.byref(n_out),
+                                                       C.byref(st)), "prefilter_outliers")
+        self._pf_count = n_out.value
+        res = out[: n_out.value].copy() if fetch else n_out.value
+        if not return_stats:
+            return res
+        return res, dict(dist=dist, n_in=st.n_in, n_valid=st.n_valid, mean=st.mean, stddev=st.stddev, threshold=st.threshold)
 
     def use_prefiltered(self, as_target: bool):
         """setInputTarget / setInputSource with the last prefilter result, device to device."""

@@ -153,11 +153,7 @@ NDT_KERNEL void k_async_prepare(const AsyncTab tab, AsyncTab* tab_dev, const int
 // count alone: the update adds those two columns with the same tree, runs no solve, and finalises the pair.  hits_total[1] (profiling) counts them.
 __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, const int tw, const int n_pts, const int rows_per_pair, PairState& Ssh, volatile double* sol,
                                              int* ring, const int ring_cap, AsyncCtl* ctl, const unsigned n_live, const int stop_thresh, unsigned long long* hits_total,
-                                             const double step_max, const double eps, const int max_iterations
-#ifdef NDT_TIMELINE
-                                             , unsigned long long* tl, unsigned long long& tl_last
-#endif
-                                             ) {
+                                             const double step_max, const double eps, const int max_iterations, Timeline& tl) {
   PairState* st = C.st;
   const double* partials = C.partials;
   mi355ndt_result* results = C.results;
@@ -376,16 +372,9 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
   // DIRECT1 items are short (one probe per point, ~0.85 hits): two consecutive items of a pair per claim / arrival halve the hand-overs
   // ... and so do two DIRECT7 items per claim where the launch hands its tail on (stream mode: +1.4-2 % measured; a launch that runs its own
   // tail loses with the coarser positions -- config 5, synchronous: -11 % --, so the host decides per launch: `claim_items`, DIRECT1: always two)
-#ifndef FAST_CLAIM1
-#define FAST_CLAIM1 4            // tolerance arithmetic, DIRECT1: a claim = one chunk (four items) going through the lane = point pipeline as one stream of tiles
-#endif
-  constexpr int CLAIM_D1 = (ORD == 2 && FAST_D1_POINT) ? FAST_CLAIM1 : ASYNC_CLAIM(1);
-  const int CLAIM = K == 1 ? CLAIM_D1 : (claim_items == 2 ? 2 : 1);
+  const int CLAIM = K == 1 ? ASYNC_CLAIM(1) : (claim_items == 2 ? 2 : 1);
   const int Iu = I / CLAIM;                        // positions per ticket (items_per_pair is a multiple of four)
-#ifdef NDT_TIMELINE
-  unsigned long long tl[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl_last = __builtin_readcyclecounter();
-#endif
+  Timeline tl;
   auto give_up = [&]() {                           // never hang: end the launch for everybody and tell the host (which takes the round-based path)
     __hip_atomic_store((gu32*)&ctl->abort_, 1u, RLX_AGENT);
     __hip_atomic_store((gu32*)&ctl->fin, n_live, RLX_AGENT);
@@ -477,30 +466,11 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
     auto items = [&](auto so_c) {
       constexpr bool SO = decltype(so_c)::value;
       if constexpr (K == 1 && ASYNC_D1_PIPE && ORD != 2) {   // DIRECT1 (exact arithmetic): the claim's items as one software pipeline (ndt_sweep.hpp), same rows bit for bit
-        sweep_rows_d1<PCA, ORD, CLAIM_D1, SO>(b, rem, C.src, C.pitch, C.gd, C.words, C.recs, C.partials, I, sc, exp_tab, pose_w, n_b, b
-#ifdef NDT_TIMELINE
-                                       , tl, tl_last
-#endif
-                                       );
-      } else if constexpr (K == 1 && ORD == 2 && FAST_D1_POINT) {   // DIRECT1, tolerance arithmetic: the claim's items as one stream of tiles, lane = point
-        float T[12], Rj[9];
-#pragma unroll
-        for (int a_ = 0; a_ < 12; a_++) T[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, a_));
-#pragma unroll
-        for (int a_ = 0; a_ < 9; a_++) Rj[a_] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a_));
-        sweep_rows_d1p<PCA, CLAIM_D1, true>(b, rem, C.src, C.pitch, T, Rj, n_b, C.gd[b], C.words, C.recs, C.partials, I, sc
-#ifdef NDT_TIMELINE
-                                            , tl, tl_last
-#endif
-                                            );
+        sweep_rows_d1<PCA, ORD, ASYNC_CLAIM(1), SO>(b, rem, C.src, C.pitch, C.gd, C.words, C.recs, C.partials, I, sc, exp_tab, pose_w, n_b, b, tl);
       } else {
 #pragma unroll 1
         for (int k = 0; k < CLAIM; k++)
-          sweep_item<PCA, K, 8, false, ORD, true, SO>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b
-#ifdef NDT_TIMELINE
-                                                  , tl, tl_last
-#endif
-                                                  );
+          sweep_item<PCA, K, 8, false, ORD, true, SO>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b, tl);
       }
     };
     if (last) items(std::true_type()); else items(std::false_type());
@@ -527,11 +497,7 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
     if (ntw >= 0) npose = sweep_pose_words(NDT_CTX_SEL(st, ntw >> ASYNC_CTX_SHIFT) + (ntw & ((1 << ASYNC_CTX_SHIFT) - 1)));
     TL_STAMP(8);                                   // row drain + claim, arrival + ticket
     if ((old + (unsigned)CLAIM) % (unsigned)I == 0u) {   // this was the sweep's last item: this wave is the pair's updater
-      async_update(C, b, tw, n_b, I, Ssh[wv], sol[wv], ring, ring_cap, ctl, n_live, stop_thresh, hits_total, step_max, eps, max_iterations
-#ifdef NDT_TIMELINE
-                   , tl, tl_last
-#endif
-                   );
+      async_update(C, b, tw, n_b, I, Ssh[wv], sol[wv], ring, ring_cap, ctl, n_live, stop_thresh, hits_total, step_max, eps, max_iterations, tl);
       TL_STAMP(15);                                // the deferred re-basing (off the pair's critical path)
     }
     if (ntw < 0) {                                 // the next position's ticket does not exist yet
@@ -541,7 +507,5 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
     }
     tw = ntw; pos = npos; pose_w = npose;
   }
-#ifdef NDT_TIMELINE
-  if (lane == 0) for (int k = 0; k < 16; k++) atomicAdd(&g_tl[k], tl[k]);
-#endif
+  tl.flush(0, 16);
 }

@@ -303,4 +303,4 @@ static bool async_served(const mi355ndt_handle* h) { return h->async_align && !m
 static double sweep_alg_bytes(double points, int K) { return points * (12.0 + 4.0 * K); }
 // resident workgroup slots of a sweep launch or a persistent launch; `fast`: the tolerance arithmetic's kernels serve it.  (Callers decide
 // `fast` by sweep_ord(...) == 2 or by fast_served(h); the two differ before the fast records are built: ndt_host_sweep.hpp, sweep_ord.)
-static int launch_slots(const mi355ndt_handle* h, const SweepConst& sc, bool fast) { return h->n_cu * sweep_wpe(sc.pca != 0, sc.K, fast); }
+static int launch_slots(const mi355ndt_handle* h, const SweepConst& sc, bool fast) { return h->n_cu * sweep_wpe(sc.K, fast); }

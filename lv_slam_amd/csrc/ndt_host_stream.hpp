@@ -59,7 +59,7 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
   make_sweep_const(h, sc);
   const int slots = launch_slots(h, sc, fast_served(h));
   {
-    const int iu = ss.items / (sc.K == 1 ? ((fast_served(h) && FAST_D1_POINT) ? FAST_CLAIM1 : 2) : sc.K == 7 ? 2 : 1);   // positions per ticket (stream_launch: two DIRECT7 items per claim when pairs are handed over)
+    const int iu = ss.items / (sc.K == 1 ? ASYNC_CLAIM(1) : sc.K == 7 ? 2 : 1);   // positions per ticket (DIRECT1: ndt_async.hpp; stream_launch: two DIRECT7 items per claim when pairs are handed over)
     const int waves = slots * WAVES;
     // automatic: four sweeps' worth of positions per resident wave -- `tools/gpu_job.sh thresh_sweep`: config 5 gains up to T = 32-64 (DIRECT7 19.1 / 19.4 / 19.5 k,
     // DIRECT1 39.4 / 40.1 / 40.9 / 41.1 k registrations/s at T = 8 / 16 / 32 / 64), the 65,536-point configurations do not care -- capped at a quarter of the batch (stream_launch)

@@ -154,10 +154,7 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
   // most of it such waits).  Two round trips are left: the run's position (cur, its point count), then the state together with the rows.
   __shared__ PairState Ssh;
   SeqState& Q = *seq;
-#ifdef NDT_TIMELINE
-  unsigned long long tl[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (slots 8..14: this kernel's phases, wave 0 / wave 1; tools/seq_run.py)
-  unsigned long long tl_last = __builtin_readcyclecounter();
-#endif
+  Timeline tl;                                                                   // (slots 8..14: this kernel's phases, wave 0 / wave 1; tools/seq_run.py)
   if (threadIdx.x == 0) sol[6] = 0.0;
 #if defined(NDT_TIMELINE) && defined(SEQ_UPDATE_REPEAT)
   // ---- analysis build only (tools/seq_run.py, docs/experiments.md 10e): "what would the update cost if its code were resident?"  The body up to
@@ -192,7 +189,7 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
         __syncthreads();
       }
     }
-    tl_last = __builtin_readcyclecounter();
+    tl.restart();
   }
 #endif
   const int done = Q.done, cur = Q.cur, n_src = Q.cur_n;                         // (block-uniform)
@@ -218,10 +215,8 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
   if (threadIdx.x >= 128) return;
   if (threadIdx.x >= 64) {                                                       // the solve, next to wave 0
     newton_solve_side(Ssh, sol);
-#ifdef NDT_TIMELINE
     TL_STAMP(13);
-    if (lane == 0) atomicAdd(&g_tl[13], tl[13]);
-#endif
+    tl.flush(13, 14);
     return;
   }
   // (the re-basing of p for this step was computed under the sweep, by its extra workgroup: ndt_sweep.hpp)
@@ -242,9 +237,7 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
   __builtin_amdgcn_wave_barrier();
   TL_STAMP(11);                                                                  // policy (when the frame's align ended)
   for (int i = lane; i < NW; i += 64) sg[i] = sl[i];
-#ifdef NDT_TIMELINE
   TL_STAMP(12);
-  tl[14] = 1;
-  if (lane == 0) for (int k = 8; k < 15; k++) if (k != 13) atomicAdd(&g_tl[k], tl[k]);
-#endif
+  tl.count(14);                                                                  // (slot 14: updates; slot 13 is wave 1's and stays 0 here)
+  tl.flush(8, 15);
 }

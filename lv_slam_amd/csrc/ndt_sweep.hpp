@@ -26,6 +26,24 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 template <int ORD>
 __device__ __forceinline__ float sum3(float t0, float t1, float t2) { return ORD == 1 ? (t0 + t2) + t1 : (t0 + t1) + t2; }
 
+// The part of an evaluation that the score needs (impl2:574-589): y = C u, q = u . y, the exponential, e1 and the validity gate.  Returns the
+// gate; `s_inc` is the hit's (gated) score term.  eval_hit goes on from here, eval_score adds s_inc and is done.
+template <int ORD>
+__device__ __forceinline__ bool eval_prefix(const float u[3], const float C[9], const double d1, const float d2f, const bool ok_in,
+                                            const double* __restrict__ exp_tab, float y[3], float& e1, float& s_inc) {
+#pragma unroll
+  for (int j = 0; j < 3; j++) y[j] = sum3<ORD>(u[0] * C[j], u[1] * C[3 + j], u[2] * C[6 + j]);
+  const float qf = sum3<ORD>(u[0] * y[0], u[1] * y[1], u[2] * y[2]);
+  const float e0 = ndtm::exp_f32arg((-d2f * qf) * 0.5f, exp_tab);                // impl2:581: exp in f64 on the f32 argument, rounded to f32
+  s_inc = (float)(-d1 * (double)e0);                                             // impl2:583
+  e1 = d2f * e0;                                                                 // impl2:585
+  // impl2:588-589, branch-free: a rejected hit (or an idle lane, ok_in = false) multiplies every term by e = 0 and so
+  // adds +0 to all 43 sums (all operands are finite here: dead voxels never enter the queue).
+  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);
+  s_inc = ok ? s_inc : 0.f;
+  return ok;
+}
+
 template <bool PCA, typename Mid = NoHook, bool SAN = false, int ORD = 0>
 __device__ __forceinline__ void eval_hit(const float u_in[3], const float r[3], const float C_in[9],
                                          const double d1, const float d2f, const double w, const bool ok_in, double acc[43],
@@ -33,19 +51,10 @@ __device__ __forceinline__ void eval_hit(const float u_in[3], const float r[3], 
   float u[3] = {u_in[0], u_in[1], u_in[2]}, C[9];
 #pragma unroll
   for (int a = 0; a < 9; a++) C[a] = C_in[a];
-  float y[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) y[j] = sum3<ORD>(u[0] * C[j], u[1] * C[3 + j], u[2] * C[6 + j]);
-  const float qf = sum3<ORD>(u[0] * y[0], u[1] * y[1], u[2] * y[2]);
-  const float e0 = ndtm::exp_f32arg((-d2f * qf) * 0.5f, exp_tab);                // impl2:581: exp in f64 on the f32 argument, rounded to f32
-  float s_inc = (float)(-d1 * (double)e0);                                       // impl2:583
-  const float e1 = d2f * e0;                                                     // impl2:585
-  // impl2:588-589, branch-free: a rejected hit (or an idle lane, ok_in = false) multiplies every term by e = 0 and so
-  // adds +0 to all 43 sums (all operands are finite here: dead voxels never enter the queue).
-  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);
+  float y[3], e1, s_inc;
+  const bool ok = eval_prefix<ORD>(u, C, d1, d2f, ok_in, exp_tab, y, e1, s_inc);
   float e = (float)((double)e1 * d1);                                            // impl2:592
   e = ok ? e : 0.f;
-  s_inc = ok ? s_inc : 0.f;
   if (SAN) {
 #pragma unroll
     for (int a = 0; a < 3; a++) { u[a] = ok ? u[a] : 0.f; y[a] = ok ? y[a] : 0.f; }
@@ -104,20 +113,13 @@ __device__ __forceinline__ void eval_hit(const float u_in[3], const float r[3], 
 #undef NDT_ACC
 }
 
-// Score-only evaluation (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): the prefix of eval_hit up to s_inc -- y, q, the exponential, e1, the validity
-// gate -- and the same term added to the same accumulator, for the last sweep of an align, whose gradient and Hessian are never read.
+// Score-only evaluation (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): eval_hit's prefix and the same term added to the same accumulator, for the
+// last sweep of an align, whose gradient and Hessian are never read.
 template <bool PCA, int ORD = 0>
 __device__ __forceinline__ void eval_score(const float u[3], const float C[9], const double d1, const float d2f, const double w, const bool ok_in,
                                            double& acc0, const double* __restrict__ exp_tab) {
-  float y[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) y[j] = sum3<ORD>(u[0] * C[j], u[1] * C[3 + j], u[2] * C[6 + j]);
-  const float qf = sum3<ORD>(u[0] * y[0], u[1] * y[1], u[2] * y[2]);
-  const float e0 = ndtm::exp_f32arg((-d2f * qf) * 0.5f, exp_tab);                // impl2:581
-  float s_inc = (float)(-d1 * (double)e0);                                       // impl2:583
-  const float e1 = d2f * e0;                                                     // impl2:585
-  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);                  // impl2:588-589
-  s_inc = ok ? s_inc : 0.f;
+  float y[3], e1, s_inc;
+  eval_prefix<ORD>(u, C, d1, d2f, ok_in, exp_tab, y, e1, s_inc);
   if (PCA) acc0 = fma(w, (double)s_inc, acc0); else acc0 += (double)s_inc;
 }
 
@@ -136,22 +138,32 @@ __device__ __forceinline__ void eval_score(const float u[3], const float C[9], c
 #define NACC_F 37
 __host__ __device__ constexpr int fsym(int i, int j) { return i <= j ? 7 + i * 6 - i * (i - 1) / 2 + (j - i) : 7 + j * 6 - j * (j - 1) / 2 + (i - j); }
 #define FA_BASE 28             // A[i][j] = a[FA_BASE + 3 i + j]
-template <bool PCA, typename Mid = NoHook>
-__device__ __forceinline__ void eval_hit_fast(const float u[3], const float r[3], const float c[6], const float d1f, const float d2f, const float kq,
-                                              const float w, const bool ok_in, float a[NACC_F], Mid mid = Mid()) {
+// ... its prefix (as eval_prefix): y, q, one v_exp_f32, e1, the gate; `s` is the hit's weighted, gated score term
+template <bool PCA>
+__device__ __forceinline__ bool eval_prefix_fast(const float u[3], const float c[6], const float d1f, const float d2f, const float kq, const float w,
+                                                 const bool ok_in, float y[3], float& e1, float& s) {
   const float c00 = c[0], c01 = c[1], c02 = c[2], c11 = c[3], c12 = c[4], c22 = c[5];
-  float y[3];
   y[0] = fmaf(c02, u[2], fmaf(c01, u[1], c00 * u[0]));
   y[1] = fmaf(c12, u[2], fmaf(c11, u[1], c01 * u[0]));
   y[2] = fmaf(c22, u[2], fmaf(c12, u[1], c02 * u[0]));
   const float q = fmaf(u[2], y[2], fmaf(u[1], y[1], u[0] * y[0]));
   const float e0 = __builtin_amdgcn_exp2f(kq * q);                               // impl2:581
-  const float e1 = d2f * e0;                                                     // impl2:585
+  e1 = d2f * e0;                                                                 // impl2:585
   const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);                  // impl2:588-589
-  float e = e1 * d1f, s = -d1f * e0;                                             // impl2:592, 583
-  if (PCA) { e *= w; s *= w; }
-  e = ok ? e : 0.f;
+  s = -d1f * e0;                                                                 // impl2:583
+  if (PCA) s *= w;
   s = ok ? s : 0.f;
+  return ok;
+}
+template <bool PCA, typename Mid = NoHook>
+__device__ __forceinline__ void eval_hit_fast(const float u[3], const float r[3], const float c[6], const float d1f, const float d2f, const float kq,
+                                              const float w, const bool ok_in, float a[NACC_F], Mid mid = Mid()) {
+  const float c00 = c[0], c01 = c[1], c02 = c[2], c11 = c[3], c12 = c[4], c22 = c[5];
+  float y[3], e1, s;
+  const bool ok = eval_prefix_fast<PCA>(u, c, d1f, d2f, kq, w, ok_in, y, e1, s);
+  float e = e1 * d1f;                                                            // impl2:592
+  if (PCA) e *= w;
+  e = ok ? e : 0.f;
   a[0] += s;
   // v = J^T y = [y ; r x y] (impl2:595 with CJ's columns 0..2 = C)
   float v[6] = {y[0], y[1], y[2], fmaf(r[1], y[2], -(r[2] * y[1])), fmaf(r[2], y[0], -(r[0] * y[2])), fmaf(r[0], y[1], -(r[1] * y[0]))};
@@ -197,22 +209,12 @@ __device__ __forceinline__ void eval_hit_fast(const float u[3], const float r[3]
     for (int j = 0; j < 3; j++) a[FA_BASE + 3 * i + j] = fmaf(er, y[j], a[FA_BASE + 3 * i + j]);
   }
 }
-// ... and its score-only prefix (as eval_score for eval_hit): same operations, same f32 sum a[0]
+// ... and its score-only form (as eval_score for eval_hit): the prefix, the same f32 sum a[0]
 template <bool PCA>
 __device__ __forceinline__ void eval_score_fast(const float u[3], const float c[6], const float d1f, const float d2f, const float kq,
                                                 const float w, const bool ok_in, float& a0) {
-  const float c00 = c[0], c01 = c[1], c02 = c[2], c11 = c[3], c12 = c[4], c22 = c[5];
-  float y[3];
-  y[0] = fmaf(c02, u[2], fmaf(c01, u[1], c00 * u[0]));
-  y[1] = fmaf(c12, u[2], fmaf(c11, u[1], c01 * u[0]));
-  y[2] = fmaf(c22, u[2], fmaf(c12, u[1], c02 * u[0]));
-  const float q = fmaf(u[2], y[2], fmaf(u[1], y[1], u[0] * y[0]));
-  const float e0 = __builtin_amdgcn_exp2f(kq * q);                               // impl2:581
-  const float e1 = d2f * e0;                                                     // impl2:585
-  const bool ok = ok_in && !(e1 > 1.f || e1 < 0.f || e1 != e1);                  // impl2:588-589
-  float s = -d1f * e0;                                                           // impl2:583
-  if (PCA) s *= w;
-  s = ok ? s : 0.f;
+  float y[3], e1, s;
+  eval_prefix_fast<PCA>(u, c, d1f, d2f, kq, w, ok_in, y, e1, s);
   a0 += s;
 }
 // A score-only work item's row: the lane sums of the score added with the pairwise tree of the reduce-scatter below (lanes l / l^32, then
@@ -267,21 +269,35 @@ __host__ __device__ constexpr int probe_off(int K, int q, int a) {
 // mi355ndt_debug_timeline; tools/sweep_timeline.py).  Costs ~10 % and is never part of the shipped library.
 #ifdef NDT_TIMELINE
 __device__ unsigned long long g_tl[16];
-#define TL_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_readcyclecounter(); tl[k] += t_ - tl_last; tl_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+struct Timeline {                // one per wave: the counters and the last clock value
+  unsigned long long t[16], last;
+  __device__ __forceinline__ Timeline() { for (int k = 0; k < 16; k++) t[k] = 0; last = __builtin_readcyclecounter(); }
+  __device__ __forceinline__ void stamp(const int k) {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t_ = __builtin_readcyclecounter();
+    t[k] += t_ - last; last = t_;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void count(const int k = 7) { t[k] += 1; }          // (slot 7: work items)
+  __device__ __forceinline__ void restart() { last = __builtin_readcyclecounter(); }
+  __device__ __forceinline__ void flush(const int k0, const int k1) const { if ((threadIdx.x & 63) == 0) for (int k = k0; k < k1; k++) atomicAdd(&g_tl[k], t[k]); }
+};
 #else
-#define TL_STAMP(k) do {} while (0)
+struct Timeline {                // the shipped library: nothing
+  __device__ __forceinline__ void stamp(int) {}
+  __device__ __forceinline__ void count(int = 7) {}
+  __device__ __forceinline__ void restart() {}
+  __device__ __forceinline__ void flush(int, int) const {}
+};
 #endif
+#define TL_STAMP(k) tl.stamp(k)
 struct SweepCtl {               // 9 ints; two of them alternate: the sweep that reads one clears the other
   int n_active;                 // pairs whose next sweep is pending (entries of active_list)
   int next_item[8];             // per-XCD work-item cursors of the sweep
 };
 #define QUARTERS WAVES          // a chunk is reduced as 4 wave-quarters of CHUNK_PTS/4 points
 
-// Per-instantiation tuning knobs (none of them changes a result bit).  LEAN = three waves per SIMD without spilling: possible
-// for DIRECT7 once the mid-evaluation record prefetch (17 VGPRs) and the two-tile probe group are dropped.  Measured
-// (tools/sweep_only.py, bench.py): ndt_omp at 1 m / 65,536 pts 1-3 % faster, but at 0.5 m / 131,072 pts (four times the voxel
-// records, fewer cache hits) 3 % slower, and ndt_pca 12 % slower there -- the prefetch matters as soon as records miss in L2,
-// so LEAN stays off.
+// Per-instantiation tuning knobs (none of them changes a result bit).
 #ifndef FAST_WPE7
 #define FAST_WPE7 4            // tolerance arithmetic: 37 f32 accumulators instead of 43 f64 ones leave room for four waves per SIMD
 #endif
@@ -300,13 +316,12 @@ struct SweepCtl {               // 9 ints; two of them alternate: the sweep that
 template <bool PCA, int K, int ORD = 0>
 struct SweepTune {
   static constexpr bool FAST = (ORD == 2);
-  static constexpr bool LEAN = false;
-  static constexpr int  WPE  = FAST ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : (LEAN ? 3 : SWEEP_WPE);                       // workgroups per CU = waves per SIMD
-  static constexpr bool PIPE = FAST ? (FAST_PIPE != 0) : !LEAN;                                      // fetch batch k+1's records in the middle of batch k
+  static constexpr int  WPE  = FAST ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE;                  // workgroups per CU = waves per SIMD
+  static constexpr bool PIPE = FAST ? (FAST_PIPE != 0) : true;                                       // fetch batch k+1's records in the middle of batch k
   // tiles probed together (8 = the whole work item); tolerance arithmetic: small super-tiles keep the LDS of a workgroup under a quarter of the CU's
-  static constexpr int  TP   = FAST ? (K == 1 ? FAST_TP1 : FAST_TP7) : (LEAN ? 1 : (K == 1 ? 8 : (K <= 7 ? 2 : 1)));
+  static constexpr int  TP   = FAST ? (K == 1 ? FAST_TP1 : FAST_TP7) : (K == 1 ? 8 : (K <= 7 ? 2 : 1));
 };
-static inline int sweep_wpe(bool pca, int K, bool fast = false) { (void)pca; return fast ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE; }
+static inline int sweep_wpe(int K, bool fast = false) { return fast ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE; }
 
 // IT = tiles of 64 points per work item.  8 is the batch mode described above (a wave-quarter of a 2048-point chunk).
 // FINE (latency mode): small items (IT = 1 or 2) dealt statically over ALL waves of the grid, for a sweep over one or a
@@ -334,21 +349,227 @@ __device__ __forceinline__ unsigned sweep_pose_words(const PairState* S) {
   return w;
 }
 
-template <bool PCA, int NROWS, bool ASYNC>
-__device__ __forceinline__ void sweep_rows_d1p(const int b, const int rem0, const float* __restrict__ src, const size_t pitch, const float T[12], const float Rj[9], const int n,
-                                               const GridDesc& g, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
-                                               double* partials, const int rows_per_pair, const SweepConst& sc
-#ifdef NDT_TIMELINE
-                                               , unsigned long long* tl, unsigned long long& tl_last
-#endif
-                                               );
+__device__ __forceinline__ void pose_from_words(const unsigned pose_w, float T[12], float Rj[9]) {
+#pragma unroll
+  for (int a = 0; a < 12; a++) T[a] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, a));
+#pragma unroll
+  for (int a = 0; a < 9; a++) Rj[a] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a));
+}
+
+// A score-only work item's row: the lane sums of the score through score_tree, then the score and the hit count are the only words of
+// the row written (agent scope: one-launch align only).
+__device__ __forceinline__ void score_row_store(const double lane_score, double* P, const unsigned nhits, const int lane) {
+  const double v = score_tree(lane_score);
+  if (lane == 0) {
+    gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(P);
+    __hip_atomic_store(PG, (unsigned long long)__double_as_longlong(v), RLX_AGENT);
+    __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
+  }
+}
+
+// Fixed-order reduction of the wave's 43 lane sums -> one 44-double row at P.  Same pairwise tree as a 64-lane xor
+// butterfly (distance 32, 16, 8, 4, 2, 1 -- so the same bits), but as a reduce-scatter: the distance-32 and -16
+// levels use gfx950's v_permlane32_swap / v_permlane16_swap to exchange HALF of the values between lane halves /
+// rows, so 43 -> 22 -> 11 values remain per lane before the in-row butterfly (66 swaps + 88 shuffles + 77 adds
+// instead of 516 shuffles + 258 adds per item).  This tree defines the bits of a row: every item body stores its rows through it.
+// AGENT: write-through (sc1) 8-byte stores -- the row's reader (the pair's updater) is another workgroup of the same launch, maybe on another XCD.
+template <bool AGENT>
+__device__ __forceinline__ void wave_row_store(const double row[43], double* P, const unsigned nhits, const int lane) {
+  typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+  double P1[22], P2[11];
+#pragma unroll
+  for (int i = 0; i < 22; i++) {
+    const double a = row[i], b2 = (i + 22 < 43) ? row[i + 22] : 0.0;
+    const u2v lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
+    const u2v hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
+    // lanes 0..31: value i of lanes L and L+32;  lanes 32..63: value i+22 of lanes L-32 and L
+    P1[i] = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
+  }
+#pragma unroll
+  for (int i = 0; i < 11; i++) {
+    const double a = P1[i], b2 = P1[i + 11];
+    const u2v lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
+    const u2v hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
+    // even rows: P1[i] of rows r and r+1;  odd rows: P1[i+11] of rows r-1 and r
+    double v = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    P2[i] = v;
+  }
+  if ((lane & 15) == 0) {
+    // row 0 (lane 0) holds values 0..10, row 1: 11..21, row 2: 22..32, row 3: 33..42 (+ the pad)
+    const int row4 = lane >> 4, base = 11 * (row4 & 1) + 22 * (row4 >> 1);
+    if (AGENT) {
+      gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(P);
+#pragma unroll
+      for (int i = 0; i < 11; i++) if (base + i < 43) __hip_atomic_store(PG + base + i, (unsigned long long)__double_as_longlong(P2[i]), RLX_AGENT);
+      if (lane == 0) __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 11; i++) if (base + i < 43) P[base + i] = P2[i];
+      if (lane == 0) P[43] = (double)nhits;
+    }
+  }
+}
+
+// ---- phase A, per point: the pieces every item body shares
+// One axis of the moved point -- PCL 1.8 transformPointCloud scalar form (row `Ta` of T) -- and of the Jacobian point r = R x (row `Ra` of Rj;
+// impl2:507-508).  Per axis, scalar outputs: the callers' unrolled loops then compile exactly as when the two lines stood in them.
+__device__ __forceinline__ void move_axis(const float* Ta, const float* Ra, const float px, const float py, const float pz, float& xt, float& r) {
+  xt = ((Ta[0] * px + Ta[1] * py) + Ta[2] * pz) + Ta[3];
+  r = (Ra[0] * px + Ra[1] * py) + Ra[2] * pz;
+}
+// ... both are staged (six floats) for phase B
+__device__ __forceinline__ void stage_point(float* sp, const float xt[3], const float r[3]) {
+  sp[0] = xt[0]; sp[1] = xt[1]; sp[2] = xt[2]; sp[3] = r[0]; sp[4] = r[1]; sp[5] = r[2];
+}
+// getNeighborhoodAtPoint (voxel_grid_covariance_omp_impl.hpp:379-399): cell of the moved point, f32 divide (x / 2^k is the same bits as
+// x * 2^-k, so a power-of-two leaf takes the one-instruction path), relative to the grid's min_b: "inside the grid" (impl:382-392) is then
+// one unsigned compare per axis.
+// (Measured: with this helper in sweep_item the tolerance arithmetic's one-launch align is 0.55-0.8 % slower than with the four lines written
+//  out; the per-axis shape that cures it costs the exact DIRECT7 headline 0.4 %.  docs/experiments.md 10i has the numbers and the decision.)
+__device__ __forceinline__ void rel_cell(const float xt[3], const SweepConst& sc, const float leaf, const int mb0, const int mb1, const int mb2,
+                                         int& r0, int& r1, int& r2) {
+  const int c0 = (int)floorf(sc.leaf_pow2 ? xt[0] * sc.inv_leaf : xt[0] / leaf);
+  const int c1 = (int)floorf(sc.leaf_pow2 ? xt[1] * sc.inv_leaf : xt[1] / leaf);
+  const int c2 = (int)floorf(sc.leaf_pow2 ? xt[2] * sc.inv_leaf : xt[2] / leaf);
+  r0 = c0 - mb0; r1 = c1 - mb1; r2 = c2 - mb2;
+}
+// A probed bitmap word (bits lo, bits hi, prefix, pad) and the cell it was read for -> is the cell occupied, and its rank among the
+// searchable leaves = voxel id.  Shift the cell's bit to the top: sign = occupied, popcount = bits at or below it.
+__device__ __forceinline__ bool bitmap_rank(const uint4 bw, const unsigned cell, unsigned& id) {
+  const unsigned long long bits = ((unsigned long long)bw.y << 32) | bw.x;
+  const unsigned long long tb = bits << (63u - (cell & 63u));
+  id = bw.z + (unsigned)__popcll(tb) - 1u;
+  return (long long)tb < 0;
+}
+
 // The LDS of a work item by purpose (SLOT) and shape, declared outside the item functions: a function's own __shared__ arrays are one set per
 // instantiation, and the score-only and the full item body of one kernel (SO) must share theirs, not each take the workgroup's LDS.
 template <typename T, int SLOT>
 __device__ __forceinline__ T& item_lds() { __shared__ T v; return v; }
-#ifndef FAST_D1_POINT
-#define FAST_D1_POINT 0          // tolerance arithmetic, DIRECT1: 1 = lane = point (sweep_rows_d1p) instead of the hit queue -- built, measured, not faster (below)
-#endif
+
+// ---- phase B: the wave's hit queue, its 64-hit batches and the lane sums they go into.  One definition for every item body: which hits
+// form a batch, and in which order a lane adds them, is part of a row's bits.
+// One batch of queued hits (one per lane): queue entry + the voxel record it points at, in registers.
+struct BatchX { unsigned slot; double m0, m1, m2; float C[9]; int weight; double w; };
+struct BatchF { unsigned slot; float mh[3], ml[3], c[6]; int weight; float w; };
+// `ent` / `qw` / `stage`: the wave's rows of the LDS queue (Q_CAP entries, a power of two), of its ndt_pca weights and of its staged points.
+// SO: hits are evaluated by eval_score / eval_score_fast (acc[0] alone).
+// W_LATE (ndt_pca, K = 1: the hit's weight is the leaf's own, read with its record): widen it when the batch is evaluated, not when it is
+// fetched -- the same value either way, but two registers fewer across the mid-evaluation prefetch.  sweep_rows_d1 needs that (with the
+// widening at the fetch the pca / DIRECT1 headline lost 5 %, docs/experiments.md 10i); sweep_item widens at the fetch as it always did.
+template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false>
+struct HitQueue {
+  static constexpr bool KD = (K == 27), FAST = (ORD == 2), PCAQ = PCA && K > 1;
+  static constexpr int NA = FAST ? NACC_F : 43;
+  typedef typename std::conditional<FAST, float, double>::type AccT;
+  // ndt_pca weight of a queued hit: the suffix product (f64: up to ~150^7) -- for DIRECT1 just the leaf's own integer weight
+  typedef typename std::conditional<K == 1, int, AccT>::type QW;
+  typedef typename std::conditional<FAST, BatchF, BatchX>::type Batch;
+  unsigned* const ent; QW* const qw; const float (*const stage)[6];
+  const VoxelRec* const R; const SweepConst& sc; const double* const exp_tab;
+  const int lane; const unsigned long long lt_mask;
+  // The lane sums of the row being built.  The item body declares the array and reads it back as Q.acc; the queue zeroes it (new_row) and adds
+  // into it.  The split is the register allocator's: with the array as a member here k_sweep<true, 7, 1, true, .> has one VGPR fewer than
+  // before the queue had a definition of its own, and kernels are held to their old register tables (docs/experiments.md 10i).
+  AccT (&acc)[NA];
+  unsigned nhits;                                  // wave-uniform
+  int head, count;                                 // wave-uniform
+  int old;                                         // queued entries that reference the OTHER staging half (older super-tile; sweep_item)
+  __device__ __forceinline__ HitQueue(AccT (&acc_)[NA], unsigned* ent_, QW* qw_, const float (*stage_)[6], const VoxelRec* R_, const SweepConst& sc_, const double* exp_tab_, const int lane_)
+      : ent(ent_), qw(qw_), stage(stage_), R(R_), sc(sc_), exp_tab(exp_tab_), lane(lane_), lt_mask((1ull << lane_) - 1ull), acc(acc_), head(0), count(0), old(0) { new_row(); }
+  __device__ __forceinline__ void new_row() {
+#pragma unroll
+    for (int a = 0; a < NA; a++) acc[a] = (AccT)0;
+    nhits = 0;
+  }
+  // the lanes with `hit` append (staging slot, voxel id) -- ballot + popcount compaction, lane order -- and, ndt_pca with K > 1, the weight
+  __device__ __forceinline__ void push(const bool hit, const unsigned slot, const unsigned id, const double w) {
+    const unsigned long long mask = __ballot(hit);
+    if (hit) {
+      const int pos = (head + count + (int)__popcll(mask & lt_mask)) & (Q_CAP - 1);
+      ent[pos] = (slot << ID_BITS) | id;
+      if (PCAQ) qw[pos] = (QW)w;
+    }
+    count += (int)__popcll(mask);
+  }
+  // read the `m` hits that sit `off` entries behind the queue head; lanes >= m re-read the last entry (and contribute +0)
+  __device__ __forceinline__ void fetch(const int off, const int m, Batch& B) const {
+    const int k = lane < m ? lane : m - 1;
+    const unsigned e = ent[(head + off + k) & (Q_CAP - 1)];
+    B.slot = e >> ID_BITS;
+    if constexpr (FAST) {
+      const VoxelRecF& vr = reinterpret_cast<const VoxelRecF*>(R)[e & ((1u << ID_BITS) - 1)];
+#pragma unroll
+      for (int a = 0; a < 3; a++) { B.mh[a] = vr.mh[a]; B.ml[a] = vr.ml[a]; }
+#pragma unroll
+      for (int a = 0; a < 6; a++) B.c[a] = vr.c[a];
+      B.weight = vr.weight;
+      if (!W_LATE) B.w = 1.f;
+      if (PCAQ) B.w = (float)qw[(head + off + k) & (Q_CAP - 1)];
+      else if (PCA && !W_LATE) B.w = (float)vr.weight;
+    } else {
+      const VoxelRec& vr = R[e & ((1u << ID_BITS) - 1)];
+      B.m0 = vr.mean[0]; B.m1 = vr.mean[1]; B.m2 = vr.mean[2];
+#pragma unroll
+      for (int a = 0; a < 9; a++) B.C[a] = vr.icov[a];
+      B.weight = vr.weight;
+      if (!W_LATE) B.w = 1.0;
+      if (PCAQ) B.w = (double)qw[(head + off + k) & (Q_CAP - 1)];
+      else if (PCA && !W_LATE) B.w = (double)vr.weight;
+    }
+  }
+  // evaluate a fetched batch (running `mid` half way through) and retire its `m` queue entries
+  template <typename Mid>
+  __device__ __forceinline__ void eval_batch(const Batch& B, const int m, Mid mid) {
+    const float* sp = stage[B.slot];               // staged point: LDS, short latency
+    const float xt0 = sp[0], xt1 = sp[1], xt2 = sp[2];
+    float r[3] = {sp[3], sp[4], sp[5]};
+    // ndt_omp: leaves with nr_points = -1 (eigen / inverse failure) are not neighbours (impl:395): filtered here
+    const bool live = lane < m && (PCAQ || KD || B.weight != VOX_DEAD);
+    if constexpr (FAST) {
+      float u[3] = {(xt0 - B.mh[0]) - B.ml[0], (xt1 - B.mh[1]) - B.ml[1], (xt2 - B.mh[2]) - B.ml[2]};
+      const float w = (W_LATE && !PCAQ) ? (PCA ? (float)B.weight : 1.f) : B.w;
+      if constexpr (SO) { mid(); eval_score_fast<PCA>(u, B.c, sc.d1f, sc.d2f, sc.kq, w, live, acc[0]); }
+      else eval_hit_fast<PCA, Mid>(u, r, B.c, sc.d1f, sc.d2f, sc.kq, w, live, acc, mid);
+    } else {
+      float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
+      const double w = (W_LATE && !PCAQ) ? (PCA ? (double)B.weight : 1.0) : B.w;
+      if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, w, live, acc[0], exp_tab); }
+      else eval_hit<PCA, Mid, KD, ORD>(u, r, B.C, sc.d1, sc.d2f, w, live, acc, exp_tab, mid);
+    }
+    nhits += PCAQ ? (unsigned)m : (unsigned)__popcll(__ballot(live));
+    head = (head + m) & (Q_CAP - 1);
+    count -= m;
+    old = old > m ? old - m : 0;
+  }
+  // evaluate `m` queued hits (m <= 64), one per lane
+  __device__ __forceinline__ void drain(const int m) {
+    Batch B;
+    fetch(0, m, B);
+    eval_batch(B, m, NoHook());
+  }
+  // All full batches in the queue, software-pipelined: the next batch's record loads are issued in the middle of the
+  // current batch's arithmetic (before its 36 Hessian terms), so their L2 latency is off the critical path.
+  __device__ __forceinline__ void drain_full() {
+    if (!SweepTune<PCA, K, ORD>::PIPE) {           // plain: one batch after the other
+      while (count >= 64) drain(64);
+      return;
+    }
+    if (count < 64) return;
+    Batch A;
+    fetch(0, 64, A);
+#pragma unroll 1
+    for (;;) {
+      const bool more = count >= 128;
+      Batch N;
+      eval_batch(A, 64, [&]() { if (more) fetch(64, 64, N); });
+      if (!more) break;
+      A = N;
+    }
+  }
+};
 
 // SO: score-only item (the pair's last sweep, PairState::last_sweep): the same probe stage, hit queue, 64-hit batches and ndt_pca weights; each
 // hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
@@ -357,18 +578,14 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
                                            const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                            double* partials, const int rows_per_pair, const SweepConst& sc, const float* __restrict__ cent,
                                            const int* __restrict__ grid_of, const double* exp_tab,
-                                           const unsigned pose_w, const int n_async, const int g_async   /* ASYNC only: pose words (sweep_pose_words), point count, grid index */
-#ifdef NDT_TIMELINE
-                                           , unsigned long long* tl, unsigned long long& tl_last
-#endif
-                                           ) {
+                                           const unsigned pose_w, const int n_async, const int g_async,  /* ASYNC only: pose words (sweep_pose_words), point count, grid index */
+                                           Timeline& tl) {
   constexpr bool KD = (K == 27);
   constexpr bool FAST = (ORD == 2);                // tolerance arithmetic (eval_hit_fast): `recs` holds VoxelRecF records
   static_assert(!SO || (ASYNC && !FINE), "score-only items belong to the one-launch align");
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
   typedef SweepTune<PCA, K, ORD> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
   // ndt_pca's per-hit multiplier is the product of the hit's own weight and those of the point's LATER hits, known only in phase A.
   // With one probe per point (DIRECT1) it is just the leaf's own weight, which phase B reads with the record anyway: no weight
   // load in the probe stage, no weight queue, dead leaves filtered in phase B exactly as for ndt_omp.
@@ -378,10 +595,9 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   constexpr int Q_NEED = (IT / TP > 1 ? 64 : 0) + TP * (K < Q_GROUP ? K : Q_GROUP) * 64;
   constexpr int Q_CAP = FAST ? (Q_NEED <= 128 ? 128 : Q_NEED <= 256 ? 256 : Q_NEED <= 512 ? 512 : 1024) : ((K > 1 && K <= Q_GROUP) ? 1024 : 512);
   static_assert(Q_NEED <= Q_CAP, "hit queue");
+  typedef HitQueue<PCA, K, ORD, SO, Q_CAP> Queue;
   auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 0>();
-  // ndt_pca weight of a queued hit: the suffix product (f64: up to ~150^7) -- for DIRECT1 just the leaf's own integer weight
-  typedef typename std::conditional<K == 1, int, typename std::conditional<FAST, float, double>::type>::type QW;
-  auto& q_w = item_lds<QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
+  auto& q_w = item_lds<typename Queue::QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
   // TP tiles of 64 points are probed together ("super-tile"): their point transforms, then ALL their bitmap loads, then all
   // their ballots -- the probe stage costs a few L2 round trips per super-tile, not per tile.  DIRECT1 has one probe per point
   // and ~0.9 hits, so it is probe-stage bound: 4 tiles at a time; DIRECT7: 2 (14 bitmap words in flight); the 26/27-cell
@@ -405,108 +621,21 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   const VoxelRec* R = recs + g.rec_off;
   const bool grid_ok = (g.status == GRID_OK);
   float T[12], Rj[9];
+  if constexpr (ASYNC) pose_from_words(pose_w, T, Rj);
+  else {
 #pragma unroll
-  for (int a = 0; a < 12; a++) T[a] = ASYNC ? __uint_as_float(__builtin_amdgcn_readlane(pose_w, a)) : S.T[a];
+    for (int a = 0; a < 12; a++) T[a] = S.T[a];
 #pragma unroll
-  for (int a = 0; a < 9; a++) Rj[a] = ASYNC ? __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a)) : S.Rj[a];
-  if constexpr (FAST && K == 1 && IT == 8 && !FINE && FAST_D1_POINT) {
-    sweep_rows_d1p<PCA, 1, ASYNC>(b, rem, src, pitch, T, Rj, n, g, words, recs, partials, rows_per_pair, sc
-#ifdef NDT_TIMELINE
-                                  , tl, tl_last
-#endif
-                                  );
-    return;
+    for (int a = 0; a < 9; a++) Rj[a] = S.Rj[a];
   }
   const float leaf = g.leaf;
   const int mb0 = g.min_b[0], mb1 = g.min_b[1], mb2 = g.min_b[2];
   const int xb0 = g.max_b[0], xb1 = g.max_b[1], xb2 = g.max_b[2];
   const int mul1 = g.mul1, mul2 = g.mul2, nwords = g.nwords;
   {
-    typedef typename std::conditional<FAST, float, double>::type AccT;
-    AccT acc[FAST ? NACC_F : 43];
-#pragma unroll
-    for (int a = 0; a < (FAST ? NACC_F : 43); a++) acc[a] = (AccT)0;
-    unsigned nhits = 0;                              // wave-uniform
-    int qhead = 0, qcount = 0;                       // wave-uniform
-    int q_old = 0;                                   // queued entries that reference the OTHER staging half (older tile)
+    typename Queue::AccT acc[Queue::NA];
+    Queue Q(acc, q_ent[wv], q_w[PCAQ ? wv : 0], stage[wv], R, sc, exp_tab, lane);
     const int wbase = rem * (IT * 64);
-
-    // One batch of queued hits (one per lane): queue entry + the voxel record it points at, in registers.
-    struct BatchX { unsigned slot; double m0, m1, m2; float C[9]; int weight; double w; };
-    struct BatchF { unsigned slot; float mh[3], ml[3], c[6]; int weight; float w; };
-    typedef typename std::conditional<FAST, BatchF, BatchX>::type Batch;
-    // read the `m` hits that sit `off` entries behind the queue head; lanes >= m re-read the last entry (and contribute +0)
-    auto fetch = [&](int off, int m, Batch& B) {
-      const int k = lane < m ? lane : m - 1;
-      const unsigned ent = q_ent[wv][(qhead + off + k) & (Q_CAP - 1)];
-      B.slot = ent >> ID_BITS;
-      if constexpr (FAST) {
-        const VoxelRecF& vr = reinterpret_cast<const VoxelRecF*>(R)[ent & ((1u << ID_BITS) - 1)];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { B.mh[a] = vr.mh[a]; B.ml[a] = vr.ml[a]; }
-#pragma unroll
-        for (int a = 0; a < 6; a++) B.c[a] = vr.c[a];
-        B.weight = vr.weight;
-        B.w = 1.f;
-        if (PCAQ) B.w = (float)q_w[wv][(qhead + off + k) & (Q_CAP - 1)];
-        else if (PCA) B.w = (float)vr.weight;
-      } else {
-        const VoxelRec& vr = R[ent & ((1u << ID_BITS) - 1)];
-        B.m0 = vr.mean[0]; B.m1 = vr.mean[1]; B.m2 = vr.mean[2];
-#pragma unroll
-        for (int a = 0; a < 9; a++) B.C[a] = vr.icov[a];
-        B.weight = vr.weight;
-        B.w = 1.0;
-        if (PCAQ) B.w = (double)q_w[wv][(qhead + off + k) & (Q_CAP - 1)];
-        else if (PCA) B.w = (double)vr.weight;
-      }
-    };
-    // evaluate a fetched batch (running `mid` half way through) and retire its `m` queue entries
-    auto eval_batch = [&](const Batch& B, int m, auto mid) {
-      const float* sp = stage[wv][B.slot];         // staged point: LDS, short latency
-      const float xt0 = sp[0], xt1 = sp[1], xt2 = sp[2];
-      float r[3] = {sp[3], sp[4], sp[5]};
-      // ndt_omp: leaves with nr_points = -1 (eigen / inverse failure) are not neighbours (impl:395): filtered here
-      const bool live = lane < m && (PCAQ || KD || B.weight != VOX_DEAD);
-      if constexpr (FAST) {
-        float u[3] = {(xt0 - B.mh[0]) - B.ml[0], (xt1 - B.mh[1]) - B.ml[1], (xt2 - B.mh[2]) - B.ml[2]};
-        if constexpr (SO) { mid(); eval_score_fast<PCA>(u, B.c, sc.d1f, sc.d2f, sc.kq, B.w, live, acc[0]); }
-        else eval_hit_fast<PCA, decltype(mid)>(u, r, B.c, sc.d1f, sc.d2f, sc.kq, B.w, live, acc, mid);
-      } else {
-        float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
-        if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, B.w, live, acc[0], exp_tab); }
-        else eval_hit<PCA, decltype(mid), KD, ORD>(u, r, B.C, sc.d1, sc.d2f, B.w, live, acc, exp_tab, mid);
-      }
-      nhits += PCAQ ? (unsigned)m : (unsigned)__popcll(__ballot(live));
-      qhead = (qhead + m) & (Q_CAP - 1);
-      qcount -= m;
-      q_old = q_old > m ? q_old - m : 0;
-    };
-    // evaluate `m` queued hits (m <= 64), one per lane
-    auto drain = [&](int m) {
-      Batch B;
-      fetch(0, m, B);
-      eval_batch(B, m, NoHook());
-    };
-    // All full batches in the queue, software-pipelined: the next batch's record loads are issued in the middle of the
-    // current batch's arithmetic (before its 36 Hessian terms), so their L2 latency is off the critical path.
-    auto drain_full = [&]() {
-      if (!Tune::PIPE) {                           // plain: one batch after the other
-        while (qcount >= 64) drain(64);
-        return;
-      }
-      if (qcount < 64) return;
-      Batch A;
-      fetch(0, 64, A);
-#pragma unroll 1
-      for (;;) {
-        const bool more = qcount >= 128;
-        Batch N;
-        eval_batch(A, 64, [&]() { if (more) fetch(64, 64, N); });
-        if (!more) break;
-        A = N;
-      }
-    };
     if (wbase < n && grid_ok) {
       constexpr int NST = IT / TP;                            // super-tiles per item
       const unsigned e0 = (unsigned)(xb0 - mb0), e1 = (unsigned)(xb1 - mb1), e2 = (unsigned)(xb2 - mb2);
@@ -525,8 +654,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
         if (wbase + st * TP * 64 >= n) break;        // wave-uniform
         // the staging area holds two super-tiles: entries of super-tile st-2 must be gone before st overwrites their half
         // (only happens when hits are sparse; dense tiles are consumed by the regular 64-wide drains)
-        if (q_old > 0) { __builtin_amdgcn_wave_barrier(); drain(q_old); }
-        q_old = qcount;
+        if (Q.old > 0) { __builtin_amdgcn_wave_barrier(); Q.drain(Q.old); }
+        Q.old = Q.count;
         int r0[TP], r1[TP], r2[TP], cc[TP];
         bool valid[TP];
         float kx[TP], ky[TP], kz[TP];                // moved points (only the KDTREE distance test reads them again)
@@ -537,28 +666,18 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           const int inext = i + TP * 64;
           if (st + 1 < NST && inext < n) { nx[p] = X[inext]; ny[p] = X[pitch + inext]; nz[p] = X[2 * pitch + inext]; }
           bool ok = i < n && finite3(px, py, pz);
-          // PCL 1.8 transformPointCloud scalar form; Jacobian point r = R x (impl2:507-508)
           float xt[3], r[3];
 #pragma unroll
-          for (int a = 0; a < 3; a++) {
-            xt[a] = ((T[a * 4 + 0] * px + T[a * 4 + 1] * py) + T[a * 4 + 2] * pz) + T[a * 4 + 3];
-            r[a] = (Rj[a * 3 + 0] * px + Rj[a * 3 + 1] * py) + Rj[a * 3 + 2] * pz;
-          }
+          for (int a = 0; a < 3; a++) move_axis(T + 4 * a, Rj + 3 * a, px, py, pz, xt[a], r[a]);
           // a non-finite moved point (NaN pose: only reachable through a NaN More-Thuente trial value) has no neighbours;
           // the reference's float->int cast is undefined there
           ok = ok && finite3(xt[0], xt[1], xt[2]);
-          float* sp = stage[wv][((st & 1) * TP + p) * 64 + lane];
-          sp[0] = xt[0]; sp[1] = xt[1]; sp[2] = xt[2]; sp[3] = r[0]; sp[4] = r[1]; sp[5] = r[2];
+          stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, r);
           kx[p] = xt[0]; ky[p] = xt[1]; kz[p] = xt[2];
-          // getNeighborhoodAtPoint (voxel_grid_covariance_omp_impl.hpp:379-399): cell of the point, f32 divide
-          // (x / 2^k is the same bits as x * 2^-k, so a power-of-two leaf takes the one-instruction path)
-          const int c0 = (int)floorf(sc.leaf_pow2 ? xt[0] * sc.inv_leaf : xt[0] / leaf);
-          const int c1 = (int)floorf(sc.leaf_pow2 ? xt[1] * sc.inv_leaf : xt[1] / leaf);
-          const int c2 = (int)floorf(sc.leaf_pow2 ? xt[2] * sc.inv_leaf : xt[2] / leaf);
           // Branch-free probe stage.  Relative cell r = c - min_b; "inside the grid" (impl:382-392) is one unsigned
           // compare per axis; a probe that falls outside (or belongs to an invalid lane) is redirected to the grid's
           // spare all-zero bitmap word, so it misses without any flag having to be kept.
-          r0[p] = c0 - mb0; r1[p] = c1 - mb1; r2[p] = c2 - mb2;
+          rel_cell(xt, sc, leaf, mb0, mb1, mb2, r0[p], r1[p], r2[p]);
           cc[p] = r0[p] + r1[p] * mul1 + r2[p] * mul2;
           valid[p] = ok;
         }
@@ -594,15 +713,12 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
 #pragma unroll
             for (int j = 0; j < Q_GROUP; j++) {
               if (q1 - 1 - j < 0) continue;
-              // shift the cell's bit to the top: sign = occupied, popcount = bits at or below it
-              const unsigned long long bits = ((unsigned long long)bwv[p][j].y << 32) | bwv[p][j].x;
-              const unsigned long long tb = bits << (63u - (cellv[p][j] & 63u));
-              idv[p][j] = bwv[p][j].z + (unsigned)__popcll(tb) - 1u;   // rank among the searchable leaves = voxel id
-              // occupied <=> the cell's bit (now the sign bit) is set; ndt_pca needs the weights now (suffix product),
-              // ndt_omp filters dead leaves in phase B instead and saves this dependent L2 round trip
-              wiv[p][j] = ((long long)tb < 0) ? 1 : VOX_DEAD;
-              if (PCAQ) { if ((long long)tb < 0) wiv[p][j] = R[idv[p][j]].weight; }
-              if (KD && (long long)tb < 0) {                     // FLANN L2_Simple distance to the leaf's f32 centroid
+              // occupied cells alone are hits; ndt_pca needs the weights now (suffix product), ndt_omp filters dead leaves in phase B
+              // instead and saves this dependent L2 round trip
+              const bool occ = bitmap_rank(bwv[p][j], cellv[p][j], idv[p][j]);
+              wiv[p][j] = occ ? 1 : VOX_DEAD;
+              if (PCAQ) { if (occ) wiv[p][j] = R[idv[p][j]].weight; }
+              if (KD && occ) {                     // FLANN L2_Simple distance to the leaf's f32 centroid
                 const float* cp = cent + 3 * (size_t)(g.rec_off + idv[p][j]);
                 const float dx = kx[p] - cp[0], dy = ky[p] - cp[1], dz = kz[p] - cp[2];
                 if (!(((dx * dx + dy * dy) + dz * dz) < sc.kd_r2)) wiv[p][j] = VOX_DEAD;
@@ -617,81 +733,27 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
               if (q1 - 1 - j < 0) continue;
               const bool hit = wiv[p][j] != VOX_DEAD;     // empty cell, or nr_points == -1: not a neighbour (impl:395)
               if (PCAQ && hit) suf[p] *= (double)wiv[p][j];
-              const unsigned long long mask = __ballot(hit);
-              if (hit) {
-                const int pos = (qhead + qcount + (int)__popcll(mask & lt_mask)) & (Q_CAP - 1);
-                q_ent[wv][pos] = ((unsigned)slot << ID_BITS) | idv[p][j];
-                if (PCAQ) q_w[wv][pos] = (QW)suf[p];
-              }
-              qcount += (int)__popcll(mask);
+              Q.push(hit, (unsigned)slot, idv[p][j], suf[p]);
             }
           }
           __builtin_amdgcn_wave_barrier();
           TL_STAMP(4);
-          drain_full();
+          Q.drain_full();
           TL_STAMP(5);
         }
       }
       __builtin_amdgcn_wave_barrier();
-      if (qcount > 0) drain(qcount);
+      if (Q.count > 0) Q.drain(Q.count);
       TL_STAMP(5);
     }
-    // Fixed-order reduction of the wave -> one 44-double row per (chunk, quarter).  Same pairwise tree as a 64-lane xor
-    // butterfly (distance 32, 16, 8, 4, 2, 1 -- so the same bits), but as a reduce-scatter: the distance-32 and -16
-    // levels use gfx950's v_permlane32_swap / v_permlane16_swap to exchange HALF of the values between lane halves /
-    // rows, so 43 -> 22 -> 11 values remain per lane before the in-row butterfly (66 swaps + 88 shuffles + 77 adds
-    // instead of 516 shuffles + 258 adds per item).
-    if constexpr (SO) {
-      const double v = score_tree((double)acc[0]);
-      if (lane == 0) {
-        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(partials + ((size_t)b * rows_per_pair + rem) * NACC);
-        __hip_atomic_store(PG, (unsigned long long)__double_as_longlong(v), RLX_AGENT);
-        __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
-      }
-    } else {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    double accd[43];
-    if constexpr (FAST) fast_acc_to_row(acc, accd);
-    else {
-#pragma unroll
-      for (int i = 0; i < 43; i++) accd[i] = acc[i];
-    }
-    double P1[22], P2[11];
-#pragma unroll
-    for (int i = 0; i < 22; i++) {
-      const double a = accd[i], b2 = (i + 22 < 43) ? accd[i + 22] : 0.0;
-      const u2v lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      // lanes 0..31: value i of lanes L and L+32;  lanes 32..63: value i+22 of lanes L-32 and L
-      P1[i] = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-    }
-#pragma unroll
-    for (int i = 0; i < 11; i++) {
-      const double a = P1[i], b2 = P1[i + 11];
-      const u2v lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      // even rows: P1[i] of rows r and r+1;  odd rows: P1[i+11] of rows r-1 and r
-      double v = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      P2[i] = v;
-    }
-    if ((lane & 15) == 0) {
-      // row 0 (lane 0) holds values 0..10, row 1: 11..21, row 2: 22..32, row 3: 33..42 (+ the pad)
-      const int row = lane >> 4, base = 11 * (row & 1) + 22 * (row >> 1);
-      double* P = FINE ? &red[FINE ? wv : 0][0] : partials + ((size_t)b * rows_per_pair + rem) * NACC;
-      if (ASYNC && !FINE) {                        // write-through (sc1) 8-byte stores: the pair's updater may run on another XCD
-        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(P);
-#pragma unroll
-        for (int i = 0; i < 11; i++) if (base + i < 43) __hip_atomic_store(PG + base + i, (unsigned long long)__double_as_longlong(P2[i]), RLX_AGENT);
-        if (lane == 0) __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 11; i++) if (base + i < 43) P[base + i] = P2[i];
-        if (lane == 0) P[43] = (double)nhits;
-      }
-    }
-    }
+    // one row per (chunk, quarter); FINE: into the block's LDS first (below)
+    double* P = FINE ? &red[FINE ? wv : 0][0] : partials + ((size_t)b * rows_per_pair + rem) * NACC;
+    if constexpr (SO) score_row_store((double)Q.acc[0], P, Q.nhits, lane);
+    else if constexpr (FAST) {
+      double accd[43];
+      fast_acc_to_row(Q.acc, accd);
+      wave_row_store<ASYNC && !FINE>(accd, P, Q.nhits, lane);
+    } else wave_row_store<ASYNC && !FINE>(Q.acc, P, Q.nhits, lane);
     if (FINE) {
       __syncthreads();                              // (uniform: the four waves of a block run the same items loop, see above)
       if (wv == 0 && lane < NACC)
@@ -699,9 +761,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
       __syncthreads();
     }
     TL_STAMP(6);
-#ifdef NDT_TIMELINE
-    tl[7] += 1;
-#endif
+    tl.count();
   }
 }
 
@@ -720,14 +780,9 @@ template <bool PCA, int ORD, int NROWS, bool SO = false>
 __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const float* __restrict__ src, const size_t pitch,
                                               const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                               double* partials, const int rows_per_pair, const SweepConst& sc, const double* exp_tab,
-                                              const unsigned pose_w, const int n, const int g_idx
-#ifdef NDT_TIMELINE
-                                              , unsigned long long* tl, unsigned long long& tl_last
-#endif
-                                              ) {
+                                              const unsigned pose_w, const int n, const int g_idx, Timeline& tl) {
   constexpr int TP = 2, IT = 8, NST = IT / TP, Q_CAP = 512;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
   auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 4>();
   auto& stage = item_lds<float[WAVES][64 * IT][6], 5>();   // one row of staged points: x'(3), R x (3)
   const GridDesc& g = gd[g_idx];
@@ -736,10 +791,7 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   const VoxelRec* R = recs + g.rec_off;
   const bool grid_ok = (g.status == GRID_OK);
   float T[12], Rj[9];
-#pragma unroll
-  for (int a = 0; a < 12; a++) T[a] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, a));
-#pragma unroll
-  for (int a = 0; a < 9; a++) Rj[a] = __uint_as_float(__builtin_amdgcn_readlane(pose_w, 12 + a));
+  pose_from_words(pose_w, T, Rj);
   const float leaf = g.leaf;
   const int mb0 = g.min_b[0], mb1 = g.min_b[1], mb2 = g.min_b[2];
   const unsigned e0 = (unsigned)(g.max_b[0] - mb0), e1 = (unsigned)(g.max_b[1] - mb1), e2 = (unsigned)(g.max_b[2] - mb2);
@@ -747,48 +799,9 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   const int base = rem0 * (IT * 64);               // first point of the first row
   constexpr int S_TOTAL = NROWS * NST;
 
+  // sweep_item<PCA, 1, 8>'s queue: one probe per point, exact arithmetic, the leaf's own weight read with its record (no weight queue)
   double acc[43];
-#pragma unroll
-  for (int a = 0; a < 43; a++) acc[a] = 0.0;
-  unsigned nhits = 0;
-  int qhead = 0, qcount = 0;                       // wave-uniform
-
-  struct Batch { unsigned slot; double m0, m1, m2; float C[9]; int weight; };
-  auto fetch = [&](int off, int m, Batch& B) {
-    const int k = lane < m ? lane : m - 1;
-    const unsigned ent = q_ent[wv][(qhead + off + k) & (Q_CAP - 1)];
-    B.slot = ent >> ID_BITS;
-    const VoxelRec& vr = R[ent & ((1u << ID_BITS) - 1)];
-    B.m0 = vr.mean[0]; B.m1 = vr.mean[1]; B.m2 = vr.mean[2];
-#pragma unroll
-    for (int a = 0; a < 9; a++) B.C[a] = vr.icov[a];
-    B.weight = vr.weight;
-  };
-  auto eval_batch = [&](const Batch& B, int m, auto mid) {
-    const float* sp = stage[wv][B.slot];
-    const float xt0 = sp[0], xt1 = sp[1], xt2 = sp[2];
-    float r[3] = {sp[3], sp[4], sp[5]};
-    const bool live = lane < m && B.weight != VOX_DEAD;
-    float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
-    if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, PCA ? (double)B.weight : 1.0, live, acc[0], exp_tab); }
-    else eval_hit<PCA, decltype(mid), false, ORD>(u, r, B.C, sc.d1, sc.d2f, PCA ? (double)B.weight : 1.0, live, acc, exp_tab, mid);
-    nhits += (unsigned)__popcll(__ballot(live));
-    qhead = (qhead + m) & (Q_CAP - 1);
-    qcount -= m;
-  };
-  auto drain_full = [&]() {                        // all full batches, the next batch's records fetched in the middle of the current one (as sweep_item)
-    if (qcount < 64) return;
-    Batch A;
-    fetch(0, 64, A);
-#pragma unroll 1
-    for (;;) {
-      const bool more = qcount >= 128;
-      Batch N;
-      eval_batch(A, 64, [&]() { if (more) fetch(64, 64, N); });
-      if (!more) break;
-      A = N;
-    }
-  };
+  HitQueue<PCA, 1, ORD, SO, Q_CAP, true> Q(acc, q_ent[wv], nullptr, stage[wv], R, sc, exp_tab, lane);
 
   // pipeline registers: points of the super-tile after the probed one; probe words of the probed one
   float nx[TP], ny[TP], nz[TP];
@@ -811,17 +824,11 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
       bool ok = grid_ok && i < n && finite3(px, py, pz);
       float xt[3], r[3];
 #pragma unroll
-      for (int a = 0; a < 3; a++) {
-        xt[a] = ((T[a * 4 + 0] * px + T[a * 4 + 1] * py) + T[a * 4 + 2] * pz) + T[a * 4 + 3];
-        r[a] = (Rj[a * 3 + 0] * px + Rj[a * 3 + 1] * py) + Rj[a * 3 + 2] * pz;
-      }
+      for (int a = 0; a < 3; a++) move_axis(T + 4 * a, Rj + 3 * a, px, py, pz, xt[a], r[a]);
       ok = ok && finite3(xt[0], xt[1], xt[2]);
-      float* sp = stage[wv][(((s % NST) * TP) + p) * 64 + lane];
-      sp[0] = xt[0]; sp[1] = xt[1]; sp[2] = xt[2]; sp[3] = r[0]; sp[4] = r[1]; sp[5] = r[2];
-      const int c0 = (int)floorf(sc.leaf_pow2 ? xt[0] * sc.inv_leaf : xt[0] / leaf);
-      const int c1 = (int)floorf(sc.leaf_pow2 ? xt[1] * sc.inv_leaf : xt[1] / leaf);
-      const int c2 = (int)floorf(sc.leaf_pow2 ? xt[2] * sc.inv_leaf : xt[2] / leaf);
-      const int r0 = c0 - mb0, r1 = c1 - mb1, r2 = c2 - mb2;
+      stage_point(stage[wv][(((s % NST) * TP) + p) * 64 + lane], xt, r);
+      int r0, r1, r2;
+      rel_cell(xt, sc, leaf, mb0, mb1, mb2, r0, r1, r2);
       const bool inside = ok && (unsigned)r0 <= e0 && (unsigned)r1 <= e1 && (unsigned)r2 <= e2;
       // (a probe that falls outside the grid -- or belongs to an invalid lane, or to a target without a grid -- reads nothing and misses)
       cellv[p] = inside ? (unsigned)(r0 + r1 * mul1 + r2 * mul2) : 0u;
@@ -833,16 +840,9 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   auto push = [&](const int s) {
 #pragma unroll
     for (int p = 0; p < TP; p++) {
-      const unsigned long long bits = ((unsigned long long)bw[p].y << 32) | bw[p].x;
-      const unsigned long long tb = bits << (63u - (cellv[p] & 63u));
-      const unsigned id = bw[p].z + (unsigned)__popcll(tb) - 1u;
-      const bool hit = (long long)tb < 0;
-      const unsigned long long mask = __ballot(hit);
-      if (hit) {
-        const int pos = (qhead + qcount + (int)__popcll(mask & lt_mask)) & (Q_CAP - 1);
-        q_ent[wv][pos] = ((unsigned)((((s % NST) * TP) + p) * 64 + lane) << ID_BITS) | id;
-      }
-      qcount += (int)__popcll(mask);
+      unsigned id;
+      const bool hit = bitmap_rank(bw[p], cellv[p], id);
+      Q.push(hit, (unsigned)((((s % NST) * TP) + p) * 64 + lane), id, 1.0);
     }
     __builtin_amdgcn_wave_barrier();
   };
@@ -858,205 +858,20 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
     push(s);
     TL_STAMP(4);
     if (!row_end) { probe(s + 1); load_points(s + 2); }        // their memory round trips ride under the evaluation below
-    drain_full();
+    Q.drain_full();
     TL_STAMP(5);
     if (!row_end) continue;
     // ---- the row is complete: flush the tail, then (the staging area is free) probe the next row's first super-tile under the reduction
     __builtin_amdgcn_wave_barrier();
-    if (qcount > 0) { Batch Bt; fetch(0, qcount, Bt); eval_batch(Bt, qcount, NoHook()); }
+    if (Q.count > 0) Q.drain(Q.count);
     TL_STAMP(5);
     if (s + 1 < S_TOTAL) { probe(s + 1); load_points(s + 2); }
-    if constexpr (SO) {
-      const double v = score_tree(acc[0]);
-      if (lane == 0) {
-        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(partials + ((size_t)b * rows_per_pair + rem0 + s / NST) * NACC);
-        __hip_atomic_store(PG, (unsigned long long)__double_as_longlong(v), RLX_AGENT);
-        __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
-      }
-    } else {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    double P1[22], P2[11];
-#pragma unroll
-    for (int i = 0; i < 22; i++) {
-      const double a = acc[i], b2 = (i + 22 < 43) ? acc[i + 22] : 0.0;
-      const u2v lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      P1[i] = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-    }
-#pragma unroll
-    for (int i = 0; i < 11; i++) {
-      const double a = P1[i], b2 = P1[i + 11];
-      const u2v lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      double v = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      P2[i] = v;
-    }
-    if ((lane & 15) == 0) {
-      const int row = lane >> 4, rb = 11 * (row & 1) + 22 * (row >> 1);
-      gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(partials + ((size_t)b * rows_per_pair + rem0 + s / NST) * NACC);
-#pragma unroll
-      for (int i = 0; i < 11; i++) if (rb + i < 43) __hip_atomic_store(PG + rb + i, (unsigned long long)__double_as_longlong(P2[i]), RLX_AGENT);
-      if (lane == 0) __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
-    }
-    }
-#pragma unroll
-    for (int a = 0; a < 43; a++) acc[a] = 0.0;
-    nhits = 0;
+    double* P = partials + ((size_t)b * rows_per_pair + rem0 + s / NST) * NACC;
+    if constexpr (SO) score_row_store(Q.acc[0], P, Q.nhits, lane);
+    else wave_row_store<true>(Q.acc, P, Q.nhits, lane);
+    Q.new_row();
     TL_STAMP(6);
-#ifdef NDT_TIMELINE
-    tl[7] += 1;
-#endif
-  }
-}
-
-// EXPERIMENT, off by default (-DFAST_D1_POINT=1): DIRECT1 under the tolerance arithmetic with lane = POINT, no hit queue, no staging, no LDS at all.
-// Measured (round 6, docs/experiments.md 11): pca / 1 m 1,402 us per launch at four waves per SIMD (spills), 1,376 at three, against 1,338 for the hit
-// queue at three; config 5 / DIRECT1 2,917 / 2,711 against 2,395 -- the idle lanes cost more than the queue, and the launch is bound by the vector
-// L1's misses in flight for the point stream (TCP busy 98 %, 55-66 % of that stalled on L2, VALU busy 0.6), which more loads in flight per wave
-// do not raise.  One probe per point and ~0.85 hits leave a
-// DIRECT1 item a third evaluation and two thirds waiting for the chain  points -> bitmap word -> record  (sweep_rows_d1 above); with 37 f32
-// sums instead of 43 f64 ones the registers are there to keep three tiles of 64 points in flight per wave instead -- one whose points are
-// being transformed and probed, one whose record loads are out, one being evaluated -- and four waves per SIMD, which the queue's LDS
-// (48 KB of staging per workgroup) never allowed.  A lane whose point has no leaf evaluates with e = 0 (11 % of the lanes at 1 m, 19 % at
-// 0.5 m): cheaper than compacting.  The NROWS consecutive items of a claim go through as ONE stream of tiles; a row's sums are reduced and
-// written when its eighth tile has been evaluated, under the loads of the next row's first tiles.  Rows depend on (pair, row, input order)
-// alone.  Used by both the round-based sweep (NROWS = 1) and the one-launch align, so a pair's bits are the same in either.
-template <bool PCA, int NROWS, bool ASYNC>
-__device__ __forceinline__ void sweep_rows_d1p(const int b, const int rem0, const float* __restrict__ src, const size_t pitch, const float T[12], const float Rj[9], const int n,
-                                               const GridDesc& g, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
-                                               double* partials, const int rows_per_pair, const SweepConst& sc
-#ifdef NDT_TIMELINE
-                                               , unsigned long long* tl, unsigned long long& tl_last
-#endif
-                                               ) {
-  constexpr int IT = 8, S_TOTAL = NROWS * IT;
-  const int lane = threadIdx.x & 63;
-  const float* X = src + (size_t)b * 3 * pitch;
-  const BitWord* W = words + g.word_off;
-  const VoxelRecF* R = reinterpret_cast<const VoxelRecF*>(recs) + g.rec_off;
-  const bool grid_ok = (g.status == GRID_OK);
-  const float leaf = g.leaf;
-  const int mb0 = g.min_b[0], mb1 = g.min_b[1], mb2 = g.min_b[2];
-  const unsigned e0 = (unsigned)(g.max_b[0] - mb0), e1 = (unsigned)(g.max_b[1] - mb1), e2 = (unsigned)(g.max_b[2] - mb2);
-  const int mul1 = g.mul1, mul2 = g.mul2;
-  const int base = rem0 * (IT * 64);
-
-  float acc[NACC_F];
-#pragma unroll
-  for (int a = 0; a < NACC_F; a++) acc[a] = 0.f;
-  unsigned nhits = 0;
-  // stage registers: P = raw points (prefetched), A = transformed + probed (bitmap word in flight), B = ranked (record in flight)
-  float px = 0.f, py = 0.f, pz = 0.f;
-  float axt[3] = {0.f, 0.f, 0.f}, ar[3] = {0.f, 0.f, 0.f}; unsigned acell = 0u; bool ain = false; uint4 abw = make_uint4(0u, 0u, 0u, 0u);
-  float bxt[3] = {0.f, 0.f, 0.f}, br[3] = {0.f, 0.f, 0.f}; bool bhit = false;
-  float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0; int bweight = 0;
-  auto load_points = [&](const int s) {
-    const int i = base + s * 64 + lane;
-    px = py = pz = 0.f;
-    if (s < S_TOTAL && i < n) { px = X[i]; py = X[pitch + i]; pz = X[2 * pitch + i]; }
-  };
-  auto probe = [&](const int s) {                    // P -> A
-    const int i = base + s * 64 + lane;
-    bool ok = grid_ok && s < S_TOTAL && i < n && finite3(px, py, pz);
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      axt[a] = ((T[a * 4 + 0] * px + T[a * 4 + 1] * py) + T[a * 4 + 2] * pz) + T[a * 4 + 3];     // PCL 1.8 transformPointCloud, uncontracted
-      ar[a] = fmaf(Rj[a * 3 + 2], pz, fmaf(Rj[a * 3 + 1], py, Rj[a * 3 + 0] * px));
-    }
-    ok = ok && finite3(axt[0], axt[1], axt[2]);
-    const int c0 = (int)floorf(sc.leaf_pow2 ? axt[0] * sc.inv_leaf : axt[0] / leaf);
-    const int c1 = (int)floorf(sc.leaf_pow2 ? axt[1] * sc.inv_leaf : axt[1] / leaf);
-    const int c2 = (int)floorf(sc.leaf_pow2 ? axt[2] * sc.inv_leaf : axt[2] / leaf);
-    const int r0 = c0 - mb0, r1 = c1 - mb1, r2 = c2 - mb2;
-    ain = ok && (unsigned)r0 <= e0 && (unsigned)r1 <= e1 && (unsigned)r2 <= e2;
-    acell = ain ? (unsigned)(r0 + r1 * mul1 + r2 * mul2) : 0u;
-    abw = make_uint4(0u, 0u, 0u, 0u);
-    if (ain) abw = *reinterpret_cast<const uint4*>(W + (acell >> 6));
-  };
-  auto rank = [&]() {                                // A -> B
-    const unsigned long long bits = ((unsigned long long)abw.y << 32) | abw.x;
-    const unsigned long long tb = bits << (63u - (acell & 63u));
-    const unsigned id = abw.z + (unsigned)__popcll(tb) - 1u;
-    bhit = ain && (long long)tb < 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) { bxt[a] = axt[a]; br[a] = ar[a]; }
-    if (bhit) {
-      const float4* rp = reinterpret_cast<const float4*>(R + id);
-      q0 = rp[0]; q1 = rp[1]; q2 = rp[2];
-      bweight = R[id].weight;
-    }
-  };
-  load_points(0);
-  TL_STAMP(1);
-  probe(0);
-  load_points(1);
-  TL_STAMP(2);
-  rank();
-  probe(1);
-  load_points(2);
-  TL_STAMP(4);
-#pragma unroll 1
-  for (int s = 0; s < S_TOTAL; s++) {
-    // in flight here: record(s), bitmap word(s + 1), points(s + 2)
-    float ext[3], er[3]; bool ehit; float4 e0q, e1q, e2q; int ew;
-    { ext[0] = bxt[0]; ext[1] = bxt[1]; ext[2] = bxt[2]; er[0] = br[0]; er[1] = br[1]; er[2] = br[2]; ehit = bhit; e0q = q0; e1q = q1; e2q = q2; ew = bweight; }
-    rank();                                          // tile s + 1: needs its bitmap word; issues its record loads
-    probe(s + 2);                                    // tile s + 2: needs its points; issues its bitmap load
-    load_points(s + 3);
-    {                                                // tile s: evaluate (its record arrived while the loads above went out)
-      const bool live = ehit && ew != VOX_DEAD;
-      const float u[3] = {(ext[0] - e0q.x) - e0q.w, (ext[1] - e0q.y) - e1q.x, (ext[2] - e0q.z) - e1q.y};
-      const float c[6] = {e1q.z, e1q.w, e2q.x, e2q.y, e2q.z, e2q.w};
-      eval_hit_fast<PCA, NoHook>(u, er, c, sc.d1f, sc.d2f, sc.kq, PCA ? (float)ew : 1.f, live, acc);
-      nhits += (unsigned)__popcll(__ballot(live));
-    }
-    TL_STAMP(5);
-    if ((s % IT) != IT - 1) continue;
-    // ---- the row is complete
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    double accd[43];
-    fast_acc_to_row(acc, accd);
-    double P1[22], P2[11];
-#pragma unroll
-    for (int i = 0; i < 22; i++) {
-      const double a = accd[i], b2 = (i + 22 < 43) ? accd[i + 22] : 0.0;
-      const u2v lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      P1[i] = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-    }
-#pragma unroll
-    for (int i = 0; i < 11; i++) {
-      const double a = P1[i], b2 = P1[i + 11];
-      const u2v lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b2), false, false);
-      const u2v hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b2), false, false);
-      double v = __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      P2[i] = v;
-    }
-    if ((lane & 15) == 0) {
-      const int row = lane >> 4, rb = 11 * (row & 1) + 22 * (row >> 1);
-      double* P = partials + ((size_t)b * rows_per_pair + rem0 + s / IT) * NACC;
-      if (ASYNC) {
-        gu64* PG = (gu64*)reinterpret_cast<unsigned long long*>(P);
-#pragma unroll
-        for (int i = 0; i < 11; i++) if (rb + i < 43) __hip_atomic_store(PG + rb + i, (unsigned long long)__double_as_longlong(P2[i]), RLX_AGENT);
-        if (lane == 0) __hip_atomic_store(PG + 43, (unsigned long long)__double_as_longlong((double)nhits), RLX_AGENT);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 11; i++) if (rb + i < 43) P[rb + i] = P2[i];
-        if (lane == 0) P[43] = (double)nhits;
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < NACC_F; a++) acc[a] = 0.f;
-    nhits = 0;
-    TL_STAMP(6);
-#ifdef NDT_TIMELINE
-    tl[7] += 1;
-#endif
+    tl.count();
   }
 }
 
@@ -1127,10 +942,7 @@ k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict
   const bool flat = FINE || (n_active * items_per_pair <= nblk * WAVES);
   const int xw = flat ? nblk * WAVES : (int)(gridDim.x >> 3) * WAVES;                    // waves per XCD (flat: of the whole grid)
   const int wx = flat ? (int)blockIdx.x * WAVES + wv : (int)(blockIdx.x >> 3) * WAVES + wv;
-#ifdef NDT_TIMELINE
-  unsigned long long tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl_last = __builtin_readcyclecounter();
-#endif
+  Timeline tl;
 #pragma unroll 1
   for (int probe = 0; probe < (flat ? 1 : 8); probe++) {        // own XCD first, then steal (flat: one queue, all static)
     const int xcd = flat ? 0 : (my_xcd + probe) & 7;
@@ -1161,16 +973,10 @@ k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict
       const int rem = item % items_per_pair;        // the pair's work item = its partial row
       TL_STAMP(0);
 
-      sweep_item<PCA, K, IT, FINE, ORD, false>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0
-#ifdef NDT_TIMELINE
-                                               , tl, tl_last
-#endif
-                                               );
+      sweep_item<PCA, K, IT, FINE, ORD, false>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0, tl);
       if (next_static) { round++; item = wx + round * xw; }
       else item = __builtin_amdgcn_readfirstlane(next_item);
     }
   }
-#ifdef NDT_TIMELINE
-  if (lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&g_tl[k], tl[k]);
-#endif
+  tl.flush(0, 8);
 }

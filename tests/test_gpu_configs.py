@@ -197,6 +197,50 @@ def test_one_launch_align_equals_the_round_based_align(mode, variant, res):
         assert dt < 1e-4 and dr < 1e-5
 
 
+RAGGED_COUNTS = [63, 64, 65, 127, 129, 511, 513, 1025, 2047, 2049]
+
+
+@pytest.mark.parametrize("arith", [0, 1])
+@pytest.mark.parametrize("mode,variant", [(ndt.DIRECT1, 1), (ndt.DIRECT7, 0), (ndt.DIRECT7, 1)])
+def test_ragged_source_counts_on_both_align_routes(mode, variant, arith):
+    """The boundaries of the probe stage and the hit queue that every item body shares (ndt_sweep.hpp): one resident batch of 4,096-point
+    targets whose sources end inside a tile of 64 points (63, 65), on a tile edge (64), inside a super-tile (127, 129), next to an item edge
+    (511, 513; an item is 512 points) and a chunk edge (2,047, 2,049; a chunk is 2,048), and at 1,025.  The round-based align (sweep_item, in
+    both arithmetics) and the forced one-launch align (sweep_rows_d1 for exact DIRECT1, sweep_item with agent-scope rows otherwise, score-only
+    last sweeps) must give every pair the same result words.  (Where such a short source ends is not the point -- under DIRECT1 the 65-point
+    pair ends at a pose where it meets no leaf at all --; that both routes end there, bit for bit, is.)"""
+    ids = list(range(400, 400 + len(RAGGED_COUNTS)))
+    T, S, host, n = resident_batch(ids, 64)
+    assert n == 4096
+    B = len(ids)
+    G = synth.default_guess()
+    kw = dict(resolution=1.0, trans_epsilon=0.01, max_iterations=64, neighbor_mode=mode, variant=variant)
+    out = {}
+    for label, ar, a in (("rounds", arith, 0), ("one_launch", arith, 2)) + ((("exact", 0, 0),) if arith else ()):
+        eng = ndt.Engine(ndt.default_params(**kw))
+        eng.set_option(ndt.OPT_ARITH, ar)
+        eng.set_option(ndt.OPT_ASYNC_ALIGN, a)
+        assert eng.get_option(ndt.OPT_ARITH) == ar and eng.get_option(ndt.OPT_ASYNC_ALIGN) == a
+        eng.batch_bind_device(T.data_ptr(), [n] * B, n, S.data_ptr(), RAGGED_COUNTS, n)
+        eng.batch_build_targets()
+        eng.profile_enable(True); eng.profile_reset()
+        out[label] = eng.batch_align(G)
+        pr = eng.profile_get()
+        eng.profile_enable(False)
+        eng.close()
+        assert (pr["update_launches"] == 0) == (a == 2), pr      # the option really selects the route
+    if arith:
+        # ... and the arithmetic: 37 f32 sums and one v_exp_f32 per hit cannot give all ten pairs the scores of 43 f64 sums and the f64 exponential,
+        # so equal score words everywhere would mean that the exact kernels had served the option
+        assert any(np.float64(x["score"]).tobytes() != np.float64(y["score"]).tobytes() for x, y in zip(out["rounds"], out["exact"]))
+    for k, (x, y) in enumerate(zip(out["rounds"], out["one_launch"])):
+        assert x["final"].tobytes() == y["final"].tobytes(), (k, RAGGED_COUNTS[k])
+        for w in ("score", "trans_probability"):                  # (bits, so that a NaN would compare too)
+            assert np.float64(x[w]).tobytes() == np.float64(y[w]).tobytes(), (k, RAGGED_COUNTS[k], w, x[w], y[w])
+        for w in ("iterations", "converged", "sweeps", "hits_last", "status"):
+            assert x[w] == y[w], (k, RAGGED_COUNTS[k], w, x[w], y[w])
+
+
 def test_one_launch_align_many_small_pairs_repeated():
     """Hand-off stress: 300 pairs of 4,096 points (8 work items per sweep, so a pair's updater changes constantly and tickets are published
     at the highest rate the engine can produce), 20 aligns in a row, every result word of every run equal to the round-based align's."""

@@ -172,7 +172,9 @@ int mi355ndt_get_incremental(mi355ndt_handle* h, int pair, float transformation_
  * src/global_graph/information_matrix_calculator.cpp:53-87): source moved by the final pose of the last align()
  * (identity before any align), exact nearest target point per source point, mean of the SQUARED distances that are
  * <= max_range (squared distance vs max_range, as the reference compares them); DBL_MAX when nothing is in range.
- * Works for any target cloud, also one whose voxel grid could not be built (status MI355NDT_ERR_GRID: exhaustive search). */
+ * Works for any target cloud, also one whose voxel grid could not be built (status MI355NDT_ERR_GRID: exhaustive search).
+ * It is mi355ndt_batch_fitness_scores on the one pair the handle holds: the first call after a target build adds an index of the target's
+ * occupied cells (16 B per 64 grid cells + 4 B per target point of device memory), later calls only search. */
 int mi355ndt_get_fitness_score(mi355ndt_handle* h, double max_range, double* score, long long* n_inliers);
 /* same with an explicit transform (column-major 4x4) */
 int mi355ndt_fitness_score_T(mi355ndt_handle* h, const float T_colmajor[16], double max_range, double* score, long long* n_inliers);
@@ -301,8 +303,8 @@ int mi355ndt_batch_size(const mi355ndt_handle* h);
  * squared distances <= max_range; DBL_MAX and 0 inliers when nothing is in range or target p is empty.  T_colmajor = n_pairs x 16
  * floats column-major, or NULL = each pair's final pose of the last mi355ndt_batch_align (the identity before any align of the current
  * batch).  n_inliers may be NULL.  Synchronous.  scores[p] / n_inliers[p] are bit for bit what mi355ndt_fitness_score_T returns on a
- * one-pair engine holding pair p's clouds and T[p], also for a target without a grid (MI355NDT_ERR_GRID: exhaustive search).  One
- * exception: a pair with an EMPTY source (or target) scores DBL_MAX, 0 here, where the one-pair call refuses (MI355NDT_ERR_STATE).  Builds the
+ * one-pair engine holding pair p's clouds and T[p] (the same search: that call is the batch of one), also for a target without a grid
+ * (MI355NDT_ERR_GRID: exhaustive search).  One exception: a pair with an EMPTY source (or target) scores DBL_MAX, 0 here, where the one-pair call refuses (MI355NDT_ERR_STATE).  Builds the
  * targets first if they are not built; MI355NDT_ERR_STATE in stream mode.  The loop detector's verification of K candidates against one
  * new keyframe (loop_detector.hpp:148-281) is one batch_align + one call of this (lv_slam_amd/loop_closure.py). */
 int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, double max_range, double* scores, long long* n_inliers);

@@ -112,10 +112,10 @@ struct mi355ndt_handle {
   DevBuf<int> d_kdw; bool kdw_built = false;     // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
   DevBuf<float4> d_sorted; bool leaf_sorted = false;   // MI355NDT_LEAF_SORTED: the sorted order as points (k_sorted_points)
   DevBuf<unsigned> d_rs_hist, d_rs_offs;         // segmented radix sort: tile histograms / offsets
-  DevBuf<unsigned> d_cstart, d_cend; bool cells_ready = false; int last_cb = 0;
+  int last_cb = 0;
+  // fitness scores (one pair or a batch, fit_scores): the block partials; the occupied-cell index of every target (ndt_fitness.hpp), built on the
+  // first call after a target build; the launch's item table and transforms
   DevBuf<double> d_fit;
-  // batched fitness (mi355ndt_batch_fitness_scores): occupied-cell index of every target (ndt_fitness.hpp), built on the first call after a
-  // target build; the launch's item table and transforms
   DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns; bool fit_index_ready = false;
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
   // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)

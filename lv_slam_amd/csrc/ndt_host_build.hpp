@@ -127,7 +127,6 @@ static int build_targets_impl(mi355ndt_handle* h) {
   }
   h->targets_built = true;
   h->grid_resolution = h->prm.resolution;
-  h->cells_ready = false;
   h->fit_index_ready = false;
   h->last_cb = cb;
   return compute_enqueued(h);                     // asynchronous: a later upload into these rows has to wait for the kernels above

@@ -12,7 +12,8 @@
 // (ordered-int extremes), the segmented radix sort whose first pass computes the cell keys from the points (rs_pass), k_fit_mark / k_fit_rank /
 // k_fit_runs -- on a one-target "batch".
 //
-// The search is exact for any cell size (fit_rings: ring by ring, stop when no unvisited ring can beat the best or be within max_range), so
+// The search is the batch surface's block of queries (fit_ring_block, ndt_fitness.hpp) with the points read in cell order instead of by id.
+// It is exact for any cell size (fit_rings: ring by ring, stop when no unvisited ring can beat the best or be within max_range), so
 // the cell rule is about speed only: start from MI355NDT_OPT_KF_FITNESS_CELL_MM and double the cell until the lattice has at most
 // `max_cells` cells; a keyframe that does not get there within KFI_MAX_DOUBLINGS doublings (a stray point at 1e12 m) has no lattice and is
 // scored by the exhaustive block kernel (fitness_brute_block) over its unsorted rows.
@@ -85,8 +86,9 @@ struct KfEdge {
 
 // The launch is k_fitness_batch's: a flat grid over (edge, 256-point block) items, workgroup L serving group L % 8 -- the workgroups of one
 // XCD -- so that an edge's blocks share one L2 with its index and its cloud1 points (FitItem / fit_item, ndt_fitness.hpp; .pair = the edge).
-// Same transform, same rings and stopping rule (fit_rings), same distance arithmetic, same block reduction: an edge's partials are those of
-// k_fitness on a one-pair engine, because the nearest distance is a minimum over the same points whatever the lattice and the visiting order.
+// The block body is k_fitness_batch's too (fit_ring_block); only the point accessor differs, contiguous in cell order here.  An edge's
+// partials are therefore those of a one-pair engine, because the nearest distance is a minimum over the same points whatever the lattice and
+// the visiting order.  The lattice's cell size is known on the device only (the index may be built by this call): ring_max is taken here.
 // An edge whose searched keyframe has no lattice leaves its partials to k_kf_fitness_brute.
 __global__ void __launch_bounds__(256) k_kf_fitness(const FitItem* __restrict__ items, const int* __restrict__ gstart, const KfEdge* __restrict__ edges,
                                                     float max_range, double max_range_d, double* partial) {
@@ -96,33 +98,11 @@ __global__ void __launch_bounds__(256) k_kf_fitness(const FitItem* __restrict__ 
   const KfEdge& e = edges[it.pair];
   const GridDesc& g = *e.gd;
   if (g.status != GRID_OK) return;
-  // rings needed to cover sqrt(max_range) (+1 cell of slack), as mi355ndt_fitness_score_T computes them
-  const double rr = sqrt(fmin(max_range_d, 1e30)) / (double)g.leaf + 2.0;
-  const int ring_max = rr > (double)(1 << 30) ? (1 << 30) : (int)rr;
-  const float* S = e.src;
   const float* X = e.sorted;
-  const size_t spitch = e.spitch, tpitch = e.tpitch;
-  double sum = 0.0;
-  unsigned long long cnt = 0;
-  const int i = bx * 256 + threadIdx.x;
-  if (i < it.n_src) {
-    const float px = S[i], py = S[spitch + i], pz = S[2 * spitch + i];
-    float q[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) q[a] = ((e.T[0 * 4 + a] * px + e.T[1 * 4 + a] * py) + e.T[2 * 4 + a] * pz) + e.T[3 * 4 + a];   // PCL 1.8 scalar form
-    if (finite3(q[0], q[1], q[2])) {
-      float best = __int_as_float(0x7f800000);
-      fit_rings(q, g, e.words, e.runs, ring_max, max_range, best, [&](unsigned j0, unsigned j1) {
-        for (unsigned j = j0; j < j1; j++) {
-          const float dx = q[0] - X[j], dy = q[1] - X[tpitch + j], dz = q[2] - X[2 * tpitch + j];
-          const float d2 = (dx * dx + dy * dy) + dz * dz;          // FLANN L2_Simple accumulation order
-          best = d2 < best ? d2 : best;
-        }
-      });
-      if (best <= max_range) { sum = (double)best; cnt = 1; }
-    }
-  }
-  fit_block_reduce(sum, cnt, partial + 2 * ((size_t)it.part0 + bx));
+  const size_t tpitch = e.tpitch;
+  fit_ring_block(e.src, e.spitch, it.n_src, e.T, g, e.words, e.runs, fit_ring_max(max_range_d, g.leaf), max_range, bx,
+                 [=](const float (&q)[3], unsigned j) { return fit_d2(q, X[j], X[tpitch + j], X[2 * tpitch + j]); },
+                 partial + 2 * ((size_t)it.part0 + bx));
 }
 
 // the edges whose searched keyframe has no lattice, in a launch of their own (a keyframe without a finite point: no target point at all)

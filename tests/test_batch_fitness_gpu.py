@@ -1,6 +1,10 @@
 """GPU (-m gpu): getFitnessScore(max_range) on the batch surface (mi355ndt_batch_fitness_scores, Engine.batch_fitness_scores) and the
 loop-closure verification built on it (lv_slam_amd/loop_closure.py).  Every pair's score and inlier count must be word for word what the
 single-registration surface (mi355ndt_fitness_score_T) returns for the same clouds and transform."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -10,6 +14,7 @@ from oracle import oracle_py as O
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DBL_MAX = 1.7976931348623157e308
 PRM = dict(trans_epsilon=0.01, max_iterations=64)
 RANGES = (0.04, 1.0, 25.0, float("inf"))
@@ -221,6 +226,86 @@ def test_batch_fitness_271_full_size_pairs_match_single_surface():
             assert (sc[k], n[k]) == e.fitness_score(mr, Ts[k]), (mr, k)
     e.close()
     assert np.all(got[float("inf")][1] == 65536) and np.all(got[1.0][1] > 0)
+
+
+def offset_and_far():
+    off = np.eye(4, dtype=np.float32)
+    off[:3, 3] = [0.3, 0.0, 0.0]
+    far = np.eye(4, dtype=np.float32)
+    far[0, 3] = 5000.0
+    return off, far
+
+
+@pytest.mark.parametrize("n_src", [1, 256, 257, 2500])
+def test_one_pair_ragged_sources_match_the_oracle(n_src):
+    """The one-pair surface is the batch of one, and a lone pair is cut into pieces that spread over the XCDs: one point, one full block,
+    one block and a point, and ten blocks with the last holding 196 points (five pieces of two)."""
+    t, s, _ = synth.make_pair(40, 256)
+    target, src = t.numpy()[:3000], s.numpy()[:n_src]
+    off, far = offset_and_far()
+    e = ndt.Engine(ndt.default_params(resolution=1.0, **PRM))
+    e.set_target(target)
+    e.set_source(src)
+    for name, T in (("identity", np.eye(4, dtype=np.float32)), ("offset", off), ("far", far)):
+        for mr in (0.04, 1.0, float("inf")):
+            sc, n = e.fitness_score(mr, T)
+            exp, m = O.fitness_score(target, src, T, mr)
+            assert n == m, (name, mr, n, m)
+            assert abs(sc - exp) <= 1e-12 * max(1.0, exp), (name, mr, sc, exp)
+    assert e.fitness_score(float("inf"), far)[1] == n_src
+    assert e.fitness_score(4.0, far) == (DBL_MAX, 0)
+    e.close()
+
+
+def test_cutting_a_big_pair_does_not_enter_any_result():
+    """One 16,384-point pair (64 blocks) among eight 700-point pairs (3 blocks each): 88 blocks, so pairs of more than 11 are cut -- the big
+    one into six pieces, the others not.  Every pair's words are those of the same pair alone in a batch of one and on the one-pair
+    surface, wherever the big pair sits, and with a target that takes the exhaustive kernel in the batch."""
+    big = small_pairs([140])[0]
+    small = [(t[:700], s[:700]) for t, s in small_pairs(range(141, 149))]
+    stray = small[3][0].copy()
+    stray[7] = [1e30, 0.0, 0.0]                                            # the leaf-too-small guard: no grid, exhaustive search
+    with_stray = small[:3] + [(stray, small[3][1])] + small[4:]
+    T = np.eye(4, dtype=np.float32)
+    T[:3, 3] = [0.3, -0.2, 0.1]
+    ranges = (1.0, float("inf"))
+
+    def alone(pair):
+        """{max_range: (score, inliers)} of one pair: a batch of one and the one-pair surface, which must agree"""
+        e1 = batch_engine([pair])
+        out = {}
+        for mr in ranges:
+            out[mr] = tuple(x[0] for x in e1.batch_fitness_scores(mr, T))
+            assert out[mr] == single_scores([pair], [T], mr)[0], mr
+        e1.close()
+        return out
+
+    want_big, want_small, want_stray = alone(big), [alone(p) for p in small], alone(with_stray[3])
+    assert want_big[1.0][1] > 0 and want_stray[float("inf")][1] == 700
+    for smalls, wants in ((small, want_small), (with_stray, want_small[:3] + [want_stray] + want_small[4:])):
+        for pairs, want in (([big] + smalls, [want_big] + wants), (smalls + [big], wants + [want_big])):
+            eng = batch_engine(pairs)
+            for mr in ranges:
+                sc, n = eng.batch_fitness_scores(mr, T)
+                for k in range(len(pairs)):
+                    assert (sc[k], n[k]) == want[k][mr], (mr, k)
+            eng.close()
+
+
+def test_one_pair_words_equal_the_parents():
+    """tests/golden/fitness_single_parent.json holds what Engine.fitness_score returned, as words, from the library of the commit before
+    the one-pair score became the batch of one (its own kernel over a dense cell table): tools/record_fitness_words.py wrote it and
+    states the cases.  Batch and keyframe tests compare against the one-pair surface; this is what the one-pair surface is held to."""
+    spec = importlib.util.spec_from_file_location("record_fitness_words", os.path.join(ROOT, "tools", "record_fitness_words.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(os.path.join(ROOT, "tests", "golden", "fitness_single_parent.json")) as f:
+        want = json.load(f)
+    assert len(want) == len(rec.CLOUDS) * 3 * len(rec.RANGES) == 72
+    got = rec.compute()
+    assert sorted(got) == sorted(want)
+    for case in sorted(want):
+        assert got[case] == want[case], (case, got[case], want[case])
 
 
 @pytest.mark.parametrize("use_bow", [False, True])

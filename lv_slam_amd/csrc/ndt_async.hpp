@@ -10,8 +10,8 @@
 // (ticket 0's items, ticket 1's, ...) are claimed with one returning fetch-add per item, issued at the END of the previous item together
 // with that item's arrival -- behind the item's loads, never in front of them (a returning atomic at the head of a wave's in-order memory
 // queue delays every load behind it); a wave whose position falls into a ticket that does not exist yet waits for it.
-// The wave that retires a pair's last item (one returning agent-scope fetch-add per item on a per-pair counter) becomes that pair's UPDATER: it adds the pair's rows with k_update's fixed tree, runs the Newton step
-// (newton_update, ndt_update.hpp -- same code, same bits) and either publishes the pair's next ticket or finalises the pair.
+// The wave that retires a pair's last item (one returning agent-scope fetch-add per item on a per-pair counter) becomes that pair's UPDATER: it adds the pair's rows with k_update's fixed tree
+// (walk_groups, ndt_update.hpp), runs the Newton step (newton_update, ndt_newton.hpp -- same code, same bits) and either publishes the pair's next ticket or finalises the pair.
 // Publication is round-robin over the rings, so the rings stay balanced to one ticket however the iteration counts are distributed.
 // A wave that has waited for its own ring's ticket for a while serves already-published positions of OTHER rings meanwhile (wait_ticket in
 // k_align_async): no ring depends on the workgroups of one XCD being resident -- two engines launching at once can split the XCDs between them.
@@ -27,6 +27,7 @@
 #include "ndt_math.hpp"
 #include "ndt_sweep.hpp"
 #include "ndt_update.hpp"
+#include "ndt_pose_record.hpp"
 
 #define ASYNC_POS_STRIDE 32      // unsigned words between the rings' position counters (one 128-B line each: eight hot atomics, eight lines)
 #define ASYNC_ARR_STRIDE 16      // ... between the pairs' arrival counters (64 B: pairs in flight together do not share an atomic's line)
@@ -127,12 +128,7 @@ NDT_KERNEL void k_async_prepare(const AsyncTab tab, AsyncTab* tab_dev, const int
   if (i < offsetof(AsyncCtl, carry) / sizeof(unsigned)) reinterpret_cast<unsigned*>(ctl)[i] = (i == 0 || i == 3) ? n_live : 0u;   // pub = n_live = tickets out
   if (sweep_ctl && i < 2 * sizeof(SweepCtl) / sizeof(int)) reinterpret_cast<int*>(sweep_ctl)[i] = i == 0 ? n_new : 0;           // n_active of the first
   if (i == 0 && done_new && n_new > 0) *done_new = 0u;
-  if (pose_new && i < (size_t)pose_cap) {          // every row starts as a padding row (pair_id = -1); a pair's updater fills its own
-    PoseRecord r;
-    memset(&r, 0, sizeof r);
-    r.pair_id = -1;
-    pose_new[i] = r;
-  }
+  if (pose_new && i < (size_t)pose_cap) pose_new[i] = pose_record_padding();   // a pair's updater fills its own row
   if (i == 0) tab_dev->c[0] = tab.c[0];
   if (i == 1) tab_dev->c[1] = tab.c[1];
   if (i == 2) tab_dev->c[2] = tab.c[2];
@@ -161,80 +157,21 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
   // the update is a chain of dependent instructions on the critical path of its pair (and of the whole batch once few pairs are left):
   // it goes first at the SIMD's issue arbiter while it runs next to a wave that streams independent evaluation work
   __builtin_amdgcn_s_setprio(3);
-  static_assert(sizeof(PairState) % 8 == 0, "PairState travels as 8-byte words");
-  constexpr int NW = (int)(sizeof(PairState) / 8);
   gu64* sg = (gu64*)reinterpret_cast<unsigned long long*>(&st[b]);
   unsigned long long* sl = reinterpret_cast<unsigned long long*>(&Ssh);
   // the pair's state (written by its previous updater: another wave, maybe another XCD -> LDS copy of this wave) and the first rows of the
   // reduction are requested together: the row addresses need only the constant point count
-  for (int i = lane; i < NW; i += 64) sl[i] = __hip_atomic_load(sg + i, RLX_AGENT);
+  state_to_lds<true>(Ssh, &st[b], lane, 64);
   if (lane == 0) sol[6] = 0.0;
-  // reduce_pair_rows' tree (ndt_update.hpp) on one wave: chunk = ((r0 + r1) + r2) + r3; group = 8 chunks in order; group k belongs to
-  // "wave" k % 4, whose groups add up in ascending order; the four sums add up in order.  Same operands, same order: same bits.
+  // k_update's tree on one wave: the groups in ascending order into four accumulators that stand for the block's four waves.
   // Two groups (64 rows) are in flight per lane at a time: the rows come from memory (write-through), ~2 us per dependent batch.
   const int nchunks = (n_pts + CHUNK_PTS - 1) / CHUNK_PTS;
-  double aw0 = 0.0, aw1 = 0.0, aw2 = 0.0, aw3 = 0.0;
-  if (lane < NACC) {
-    const gu64* P = (const gu64*)reinterpret_cast<const unsigned long long*>(partials + (size_t)b * rows_per_pair * NACC + lane);
-    auto ldq = [&](int c, int k) -> double { return __longlong_as_double((long long)__hip_atomic_load(P + ((size_t)c * 4 + k) * NACC, RLX_AGENT)); };
-    auto addw = [&](int g, double gs) { const int w = g & 3; if (w == 0) aw0 += gs; else if (w == 1) aw1 += gs; else if (w == 2) aw2 += gs; else aw3 += gs; };
-#pragma unroll 1
-    for (int c0 = 0; c0 < nchunks; c0 += 16) {
-      if (c0 + 16 <= nchunks) {
-        double q[16][4];
-#pragma unroll
-        for (int u = 0; u < 16; u++)
-#pragma unroll
-          for (int k = 0; k < 4; k++) q[u][k] = ldq(c0 + u, k);
-        double gs = 0.0;
-#pragma unroll
-        for (int u = 0; u < 8; u++) gs += ((q[u][0] + q[u][1]) + q[u][2]) + q[u][3];
-        addw(c0 >> 3, gs);
-        gs = 0.0;
-#pragma unroll
-        for (int u = 8; u < 16; u++) gs += ((q[u][0] + q[u][1]) + q[u][2]) + q[u][3];
-        addw((c0 >> 3) + 1, gs);
-      } else {
-#pragma unroll 1
-        for (int g0 = c0; g0 < nchunks; g0 += 8) {
-          double gs = 0.0;
-          if (g0 + 8 <= nchunks) {
-            double q[8][4];
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-#pragma unroll
-              for (int k = 0; k < 4; k++) q[u][k] = ldq(g0 + u, k);
-#pragma unroll
-            for (int u = 0; u < 8; u++) gs += ((q[u][0] + q[u][1]) + q[u][2]) + q[u][3];
-          } else {
-            for (int c = g0; c < nchunks; c++) {
-              double r[4];
-#pragma unroll
-              for (int k = 0; k < 4; k++) r[k] = ldq(c, k);
-              gs += ((r[0] + r[1]) + r[2]) + r[3];
-            }
-          }
-          addw(g0 >> 3, gs);
-        }
-      }
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  double aw[UPD_WAVES] = {0.0, 0.0, 0.0, 0.0};
+  if (lane < NACC) walk_groups<4, true, 2, UPD_WAVES>(partials + (size_t)b * rows_per_pair * NACC + lane, nchunks, 0, 1, aw);
+  wave_lds_sync();
   const bool last = __builtin_amdgcn_readfirstlane(Ssh.last_sweep) != 0;   // (the state has landed in LDS)
-  if (lane < NACC && (!last || lane == 0 || lane == NACC - 1)) {             // (a score-only row: the other columns are stale)
-    double v = 0.0;
-    v += aw0; v += aw1; v += aw2; v += aw3;
-    if (lane == 0) Ssh.score = v;
-    else if (lane < 7) Ssh.g[lane - 1] = v;
-    else if (lane < 43) Ssh.H[lane - 7] = v;
-    else {
-      Ssh.hits = (long long)v;
-      if (hits_total) { atomicAdd(hits_total, (unsigned long long)v); if (last) atomicAdd(hits_total + 1, 1ull); }
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  store_sums(Ssh, lane, wave_sums_total(aw[0], aw[1], aw[2], aw[3]), false, last, hits_total);
+  wave_lds_sync();
   TL_STAMP(12);                                    // state + rows
   // The re-basing of p for this step was computed by the previous updater after it published this sweep (below).  Its words are fetched
   // AFTER its tag has been seen (the state above was one multi-word load: a new tag does not vouch for the words that came with it), and the
@@ -250,8 +187,7 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
     for (int a = 0; a < 6; a++) sol[a] = 0.0;      // ever disagree with the flag, the zero step ends the pair there (impl2:147-152) -- no wait on a solve that never comes
     sol[6] = 1.0;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   TL_STAMP(13);                                    // solve
   if (want_reb && !reb_ok) {                       // rare: the tag had not landed yet -- wait for it (bounded), then fetch the words
     unsigned spins = 0;
@@ -264,16 +200,14 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
     if (reb_ok && lane < 14) rbw = __hip_atomic_load(sg + RB0 + lane, RLX_AGENT);
   }
   if (reb_ok && lane < 14) sl[RB0 + lane] = rbw;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   const bool rebased = reb_ok;                     // (a tag that never came: newton_update computes the re-basing itself, same bits)
   int rc = newton_update(Ssh, &results[b], step_max, eps, max_iterations, 0, sol, rebased, C.score_only != 0);
   rc = __builtin_amdgcn_readfirstlane(rc);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   TL_STAMP(14);                                    // Newton step
   // the state goes back write-through; it is complete in memory before the ticket that lets other waves read it exists
-  for (int i = lane; i < NW; i += 64) __hip_atomic_store(sg + i, sl[i], RLX_AGENT);
+  state_from_lds<true>(&st[b], Ssh, lane, 64);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (lane == 0) {
     bool suspend = false;
@@ -288,13 +222,7 @@ __device__ __forceinline__ void async_update(const AsyncCtx& C, const int b, con
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __hip_atomic_fetch_add((gu32*)&ctl->fin, 1u, RLX_AGENT);
     } else {
-      if (C.pose) {
-        PoseRecord r;
-        for (int a = 0; a < 16; a++) r.final_cm[a] = Ssh.final_cm[a];
-        r.score = (float)Ssh.score; r.iterations = Ssh.it; r.converged = Ssh.converged; r.pair_id = C.pose_base + b * C.pose_stride;
-        for (int a = 0; a < 4; a++) r.pad[a] = 0;
-        C.pose[b] = r;
-      }
+      if (C.pose) C.pose[b] = pose_record(Ssh.final_cm, Ssh.score, Ssh.it, Ssh.converged, C.pose_base + b * C.pose_stride);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (finalize_pair's result record, the pose record)
       if (C.n_done) __hip_atomic_fetch_add((gu32*)C.n_done, 1u, RLX_AGENT);
       __hip_atomic_fetch_add((gu32*)&ctl->fin, 1u, RLX_AGENT);

@@ -85,10 +85,10 @@ __global__ void k_seq_begin(SeqState* seq, PairState* st, const GridDesc* __rest
   ctl->n_active = 1;
 }
 
-// The call-site policy after the align of frame `cur` ended (scan_matching_odom_nodelet.cpp:221-250), shared by the pumped update kernel and
-// the persistent one.  S = the frame's pair state, Sn = where the NEXT frame's initial state goes (k_seq_update: st[cur + 1] itself; the
-// persistent kernel: an LDS copy it writes through afterwards).  Returns SEQ_SAME (frame 1's second align: S was re-initialised, sweep it
-// again), SEQ_NEXT (Sn holds frame cur + 1's state, matched against grid Q.key_id) or SEQ_END (that was the last frame).
+// The call-site policy after the align of frame `cur` ended (scan_matching_odom_nodelet.cpp:221-250), called by k_seq_update.  S = the frame's
+// pair state (the kernel's LDS copy), Sn = where the NEXT frame's initial state goes (st[cur + 1] itself).  Returns SEQ_SAME (frame 1's second
+// align: S was re-initialised, sweep it again), SEQ_NEXT (Sn holds frame cur + 1's state, matched against grid Q.key_id) or SEQ_END (that was
+// the last frame).
 enum { SEQ_SAME = 0, SEQ_NEXT = 1, SEQ_END = 2 };
 __device__ inline int seq_policy(SeqState& Q, PairState& S, PairState& Sn, const int cur, const int cur_grid, const GridDesc* __restrict__ gd,
                                  const int* __restrict__ cnt, const double* __restrict__ stamps, mi355ndt_seq_frame* out, int* grid_of) {
@@ -140,8 +140,9 @@ __device__ inline int seq_policy(SeqState& Q, PairState& S, PairState& Sn, const
   return SEQ_NEXT;
 }
 
-// One launch = "the next thing the run needs after a sweep": reduce the current frame's rows, take its Newton step; when its align
-// is over, run the call-site policy and set the next frame up.  One block; the host launches it blindly between sweeps.
+// One launch = "the next thing the run needs after a sweep": reduce the current frame's rows, take its Newton step (update_block,
+// ndt_update.hpp: k_update's body, on chunk rows); when its align is over, run the call-site policy and set the next frame up.  One block;
+// the host launches it blindly between sweeps.
 __global__ void __launch_bounds__(UPD_THREADS)
 k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, int rows_per_pair, int pts_per_chunk, mi355ndt_result* results,
              const GridDesc* __restrict__ gd, const int* __restrict__ cnt, const double* __restrict__ stamps, mi355ndt_seq_frame* out,
@@ -149,80 +150,31 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
              double step_max, double eps, int max_iterations) {
   __shared__ double sm[UPD_WAVES][NACC];
   __shared__ double sol[SOL_WORDS];
-  // The frame's pair state lives in LDS for the duration of the update: the Newton step reads and writes some sixty of its fields one after the
-  // other, and through a global reference every first touch of a line was a memory round trip of its own (rounds 3-4: 11.5 us per update,
-  // most of it such waits).  Two round trips are left: the run's position (cur, its point count), then the state together with the rows.
+  // Two memory round trips: the run's position (cur, its point count), then the frame's state together with its rows.
   __shared__ PairState Ssh;
   SeqState& Q = *seq;
   Timeline tl;                                                                   // (slots 8..14: this kernel's phases, wave 0 / wave 1; tools/seq_run.py)
-  if (threadIdx.x == 0) sol[6] = 0.0;
-#if defined(NDT_TIMELINE) && defined(SEQ_UPDATE_REPEAT)
-  // ---- analysis build only (tools/seq_run.py, docs/experiments.md 10e): "what would the update cost if its code were resident?"  The body up to
-  // the Newton step runs SEQ_UPDATE_REPEAT times on the same inputs -- state and rows re-read with agent-scope loads (L2, as a resident updater would
-  // have to), nothing written back in between -- and only the LAST pass is stamped: same instructions, instruction cache warm.
-  {
-    static_assert(sizeof(PairState) % 8 == 0, "PairState travels as 8-byte words");
-    constexpr int NWr = (int)(sizeof(PairState) / 8);
-    if (Q.done == 0) {
-      const int cur_r = Q.cur, n_r = Q.cur_n;
-      const int nch = (n_r + pts_per_chunk - 1) / pts_per_chunk;
-      const gu64* sgr = (const gu64*)reinterpret_cast<const unsigned long long*>(&st[cur_r]);
-      unsigned long long* slr = reinterpret_cast<unsigned long long*>(&Ssh);
-      for (int rep = 0; rep < SEQ_UPDATE_REPEAT - 1; rep++) {
-        for (int i = threadIdx.x; i < NWr; i += UPD_THREADS) slr[i] = __hip_atomic_load(sgr + i, RLX_AGENT);
-        const double vr = reduce_pair_rows<true>(partials + (size_t)cur_r * rows_per_pair * NACC, nch, true, sm, true);
-        const int ln = threadIdx.x & 63;
-        if (threadIdx.x < NACC) {
-          if (ln == 0) Ssh.score = vr;
-          else if (ln < 7) Ssh.g[ln - 1] = vr;
-          else if (ln < 43) Ssh.H[ln - 7] = vr;
-          else Ssh.hits = (long long)vr;
-        }
-        __syncthreads();
-        if (threadIdx.x >= 64 && threadIdx.x < 128) newton_solve_side(Ssh, sol);
-        if (threadIdx.x < 64) {
-          const bool reb = Ssh.phase == PH_STEP && Ssh.reb_tag == (long long)Ssh.sweeps;
-          (void)newton_update(Ssh, &results[cur_r], step_max, eps, max_iterations, 0, sol, reb);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) sol[6] = 0.0;
-        __syncthreads();
-      }
-    }
-    tl.restart();
-  }
-#endif
   const int done = Q.done, cur = Q.cur, n_src = Q.cur_n;                         // (block-uniform)
+  const double* rows = partials + (size_t)cur * rows_per_pair * NACC;
+#if defined(NDT_TIMELINE) && defined(SEQ_UPDATE_REPEAT)
+  // ---- analysis build only (tools/seq_run.py, docs/experiments.md 10e): "what would the update cost if its code were resident?"  The update
+  // runs SEQ_UPDATE_REPEAT times on the same inputs -- state and rows re-read with agent-scope loads (L2, as a resident updater would have to),
+  // nothing written back in between -- and only the LAST pass is stamped: same instructions, instruction cache warm.
+  if (!done) {
+    for (int rep = 0; rep < SEQ_UPDATE_REPEAT - 1; rep++) {
+      (void)update_block<true, false>(&st[cur], Ssh, sm, sol, rows, n_src, pts_per_chunk, true, &results[cur], nullptr, step_max, eps, max_iterations, 0, 0, nullptr);
+      __syncthreads();
+    }
+  }
+  tl.restart();
+#endif
   if (threadIdx.x == 0) { const int l = Q.launches + 1; Q.launches = l; host_flags[1] = l; }   // launches executed (the host bounds its queue depth with it)
   if (done) return;                                                              // (the pump's overshoot)
   TL_STAMP(8);                                                                   // run position
-  static_assert(sizeof(PairState) % 8 == 0, "PairState travels as 8-byte words");
-  constexpr int NW = (int)(sizeof(PairState) / 8);
-  unsigned long long* sg = reinterpret_cast<unsigned long long*>(&st[cur]);
-  unsigned long long* sl = reinterpret_cast<unsigned long long*>(&Ssh);
-  for (int i = threadIdx.x; i < NW; i += UPD_THREADS) sl[i] = sg[i];
-  const int lane = threadIdx.x & 63;
-  const int nchunks = (n_src + pts_per_chunk - 1) / pts_per_chunk;
-  const double v = reduce_pair_rows(partials + (size_t)cur * rows_per_pair * NACC, nchunks, true, sm, true);   // latency mode: chunk rows (its barrier also publishes Ssh)
-  if (threadIdx.x < NACC) {
-    if (lane == 0) Ssh.score = v;
-    else if (lane < 7) Ssh.g[lane - 1] = v;
-    else if (lane < 43) Ssh.H[lane - 7] = v;
-    else Ssh.hits = (long long)v;
-  }
-  __syncthreads();
-  TL_STAMP(9);                                                                   // state + rows
-  if (threadIdx.x >= 128) return;
-  if (threadIdx.x >= 64) {                                                       // the solve, next to wave 0
-    newton_solve_side(Ssh, sol);
-    TL_STAMP(13);
-    tl.flush(13, 14);
-    return;
-  }
-  // (the re-basing of p for this step was computed under the sweep, by its extra workgroup: ndt_sweep.hpp)
-  const bool rebased = Ssh.phase == PH_STEP && Ssh.reb_tag == (long long)Ssh.sweeps;
-  const int rc = newton_update(Ssh, &results[cur], step_max, eps, max_iterations, 0, sol, rebased);
+  const int rc = update_block<false, false>(&st[cur], Ssh, sm, sol, rows, n_src, pts_per_chunk, true, &results[cur], nullptr, step_max, eps, max_iterations, 0, 0, &tl);
+  if (rc == UPD_EXIT) return;
   TL_STAMP(10);                                                                  // Newton step (incl. the wait for the solve)
+  const int lane = threadIdx.x;                                                  // (wave 0)
   if (lane == 0) {
     if (rc == NEWTON_SWEEP) { active_list[0] = cur; ctl->n_active = 1; }
     else {
@@ -233,10 +185,9 @@ k_seq_update(SeqState* seq, PairState* st, const double* __restrict__ partials, 
     }
   }
   // the state goes back (frame cur's: updated, finalised, or re-initialised for frame 1's second align)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   TL_STAMP(11);                                                                  // policy (when the frame's align ended)
-  for (int i = lane; i < NW; i += 64) sg[i] = sl[i];
+  state_from_lds<false>(&st[cur], Ssh, lane, 64);
   TL_STAMP(12);
   tl.count(14);                                                                  // (slot 14: updates; slot 13 is wave 1's and stays 0 here)
   tl.flush(8, 15);

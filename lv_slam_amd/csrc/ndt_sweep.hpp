@@ -3,6 +3,7 @@
 #pragma once
 #include "ndt_types.hpp"
 #include "ndt_math.hpp"
+#include "ndt_newton.hpp"
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------ derivative sweep
@@ -334,9 +335,6 @@ static inline int sweep_wpe(int K, bool fast = false) { return fast ? (K == 1 ? 
 // Shared by the lockstep kernel (k_sweep: one launch per Newton round) and the asynchronous one (k_align_async: one launch per align).
 // ASYNC: the pair's pose is read, and its row is written, with agent-scope (sc1) accesses -- another workgroup wrote / will read them
 // inside the same launch (ndt_async.hpp) -- and the FINE block reduction does not apply.
-typedef __attribute__((address_space(1))) unsigned int gu32;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 // ASYNC: the 21 pose words of pair state S (T: 12, Rj: 9) and its last_sweep flag (word 21), lane k holding word k -- one agent-scope
 // (L1-bypassing) vector load, never the scalar cache: the pair's updater, some other workgroup of the same launch, rewrote them since the
 // pair's previous sweep
@@ -874,9 +872,6 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
     tl.count();
   }
 }
-
-// (ndt_update.hpp, which includes this file)
-__device__ __forceinline__ void newton_rebase(const double p[6], const double dir[6], const double a_t, double pn[6], float inc_cm[16]);
 
 template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0>
 __global__ void __launch_bounds__(SWEEP_THREADS, (SweepTune<PCA, K, ORD>::WPE))

@@ -124,6 +124,12 @@ __constant__ int c_off[3][26][3] = {
 };
 
 // ------------------------------------------------------------------------------------ helpers
+// Words that cross workgroups inside one launch are read and written with agent-scope relaxed atomics on global-address-space pointers
+// (sc1 accesses: L1-bypassing loads, write-through stores; ndt_async.hpp)
+typedef __attribute__((address_space(1))) unsigned int gu32;
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
 __device__ __forceinline__ int f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }
 __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
 

@@ -19,7 +19,7 @@
 #include <vector>
 #include "ndt_types.hpp"
 #include "ndt_math.hpp"
-#include "ndt_update.hpp"
+#include "ndt_newton.hpp"
 
 #define REC_IN 32
 #define REC_OUT 72

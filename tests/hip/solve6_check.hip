@@ -11,7 +11,7 @@
 #include <vector>
 #include "ndt_types.hpp"
 #include "ndt_math.hpp"
-#include "ndt_update.hpp"
+#include "ndt_newton.hpp"
 
 __global__ void k_solve(const double* __restrict__ in, double* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the SE(3) pose math of the Newton control on the device (lv_slam_amd/csrc/ndt_math.hpp, init_pair_state and newton_rebase of
-ndt_update.hpp; Sophus a621ff2 / Eigen 3.3 restated, ndt_omp_impl2.hpp:102-129, 163-166) at the angles no align in the suite reaches: around the 1e-10
+ndt_newton.hpp; Sophus a621ff2 / Eigen 3.3 restated, ndt_omp_impl2.hpp:102-129, 163-166) at the angles no align in the suite reaches: around the 1e-10
 small-angle threshold, beyond 120 degrees (the trace <= 0 branch of the matrix -> quaternion conversion with its three sub-branches), w -> 0 and w < 0
 (where the SIGNED `theta < 1e-10` test of SE3::log takes the small-angle V^-1 for a large negative angle: the reference's Sophus, so a contract), half
 turns, f32-rounded guesses, translations from 0 to 1e5 m.  tests/hip/se3_check (built by build()) evaluates the records of tests/se3_ref.py on the device.

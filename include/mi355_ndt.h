@@ -544,6 +544,67 @@ typedef struct mi355ndt_inf_params {
 void mi355ndt_inf_params_default(mi355ndt_inf_params* p);
 int  mi355ndt_information_matrix(const mi355ndt_inf_params* p, double fitness_score, double inf[36]);
 
+/* ---- GICP: pclomp::GeneralizedIterativeClosestPoint (registration_method = GICP_OMP) ---------------------------- */
+/* replaces pclomp::GeneralizedIterativeClosestPoint (include/ndt_omp/gicp_omp.h, gicp_omp_impl.hpp), the registration
+ * select_registration_method hands out for registration_method = GICP_OMP (src/global_graph/registrations.cpp:43-53), for one pair at a time,
+ * synchronously.  Three stages run on the device -- the k-nearest-neighbour covariances of both clouds (computeCovariances), the
+ * correspondences with their Mahalanobis matrices, the cost / gradient sums -- and the BFGS optimiser and the outer loop of
+ * computeTransformation run on the host, reading one small record per evaluation.  The rules are the reference's as restated in
+ * tools/gicp_ref.py; FLANN's tie order, PCL's bfgs.h and Eigen's JacobiSVD are unpinned.
+ * mi355ndt_gicp_params_default gives the constructor's values (gicp_omp.h:110-120): k_correspondences 20, gicp_epsilon 1e-3,
+ * rotation_epsilon 2e-3, transformation_epsilon 5e-4, max_iterations 200, max_inner_iterations 20, corr_dist_threshold 5.0.  The factory
+ * overrides four of them (registrations.cpp:47-51): transformation_epsilon 0.01, max_iterations 64, k_correspondences 20,
+ * max_inner_iterations 20.  use_reciprocal_correspondences (false there) is not served.
+ * Clouds: host records (x, y, z f32 first, stride_bytes apart) or resident keyframes by id.  A cloud's covariances are computed on first
+ * use and kept until the cloud, k_correspondences or gicp_epsilon changes, as PCL keeps target_covariances_; a keyframe's stay with the
+ * keyframe (beside an index of their own: about 12 + 4 + 72 B per point) until mi355ndt_keyframe_release, so the new keyframe of a loop
+ * check is decomposed once for all its candidates.  A released id is refused (MI355NDT_ERR_BAD_ARG) by the next call that needs the cloud.
+ * Errors: MI355NDT_ERR_STATE in stream mode, and from the calls that need a cloud (or correspondences) that was not set (computed);
+ * MI355NDT_ERR_BAD_ARG with a mi355ndt_last_error text for k_correspondences outside 1..64 or above the number of searchable points (three
+ * finite coordinates) of a cloud -- the reference prints an error and reads unsized storage --, a NaN or negative epsilon or threshold,
+ * negative iteration counts.  The batch, the grids, the keyframes' rows and fitness indexes, the prefilter result and the other workspaces
+ * of the handle are left as they were.
+ *   role: MI355NDT_GICP_TARGET / MI355NDT_GICP_SOURCE.
+ *   mi355ndt_gicp_covariances: n records of nine f64 (row-major 3x3), input order, zeros for a non-finite point; out may be NULL
+ *     (compute and keep only); a count above capacity is MI355NDT_ERR_BAD_ARG.
+ *   mi355ndt_gicp_correspondences: one pass of the matching loop (:415-466) with transformation_ = T (column-major f32; NULL: identity):
+ *     idx (may be NULL) gets the target index per source point, -1 = none; maha (may be NULL) nine f64 per source point, zeros where
+ *     unmatched; *m the number of matches.  The result stays resident for mi355ndt_gicp_cost.
+ *   mi355ndt_gicp_cost: fdf (:343-378) over the resident correspondences at the state x[6] (x, y, z, roll, pitch, yaw) with base
+ *     transformation `base`: *f and g[6] (either may be NULL).  MI355NDT_ERR_STATE with fewer than one match.
+ *   mi355ndt_gicp_align: align(output, guess).  inner_status: the optimiser's last exit code (BFGSSpace::Status: -1 running, 0 success,
+ *     1 no progress; -2 when it never ran); n_matched and delta: of the last outer iteration.
+ *   mi355ndt_gicp_get_aligned: the source moved by the last final transformation, x, y, z into records of out_stride_bytes. */
+enum { MI355NDT_GICP_TARGET = 0, MI355NDT_GICP_SOURCE = 1 };
+typedef struct mi355ndt_gicp_params {
+  int    k_correspondences;       /* setCorrespondenceRandomness      20   */
+  double gicp_epsilon;            /* (no setter in the reference)     1e-3 */
+  double rotation_epsilon;        /* setRotationEpsilon               2e-3 */
+  double transformation_epsilon;  /* setTransformationEpsilon         5e-4 */
+  int    max_iterations;          /* setMaximumIterations             200  */
+  int    max_inner_iterations;    /* setMaximumOptimizerIterations    20   */
+  double corr_dist_threshold;     /* setMaxCorrespondenceDistance     5.0  */
+} mi355ndt_gicp_params;
+typedef struct mi355ndt_gicp_result {
+  float  final_colmajor[16];      /* getFinalTransformation(): [R_t R_g | t_t + t_g] (:508-511) */
+  int    converged;               /* hasConverged() */
+  int    iterations;              /* nr_iterations_: outer iterations */
+  int    inner_status;
+  int    n_matched;
+  double delta;
+} mi355ndt_gicp_result;
+int mi355ndt_gicp_params_default(mi355ndt_gicp_params* p);
+int mi355ndt_gicp_set_params(mi355ndt_handle* h, const mi355ndt_gicp_params* p);
+int mi355ndt_gicp_set_target(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_gicp_set_source(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_gicp_set_target_keyframe(mi355ndt_handle* h, int id);
+int mi355ndt_gicp_set_source_keyframe(mi355ndt_handle* h, int id);
+int mi355ndt_gicp_covariances(mi355ndt_handle* h, int role, double* out, size_t capacity);
+int mi355ndt_gicp_correspondences(mi355ndt_handle* h, const float* guess_colmajor, const float* T_colmajor, int* idx, double* maha, int* m);
+int mi355ndt_gicp_cost(mi355ndt_handle* h, const double* x, const float* base_colmajor, double* f, double* g);
+int mi355ndt_gicp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355ndt_gicp_result* result);
+int mi355ndt_gicp_get_aligned(mi355ndt_handle* h, void* out_pts, size_t out_stride_bytes);
+
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);
 int mi355ndt_profile_reset(mi355ndt_handle* h);

@@ -4,6 +4,8 @@
 //   target build  : k_minmax -> k_griddesc -> radix sort (cell from the points, input order) -> k_mark (+ run heads)
 //                   -> k_rank (+ run starts by voxel id) -> k_leafsum -> k_voxels          (VoxelGridCovariance::applyFilter,
 //                   include/ndt_omp/voxel_grid_covariance_omp_impl.hpp:48-370)
+//   GICP          : k_gc_cov -> [k_gc_match -> (k_gc_cost -> k_gc_cost_final)*]*   (pclomp::GeneralizedIterativeClosestPoint, gicp_omp_impl.hpp; the
+//                   BFGS optimiser and the outer loop on the host: ndt_gicp.hpp, gicp_bfgs.hpp, ndt_host_gicp.hpp)
 //   align         : k_init_state -> k_sweep -> [k_update -> k_sweep]*      (computeTransformation +
 //                   computeDerivatives + computeStepLengthMT, include/ndt_omp/ndt_omp_impl2.hpp:87-188, 196-305, 841-1003;
 //                   step_size <= eps/2 only: [k_update -> k_hessian -> k_update -> k_sweep]*, impl2:622-714, 920-1000)
@@ -53,6 +55,8 @@
 #include "ndt_keyframe.hpp"
 #include "ndt_kffitness.hpp"
 #include "ndt_outlier.hpp"
+#include "ndt_gicp.hpp"
+#include "gicp_bfgs.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
@@ -81,5 +85,6 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id
 #include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
 #include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result
+#include "ndt_host_gicp.hpp"       // GICP: covariances, correspondences, cost, BFGS driver, align
 #include "ndt_host_sequence.hpp"   // latency mode, sequence run
 #include "ndt_host_stream.hpp"     // stream mode

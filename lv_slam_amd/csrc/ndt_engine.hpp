@@ -74,6 +74,21 @@ struct VoxelScratch {
   bool pending = false;                           // a copy out of h_tab is enqueued and the stream has not been waited for since
 };
 
+// ---- GICP (mi355ndt_gicp_*, ndt_gicp.hpp / ndt_host_gicp.hpp): what the surface keeps per cloud -- a spatial index of its own (the keyframe
+// index's layout, ndt_host_kffitness.hpp, plus the point ids in cell order, which the (d2, id) tie rules need) and the nine f64 covariance
+// rows -- keyed by the (k_correspondences, gicp_epsilon) the covariances were computed with.  A host cloud's lives with the surface's side, a
+// keyframe's with the keyframe (released with it).
+struct GicpCache {
+  DevBuf<unsigned char> index; DevBuf<unsigned> ids; DevBuf<double> cov;
+  int status = -1, n_fin = 0;                     // the lattice's GRID_* status (-1: no index yet), searchable points
+  int k = -1; double eps = 0.0;                   // what cov holds (k < 0: nothing)
+};
+struct GicpSide {
+  DevBuf<float> rows_own; size_t n = 0, pitch = 0; // a host cloud's rows ([3][pitch], the tail zeroed)
+  int kf_id = -1; bool set = false;               // kf_id >= 0: the rows and the cache are the keyframe's
+  GicpCache cache;                                // a host cloud's
+};
+
 struct mi355ndt_handle {
   int device = 0;
   HipStream own_stream;                         // the engine's compute stream, unless mi355ndt_set_stream gave it one
@@ -133,10 +148,21 @@ struct mi355ndt_handle {
     static constexpr int NO_INDEX = -1;
     DevBuf<float> rows; size_t n = 0, pitch = 0; int ch = 3;
     DevBuf<unsigned char> index; int index_status = NO_INDEX;
+    std::unique_ptr<GicpCache> gicp;              // the GICP surface's index and covariances over this keyframe, once it has been one of its clouds
   };
   std::map<int, Keyframe> keyframes;
   int kf_next_id = 0;
   int kff_cell_mm = 100;                          // MI355NDT_OPT_KF_FITNESS_CELL_MM
+  // GICP surface: parameters, the two clouds, the resident correspondences (idx, M SoA over the source's pitch), the sweep's chunk partials,
+  // the mapped result record the host reads after every evaluation, the last final transformation
+  struct Gicp {
+    mi355ndt_gicp_params prm{20, 1e-3, 2e-3, 5e-4, 200, 20, 5.0};
+    GicpSide side[2];
+    DevBuf<int> idx, m; DevBuf<double> maha, part; DevBuf<float> moved;
+    PinBuf<double> h_rec; double* d_rec = nullptr;   // (h_rec is mapped; d_rec: the device's view)
+    bool have_corr = false, have_final = false; int n_matched = 0;
+    float final_cm[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
+  } gicp;
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 

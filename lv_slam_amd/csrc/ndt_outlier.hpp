@@ -25,41 +25,69 @@
 
 // the K smallest squared distances a lane has seen, unsorted, with the largest of them (`worst`, at `wslot`) tracked: a candidate that does
 // not beat it costs one compare.  worst = +inf until the list is full -- what fit_rings reads as `best`.
-template <int CAP>
+// IDS: every entry carries its point id in a second column and the order is (d2, id) -- the GICP covariances (ndt_gicp.hpp), whose sums
+// depend on which of two equally distant points is kept and on the order they are added in.  Without ids, equal distances are equal entries.
+template <int CAP, bool IDS = false>
 struct OlList {
   float* L;                              // this lane's column: slot s at L[s * OL_LANES]
+  unsigned* I;                           // (IDS) the ids' column
   int K, cnt, wslot;
   float worst;
-  __device__ __forceinline__ void init(float (*lst)[OL_LANES], int k) {
-    L = &lst[0][threadIdx.x]; K = k; cnt = 0; wslot = 0; worst = __int_as_float(0x7f800000);
+  unsigned wid;
+  __device__ __forceinline__ void init(float (*lst)[OL_LANES], int k, unsigned (*ids)[OL_LANES] = nullptr) {
+    L = &lst[0][threadIdx.x]; I = IDS ? &ids[0][threadIdx.x] : nullptr;
+    K = k; cnt = 0; wslot = 0; worst = __int_as_float(0x7f800000); wid = 0u;
   }
+  static __device__ __forceinline__ bool before(float a, unsigned ia, float b, unsigned ib) {
+    if constexpr (IDS) return a < b || (a == b && ia < ib);
+    else return a < b;
+  }
+  __device__ __forceinline__ unsigned id_at(int s) const { if constexpr (IDS) return I[s * OL_LANES]; else return 0u; }
   __device__ __forceinline__ void rescan() {
     float w = L[0];
+    unsigned wi = id_at(0);
     int ws = 0;
-    for (int s = 1; s < K; s++) { const float v = L[s * OL_LANES]; if (v > w) { w = v; ws = s; } }
-    worst = w; wslot = ws;
+    for (int s = 1; s < K; s++) {
+      const float v = L[s * OL_LANES];
+      const unsigned vi = id_at(s);
+      if (before(w, wi, v, vi)) { w = v; wi = vi; ws = s; }
+    }
+    worst = w; wid = wi; wslot = ws;
   }
-  __device__ __forceinline__ void insert(float d2) {
+  __device__ __forceinline__ void insert(float d2, unsigned id = 0u) {
     if (cnt < K) {
       L[cnt * OL_LANES] = d2;
+      if constexpr (IDS) I[cnt * OL_LANES] = id;
       if (++cnt == K) rescan();
-    } else if (d2 < worst) {
+    } else if (before(d2, id, worst, wid)) {
       L[wslot * OL_LANES] = d2;
+      if constexpr (IDS) I[wslot * OL_LANES] = id;
       rescan();
     }
   }
-  // STATISTICAL: selection sort, ascending; s += (double)sqrtf(d2) in that order; (float)(s / mean_k).  sqrtf, correctly rounded under
+  // the entries in ascending order, by selection (the list is consumed): take(d2, id) for each
+  template <typename Take>
+  __device__ __forceinline__ void ascending(Take take) {
+    for (int m = 0; m < K; m++) {
+      float v = L[m * OL_LANES];
+      unsigned vi = id_at(m);
+      int at = m;
+      for (int t = m + 1; t < K; t++) {
+        const float u = L[t * OL_LANES];
+        const unsigned ui = id_at(t);
+        if (before(u, ui, v, vi)) { v = u; vi = ui; at = t; }
+      }
+      L[at * OL_LANES] = L[m * OL_LANES];
+      if constexpr (IDS) I[at * OL_LANES] = I[m * OL_LANES];
+      take(v, vi);
+    }
+  }
+  // STATISTICAL: s += (double)sqrtf(d2) in ascending order; (float)(s / mean_k).  sqrtf, correctly rounded under
   // the build's -fhip-fp32-correctly-rounded-divide-sqrt -- not __fsqrt_rn, which this toolchain maps to the native approximate
   // square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined (one ulp off in some terms, which reaches dist[] now and then).
   __device__ __forceinline__ float mean_distance() {
     double s = 0.0;
-    for (int m = 0; m < K; m++) {
-      float v = L[m * OL_LANES];
-      int at = m;
-      for (int t = m + 1; t < K; t++) { const float u = L[t * OL_LANES]; if (u < v) { v = u; at = t; } }
-      L[at * OL_LANES] = L[m * OL_LANES];
-      s += (double)sqrtf(v);
-    }
+    ascending([&](float v, unsigned) { s += (double)sqrtf(v); });
     return (float)(s / (double)K);
   }
   __device__ __forceinline__ bool full() const { return cnt == K; }

@@ -75,6 +75,17 @@ class OutlierStats(C.Structure):
     _fields_ = [("n_in", C.c_longlong), ("n_valid", C.c_longlong), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
 
 
+class GicpParams(C.Structure):
+    """mi355ndt_gicp_params: pclomp::GeneralizedIterativeClosestPoint's parameters (gicp_omp.h:110-120)."""
+    _fields_ = [("k_correspondences", C.c_int), ("gicp_epsilon", C.c_double), ("rotation_epsilon", C.c_double), ("transformation_epsilon", C.c_double),
+                ("max_iterations", C.c_int), ("max_inner_iterations", C.c_int), ("corr_dist_threshold", C.c_double)]
+
+
+class GicpResult(C.Structure):
+    _fields_ = [("final_colmajor", C.c_float * 16), ("converged", C.c_int), ("iterations", C.c_int), ("inner_status", C.c_int), ("n_matched", C.c_int),
+                ("delta", C.c_double)]
+
+
 class SeqParams(C.Structure):
     _fields_ = [("keyframe_delta_trans", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double)]
 
@@ -107,7 +118,11 @@ SYMBOLS = [
     "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
     "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
     "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers",
+    "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
+    "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
+    "mi355ndt_gicp_get_aligned",
 ]
+GICP_TARGET, GICP_SOURCE = 0, 1  # mi355ndt_gicp_covariances' role
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
 OPT_DEBUG_ASYNC_RINGS = 6      # mi355ndt_option (test hook): bit x clear -> ring x of a one-launch align has no workgroups of its own
@@ -157,6 +172,17 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
     L.mi355ndt_outlier_params_default.argtypes = [C.POINTER(OutlierParams)]
     L.mi355ndt_prefilter_outliers.argtypes = [vp, C.POINTER(OutlierParams), vp, vp, sz, sz, C.POINTER(sz), C.POINTER(OutlierStats)]
+    L.mi355ndt_gicp_params_default.argtypes = [C.POINTER(GicpParams)]
+    L.mi355ndt_gicp_set_params.argtypes = [vp, C.POINTER(GicpParams)]
+    L.mi355ndt_gicp_set_target.argtypes = [vp, vp, sz, sz]
+    L.mi355ndt_gicp_set_source.argtypes = [vp, vp, sz, sz]
+    L.mi355ndt_gicp_set_target_keyframe.argtypes = [vp, i]
+    L.mi355ndt_gicp_set_source_keyframe.argtypes = [vp, i]
+    L.mi355ndt_gicp_covariances.argtypes = [vp, i, vp, sz]
+    L.mi355ndt_gicp_correspondences.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i)]
+    L.mi355ndt_gicp_cost.argtypes = [vp, vp, vp, C.POINTER(C.c_double), vp]
+    L.mi355ndt_gicp_align.argtypes = [vp, vp, C.POINTER(GicpResult)]
+    L.mi355ndt_gicp_get_aligned.argtypes = [vp, vp, sz]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
@@ -239,6 +265,17 @@ def information_matrix(fitness: float, params: InfParams | None = None, **kw) ->
     return out.reshape(6, 6)
 
 
+def default_gicp_params(**kw) -> GicpParams:
+    """The constructor's values of pclomp::GeneralizedIterativeClosestPoint (gicp_omp.h:110-120), `kw` overriding fields."""
+    p = GicpParams()
+    load_library().mi355ndt_gicp_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"no GICP parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def _as_points(cloud) -> np.ndarray:
     """Accept [N,3]/[N,4+] float arrays (PCL-like records: x,y,z first); returns C-contiguous f32."""
     a = np.asarray(cloud)
@@ -271,6 +308,7 @@ class Engine:
             self.h = None
             raise NDTError(rc, "mi355ndt_create")
         self._keep = []
+        self._gicp_n = [0, 0]                       # points of the GICP surface's target and source
 
     def close(self):
         if getattr(self, "h", None):
@@ -523,6 +561,68 @@ class Engine:
                                                             pcm.ctypes.data_as(C.c_void_p), mr, scores.ctypes.data_as(C.c_void_p),
                                                             inliers.ctypes.data_as(C.c_void_p)), "keyframe_fitness_scores")
         return scores[:E], inliers[:E]
+
+    # -- GICP (pclomp::GeneralizedIterativeClosestPoint, registration_method = GICP_OMP): one pair, synchronous
+    def gicp_set_params(self, p: GicpParams):
+        self._chk(self.lib.mi355ndt_gicp_set_params(self.h, C.byref(p)), "gicp_set_params")
+
+    def _gicp_set(self, role: int, cloud=None, kid=None):
+        name = "gicp_set_target" if role == GICP_TARGET else "gicp_set_source"
+        if kid is not None:
+            fn = self.lib.mi355ndt_gicp_set_target_keyframe if role == GICP_TARGET else self.lib.mi355ndt_gicp_set_source_keyframe
+            self._chk(fn(self.h, int(kid)), name + "_keyframe")
+            n = self.keyframe_get(int(kid), fetch=False)
+        else:
+            a = _as_points(cloud)
+            fn = self.lib.mi355ndt_gicp_set_target if role == GICP_TARGET else self.lib.mi355ndt_gicp_set_source
+            self._chk(fn(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0]), name)
+            n = a.shape[0]
+        self._gicp_n[role] = int(n)
+
+    def gicp_set_target(self, cloud=None, keyframe=None):
+        """the target cloud: a host cloud, or a resident keyframe by id (its covariances stay with the keyframe)"""
+        self._gicp_set(GICP_TARGET, cloud, keyframe)
+
+    def gicp_set_source(self, cloud=None, keyframe=None):
+        self._gicp_set(GICP_SOURCE, cloud, keyframe)
+
+    def gicp_covariances(self, role: int, fetch: bool = True):
+        """computeCovariances of the target (GICP_TARGET) or source (GICP_SOURCE): [n, 3, 3] f64, zeros for a non-finite point"""
+        n = self._gicp_n[role]
+        out = np.zeros((n, 3, 3), np.float64)
+        self._chk(self.lib.mi355ndt_gicp_covariances(self.h, role, out.ctypes.data_as(C.c_void_p) if fetch else None, n), "gicp_covariances")
+        return out if fetch else None
+
+    def gicp_correspondences(self, guess, T=None):
+        """one pass of the matching loop: (idx [n_src] int32, -1 = none; M [n_src, 3, 3] f64; m)"""
+        n = self._gicp_n[GICP_SOURCE]
+        g = _colmajor(guess)
+        t = _colmajor(T) if T is not None else None
+        idx, M, m = np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float64), C.c_int(0)
+        self._chk(self.lib.mi355ndt_gicp_correspondences(self.h, g.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p) if t is not None else None,
+                                                         idx.ctypes.data_as(C.c_void_p), M.ctypes.data_as(C.c_void_p), C.byref(m)), "gicp_correspondences")
+        return idx, M, m.value
+
+    def gicp_cost(self, x, base):
+        """fdf over the resident correspondences at the state x[6] with base transformation `base`: (f, g[6])"""
+        xx = np.ascontiguousarray(x, np.float64)
+        b = _colmajor(base)
+        f, g = C.c_double(0.0), np.zeros(6, np.float64)
+        self._chk(self.lib.mi355ndt_gicp_cost(self.h, xx.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(f), g.ctypes.data_as(C.c_void_p)), "gicp_cost")
+        return f.value, g
+
+    def gicp_align(self, guess) -> dict:
+        g = _colmajor(guess)
+        r = GicpResult()
+        self._chk(self.lib.mi355ndt_gicp_align(self.h, g.ctypes.data_as(C.c_void_p), C.byref(r)), "gicp_align")
+        return dict(final=np.array(r.final_colmajor, np.float32).reshape(4, 4).T.copy(), converged=bool(r.converged), iterations=r.iterations,
+                    inner_status=r.inner_status, n_matched=r.n_matched, delta=r.delta)
+
+    def gicp_get_aligned(self) -> np.ndarray:
+        out = np.zeros((self._gicp_n[GICP_SOURCE], 3), np.float32)
+        if len(out):
+            self._chk(self.lib.mi355ndt_gicp_get_aligned(self.h, out.ctypes.data_as(C.c_void_p), 12), "gicp_get_aligned")
+        return out
 
     # -- parity hooks
     def derivatives(self, p):

@@ -520,8 +520,9 @@ int mi355ndt_batch_set_source_keyframe(mi355ndt_handle* h, int pair, int id);
  * nothing is in range or either keyframe is empty.  Points with a non-finite coordinate take no part, on either side.  scores[e] and
  * n_inliers[e] (may be NULL) are word for word what mi355ndt_fitness_score_T returns on a one-pair engine with cloud1 as target, cloud2 as
  * source and the f32-cast pose as T.  A keyframe may appear in any number of edges and on either side; ids1[e] == ids2[e] is allowed.
- * The first call that searches a keyframe builds a spatial index over it, which stays with the keyframe until it is released (about
- * 16 + 16 B per point beside the keyframe's own 12; MI355NDT_OPT_KF_FITNESS_CELL_MM); later calls find it.  n_edges == 0 is MI355NDT_OK;
+ * The first call that searches a keyframe builds a spatial index over it unless the GICP surface has (a keyframe has one index, which both
+ * surfaces search); it stays with the keyframe until it is released (at most 16 + 20 B per point beside the keyframe's own 12;
+ * MI355NDT_OPT_KF_FITNESS_CELL_MM); later calls find it.  n_edges == 0 is MI355NDT_OK;
  * an unknown or released id is MI355NDT_ERR_BAD_ARG with a message and nothing is written; MI355NDT_ERR_STATE in stream mode.  Nothing
  * crosses PCIe on the way in (cloud_uploads does not move); synchronous, one wait for the device per call.  Uses buffers of its own: the
  * batch, grids, prefilter result, map-cloud and window workspaces of the handle are left as they were. */
@@ -557,13 +558,14 @@ int  mi355ndt_information_matrix(const mi355ndt_inf_params* p, double fitness_sc
  * max_inner_iterations 20.  use_reciprocal_correspondences (false there) is not served.
  * Clouds: host records (x, y, z f32 first, stride_bytes apart) or resident keyframes by id.  A cloud's covariances are computed on first
  * use and kept until the cloud, k_correspondences or gicp_epsilon changes, as PCL keeps target_covariances_; a keyframe's stay with the
- * keyframe (beside an index of their own: about 12 + 4 + 72 B per point) until mi355ndt_keyframe_release, so the new keyframe of a loop
- * check is decomposed once for all its candidates.  A released id is refused (MI355NDT_ERR_BAD_ARG) by the next call that needs the cloud.
+ * keyframe (72 B per point, beside the keyframe's one spatial index -- the one mi355ndt_keyframe_fitness_scores searches, built here if
+ * that call has not built it; measured on a 65,536-point keyframe both surfaces have used: 128 B per point beside the rows) until
+ * mi355ndt_keyframe_release, so the new keyframe of a loop check is decomposed once for all its candidates.  A released id is refused (MI355NDT_ERR_BAD_ARG) by the next call that needs the cloud.
  * Errors: MI355NDT_ERR_STATE in stream mode, and from the calls that need a cloud (or correspondences) that was not set (computed);
  * MI355NDT_ERR_BAD_ARG with a mi355ndt_last_error text for k_correspondences outside 1..64 or above the number of searchable points (three
  * finite coordinates) of a cloud -- the reference prints an error and reads unsized storage --, a NaN or negative epsilon or threshold,
- * negative iteration counts.  The batch, the grids, the keyframes' rows and fitness indexes, the prefilter result and the other workspaces
- * of the handle are left as they were.
+ * negative iteration counts.  The batch, the grids, the keyframes' rows, the prefilter result and the other workspaces of the handle are left as they
+ * were; fitness indexes are left as they were or built as the fitness surface would build them.
  *   role: MI355NDT_GICP_TARGET / MI355NDT_GICP_SOURCE.
  *   mi355ndt_gicp_covariances: n records of nine f64 (row-major 3x3), input order, zeros for a non-finite point; out may be NULL
  *     (compute and keep only); a count above capacity is MI355NDT_ERR_BAD_ARG.

@@ -48,8 +48,8 @@ struct StreamState {
 };
 
 // ---- scratch of the sort-and-compact chain: stage clouds -> extremes -> grid -> keys -> one-segment radix sort -> run heads -> exclusive
-// scan -> emit -> count.  The prefilter, its outlier removal, the map cloud (both routes), the window map and the keyframe index builds of
-// mi355ndt_keyframe_fitness_scores share this one instance; results (d_pf_out, the keyframe store and its indexes) are not in it.
+// scan -> emit -> count.  The prefilter, its outlier removal, the map cloud (both routes), the window map and the cloud index builds
+// (kfi_build_rows: the keyframe fitness scores, GICP) share this one instance; results (d_pf_out, the keyframe store, the indexes) are not in it.
 // Sharing is safe because
 //   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;
 //   * every user waits for the stream before it returns, except mi355ndt_window_keyframe, whose trailing k_kf_emit still reads x, keys, vals,
@@ -66,7 +66,7 @@ struct VoxelScratch {
   DevBuf<unsigned> hist, offs, tmp;               // radix sort tile histograms / offsets, scan chunk totals
   DevBuf<int> flag, pos;                          // run heads, their exclusive scan.  pos grows last: its capacity vouches for every per-point member
   DevBuf<int> mm, cnt, aabb, stat;                // six extreme words (k_minmax / k_kfi_begin take them as unsigned), a point count, the map
-                                                  // cloud's per-chunk boxes, the index builds' status words
+                                                  // cloud's per-chunk boxes, the index builds' status and count words
   DevBuf<PfGrid> grid; DevBuf<McBox> box;
   DevBuf<unsigned char> tab; PinBuf<unsigned char> h_tab;   // per-call tables (scan / keyframe table + poses; edges + item tables) and their pinned twin
   DevBuf<double> part; PinBuf<double> h_part;     // block partials of the keyframe fitness kernels
@@ -74,19 +74,25 @@ struct VoxelScratch {
   bool pending = false;                           // a copy out of h_tab is enqueued and the stream has not been waited for since
 };
 
-// ---- GICP (mi355ndt_gicp_*, ndt_gicp.hpp / ndt_host_gicp.hpp): what the surface keeps per cloud -- a spatial index of its own (the keyframe
-// index's layout, ndt_host_kffitness.hpp, plus the point ids in cell order, which the (d2, id) tie rules need) and the nine f64 covariance
-// rows -- keyed by the (k_correspondences, gicp_epsilon) the covariances were computed with.  A host cloud's lives with the surface's side, a
-// keyframe's with the keyframe (released with it).
+// ---- the spatial index of one resident cloud (ndt_kffitness.hpp: lattice, occupancy words, run starts, the points and their ids in cell
+// order -- one block), built by kfi_build_rows (ndt_host_kffitness.hpp) for whichever surface searches the cloud first.  status: NO_INDEX,
+// else the lattice's GRID_* status; n_fin: the cloud's searchable points -- both as the host learned them at the end of the call that built it.
+struct CloudIndex {
+  static constexpr int NO_INDEX = -1;
+  DevBuf<unsigned char> blob; int status = NO_INDEX; int n_fin = 0;
+};
+
+// ---- GICP (mi355ndt_gicp_*, ndt_gicp.hpp / ndt_host_gicp.hpp): what the surface keeps per cloud beside its index -- the nine f64 covariance
+// rows, keyed by the (k_correspondences, gicp_epsilon) they were computed with.  A host cloud's live with the surface's side, a keyframe's
+// with the keyframe (released with it).
 struct GicpCache {
-  DevBuf<unsigned char> index; DevBuf<unsigned> ids; DevBuf<double> cov;
-  int status = -1, n_fin = 0;                     // the lattice's GRID_* status (-1: no index yet), searchable points
+  DevBuf<double> cov;
   int k = -1; double eps = 0.0;                   // what cov holds (k < 0: nothing)
 };
 struct GicpSide {
   DevBuf<float> rows_own; size_t n = 0, pitch = 0; // a host cloud's rows ([3][pitch], the tail zeroed)
-  int kf_id = -1; bool set = false;               // kf_id >= 0: the rows and the cache are the keyframe's
-  GicpCache cache;                                // a host cloud's
+  int kf_id = -1; bool set = false;               // kf_id >= 0: the rows, the index and the cache are the keyframe's
+  CloudIndex index; GicpCache cache;              // a host cloud's
 };
 
 struct mi355ndt_handle {
@@ -135,20 +141,18 @@ struct mi355ndt_handle {
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
   // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)
   DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0;
-  // outlier removal over it (mi355ndt_prefilter_outliers): the index block rebuilt by every call, dist[] and its pinned twin
-  DevBuf<unsigned char> d_ol_index; DevBuf<float> d_ol_dist; PinBuf<float> h_ol_dist;
+  // outlier removal over it (mi355ndt_prefilter_outliers): the index rebuilt by every call, dist[] and its pinned twin
+  CloudIndex ol_index; DevBuf<float> d_ol_dist; PinBuf<float> h_ol_dist;
   int ol_cell_mm = 100;                           // MI355NDT_OPT_OUTLIER_CELL_MM
   VoxelScratch vs;                                // scratch of the prefilter, the map cloud, the window map and the keyframe index builds
   // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
   // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice
-  // ... and, once it has been the searched side of mi355ndt_keyframe_fitness_scores, its spatial index (ndt_kffitness.hpp: lattice, occupancy
-  // words, run starts, the points in cell order -- one block), kept until the keyframe is released.  index_status: NO_INDEX, else the
-  // lattice's GRID_* status as the host learned it at the end of the call that built the index.
+  // ... and, once it has been the searched side of mi355ndt_keyframe_fitness_scores or a cloud of the GICP surface, its one spatial index,
+  // kept until the keyframe is released.
   struct Keyframe {
-    static constexpr int NO_INDEX = -1;
     DevBuf<float> rows; size_t n = 0, pitch = 0; int ch = 3;
-    DevBuf<unsigned char> index; int index_status = NO_INDEX;
-    std::unique_ptr<GicpCache> gicp;              // the GICP surface's index and covariances over this keyframe, once it has been one of its clouds
+    CloudIndex index;
+    GicpCache gicp;                               // the GICP surface's covariances over this keyframe, once it has been one of its clouds
   };
   std::map<int, Keyframe> keyframes;
   int kf_next_id = 0;

@@ -15,7 +15,8 @@
 //   fit_rings         the exact 1-NN over an occupied-cell index: cells are visited ring by ring around the query's cell and the search stops
 //                     once the best distance cannot be beaten by an unvisited ring (fit_ring_max: the rings that cover sqrt(max_range))
 //   fit_ring_block    one 256-point block of queries through fit_rings; the two index layouts differ in the point accessor only
-//   fitness_brute_block   the same block by exhaustive search, for a target without a grid
+//   fit_tiles         the exhaustive walk over a cloud without a lattice, through LDS tiles (also ndt_outlier.hpp, ndt_gicp.hpp)
+//   fitness_brute_block   one 256-point block of queries through fit_tiles, for a target without a grid
 //   fit_block_score   the `best <= max_range` tail and the deterministic block reduction every block ends with
 // so a pair's block partials are the same words whichever surface made them.
 
@@ -64,32 +65,43 @@ __host__ __device__ inline int fit_ring_max(double max_range, float leaf) {
   return rr > (double)(1 << 30) ? (1 << 30) : (int)rr;
 }
 
-// The score for a target that has no voxel grid (the leaf-too-small guard or the engine's cell cap: GRID_OVERFLOW / GRID_CAP) --
-// pcl::Registration::getFitnessScore searches a kd-tree over the target CLOUD and does not care.  Exhaustive search, the target
-// staged through LDS 256 points at a time.
-// (block `blk` of one pair: source points blk * 256 .. blk * 256 + 255)
+// The exhaustive walk over a cloud that has no lattice to search (GRID_OVERFLOW, GRID_CAP: a stray point at 1e12 m): the rows staged through
+// LDS 256 points at a time, visit(x, y, z, id) for every finite point (a non-finite one is in no tree), id = its input position.  The WHOLE
+// workgroup of BLOCK threads calls it (256, or one wave: OL_LANES); a lane without a live query masks itself inside `visit`.
+template <int BLOCK, typename Visit>
+__device__ __forceinline__ void fit_tiles(const float* __restrict__ rows, size_t pitch, int n, Visit visit) {
+  __shared__ float tx[256], ty[256], tz[256];
+  constexpr int U = 256 / BLOCK;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    float x[U], y[U], z[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int j = j0 + u * BLOCK + (int)threadIdx.x;
+      x[u] = y[u] = z[u] = __int_as_float(0x7fc00000);                             // past the end: NaN, skipped below
+      if (j < n) { x[u] = rows[j]; y[u] = rows[pitch + j]; z[u] = rows[2 * pitch + j]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < U; u++) { const int k = u * BLOCK + (int)threadIdx.x; tx[k] = x[u]; ty[k] = y[u]; tz[k] = z[u]; }
+    __syncthreads();
+    for (int k = 0; k < 256; k++)
+      if (finite3(tx[k], ty[k], tz[k])) visit(tx[k], ty[k], tz[k], (unsigned)(j0 + k));
+  }
+}
+
+// The score for a target that has no voxel grid -- pcl::Registration::getFitnessScore searches a kd-tree over the target CLOUD and does not
+// care.  (block `blk` of one pair: source points blk * 256 .. blk * 256 + 255)
 __device__ __forceinline__ void fitness_brute_block(const float* __restrict__ src, size_t spitch, int n_src,
                                                     const float* __restrict__ tgt, size_t tpitch, int n_tgt,
                                                     const float* __restrict__ Tcm, float max_range, int blk, double* out) {
-  __shared__ float tx[256], ty[256], tz[256];
   float q[3];
   const bool live = fit_query(src, spitch, n_src, blk * 256 + threadIdx.x, Tcm, q);
   float best = __int_as_float(0x7f800000);
-  for (int j0 = 0; j0 < n_tgt; j0 += 256) {
-    const int j = j0 + threadIdx.x;
-    float x = __int_as_float(0x7fc00000), y = x, z = x;                            // past the end: NaN, skipped below
-    if (j < n_tgt) { x = tgt[j]; y = tgt[tpitch + j]; z = tgt[2 * tpitch + j]; }
-    __syncthreads();
-    tx[threadIdx.x] = x; ty[threadIdx.x] = y; tz[threadIdx.x] = z;
-    __syncthreads();
-    if (live) {
-      for (int k = 0; k < 256; k++) {
-        if (!finite3(tx[k], ty[k], tz[k])) continue;                                // non-finite target points are in no tree
-        const float d2 = fit_d2(q, tx[k], ty[k], tz[k]);
-        best = d2 < best ? d2 : best;
-      }
-    }
-  }
+  fit_tiles<256>(tgt, tpitch, n_tgt, [&](float x, float y, float z, unsigned) {
+    if (!live) return;
+    const float d2 = fit_d2(q, x, y, z);
+    best = d2 < best ? d2 : best;
+  });
   fit_block_score(live, best, max_range, out);
 }
 
@@ -196,7 +208,7 @@ __device__ __forceinline__ bool fit_item(const FitItem* __restrict__ items, cons
 
 // The ring walk over an occupied-cell index: the query's cell, the rings r_first .. r_last around it, the stopping rule.  visit(j0, j1)
 // takes the sorted positions j0 .. j1 - 1 of one row's (or one cell's) points and lowers `best`, the squared distance of the nearest point
-// so far, which the walk reads to stop.  Shared by fit_ring_block (k_fitness_batch, k_kf_fitness) and k_ol_knn (ndt_outlier.hpp).
+// so far, which the walk reads to stop.  Shared by fit_ring_block (k_fitness_batch, k_kf_fitness), knn_fill (ndt_outlier.hpp) and k_gc_match (ndt_gicp.hpp).
 // The query's cell is taken relative to the grid and clamped to +-2^29 cells: a query further out than that (a stray source point at
 // 1e12 m) still sees every target cell in rings r_first .. r_first + extent, and (r - 1) * leaf stays a lower bound of its distances.
 // r_first = the distance from the query's cell to the grid box in cells (0 inside): rings closer than that are empty.  Every point in

@@ -9,10 +9,10 @@
 //    the reference runs Eigen::JacobiSVD); with c0, c1, c2 the eigenvectors by descending eigenvalue (equal ones in column order),
 //    cov(r,c) = (c0[r]*c0[c] + c1[r]*c1[c]) + (eps*c2[r])*c2[c].  Nine f64 per point, SoA: cov[e * pitch + id], e = 3 r + c.  A non-finite
 //    point keeps the zeros the host wrote.
-//    The search is the outlier stage's (ndt_outlier.hpp): OlList with its id column, [slot][lane] in LDS, one wave per workgroup, queries in
-//    cell order over the keyframe lattice (fit_rings with the list's worst entry as `best`: every point of an unvisited ring is strictly
-//    further than that, so no tie is lost), or exhaustive over LDS tiles for a cloud whose lattice gave GRID_CAP.  One kernel, the path
-//    taken by the lattice's status.  LDS per workgroup: CAP * 64 * 8 B of list + 3 KB of tile = 19 KB (CAP 32) / 35 KB (CAP 64).
+//    The search is the outlier stage's (knn_fill, ndt_outlier.hpp): OlList with its id column, [slot][lane] in LDS, one wave per workgroup,
+//    queries in cell order over the cloud's lattice (fit_rings with the list's worst entry as `best`: every point of an unvisited ring is
+//    strictly further than that, so no tie is lost), or exhaustive over LDS tiles for a cloud whose lattice gave GRID_CAP.  One kernel, the
+//    path taken by the lattice's status.  LDS per workgroup: CAP * 64 * 8 B of list + 3 KB of tile = 19 KB (CAP 32) / 35 KB (CAP 64).
 // 2. k_gc_match -- the correspondence loop (:415-466).  Source point i, in input order: q = T (G p), two f32 products, each coordinate
 //    ((a*x + b*y) + c*z) + d (w = 1); exact 1-NN over the target's index, a tie to the lower point id; matched iff (double)d2 < threshold^2;
 //    M_i = (R C1_i R' + C2_j)^-1 in f64, R = the 3x3 block of the f64 product T G (the host forms it, k ascending), in this order:
@@ -41,51 +41,17 @@
 
 // ---- 1. covariances ------------------------------------------------------------------------------------------
 template <int CAP>
-__global__ void __launch_bounds__(OL_LANES) k_gc_cov(const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const unsigned* __restrict__ runs,
-                                                     const float* __restrict__ X, const unsigned* __restrict__ ids, const float* __restrict__ rows,
-                                                     size_t pitch, int n, int nf, int K, double eps, double* __restrict__ cov) {
+__global__ void __launch_bounds__(OL_LANES) k_gc_cov(KfiView v, int K, double eps, double* __restrict__ cov) {
   __shared__ float lst[CAP][OL_LANES];
   __shared__ unsigned lid[CAP][OL_LANES];
-  __shared__ float tx[256], ty[256], tz[256];
-  const GridDesc& g = *gd;
+  const float* rows = v.rows;
+  const size_t pitch = v.pitch;
   OlList<CAP, true> list;
   list.init(lst, K, lid);
   const unsigned j = blockIdx.x * OL_LANES + threadIdx.x;
-  unsigned id = j;
-  bool live = false;
-  float q[3] = {0.f, 0.f, 0.f};
-  if (g.status == GRID_OK) {                       // queries in cell order: sorted position j, point id ids[j] (a lattice bins every searchable point)
-    live = j < (unsigned)nf;
-    if (live) {
-      q[0] = X[j]; q[1] = X[pitch + j]; q[2] = X[2 * pitch + j];
-      id = ids[j];
-      fit_rings(q, g, words, runs, 1 << 30, __int_as_float(0x7f800000), list.worst, [&](unsigned j0, unsigned j1) {
-        for (unsigned t = j0; t < j1; t++) list.insert(fit_d2(q, X[t], X[pitch + t], X[2 * pitch + t]), ids[t]);
-      });
-    }
-  } else {                                         // no lattice: queries in input order, the rows staged through LDS 256 points at a time
-    if (j < (unsigned)n) {
-      q[0] = rows[j]; q[1] = rows[pitch + j]; q[2] = rows[2 * pitch + j];
-      live = finite3(q[0], q[1], q[2]);
-    }
-    for (int j0 = 0; j0 < n; j0 += 256) {
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < 256 / OL_LANES; u++) {
-        const int k = u * OL_LANES + threadIdx.x, t = j0 + k;
-        float x = __int_as_float(0x7fc00000), y = x, z = x;                        // past the end: NaN, skipped below
-        if (t < n) { x = rows[t]; y = rows[pitch + t]; z = rows[2 * pitch + t]; }
-        tx[k] = x; ty[k] = y; tz[k] = z;
-      }
-      __syncthreads();
-      if (live) {
-        for (int k = 0; k < 256; k++) {
-          if (!finite3(tx[k], ty[k], tz[k])) continue;                             // non-finite points are in no tree
-          list.insert(fit_d2(q, tx[k], ty[k], tz[k]), (unsigned)(j0 + k));
-        }
-      }
-    }
-  }
+  const float inf = __int_as_float(0x7f800000);
+  unsigned id;
+  const bool live = v.gd->status == GRID_OK ? knn_fill<true, false>(v, j, inf, list, id) : knn_fill<false, false>(v, j, inf, list, id);
   if (!live || !list.full()) return;
   double mean[3] = {0.0, 0.0, 0.0}, c00 = 0.0, c10 = 0.0, c11 = 0.0, c20 = 0.0, c21 = 0.0, c22 = 0.0;
   list.ascending([&](float, unsigned t) {
@@ -135,14 +101,11 @@ __device__ __forceinline__ void gc_nearer(float d2, unsigned id, float& best, un
   if (d2 < best || (d2 == best && id < bid)) { best = d2; bid = id; }
 }
 
-__global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src, size_t spitch, int n_src,
-                                                  const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const unsigned* __restrict__ runs,
-                                                  const float* __restrict__ X, const unsigned* __restrict__ ids,
-                                                  const float* __restrict__ tgt, size_t tpitch, int n_tgt, GcMatch a,
+__global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src, size_t spitch, int n_src, KfiView tgt, GcMatch a,
                                                   const double* __restrict__ c1, const double* __restrict__ c2,
                                                   int* __restrict__ idx, double* __restrict__ maha, int* m) {
-  __shared__ float tx[256], ty[256], tz[256];
-  const GridDesc& g = *gd;
+  const GridDesc& g = *tgt.gd;
+  const size_t tpitch = tgt.pitch;
   const int i = blockIdx.x * 256 + threadIdx.x;
   float q[3] = {0.f, 0.f, 0.f};
   bool live = false;
@@ -158,25 +121,16 @@ __global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src,
   float best = __int_as_float(0x7f800000);
   unsigned bid = 0xFFFFFFFFu;
   if (g.status == GRID_OK) {
+    const float* X = tgt.sorted;
+    const unsigned* ids = tgt.ids;
     if (live)
-      fit_rings(q, g, words, runs, 1 << 30, a.range, best, [&](unsigned j0, unsigned j1) {
+      fit_rings(q, g, tgt.words, tgt.runs, 1 << 30, a.range, best, [&](unsigned j0, unsigned j1) {
         for (unsigned t = j0; t < j1; t++) gc_nearer(fit_d2(q, X[t], X[tpitch + t], X[2 * tpitch + t]), ids[t], best, bid);
       });
-  } else if (g.status == GRID_CAP) {               // no lattice: exhaustive, the target staged through LDS (a target without a finite point: nothing)
-    for (int j0 = 0; j0 < n_tgt; j0 += 256) {
-      const int t = j0 + threadIdx.x;
-      float x = __int_as_float(0x7fc00000), y = x, z = x;
-      if (t < n_tgt) { x = tgt[t]; y = tgt[tpitch + t]; z = tgt[2 * tpitch + t]; }
-      __syncthreads();
-      tx[threadIdx.x] = x; ty[threadIdx.x] = y; tz[threadIdx.x] = z;
-      __syncthreads();
-      if (live) {
-        for (int k = 0; k < 256; k++) {
-          if (!finite3(tx[k], ty[k], tz[k])) continue;
-          gc_nearer(fit_d2(q, tx[k], ty[k], tz[k]), (unsigned)(j0 + k), best, bid);
-        }
-      }
-    }
+  } else if (g.status == GRID_CAP) {               // no lattice: exhaustive (a target without a finite point: nothing)
+    fit_tiles<256>(tgt.rows, tpitch, tgt.n, [&](float x, float y, float z, unsigned t) {
+      if (live) gc_nearer(fit_d2(q, x, y, z), t, best, bid);
+    });
   }
   const bool matched = live && bid != 0xFFFFFFFFu && (double)best < a.thr2;
   const unsigned long long b = __ballot(matched);

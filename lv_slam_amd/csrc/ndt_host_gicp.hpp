@@ -1,9 +1,10 @@
 // ndt_host_gicp.hpp -- mi355ndt_gicp_*: pclomp::GeneralizedIterativeClosestPoint for one pair, synchronously (kernels: ndt_gicp.hpp; the
 // optimiser: gicp_bfgs.hpp).  The host holds what the reference's object holds between calls -- the parameters, the two clouds, their
 // covariances -- runs the outer loop of computeTransformation (gicp_omp_impl.hpp:380-515) and the BFGS driver of
-// estimateRigidTransformationBFGS (:189-252), and reads one mapped record per evaluation of the cost.  A cloud's index and covariances are
-// built on first use (GicpCache, ndt_engine.hpp); the index build's sort uses the shared scratch (h->vs).  The batch, the grids, the keyframes'
-// rows and fitness indexes, the prefilter result and the other workspaces are left as they were.
+// estimateRigidTransformationBFGS (:189-252), and reads one mapped record per evaluation of the cost.  A cloud's index (CloudIndex: a
+// keyframe's is the one the fitness scores search, built here if they have not built it) and covariances (GicpCache) are made on first use;
+// the index build's sort uses the shared scratch (h->vs).  The batch, the grids, the keyframes' rows, the prefilter result and the other
+// workspaces are left as they were.
 #pragma once
 
 int mi355ndt_gicp_params_default(mi355ndt_gicp_params* p) {
@@ -37,7 +38,7 @@ static int gicp_set_host(mi355ndt_handle* h, int role, const void* pts, size_t n
   GicpSide& sd = h->gicp.side[role];
   sd.set = false; sd.kf_id = -1;
   sd.n = n; sd.pitch = (n + 63) & ~(size_t)63;
-  sd.cache.status = -1; sd.cache.k = -1;
+  sd.index.status = CloudIndex::NO_INDEX; sd.cache.k = -1;
   h->gicp.have_corr = false;
   if (sd.pitch) {
     HIPCHK(h, sd.rows_own.reserve(3 * sd.pitch));
@@ -68,36 +69,27 @@ int mi355ndt_gicp_set_source(mi355ndt_handle* h, const void* pts, size_t n, size
 int mi355ndt_gicp_set_target_keyframe(mi355ndt_handle* h, int id) { return gicp_set_keyframe(h, MI355NDT_GICP_TARGET, id); }
 int mi355ndt_gicp_set_source_keyframe(mi355ndt_handle* h, int id) { return gicp_set_keyframe(h, MI355NDT_GICP_SOURCE, id); }
 
-// a side as the kernels take it: the rows and the cache, the surface's own or the keyframe's
-struct GicpView { const float* rows; size_t n, pitch; GicpCache* cache; };
+// a side as the host takes it: the rows, the index and the cache, the surface's own or the keyframe's
+struct GicpView { const float* rows; size_t n, pitch; CloudIndex* index; GicpCache* cache; };
 static int gicp_view(mi355ndt_handle* h, int role, const char* where, GicpView* v) {
   GicpSide& sd = h->gicp.side[role];
   if (!sd.set) { h->err = std::string(where) + (role == MI355NDT_GICP_TARGET ? ": no target cloud is set" : ": no source cloud is set"); return MI355NDT_ERR_STATE; }
-  if (sd.kf_id < 0) { *v = GicpView{sd.rows_own, sd.n, sd.pitch, &sd.cache}; return MI355NDT_OK; }
+  if (sd.kf_id < 0) { *v = GicpView{sd.rows_own, sd.n, sd.pitch, &sd.index, &sd.cache}; return MI355NDT_OK; }
   mi355ndt_handle::Keyframe* kf = kf_find(h, sd.kf_id, where);
   if (!kf) return MI355NDT_ERR_BAD_ARG;
-  if (!kf->gicp) kf->gicp.reset(new GicpCache);
-  *v = GicpView{kf->rows, kf->n, kf->pitch, kf->gicp.get()};
+  *v = GicpView{kf->rows, kf->n, kf->pitch, &kf->index, &kf->gicp};
   return MI355NDT_OK;
-}
-
-template <int CAP>
-static void gicp_cov_launch(hipStream_t s, const GicpView& v, const KfiLayout& L, int K, double eps) {
-  const unsigned char* blob = v.cache->index;
-  k_gc_cov<CAP><<<(unsigned)((v.n + OL_LANES - 1) / OL_LANES), OL_LANES, 0, s>>>(
-      reinterpret_cast<const GridDesc*>(blob), reinterpret_cast<const BitWord*>(blob + L.words), reinterpret_cast<const unsigned*>(blob + L.runs),
-      reinterpret_cast<const float*>(blob + L.sorted), v.cache->ids, v.rows, v.pitch, (int)v.n, v.cache->n_fin, K, eps, v.cache->cov);
 }
 
 // the side's index (first use of the cloud) and its covariances for the current (k_correspondences, gicp_epsilon); waits for the device
 static int gicp_prepare(mi355ndt_handle* h, const char* where, const GicpView& v) {
+  CloudIndex& ix = *v.index;
   GicpCache& c = *v.cache;
   const int K = h->gicp.prm.k_correspondences;
   const double eps = h->gicp.prm.gicp_epsilon;
   hipStream_t s = h->stream;
   if (v.n == 0) { h->err = std::string(where) + ": k_correspondences exceeds the cloud's searchable points (an empty cloud)"; return MI355NDT_ERR_BAD_ARG; }
-  const KfiLayout L = kfi_layout(v.pitch);
-  if (c.status < 0) {
+  if (ix.status == CloudIndex::NO_INDEX) {
     int rc = uploads_before_compute(h);           // (a keyframe_add's transfer may still be on its way)
     if (rc) return rc;
     VsNeed need;
@@ -105,30 +97,26 @@ static int gicp_prepare(mi355ndt_handle* h, const char* where, const GicpView& v
     rc = vs_reserve(h, need);
     if (rc) return rc;
     VoxelScratch& w = h->vs;
-    HIPCHK(h, c.index.realloc_exact(L.bytes));
-    HIPCHK(h, c.ids.realloc_exact(v.pitch));
     c.k = -1;
-    HIPCHK(h, hipMemsetAsync(w.stat, 0, 2 * sizeof(int), s));
-    k_ol_finite<<<(unsigned)((v.n + 255) / 256), 256, 0, s>>>(v.rows, v.pitch, (int)v.n, w.stat + 1, nullptr);
-    const unsigned* ids = nullptr;
-    rc = kfi_build_rows(h, v.rows, v.pitch, v.n, h->kff_cell_mm, c.index, 0, &ids);
+    rc = kfi_build_rows(h, v.rows, v.pitch, v.n, h->kff_cell_mm, ix, 0);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(c.ids, ids, v.pitch * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(w.h_ret, w.stat, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     w.pending = false;
     HIPCHK(h, hipGetLastError());
-    c.status = w.h_ret[0]; c.n_fin = w.h_ret[1];
+    kfi_built(ix, w.h_ret, 0);
   }
   if (c.k != K || c.eps != eps) {
-    if (K > c.n_fin) {
-      h->err = std::string(where) + ": k_correspondences (" + std::to_string(K) + ") exceeds the cloud's searchable points (" + std::to_string(c.n_fin) + ")";
+    if (K > ix.n_fin) {
+      h->err = std::string(where) + ": k_correspondences (" + std::to_string(K) + ") exceeds the cloud's searchable points (" + std::to_string(ix.n_fin) + ")";
       return MI355NDT_ERR_BAD_ARG;
     }
     c.k = -1;
     HIPCHK(h, c.cov.reserve(9 * v.pitch));
     HIPCHK(h, hipMemsetAsync(c.cov, 0, 9 * v.pitch * sizeof(double), s));
-    if (K <= 32) gicp_cov_launch<32>(s, v, L, K, eps); else gicp_cov_launch<64>(s, v, L, K, eps);
+    const KfiView view = kfi_view(ix, v.rows, v.pitch, v.n);
+    const unsigned blocks = (unsigned)((v.n + OL_LANES - 1) / OL_LANES);
+    if (K <= 32) k_gc_cov<32><<<blocks, OL_LANES, 0, s>>>(view, K, eps, c.cov); else k_gc_cov<64><<<blocks, OL_LANES, 0, s>>>(view, K, eps, c.cov);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(s));
     c.k = K; c.eps = eps;
@@ -220,12 +208,9 @@ static int gicp_match(mi355ndt_handle* h, const char* where, const float* G, con
     }
   a.thr2 = gc.prm.corr_dist_threshold * gc.prm.corr_dist_threshold;
   a.range = (float)a.thr2 * 1.0001f + 1e-30f;     // (f32, above thr2: what lies further cannot match)
-  const KfiLayout L = kfi_layout(D.pitch);
-  const unsigned char* blob = D.cache->index;
   HIPCHK(h, hipMemsetAsync(gc.m, 0, sizeof(int), s));
-  k_gc_match<<<(unsigned)((S.n + 255) / 256), 256, 0, s>>>(S.rows, S.pitch, (int)S.n, reinterpret_cast<const GridDesc*>(blob),
-      reinterpret_cast<const BitWord*>(blob + L.words), reinterpret_cast<const unsigned*>(blob + L.runs), reinterpret_cast<const float*>(blob + L.sorted),
-      D.cache->ids, D.rows, D.pitch, (int)D.n, a, S.cache->cov, D.cache->cov, gc.idx, gc.maha, gc.m);
+  k_gc_match<<<(unsigned)((S.n + 255) / 256), 256, 0, s>>>(S.rows, S.pitch, (int)S.n, kfi_view(*D.index, D.rows, D.pitch, D.n), a,
+                                                           S.cache->cov, D.cache->cov, gc.idx, gc.maha, gc.m);
   HIPCHK(h, hipGetLastError());
   int m = 0;
   HIPCHK(h, hipMemcpyAsync(&m, gc.m, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -1,67 +1,73 @@
 // ndt_host_kffitness.hpp -- mi355ndt_keyframe_fitness_scores (graph edges between resident keyframes, ndt_kffitness.hpp) and the host
-// arithmetic of InformationMatrixCalculator::calc_information_matrix (mi355ndt_information_matrix).  The batch, the grids, the prefilter result
-// and the keyframes' rows are left as they were; the index builds' sort and the call's tables use the shared scratch (h->vs).
+// arithmetic of InformationMatrixCalculator::calc_information_matrix (mi355ndt_information_matrix), and the build of a cloud's index, which
+// the outlier removal and GICP call too.  The batch, the grids, the prefilter result, the keyframes' rows and the indexes that exist are left
+// as they were; the index builds' sort and the call's tables use the shared scratch (h->vs).
 #pragma once
 
-// ---- a keyframe's spatial index ----------------------------------------------------------------------
-// one block: GridDesc (128 B) | BitWord words[nw] | unsigned runs[pitch + 1] (to 16 B) | float sorted[3][pitch]
-struct KfiLayout { size_t words, runs, sorted, bytes; int max_cells; };
+// ---- a cloud's spatial index -------------------------------------------------------------------------
+// one block: KfiHead (128 B) | BitWord words[nw] | unsigned runs[pitch + 1] (to 16 B) | float sorted[3][pitch] | unsigned ids[pitch]
+struct KfiLayout { size_t words, runs, sorted, ids, bytes; int max_cells; };
 static KfiLayout kfi_layout(size_t pitch) {
   KfiLayout L;
   L.max_cells = (int)std::min((size_t)KFI_MAX_CELLS, std::max((size_t)4096, 64 * pitch));   // at most 16 B of bitmap per point
   const size_t nw = (size_t)L.max_cells / 64 + 2;
-  static_assert(sizeof(GridDesc) <= 128, "the index block's header");
   L.words = 128;
   L.runs = L.words + nw * sizeof(BitWord);
   L.sorted = L.runs + (((pitch + 1) * sizeof(unsigned) + 15) & ~(size_t)15);
-  L.bytes = L.sorted + 3 * pitch * sizeof(float);
+  L.ids = L.sorted + 3 * pitch * sizeof(float);
+  L.bytes = L.ids + pitch * sizeof(unsigned);
   return L;
 }
 
-// enqueue the build of an index over `n` points of SoA rows (n > 0) into `blob` (kfi_layout(pitch).bytes, the caller's), the lattice starting
-// from cells of `cell_mm`; the status lands in vs.stat[slot], the point ids in cell order in *ids (scratch: valid until the scratch is used
-// again).  The scratch is sized by the caller.  Shared by the keyframe indexes and the outlier removal (ndt_host_outlier.hpp).
-static int kfi_build_rows(mi355ndt_handle* h, const float* rows, size_t pitch, size_t n, int cell_mm, unsigned char* blob, int slot,
-                          const unsigned** ids = nullptr) {
+// the index of a cloud as the kernels take it, with the cloud's own rows ([3][pitch], n points)
+static KfiView kfi_view(const CloudIndex& ix, const float* rows, size_t pitch, size_t n) {
+  const KfiLayout L = kfi_layout(pitch);
+  const unsigned char* blob = ix.blob;
+  return KfiView{reinterpret_cast<const GridDesc*>(blob), reinterpret_cast<const BitWord*>(blob + L.words), reinterpret_cast<const unsigned*>(blob + L.runs),
+                 reinterpret_cast<const float*>(blob + L.sorted), reinterpret_cast<const unsigned*>(blob + L.ids), rows, (unsigned)pitch, (int)n};
+}
+
+// enqueue the build of `ix` over `n` points of SoA rows (n > 0), the lattice starting from cells of `cell_mm`; the lattice's status and the
+// cloud's searchable points land in vs.stat[2 * slot] and [2 * slot + 1]: the caller fetches them with its results and hands them to
+// kfi_built.  The scratch is sized by the caller (pitch; two status words per slot).  Every surface's index is built here.
+static int kfi_build_rows(mi355ndt_handle* h, const float* rows, size_t pitch, size_t n, int cell_mm, CloudIndex& ix, int slot) {
   hipStream_t s = h->stream;
   const KfiLayout L = kfi_layout(pitch);
-  GridDesc* gd = reinterpret_cast<GridDesc*>(blob);
+  ix.status = CloudIndex::NO_INDEX;
+  HIPCHK(h, ix.blob.reserve(L.bytes));
+  unsigned char* blob = ix.blob;
+  KfiHead* head = reinterpret_cast<KfiHead*>(blob);
+  GridDesc* gd = &head->gd;
   BitWord* words = reinterpret_cast<BitWord*>(blob + L.words);
   unsigned* runs = reinterpret_cast<unsigned*>(blob + L.runs);
-  float* sorted = reinterpret_cast<float*>(blob + L.sorted);
-  HIPCHK(h, hipMemsetAsync(blob, 0, L.runs, s));   // header and bitmap (k_fit_mark ORs into it)
+  HIPCHK(h, hipMemsetAsync(blob, 0, L.runs, s));   // header and bitmap (k_kfi_gather adds into the one, k_fit_mark ORs into the other)
   const int gx = (int)((pitch + 255) / 256);
   const int cb = KFI_CELL_BITS;
   VoxelScratch& w = h->vs;
   unsigned* mm = reinterpret_cast<unsigned*>(w.mm.p);
   k_kfi_begin<<<1, 64, 0, s>>>(mm, w.cnt, (int)n);
   k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), 1), 256, 0, s>>>(rows, pitch, w.cnt, mm);
-  k_kfi_grid<<<1, 1, 0, s>>>(mm, (float)cell_mm * 1e-3f, L.max_cells, gd, w.stat + slot);
+  k_kfi_grid<<<1, 1, 0, s>>>(mm, (float)cell_mm * 1e-3f, L.max_cells, head, w.stat + 2 * slot);
   // stable sort by cell, the first pass computing the keys from the points (ndt_segsort.hpp); one segment
   const RsPoints points = {rows, w.cnt, gd, cb, w.keys};
   const RsSorted r = rs_sort_one_segment(s, cb, w.keys, w.vals, w.keys + pitch, w.vals + pitch, pitch, w.hist, w.offs, &points);
-  unsigned *kin = r.keys, *vin = r.vals;
   const dim3 pg((unsigned)gx, 1u);
-  k_fit_mark<<<pg, 256, 0, s>>>(kin, pitch, gd, words, cb);
+  k_fit_mark<<<pg, 256, 0, s>>>(r.keys, pitch, gd, words, cb);
   k_fit_rank<<<1, 1024, 0, s>>>(gd, words);
-  k_fit_runs<<<pg, 256, 0, s>>>(kin, pitch, gd, words, runs, cb);
-  k_kfi_gather<<<gx, 256, 0, s>>>(rows, pitch, vin, sorted);
+  k_fit_runs<<<pg, 256, 0, s>>>(r.keys, pitch, gd, words, runs, cb);
+  k_kfi_gather<<<gx, 256, 0, s>>>(rows, pitch, (int)n, r.vals, reinterpret_cast<float*>(blob + L.sorted), reinterpret_cast<unsigned*>(blob + L.ids), head,
+                                  w.stat + 2 * slot);
   HIPCHK(h, hipGetLastError());
-  if (ids) *ids = vin;
   return MI355NDT_OK;
 }
-
-// enqueue the build of kf's index (kf.n > 0); the status lands in vs.stat[slot].  The scratch is sized by the caller.
-static int kfi_build(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, int slot) {
-  kf.index_status = mi355ndt_handle::Keyframe::NO_INDEX;
-  HIPCHK(h, kf.index.realloc_exact(kfi_layout(kf.pitch).bytes));
-  return kfi_build_rows(h, kf.rows, kf.pitch, kf.n, h->kff_cell_mm, kf.index, slot);
-}
+// ... and what the host learned of it: ret = the fetched vs.stat
+static void kfi_built(CloudIndex& ix, const int* ret, int slot) { ix.status = ret[2 * slot]; ix.n_fin = ret[2 * slot + 1]; }
 
 // replaces InformationMatrixCalculator::calc_fitness_score (information_matrix_calculator.cpp:53-87) for E graph edges at once
 int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int* ids1, const int* ids2, const double* relposes, double max_range,
                                      double* scores, long long* n_inliers) {
   using Keyframe = mi355ndt_handle::Keyframe;
+  constexpr int NO_INDEX = CloudIndex::NO_INDEX;
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   NOT_IN_STREAM(h);
   if (n_edges < 0) return MI355NDT_ERR_BAD_ARG;
@@ -87,7 +93,7 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
   size_t ws_pitch = 0;
   for (int e = 0; e < E; e++) {
     Keyframe* kf = k1[(size_t)e];
-    if (kf->n == 0 || k2[(size_t)e]->n == 0 || kf->index_status != Keyframe::NO_INDEX || todo.count(kf)) continue;
+    if (kf->n == 0 || k2[(size_t)e]->n == 0 || kf->index.status != NO_INDEX || todo.count(kf)) continue;
     const int slot = (int)todo.size();
     todo.emplace(kf, slot);
     ws_pitch = std::max(ws_pitch, kf->pitch);
@@ -99,8 +105,8 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
   int n_part = 0;
   for (int e = 0; e < E; e++) {
     const Keyframe *a = k1[(size_t)e], *b = k2[(size_t)e];
-    if (a->n == 0 || b->n == 0 || a->index_status == GRID_EMPTY) continue;   // DBL_MAX, 0 without a launch
-    st[(size_t)e] = a->index_status;
+    if (a->n == 0 || b->n == 0 || a->index.status == GRID_EMPTY) continue;   // DBL_MAX, 0 without a launch
+    st[(size_t)e] = a->index.status;
     nblk[(size_t)e] = (int)((b->n + 255) / 256);
     part0[(size_t)e] = n_part;
     n_part += nblk[(size_t)e];
@@ -110,17 +116,17 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
   std::vector<int> tab, tab_brute;
   int gmax = 0, gmax_brute = 0;
   for (const bool with_grid : {true, false})
-    fit_item_table(E, nblk, part0, [&](int e) { return st[(size_t)e] == Keyframe::NO_INDEX || (st[(size_t)e] == GRID_OK) == with_grid; },
+    fit_item_table(E, nblk, part0, [&](int e) { return st[(size_t)e] == NO_INDEX || (st[(size_t)e] == GRID_OK) == with_grid; },
                    [&](int e) { return std::array<int, 3>{(int)k2[(size_t)e]->n, (int)k1[(size_t)e]->n, 0}; },
                    with_grid ? tab : tab_brute, with_grid ? gmax : gmax_brute);
   static_assert(sizeof(KfEdge) % 8 == 0, "the tables' layout");
   const size_t at_ok = (size_t)E * sizeof(KfEdge), at_brute = at_ok + tab.size() * sizeof(int), bytes = at_brute + tab_brute.size() * sizeof(int);
   VoxelScratch& w = h->vs;
   VsNeed need;
-  need.pitch = ws_pitch; need.tab = n_part > 0 ? bytes : 0; need.part = (size_t)2 * n_part; need.stat = todo.size();
+  need.pitch = ws_pitch; need.tab = n_part > 0 ? bytes : 0; need.part = (size_t)2 * n_part; need.stat = 2 * todo.size();
   rc = vs_reserve(h, need);
   if (rc) return rc;
-  for (auto& t : todo) { rc = kfi_build(h, *t.first, t.second); if (rc) return rc; }
+  for (auto& t : todo) { rc = kfi_build_rows(h, t.first->rows, t.first->pitch, t.first->n, h->kff_cell_mm, t.first->index, t.second); if (rc) return rc; }
   if (n_part > 0) {
     unsigned char* ht = w.h_tab;
     KfEdge* he = reinterpret_cast<KfEdge*>(ht);
@@ -128,14 +134,7 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
       const Keyframe *a = k1[(size_t)e], *b = k2[(size_t)e];
       KfEdge& x = he[e];
       memset(&x, 0, sizeof x);
-      if (nblk[(size_t)e]) {
-        const KfiLayout L = kfi_layout(a->pitch);
-        const unsigned char* blob = a->index;
-        x.src = b->rows; x.tgt = a->rows; x.sorted = reinterpret_cast<const float*>(blob + L.sorted);
-        x.gd = reinterpret_cast<const GridDesc*>(blob); x.words = reinterpret_cast<const BitWord*>(blob + L.words);
-        x.runs = reinterpret_cast<const unsigned*>(blob + L.runs);
-        x.spitch = (unsigned)b->pitch; x.tpitch = (unsigned)a->pitch;
-      }
+      if (nblk[(size_t)e]) { x.src = b->rows; x.spitch = (unsigned)b->pitch; x.tgt = kfi_view(a->index, a->rows, a->pitch, a->n); }
       for (int k = 0; k < 16; k++) x.T[k] = (float)relposes[16 * (size_t)e + k];   // relpose.cast<float>() (:62)
     }
     memcpy(ht + at_ok, tab.data(), tab.size() * sizeof(int));
@@ -151,11 +150,11 @@ int mi355ndt_keyframe_fitness_scores(mi355ndt_handle* h, int n_edges, const int*
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(w.h_part, w.part, (size_t)2 * n_part * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  if (!todo.empty()) HIPCHK(h, hipMemcpyAsync(w.h_ret, w.stat, todo.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!todo.empty()) HIPCHK(h, hipMemcpyAsync(w.h_ret, w.stat, 2 * todo.size() * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));             // the call's one wait
   w.pending = false;
   HIPCHK(h, hipGetLastError());
-  for (auto& t : todo) t.first->index_status = w.h_ret[t.second];
+  for (auto& t : todo) kfi_built(t.first->index, w.h_ret, t.second);
   for (int e = 0; e < E; e++) fit_reduce(w.h_part + 2 * (size_t)part0[(size_t)e], nblk[(size_t)e], scores + e, n_inliers ? n_inliers + e : nullptr);
   return MI355NDT_OK;
 }

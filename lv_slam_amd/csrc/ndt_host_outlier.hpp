@@ -1,7 +1,7 @@
 // ndt_host_outlier.hpp -- mi355ndt_prefilter_outliers: PrefilteringNodelet::outlier_removal (prefiltering_nodelet.cpp:128, 150-161) over the
-// resident prefilter result, in place (ndt_outlier.hpp).  The index block, dist[] and its pinned twin are this surface's own; the index
-// build's sort, the flags, the scan and the compaction target use the shared scratch (h->vs).  The batch, the grids, the keyframes and their
-// indexes, the map-cloud and window workspaces are left as they were.
+// resident prefilter result, in place (ndt_outlier.hpp).  The index (a CloudIndex, rebuilt by every call), dist[] and its pinned twin are this
+// surface's own; the index build's sort, the flags, the scan and the compaction target use the shared scratch (h->vs).  The batch, the
+// grids, the keyframes and their indexes, the map-cloud and window workspaces are left as they were.
 #pragma once
 
 int mi355ndt_outlier_params_default(mi355ndt_outlier_params* p) {
@@ -25,12 +25,9 @@ static void outlier_statistics(const float* dist, size_t n, long long n_valid, d
 }
 
 template <int CAP>
-static void outlier_knn_launch(hipStream_t s, unsigned blocks, const unsigned char* blob, const KfiLayout& L, size_t pitch, const unsigned* ids,
-                               const float* rows, int n, const int* n_fin, int method, int K, float r2, float* dist, int* keep) {
-  const GridDesc* gd = reinterpret_cast<const GridDesc*>(blob);
-  k_ol_knn<CAP><<<blocks, OL_LANES, 0, s>>>(gd, reinterpret_cast<const BitWord*>(blob + L.words), reinterpret_cast<const unsigned*>(blob + L.runs),
-                                            reinterpret_cast<const float*>(blob + L.sorted), pitch, ids, n_fin, method, K, r2, dist, keep);
-  k_ol_knn_brute<CAP><<<blocks, OL_LANES, 0, s>>>(gd, rows, pitch, n, n_fin, method, K, r2, dist, keep);   // (the kernels decide by the lattice's status)
+static void outlier_knn_launch(hipStream_t s, unsigned blocks, const KfiView& v, int method, int K, float r2, float* dist, int* keep) {
+  k_ol_knn<CAP><<<blocks, OL_LANES, 0, s>>>(v, method, K, r2, dist, keep);
+  k_ol_knn_brute<CAP><<<blocks, OL_LANES, 0, s>>>(v, method, K, r2, dist, keep);   // (the kernels decide by the lattice's status)
 }
 
 int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_params* p, float* mean_distances,
@@ -59,25 +56,22 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
   need.pitch = pitch; need.x = 3 * pitch; need.stat = 2;
   int rc = vs_reserve(h, need);
   if (rc) return rc;
-  const KfiLayout L = kfi_layout(pitch);
-  HIPCHK(h, h->d_ol_index.reserve(L.bytes));
   HIPCHK(h, h->d_ol_dist.reserve(pitch));
   HIPCHK(h, h->h_ol_dist.reserve(pitch));
   float* rows = h->d_pf_out;
-  int* n_fin = w.stat + 1;                        // the number of searchable points (w.stat[0]: the lattice's status, k_kfi_grid)
   const int gx = (int)((pitch + 255) / 256);
-  HIPCHK(h, hipMemsetAsync(w.stat, 0, 2 * sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->d_ol_dist, 0, pitch * sizeof(float), s));
   HIPCHK(h, hipMemsetAsync(w.flag, 0, pitch * sizeof(int), s));
-  k_ol_finite<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(rows, pitch, (int)n, n_fin, K == 0 ? w.flag.p : nullptr);
-  if (K > 0) {
-    const unsigned* ids = nullptr;
-    rc = kfi_build_rows(h, rows, pitch, n, h->ol_cell_mm, h->d_ol_index, 0, &ids);
+  if (K > 0) {                                    // (w.stat[0], [1]: the lattice's status and the number of searchable points)
+    rc = kfi_build_rows(h, rows, pitch, n, h->ol_cell_mm, h->ol_index, 0);
     if (rc) return rc;
+    const KfiView v = kfi_view(h->ol_index, rows, pitch, n);
     const unsigned blocks = (unsigned)((n + OL_LANES - 1) / OL_LANES);
-    if (K <= 32) outlier_knn_launch<32>(s, blocks, h->d_ol_index, L, pitch, ids, rows, (int)n, n_fin, method, K, r2, h->d_ol_dist, w.flag);
-    else outlier_knn_launch<64>(s, blocks, h->d_ol_index, L, pitch, ids, rows, (int)n, n_fin, method, K, r2, h->d_ol_dist, w.flag);
+    if (K <= 32) outlier_knn_launch<32>(s, blocks, v, method, K, r2, h->d_ol_dist, w.flag);
+    else outlier_knn_launch<64>(s, blocks, v, method, K, r2, h->d_ol_dist, w.flag);
     HIPCHK(h, hipGetLastError());
+  } else {                                        // RADIUS with min_neighbors = 0: every searchable point is kept
+    k_ol_finite<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(rows, pitch, (int)n, w.flag);
   }
   if (statistical) {
     // the index-order f64 sums are two dependent chains over n values: dist[] comes back once, the host forms the threshold, and the

@@ -1,22 +1,27 @@
-// ndt_kffitness.hpp -- fitness scores of graph edges between resident keyframes (mi355ndt_keyframe_fitness_scores):
-// InformationMatrixCalculator::calc_fitness_score (src/global_graph/information_matrix_calculator.cpp:53-87) for E edges in one launch.
+// ndt_kffitness.hpp -- the spatial index over a resident cloud, and the fitness scores of graph edges between resident keyframes
+// (mi355ndt_keyframe_fitness_scores): InformationMatrixCalculator::calc_fitness_score
+// (src/global_graph/information_matrix_calculator.cpp:53-87) for E edges in one launch.
 //
-// The searched keyframe of an edge (cloud1, the kd-tree side of the reference) owns a spatial index, built the first time it is searched and
-// kept until the keyframe is released: one block of device memory holding
-//   GridDesc           the cell lattice over the keyframe's finite points (k_kfi_grid: the cell rule below); status != GRID_OK = no lattice
+// A cloud that is searched -- a keyframe by the fitness scores or by GICP, a GICP host cloud, the prefilter result by the outlier removal --
+// owns ONE index (CloudIndex, ndt_engine.hpp), built by whichever surface searches it first (kfi_build_rows, ndt_host_kffitness.hpp) and, for
+// a keyframe, kept until it is released: one block of device memory holding
+//   KfiHead            the cell lattice over the cloud's finite points (k_kfi_grid: the cell rule below; status != GRID_OK = no lattice) and
+//                      the number of searchable points (three finite coordinates), in 128 bytes
 //   BitWord words[]    occupancy of 64 cells + rank of the first, the layout k_fit_mark / k_fit_rank write and fit_rank reads (ndt_fitness.hpp)
 //   unsigned runs[]    sorted position of the first point of the k-th occupied cell; runs[n_occ] = number of binned points
 //   float sorted[3][pitch]  x, y, z of the points IN CELL ORDER: a row of a ring face is one contiguous run of floats per coordinate, where
-//                      the batch surface gathers every point through its id (the index lives as long as the keyframe; the copy pays once)
+//                      the batch surface gathers every point through its id (the index lives as long as the cloud; the copy pays once)
+//   unsigned ids[pitch]     the input position of the point at each sorted position (the k-NN lists' and GICP's (d2, id) tie rules; results by id)
+// The kernels take it as a KfiView, made by kfi_view (ndt_host_kffitness.hpp) and by nothing else.
 // No NDT leaves: no sums, no eigen decomposition, no inverse covariances.  The build reuses the engine's kernels as they are -- k_minmax
 // (ordered-int extremes), the segmented radix sort whose first pass computes the cell keys from the points (rs_pass), k_fit_mark / k_fit_rank /
 // k_fit_runs -- on a one-target "batch".
 //
-// The search is the batch surface's block of queries (fit_ring_block, ndt_fitness.hpp) with the points read in cell order instead of by id.
-// It is exact for any cell size (fit_rings: ring by ring, stop when no unvisited ring can beat the best or be within max_range), so
+// The fitness search is the batch surface's block of queries (fit_ring_block, ndt_fitness.hpp) with the points read in cell order instead of
+// by id.  It is exact for any cell size (fit_rings: ring by ring, stop when no unvisited ring can beat the best or be within max_range), so
 // the cell rule is about speed only: start from MI355NDT_OPT_KF_FITNESS_CELL_MM and double the cell until the lattice has at most
-// `max_cells` cells; a keyframe that does not get there within KFI_MAX_DOUBLINGS doublings (a stray point at 1e12 m) has no lattice and is
-// scored by the exhaustive block kernel (fitness_brute_block) over its unsorted rows.
+// `max_cells` cells; a cloud that does not get there within KFI_MAX_DOUBLINGS doublings (a stray point at 1e12 m) has no lattice and is
+// searched exhaustively over its unsorted rows (fit_tiles).
 #pragma once
 #include "ndt_types.hpp"
 #include "ndt_build.hpp"
@@ -33,8 +38,21 @@ __global__ void k_kfi_begin(unsigned* mm, int* cnt, int n) {
   if (threadIdx.x == 6) *cnt = n;
 }
 
-// the cell rule; *stat_out = the status, for the host (one word per index built in a call, fetched with the call's partials)
-__global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max_cells, GridDesc* gd, int* stat_out) {
+// the block's header: the lattice, then the cloud's searchable points (k_kfi_gather counts them at the end of the build)
+struct KfiHead { GridDesc gd; int n_fin; };
+static_assert(offsetof(KfiHead, gd) == 0 && sizeof(KfiHead) <= 128, "the index block's header");
+
+// One cloud's index as the kernels take it (kfi_view, ndt_host_kffitness.hpp): the block's parts, then the cloud's own rows
+// ([3][pitch], n points, input order), which the exhaustive walk reads when there is no lattice.
+struct KfiView {
+  const GridDesc* gd; const BitWord* words; const unsigned* runs; const float* sorted; const unsigned* ids;
+  const float* rows; unsigned pitch; int n;
+  __device__ __forceinline__ int n_fin() const { return reinterpret_cast<const KfiHead*>(gd)->n_fin; }
+};
+
+// the cell rule; stat_out[0] = the status, for the host (two words per index built in a call, fetched with the call's results; the second:
+// the searchable points, cleared here for k_kfi_gather)
+__global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max_cells, KfiHead* head, int* stat_out) {
   GridDesc g;
   memset(&g, 0, sizeof g);
   g.leaf = cell0;
@@ -63,25 +81,35 @@ __global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max
       break;
     }
   }
-  *gd = g;
-  *stat_out = g.status;
+  head->gd = g;
+  stat_out[0] = g.status;
+  stat_out[1] = 0;
 }
 
-// the points in cell order (positions past the binned points hold the not-binned points and the padding: never read, runs[n_occ] ends the last run)
-__global__ void __launch_bounds__(256) k_kfi_gather(const float* __restrict__ rows, size_t pitch, const unsigned* __restrict__ vals, float* __restrict__ sorted) {
+// the points and their ids in cell order (positions past the binned points hold the not-binned points and the padding: never read,
+// runs[n_occ] ends the last run).  vals is a permutation of 0 .. pitch - 1 whatever the lattice's status, so every point passes here once:
+// the searchable ones are counted, one integer atomic per block into the header (zeroed by the host) and one into the host's word.
+__global__ void __launch_bounds__(256) k_kfi_gather(const float* __restrict__ rows, size_t pitch, int n, const unsigned* __restrict__ vals,
+                                                    float* __restrict__ sorted, unsigned* __restrict__ ids, KfiHead* head, int* stat_out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= pitch) return;
-  const unsigned v = vals[i];
-  sorted[i] = rows[v]; sorted[pitch + i] = rows[pitch + v]; sorted[2 * pitch + i] = rows[2 * pitch + v];
+  bool fin = false;
+  if (i < pitch) {
+    const unsigned v = vals[i];
+    const float x = rows[v], y = rows[pitch + v], z = rows[2 * pitch + v];
+    ids[i] = v;
+    sorted[i] = x; sorted[pitch + i] = y; sorted[2 * pitch + i] = z;
+    fin = v < (unsigned)n && finite3(x, y, z);
+  }
+  const int c = __syncthreads_count(fin);
+  if (threadIdx.x == 0 && c) { atomicAdd(&head->n_fin, c); atomicAdd(stat_out + 1, c); }
 }
 
-// One scored edge.  src: the rows of keyframe ids2[e] (moved by T); tgt: the rows of keyframe ids1[e] as they are (exhaustive search);
-// gd / words / runs / sorted: the index of keyframe ids1[e].
+// One scored edge.  src: the rows of keyframe ids2[e] (moved by T); tgt: keyframe ids1[e], the searched side.
 struct KfEdge {
-  const float* src; const float* tgt; const float* sorted;
-  const GridDesc* gd; const BitWord* words; const unsigned* runs;
-  unsigned spitch, tpitch;
+  const float* src;
+  KfiView tgt;
   float T[16];                                    // relpose.cast<float>(), column-major
+  unsigned spitch;
 };
 
 // The launch is k_fitness_batch's: a flat grid over (edge, 256-point block) items, workgroup L serving group L % 8 -- the workgroups of one
@@ -96,11 +124,11 @@ __global__ void __launch_bounds__(256) k_kf_fitness(const FitItem* __restrict__ 
   int bx;
   if (!fit_item(items, gstart, it, bx)) return;
   const KfEdge& e = edges[it.pair];
-  const GridDesc& g = *e.gd;
+  const GridDesc& g = *e.tgt.gd;
   if (g.status != GRID_OK) return;
-  const float* X = e.sorted;
-  const size_t tpitch = e.tpitch;
-  fit_ring_block(e.src, e.spitch, it.n_src, e.T, g, e.words, e.runs, fit_ring_max(max_range_d, g.leaf), max_range, bx,
+  const float* X = e.tgt.sorted;
+  const size_t tpitch = e.tgt.pitch;
+  fit_ring_block(e.src, e.spitch, it.n_src, e.T, g, e.tgt.words, e.tgt.runs, fit_ring_max(max_range_d, g.leaf), max_range, bx,
                  [=](const float (&q)[3], unsigned j) { return fit_d2(q, X[j], X[tpitch + j], X[2 * tpitch + j]); },
                  partial + 2 * ((size_t)it.part0 + bx));
 }
@@ -112,8 +140,8 @@ __global__ void __launch_bounds__(256) k_kf_fitness_brute(const FitItem* __restr
   int bx;
   if (!fit_item(items, gstart, it, bx)) return;
   const KfEdge& e = edges[it.pair];
-  const int status = e.gd->status;
+  const int status = e.tgt.gd->status;
   if (status == GRID_OK) return;
-  fitness_brute_block(e.src, e.spitch, it.n_src, e.tgt, e.tpitch, status == GRID_EMPTY ? 0 : it.n_tgt, e.T, max_range, bx,
+  fitness_brute_block(e.src, e.spitch, it.n_src, e.tgt.rows, e.tgt.pitch, status == GRID_EMPTY ? 0 : it.n_tgt, e.T, max_range, bx,
                       partial + 2 * ((size_t)it.part0 + bx));
 }

@@ -8,11 +8,13 @@
 //   RADIUS       kept iff at least min_neighbors others have d2 < r2 (strict): the K-th smallest distance to the others, K = min_neighbors, is < r2.
 // The multiset of the K smallest does not depend on the visiting order or on how ties are broken, so the search is exact word for word.
 //
-// The index is the keyframe index (ndt_kffitness.hpp: lattice, rank words, run starts, points in cell order), built per call into a block of
-// this surface's own.  k_ol_knn takes its queries in cell order -- a wave's lanes sit in neighbouring cells and walk similar rings -- and
-// scatters the results by point id; fit_rings drives it with the list's worst entry as `best` once the list is full.  Each lane's list lives in
-// LDS, [slot][lane]: a wave's access to one slot touches 64 consecutive words (no bank conflict), and no lane needs scratch memory for it.
-// A cloud without a lattice (GRID_CAP: a stray point at 1e12 m) goes through k_ol_knn_brute, exhaustive over LDS tiles of the rows.
+// The index is a cloud index (ndt_kffitness.hpp: lattice, rank words, run starts, points and ids in cell order), this surface's own and
+// rebuilt by every call.  The list of one query is filled in one place, knn_fill, which the GICP covariances share (ndt_gicp.hpp): with a
+// lattice the queries are taken in cell order -- a wave's lanes sit in neighbouring cells and walk similar rings -- and the results scattered
+// by point id; fit_rings drives the walk with the list's worst entry as `best` once the list is full.  A cloud without a lattice (GRID_CAP:
+// a stray point at 1e12 m) is walked exhaustively (fit_tiles), the queries in input order.  Each lane's list lives in LDS, [slot][lane]: a
+// wave's access to one slot touches 64 consecutive words (no bank conflict), and no lane needs scratch memory for it.  The two paths are two
+// kernels here (k_ol_knn, k_ol_knn_brute): one wave per workgroup, occupancy bound by LDS, and the lattice kernel does not carry the 3 KB tile.
 #pragma once
 #include "ndt_types.hpp"
 #include "ndt_fitness.hpp"
@@ -29,6 +31,7 @@
 // depend on which of two equally distant points is kept and on the order they are added in.  Without ids, equal distances are equal entries.
 template <int CAP, bool IDS = false>
 struct OlList {
+  static constexpr bool ids = IDS;
   float* L;                              // this lane's column: slot s at L[s * OL_LANES]
   unsigned* I;                           // (IDS) the ids' column
   int K, cnt, wslot;
@@ -93,83 +96,66 @@ struct OlList {
   __device__ __forceinline__ bool full() const { return cnt == K; }
 };
 
-// searchable points: *n_fin += their number; keep (may be null): 1 for each of them (RADIUS with min_neighbors = 0)
-__global__ void __launch_bounds__(256) k_ol_finite(const float* __restrict__ rows, size_t pitch, int n, int* n_fin, int* keep) {
+// keep = 1 for each searchable point (RADIUS with min_neighbors = 0: no search, no index)
+__global__ void __launch_bounds__(256) k_ol_finite(const float* __restrict__ rows, size_t pitch, int n, int* keep) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool f = i < n && finite3(rows[i], rows[pitch + i], rows[2 * pitch + i]);
-  if (keep && i < n) keep[i] = f ? 1 : 0;
-  const unsigned long long b = __ballot(f);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_fin, __popcll(b));
+  if (i < n) keep[i] = finite3(rows[i], rows[pitch + i], rows[2 * pitch + i]) ? 1 : 0;
 }
 
-// One lane per searchable point, in cell order (sorted position j, point id vals[j]).  method STATISTICAL: dist[id]; RADIUS: keep[id].
-// The caller has zeroed both; non-searchable points keep their zero.
-template <int CAP>
-__global__ void __launch_bounds__(OL_LANES) k_ol_knn(const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const unsigned* __restrict__ runs,
-                                                     const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ vals,
-                                                     const int* __restrict__ n_fin, int method, int K, float r2, float* dist, int* keep) {
+// The list of one lane's query, filled: the `list.K` nearest searchable points of the cloud, SKIP_SELF: other than the query itself.
+// LATTICE: query j = the point at sorted position j (a lattice bins every searchable point: positions 0 .. n_fin - 1), the ring walk,
+// nothing beyond max_range.  Otherwise: query j = point j of the rows, the exhaustive walk -- every lane of the workgroup (OL_LANES) calls.
+// Returns whether the lane has a query; id = its point id.
+template <bool LATTICE, bool SKIP_SELF, typename List>
+__device__ __forceinline__ bool knn_fill(const KfiView& v, unsigned j, float max_range, List& list, unsigned& id) {
+  const size_t pitch = v.pitch;
+  float q[3] = {0.f, 0.f, 0.f};
+  id = j;
+  if constexpr (LATTICE) {
+    if (j >= (unsigned)v.n_fin()) return false;
+    const float* X = v.sorted;
+    q[0] = X[j]; q[1] = X[pitch + j]; q[2] = X[2 * pitch + j];
+    id = v.ids[j];
+    fit_rings(q, *v.gd, v.words, v.runs, 1 << 30, max_range, list.worst, [&](unsigned j0, unsigned j1) {
+      for (unsigned t = j0; t < j1; t++) {
+        if (SKIP_SELF && t == j) continue;
+        unsigned tid = 0u;
+        if constexpr (List::ids) tid = v.ids[t];
+        list.insert(fit_d2(q, X[t], X[pitch + t], X[2 * pitch + t]), tid);
+      }
+    });
+    return true;
+  } else {
+    bool live = false;
+    if (j < (unsigned)v.n) {
+      q[0] = v.rows[j]; q[1] = v.rows[pitch + j]; q[2] = v.rows[2 * pitch + j];
+      live = finite3(q[0], q[1], q[2]);
+    }
+    fit_tiles<OL_LANES>(v.rows, pitch, v.n, [&](float x, float y, float z, unsigned t) {
+      if (live && !(SKIP_SELF && t == j)) list.insert(fit_d2(q, x, y, z), t);
+    });
+    return live;
+  }
+}
+
+// One lane per searchable point.  method STATISTICAL: dist[id]; RADIUS: keep[id].  The caller has zeroed both; non-searchable points keep
+// their zero.  Both kernels are launched and the cloud's status picks the one that works.
+template <int CAP, bool LATTICE>
+__device__ __forceinline__ void ol_knn(const KfiView& v, int method, int K, float r2, float* dist, int* keep) {
   __shared__ float lst[CAP][OL_LANES];
-  const GridDesc& g = *gd;
-  if (g.status != GRID_OK) return;
-  const int nf = *n_fin;                           // (a lattice bins every searchable point: sorted positions 0 .. nf - 1)
-  if (method == OL_STATISTICAL && nf < K + 1) return;   // nearestKSearch(mean_k + 1) comes back short: dist = 0, not valid
-  const unsigned j = blockIdx.x * OL_LANES + threadIdx.x;
-  if (j >= (unsigned)nf) return;
-  const float q[3] = {X[j], X[pitch + j], X[2 * pitch + j]};
+  if (v.gd->status != (LATTICE ? GRID_OK : GRID_CAP)) return;
+  if (method == OL_STATISTICAL && v.n_fin() < K + 1) return;   // nearestKSearch(mean_k + 1) comes back short: dist = 0, not valid
   OlList<CAP> list;
   list.init(lst, K);
-  const float inf = __int_as_float(0x7f800000);
-  fit_rings(q, g, words, runs, 1 << 30, method == OL_RADIUS ? r2 : inf, list.worst, [&](unsigned j0, unsigned j1) {
-    for (unsigned t = j0; t < j1; t++) {
-      if (t == j) continue;                       // the point itself
-      const float dx = q[0] - X[t], dy = q[1] - X[pitch + t], dz = q[2] - X[2 * pitch + t];
-      list.insert((dx * dx + dy * dy) + dz * dz);                // FLANN L2_Simple accumulation order
-    }
-  });
-  const unsigned id = vals[j];
+  unsigned id;
+  if (!knn_fill<LATTICE, true>(v, blockIdx.x * OL_LANES + threadIdx.x, method == OL_RADIUS ? r2 : __int_as_float(0x7f800000), list, id)) return;
   if (method == OL_STATISTICAL) dist[id] = list.mean_distance();
   else keep[id] = (list.full() && list.worst < r2) ? 1 : 0;
 }
-
-// the same lists for a cloud without a lattice: queries in input order, the rows staged through LDS 256 points at a time
 template <int CAP>
-__global__ void __launch_bounds__(OL_LANES) k_ol_knn_brute(const GridDesc* __restrict__ gd, const float* __restrict__ rows, size_t pitch, int n,
-                                                           const int* __restrict__ n_fin, int method, int K, float r2, float* dist, int* keep) {
-  __shared__ float lst[CAP][OL_LANES];
-  __shared__ float tx[256], ty[256], tz[256];
-  if (gd->status != GRID_CAP) return;
-  if (method == OL_STATISTICAL && *n_fin < K + 1) return;
-  const int i = blockIdx.x * OL_LANES + threadIdx.x;
-  float q[3] = {0.f, 0.f, 0.f};
-  bool live = false;
-  if (i < n) {
-    q[0] = rows[i]; q[1] = rows[pitch + i]; q[2] = rows[2 * pitch + i];
-    live = finite3(q[0], q[1], q[2]);
-  }
-  OlList<CAP> list;
-  list.init(lst, K);
-  for (int j0 = 0; j0 < n; j0 += 256) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 256 / OL_LANES; u++) {
-      const int k = u * OL_LANES + threadIdx.x, j = j0 + k;
-      float x = __int_as_float(0x7fc00000), y = x, z = x;                        // past the end: NaN, skipped below
-      if (j < n) { x = rows[j]; y = rows[pitch + j]; z = rows[2 * pitch + j]; }
-      tx[k] = x; ty[k] = y; tz[k] = z;
-    }
-    __syncthreads();
-    if (live) {
-      for (int k = 0; k < 256; k++) {
-        if (j0 + k == i || !finite3(tx[k], ty[k], tz[k])) continue;              // itself; non-finite points are in no tree
-        const float dx = q[0] - tx[k], dy = q[1] - ty[k], dz = q[2] - tz[k];
-        list.insert((dx * dx + dy * dy) + dz * dz);
-      }
-    }
-  }
-  if (!live) return;
-  if (method == OL_STATISTICAL) dist[i] = list.mean_distance();
-  else keep[i] = (list.full() && list.worst < r2) ? 1 : 0;
-}
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, true>(v, method, K, r2, dist, keep); }
+template <int CAP>
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn_brute(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, false>(v, method, K, r2, dist, keep); }
 
 // STATISTICAL: removed iff (double)dist > threshold (a NaN threshold removes nothing); positions past n: 0
 __global__ void __launch_bounds__(256) k_ol_flag(const float* __restrict__ dist, int n, size_t pitch, double threshold, int* flag) {

@@ -547,8 +547,8 @@ int  mi355ndt_information_matrix(const mi355ndt_inf_params* p, double fitness_sc
 
 /* ---- GICP: pclomp::GeneralizedIterativeClosestPoint (registration_method = GICP_OMP) ---------------------------- */
 /* replaces pclomp::GeneralizedIterativeClosestPoint (include/ndt_omp/gicp_omp.h, gicp_omp_impl.hpp), the registration
- * select_registration_method hands out for registration_method = GICP_OMP (src/global_graph/registrations.cpp:43-53), for one pair at a time,
- * synchronously.  Three stages run on the device -- the k-nearest-neighbour covariances of both clouds (computeCovariances), the
+ * select_registration_method hands out for registration_method = GICP_OMP (src/global_graph/registrations.cpp:43-53): one pair at a time,
+ * synchronously, here; all candidates of a loop check in one lockstep batch below (mi355ndt_gicp_batch_*).  Three stages run on the device -- the k-nearest-neighbour covariances of both clouds (computeCovariances), the
  * correspondences with their Mahalanobis matrices, the cost / gradient sums -- and the BFGS optimiser and the outer loop of
  * computeTransformation run on the host, reading one small record per evaluation.  The rules are the reference's as restated in
  * tools/gicp_ref.py; FLANN's tie order, PCL's bfgs.h and Eigen's JacobiSVD are unpinned.
@@ -606,6 +606,32 @@ int mi355ndt_gicp_correspondences(mi355ndt_handle* h, const float* guess_colmajo
 int mi355ndt_gicp_cost(mi355ndt_handle* h, const double* x, const float* base_colmajor, double* f, double* g);
 int mi355ndt_gicp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355ndt_gicp_result* result);
 int mi355ndt_gicp_get_aligned(mi355ndt_handle* h, void* out_pts, size_t out_stride_bytes);
+
+/* ---- GICP, every candidate of a loop check in one lockstep batch ------------------------------------------------ */
+/* The loop detector registers every candidate keyframe against the one new keyframe (loop_detector.hpp:148-205, :211-281).  The target is
+ * the one mi355ndt_gicp_set_target / _set_target_keyframe set (setInputTarget(new_keyframe), once per loop check), the parameters are the
+ * handle's mi355ndt_gicp_params; candidate k is the source of slot k.  mi355ndt_gicp_batch_align runs the K optimisers in lockstep: the
+ * host keeps BFGS and the outer loop, one worker thread per slot, and every round ONE table copy, ONE matching launch, ONE cost launch,
+ * ONE final launch and ONE wait serve all slots that wait for an evaluation -- the round trip is paid per round, not per candidate.
+ * results[k] and mi355ndt_gicp_batch_get_aligned(k) are, byte for byte, what mi355ndt_gicp_set_source* + mi355ndt_gicp_align(guess k) +
+ * mi355ndt_gicp_get_aligned give for that source against the same target.
+ *   mi355ndt_gicp_batch_reserve: 1..MI355NDT_GICP_BATCH_MAX slots; drops the earlier slots.
+ *   mi355ndt_gicp_batch_set_source / _set_source_keyframe: a host cloud (the slot owns its rows, index and covariances) or a resident
+ *     keyframe (the keyframe's one index and its covariance cache are used, and filled; two slots may name the same keyframe).
+ *   mi355ndt_gicp_batch_align: guesses n_slots x 16 floats (column-major 4x4 each), results n_slots records.
+ *   mi355ndt_gicp_batch_stats: of the last batch align -- *rounds = the waits on the device, requests[k] (n_slots; may be NULL) = the
+ *     device requests slot k made, a request being one matching pass or one cost evaluation.  rounds = the largest requests[k].
+ * Errors: MI355NDT_ERR_STATE in stream mode, with no slots reserved, no target set or a slot unset; MI355NDT_ERR_BAD_ARG for a slot out of
+ * range, n_slots outside 1..MI355NDT_GICP_BATCH_MAX, a released or unknown keyframe, and k_correspondences above a slot's searchable
+ * points (the text names the slot).  A refused or failed call leaves the handle usable.  The single-pair surface (its two clouds, its resident
+ * correspondences, its last final transformation), the NDT batch, the grids, the keyframes' rows and the other workspaces are left as they were. */
+#define MI355NDT_GICP_BATCH_MAX 64
+int mi355ndt_gicp_batch_reserve(mi355ndt_handle* h, int n_slots);
+int mi355ndt_gicp_batch_set_source(mi355ndt_handle* h, int slot, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_gicp_batch_set_source_keyframe(mi355ndt_handle* h, int slot, int id);
+int mi355ndt_gicp_batch_align(mi355ndt_handle* h, const float* guesses_colmajor, mi355ndt_gicp_result* results);
+int mi355ndt_gicp_batch_get_aligned(mi355ndt_handle* h, int slot, void* out_pts, size_t out_stride_bytes);
+int mi355ndt_gicp_batch_stats(mi355ndt_handle* h, int* rounds, int* requests);
 
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);

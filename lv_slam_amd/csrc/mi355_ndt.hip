@@ -6,6 +6,8 @@
 //                   include/ndt_omp/voxel_grid_covariance_omp_impl.hpp:48-370)
 //   GICP          : k_gc_cov -> [k_gc_match -> (k_gc_cost -> k_gc_cost_final)*]*   (pclomp::GeneralizedIterativeClosestPoint, gicp_omp_impl.hpp; the
 //                   BFGS optimiser and the outer loop on the host: ndt_gicp.hpp, gicp_bfgs.hpp, ndt_host_gicp.hpp)
+//   GICP batch    : k_gc_cov per cloud -> [table copy -> k_gc_match_batch -> k_gc_cost_batch -> k_gc_cost_final_batch]*, one round for all
+//                   candidates of a loop check (gicp_lockstep.hpp, ndt_host_gicp_batch.hpp)
 //   align         : k_init_state -> k_sweep -> [k_update -> k_sweep]*      (computeTransformation +
 //                   computeDerivatives + computeStepLengthMT, include/ndt_omp/ndt_omp_impl2.hpp:87-188, 196-305, 841-1003;
 //                   step_size <= eps/2 only: [k_update -> k_hessian -> k_update -> k_sweep]*, impl2:622-714, 920-1000)
@@ -57,6 +59,7 @@
 #include "ndt_outlier.hpp"
 #include "ndt_gicp.hpp"
 #include "gicp_bfgs.hpp"
+#include "gicp_lockstep.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
@@ -86,5 +89,6 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
 #include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result
 #include "ndt_host_gicp.hpp"       // GICP: covariances, correspondences, cost, BFGS driver, align
+#include "ndt_host_gicp_batch.hpp" // GICP: all candidates of a loop check in one lockstep batch
 #include "ndt_host_sequence.hpp"   // latency mode, sequence run
 #include "ndt_host_stream.hpp"     // stream mode

@@ -167,6 +167,21 @@ struct mi355ndt_handle {
     bool have_corr = false, have_final = false; int n_matched = 0;
     float final_cm[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   } gicp;
+  // GICP batch (mi355ndt_gicp_batch_*, ndt_host_gicp_batch.hpp): the candidates of one loop check against the surface's target.  A slot is a
+  // source side (a host cloud's rows, index and cache, or a keyframe id) with correspondences, chunk partials and a final transformation of
+  // its own; the slots share one block of match counters, one mapped block of result records and the round's table (pinned twin -> device).
+  struct GicpBatch {
+    struct Slot {
+      GicpSide side;
+      DevBuf<int> idx; DevBuf<double> maha, part;
+      bool have_final = false; float final_cm[16];
+    };
+    std::vector<Slot> slot;
+    DevBuf<int> m;
+    PinBuf<double> h_rec; double* d_rec = nullptr;   // (h_rec is mapped; d_rec: the device's view)
+    PinBuf<GcSlot> h_tab; DevBuf<GcSlot> d_tab;
+    int rounds = 0; std::vector<int> requests;      // of the last batch align
+  } gicp_batch;
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 

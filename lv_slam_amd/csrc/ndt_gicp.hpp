@@ -28,6 +28,9 @@
 //    The tree is fixed by the source index alone: 256 consecutive points per chunk -- 64 lanes by shuffle-xor 32, 16, ... 1, then the chunk's
 //    four wave sums in wave order -- then chunk c into slot c % 256 in ascending c, then the 256 slots by halving (slot t += slot t + s,
 //    s = 128 ... 1).  No float atomics.  The record (13 sums, m) is written into mapped host memory.
+// 4. k_gc_match_batch + k_gc_cost_batch + k_gc_cost_final_batch -- stages 2 and 3 for every slot of mi355ndt_gicp_batch_align that waits for
+//    one, in one round.  The per-thread bodies of 2 and 3 are __device__ functions (gc_match_body, gc_cost_body, gc_final_body) which the
+//    single-pair and the batch kernels both instantiate; see section 4 below.
 #pragma once
 #include "ndt_types.hpp"
 #include "ndt_math.hpp"
@@ -101,12 +104,14 @@ __device__ __forceinline__ void gc_nearer(float d2, unsigned id, float& best, un
   if (d2 < best || (d2 == best && id < bid)) { best = d2; bid = id; }
 }
 
-__global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src, size_t spitch, int n_src, KfiView tgt, GcMatch a,
-                                                  const double* __restrict__ c1, const double* __restrict__ c2,
-                                                  int* __restrict__ idx, double* __restrict__ maha, int* m) {
+// the per-thread body of the matching kernels: source points chunk * 256 .. + 255 of one cloud.  The WHOLE workgroup calls it (fit_tiles and
+// the ballot); k_gc_match and k_gc_match_batch instantiate this one copy, which is what makes their bytes equal.
+__device__ __forceinline__ void gc_match_body(const float* __restrict__ src, size_t spitch, int n_src, const KfiView& tgt, const GcMatch& a,
+                                              const double* __restrict__ c1, const double* __restrict__ c2,
+                                              int* __restrict__ idx, double* __restrict__ maha, int* m, int chunk) {
   const GridDesc& g = *tgt.gd;
   const size_t tpitch = tgt.pitch;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = chunk * 256 + threadIdx.x;
   float q[3] = {0.f, 0.f, 0.f};
   bool live = false;
   if (i < n_src) {
@@ -154,13 +159,21 @@ __global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src,
   for (int e = 0; e < 9; e++) maha[(size_t)e * spitch + i] = M[e];
 }
 
+__global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src, size_t spitch, int n_src, KfiView tgt, GcMatch a,
+                                                  const double* __restrict__ c1, const double* __restrict__ c2,
+                                                  int* __restrict__ idx, double* __restrict__ maha, int* m) {
+  gc_match_body(src, spitch, n_src, tgt, a, c1, c2, idx, maha, m, (int)blockIdx.x);
+}
+
 // ---- 3. cost sweep ---------------------------------------------------------------------------------------------
 struct GcCost { float Tx[16], B[16]; };            // applyState(base, x) and the base transformation, column-major
 
-__global__ void __launch_bounds__(GC_CHUNK) k_gc_cost(const float* __restrict__ src, size_t spitch, int n_src, const float* __restrict__ tgt, size_t tpitch,
-                                                      const int* __restrict__ idx, const double* __restrict__ maha, GcCost a, double* __restrict__ part) {
+// the per-thread body of the cost kernels: chunk `chunk` of one cloud -> part[chunk][13]; one copy behind k_gc_cost and k_gc_cost_batch
+__device__ __forceinline__ void gc_cost_body(const float* __restrict__ src, size_t spitch, int n_src, const float* __restrict__ tgt, size_t tpitch,
+                                             const int* __restrict__ idx, const double* __restrict__ maha, const GcCost& a, double* __restrict__ part,
+                                             int chunk) {
   __shared__ double ws[GC_CHUNK / 64][GC_SUMS];
-  const int i = blockIdx.x * GC_CHUNK + threadIdx.x;
+  const int i = chunk * GC_CHUNK + threadIdx.x;
   double v[GC_SUMS];
 #pragma unroll
   for (int k = 0; k < GC_SUMS; k++) v[k] = 0.0;
@@ -196,12 +209,17 @@ __global__ void __launch_bounds__(GC_CHUNK) k_gc_cost(const float* __restrict__ 
   __syncthreads();
   if (threadIdx.x < GC_SUMS) {
     const int k = threadIdx.x;
-    part[(size_t)blockIdx.x * GC_SUMS + k] = ((ws[0][k] + ws[1][k]) + ws[2][k]) + ws[3][k];
+    part[(size_t)chunk * GC_SUMS + k] = ((ws[0][k] + ws[1][k]) + ws[2][k]) + ws[3][k];
   }
 }
 
-// the chunks' partials -> the record: rec[0 .. 12] = the sums, rec[13] = m
-__global__ void __launch_bounds__(256) k_gc_cost_final(const double* __restrict__ part, int n_chunks, const int* __restrict__ m, double* rec) {
+__global__ void __launch_bounds__(GC_CHUNK) k_gc_cost(const float* __restrict__ src, size_t spitch, int n_src, const float* __restrict__ tgt, size_t tpitch,
+                                                      const int* __restrict__ idx, const double* __restrict__ maha, GcCost a, double* __restrict__ part) {
+  gc_cost_body(src, spitch, n_src, tgt, tpitch, idx, maha, a, part, (int)blockIdx.x);
+}
+
+// one cloud's tree over its chunks' partials, by one workgroup of 256: rec[0 .. 12] = the sums
+__device__ __forceinline__ void gc_final_body(const double* __restrict__ part, int n_chunks, double* rec) {
   __shared__ double sm[256];
   for (int k = 0; k < GC_SUMS; k++) {
     double s = 0.0;
@@ -215,7 +233,66 @@ __global__ void __launch_bounds__(256) k_gc_cost_final(const double* __restrict_
     }
     if (threadIdx.x == 0) rec[k] = sm[0];
   }
+}
+
+// the chunks' partials -> the record: rec[0 .. 12] = the sums, rec[13] = m
+__global__ void __launch_bounds__(256) k_gc_cost_final(const double* __restrict__ part, int n_chunks, const int* __restrict__ m, double* rec) {
+  gc_final_body(part, n_chunks, rec);
   if (threadIdx.x == 0) { rec[GC_SUMS] = (double)*m; rec[GC_SUMS + 1] = 0.0; rec[GC_SUMS + 2] = 0.0; }
+}
+
+// ---- 4. the batch round (mi355ndt_gicp_batch_align, ndt_host_gicp_batch.hpp) -------------------------------------------
+// One round serves every slot that waits for an evaluation: one table in device memory, first the slots asking for a matching pass, then
+// the slots asking for a cost (at 64 slots the table is 20 KB, too large for kernel arguments).  A workgroup of 256 belongs to exactly one
+// slot, found from the entries' first chunks (ascending: a slot's last, partial chunk is followed by the next slot's first chunk in the same
+// grid), and runs the single-pair body on that slot's chunk.  Each slot keeps its own idx / maha / part / match counter and its own tree;
+// k_gc_cost_final_batch, one workgroup per entry of the table, writes rec[slot][GC_REC] into mapped host memory: for a cost the sums and the
+// m the host learned from the slot's matching pass, for a matching pass m alone -- and it clears the counter, which nothing reads until the
+// slot's next matching pass adds to it (an integer atomic per wave, as in k_gc_match; no float atomics anywhere).
+struct GcSlot {
+  const float* src; const double* c1;              // the slot's cloud: rows [3][spitch], covariances [9][spitch]
+  int* idx; double* maha; int* m; double* part;    // the slot's own correspondences, match counter and chunk partials
+  double* rec;                                     // the slot's record in mapped host memory (the device's view)
+  unsigned spitch; int n, chunk0, n_chunks;        // chunk0: the slot's first workgroup in its kernel's grid
+  int m_host, pad;                                 // cost: the matches of the slot's last matching pass
+  union { GcMatch match; GcCost cost; };
+};
+
+// the entry whose chunks hold workgroup `wg`: the last one with chunk0 <= wg (every entry has at least one chunk)
+__device__ __forceinline__ const GcSlot& gc_slot_of(const GcSlot* __restrict__ tab, int n, int wg) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].chunk0 <= wg) lo = mid; else hi = mid - 1;
+  }
+  return tab[lo];
+}
+
+__global__ void __launch_bounds__(256) k_gc_match_batch(const GcSlot* __restrict__ tab, int n_entries, KfiView tgt, const double* __restrict__ c2) {
+  const GcSlot& e = gc_slot_of(tab, n_entries, (int)blockIdx.x);
+  gc_match_body(e.src, e.spitch, e.n, tgt, e.match, e.c1, c2, e.idx, e.maha, e.m, (int)blockIdx.x - e.chunk0);
+}
+
+__global__ void __launch_bounds__(GC_CHUNK) k_gc_cost_batch(const GcSlot* __restrict__ tab, int n_entries, const float* __restrict__ tgt, size_t tpitch) {
+  const GcSlot& e = gc_slot_of(tab, n_entries, (int)blockIdx.x);
+  gc_cost_body(e.src, e.spitch, e.n, tgt, tpitch, e.idx, e.maha, e.cost, e.part, (int)blockIdx.x - e.chunk0);
+}
+
+// entries 0 .. n_match - 1 asked for a matching pass, the rest for a cost
+__global__ void __launch_bounds__(256) k_gc_cost_final_batch(const GcSlot* __restrict__ tab, int n_match) {
+  const GcSlot& e = tab[blockIdx.x];
+  const bool cost = (int)blockIdx.x >= n_match;
+  if (cost) gc_final_body(e.part, e.n_chunks, e.rec);
+  if (threadIdx.x == 0) {
+    if (cost) {
+      e.rec[GC_SUMS] = (double)e.m_host;
+    } else {
+      for (int k = 0; k < GC_SUMS; k++) e.rec[k] = 0.0;
+      e.rec[GC_SUMS] = (double)*e.m;
+      *e.m = 0;
+    }
+    e.rec[GC_SUMS + 1] = 0.0; e.rec[GC_SUMS + 2] = 0.0;
+  }
 }
 
 // the source moved by the final transformation (pcl::transformPointCloud, the PCL 1.8 scalar form): x, y, z records of 12 B

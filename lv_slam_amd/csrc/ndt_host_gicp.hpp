@@ -4,7 +4,8 @@
 // estimateRigidTransformationBFGS (:189-252), and reads one mapped record per evaluation of the cost.  A cloud's index (CloudIndex: a
 // keyframe's is the one the fitness scores search, built here if they have not built it) and covariances (GicpCache) are made on first use;
 // the index build's sort uses the shared scratch (h->vs).  The batch, the grids, the keyframes' rows, the prefilter result and the other
-// workspaces are left as they were.
+// workspaces are left as they were.  The pieces the batch form shares (ndt_host_gicp_batch.hpp): GicpSide / GicpView / gicp_prepare, what a
+// request takes to the device (gicp_make_match, gicp_make_cost), fdf from the sums (gicp_fdf_sums), the outer loop (gicp_outer).
 #pragma once
 
 int mi355ndt_gicp_params_default(mi355ndt_gicp_params* p) {
@@ -29,17 +30,14 @@ int mi355ndt_gicp_set_params(mi355ndt_handle* h, const mi355ndt_gicp_params* p) 
 }
 
 // ---- the two clouds -----------------------------------------------------------------------------------
-static int gicp_set_host(mi355ndt_handle* h, int role, const void* pts, size_t n, size_t stride) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  NOT_IN_STREAM(h);
+// a host cloud becomes a side's own rows (the single-pair surface's two sides, the batch's slots)
+static int gicp_side_set_host(mi355ndt_handle* h, GicpSide& sd, const void* pts, size_t n, size_t stride) {
   if ((n && (!pts || stride < 12)) || n >= (1u << 30)) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));     // nothing enqueued may still read the rows this replaces
-  GicpSide& sd = h->gicp.side[role];
   sd.set = false; sd.kf_id = -1;
   sd.n = n; sd.pitch = (n + 63) & ~(size_t)63;
   sd.index.status = CloudIndex::NO_INDEX; sd.cache.k = -1;
-  h->gicp.have_corr = false;
   if (sd.pitch) {
     HIPCHK(h, sd.rows_own.reserve(3 * sd.pitch));
     std::vector<float> rows(3 * sd.pitch, 0.f);
@@ -54,6 +52,13 @@ static int gicp_set_host(mi355ndt_handle* h, int role, const void* pts, size_t n
   }
   sd.set = true;
   return MI355NDT_OK;
+}
+static int gicp_set_host(mi355ndt_handle* h, int role, const void* pts, size_t n, size_t stride) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  const int rc = gicp_side_set_host(h, h->gicp.side[role], pts, n, stride);
+  if (rc != MI355NDT_ERR_BAD_ARG) h->gicp.have_corr = false;   // (refused arguments change nothing)
+  return rc;
 }
 static int gicp_set_keyframe(mi355ndt_handle* h, int role, int id) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
@@ -71,14 +76,16 @@ int mi355ndt_gicp_set_source_keyframe(mi355ndt_handle* h, int id) { return gicp_
 
 // a side as the host takes it: the rows, the index and the cache, the surface's own or the keyframe's
 struct GicpView { const float* rows; size_t n, pitch; CloudIndex* index; GicpCache* cache; };
-static int gicp_view(mi355ndt_handle* h, int role, const char* where, GicpView* v) {
-  GicpSide& sd = h->gicp.side[role];
-  if (!sd.set) { h->err = std::string(where) + (role == MI355NDT_GICP_TARGET ? ": no target cloud is set" : ": no source cloud is set"); return MI355NDT_ERR_STATE; }
+static int gicp_view_side(mi355ndt_handle* h, GicpSide& sd, const char* where, const char* unset, GicpView* v) {
+  if (!sd.set) { h->err = std::string(where) + unset; return MI355NDT_ERR_STATE; }
   if (sd.kf_id < 0) { *v = GicpView{sd.rows_own, sd.n, sd.pitch, &sd.index, &sd.cache}; return MI355NDT_OK; }
   mi355ndt_handle::Keyframe* kf = kf_find(h, sd.kf_id, where);
   if (!kf) return MI355NDT_ERR_BAD_ARG;
   *v = GicpView{kf->rows, kf->n, kf->pitch, &kf->index, &kf->gicp};
   return MI355NDT_OK;
+}
+static int gicp_view(mi355ndt_handle* h, int role, const char* where, GicpView* v) {
+  return gicp_view_side(h, h->gicp.side[role], where, role == MI355NDT_GICP_TARGET ? ": no target cloud is set" : ": no source cloud is set", v);
 }
 
 // the side's index (first use of the cloud) and its covariances for the current (k_correspondences, gicp_epsilon); waits for the device
@@ -186,6 +193,27 @@ static void gicp_apply_state(float t[16], const double x[6]) {
 }
 
 // ---- correspondences ----------------------------------------------------------------------------------
+// what a matching pass with transformation_ = T takes to the device (host arithmetic only)
+static GcMatch gicp_make_match(const mi355ndt_gicp_params& p, const float* G, const float* T) {
+  GcMatch a;
+  memcpy(a.G, G, sizeof a.G); memcpy(a.T, T, sizeof a.T);
+  for (int i = 0; i < 3; i++)                     // transform_R (:423-429): f64 products of the f32 entries, k ascending
+    for (int j = 0; j < 3; j++) {
+      double r = 0.0;
+      for (int k = 0; k < 4; k++) r += (double)T[k * 4 + i] * (double)G[j * 4 + k];
+      a.R[3 * i + j] = r;
+    }
+  a.thr2 = p.corr_dist_threshold * p.corr_dist_threshold;
+  a.range = (float)a.thr2 * 1.0001f + 1e-30f;     // (f32, above thr2: what lies further cannot match)
+  return a;
+}
+// ... and a cost evaluation at applyState(base, x)
+static GcCost gicp_make_cost(const double x[6], const float* base) {
+  GcCost a;
+  memcpy(a.Tx, base, 16 * sizeof(float)); memcpy(a.B, base, 16 * sizeof(float));
+  gicp_apply_state(a.Tx, x);
+  return a;
+}
 // one pass of the matching loop with transformation_ = T; the result stays resident (idx, maha, n_matched)
 static int gicp_match(mi355ndt_handle* h, const char* where, const float* G, const float* T) {
   auto& gc = h->gicp;
@@ -198,16 +226,7 @@ static int gicp_match(mi355ndt_handle* h, const char* where, const float* G, con
   if (rc) return rc;
   hipStream_t s = h->stream;
   HIPCHK(h, gc.idx.reserve(S.pitch)); HIPCHK(h, gc.maha.reserve(9 * S.pitch)); HIPCHK(h, gc.m.reserve(1));
-  GcMatch a;
-  memcpy(a.G, G, sizeof a.G); memcpy(a.T, T, sizeof a.T);
-  for (int i = 0; i < 3; i++)                     // transform_R (:423-429): f64 products of the f32 entries, k ascending
-    for (int j = 0; j < 3; j++) {
-      double r = 0.0;
-      for (int k = 0; k < 4; k++) r += (double)T[k * 4 + i] * (double)G[j * 4 + k];
-      a.R[3 * i + j] = r;
-    }
-  a.thr2 = gc.prm.corr_dist_threshold * gc.prm.corr_dist_threshold;
-  a.range = (float)a.thr2 * 1.0001f + 1e-30f;     // (f32, above thr2: what lies further cannot match)
+  const GcMatch a = gicp_make_match(gc.prm, G, T);
   HIPCHK(h, hipMemsetAsync(gc.m, 0, sizeof(int), s));
   k_gc_match<<<(unsigned)((S.n + 255) / 256), 256, 0, s>>>(S.rows, S.pitch, (int)S.n, kfi_view(*D.index, D.rows, D.pitch, D.n), a,
                                                            S.cache->cov, D.cache->cov, gc.idx, gc.maha, gc.m);
@@ -255,9 +274,7 @@ static int gicp_sums(mi355ndt_handle* h, const char* where, const double x[6], c
     gc.d_rec = gc.h_rec.dev();
     if (!gc.d_rec) { h->err = std::string(where) + ": no device view of the mapped result record"; return MI355NDT_ERR_HIP; }
   }
-  GcCost a;
-  memcpy(a.Tx, base, sizeof a.Tx); memcpy(a.B, base, sizeof a.B);
-  gicp_apply_state(a.Tx, x);
+  const GcCost a = gicp_make_cost(x, base);
   k_gc_cost<<<chunks, GC_CHUNK, 0, s>>>(S.rows, S.pitch, (int)S.n, D.rows, D.pitch, gc.idx, gc.maha, a, gc.part);
   k_gc_cost_final<<<1, 256, 0, s>>>(gc.part, (int)chunks, gc.m, gc.d_rec);
   HIPCHK(h, hipGetLastError());
@@ -289,12 +306,7 @@ static void gicp_r_derivative(const double x[6], const double R[9], double g[6])
 }
 
 // fdf (:343-378) from the sums: f /= m, g_t *= 2/m, R *= 2/m, computeRDerivative
-static int gicp_fdf(mi355ndt_handle* h, const char* where, const double x[6], const float* base, double* f, double* g) {
-  double sums[GC_SUMS];
-  int rc = gicp_sums(h, where, x, base, sums);
-  if (rc) return rc;
-  const int m = h->gicp.n_matched;
-  if (m < 1) { h->err = std::string(where) + ": no point is matched"; return MI355NDT_ERR_STATE; }
+static void gicp_fdf_sums(const double sums[GC_SUMS], int m, const double x[6], double* f, double* g) {
   if (f) *f = sums[0] / (double)m;
   if (g) {
     const double w = 2.0 / m;
@@ -303,6 +315,14 @@ static int gicp_fdf(mi355ndt_handle* h, const char* where, const double x[6], co
     for (int k = 0; k < 9; k++) R[k] = sums[4 + k] * w;
     gicp_r_derivative(x, R, g);
   }
+}
+static int gicp_fdf(mi355ndt_handle* h, const char* where, const double x[6], const float* base, double* f, double* g) {
+  double sums[GC_SUMS];
+  int rc = gicp_sums(h, where, x, base, sums);
+  if (rc) return rc;
+  const int m = h->gicp.n_matched;
+  if (m < 1) { h->err = std::string(where) + ": no point is matched"; return MI355NDT_ERR_STATE; }
+  gicp_fdf_sums(sums, m, x, f, g);
   return MI355NDT_OK;
 }
 
@@ -315,38 +335,42 @@ int mi355ndt_gicp_cost(mi355ndt_handle* h, const double* x, const float* base_co
 }
 
 // ---- align --------------------------------------------------------------------------------------------
-// OptimizationFunctorWithIndices over the device's sums; a failed evaluation is remembered and ends the align
-struct GicpFunctor {
-  mi355ndt_handle* h; const float* base; int rc = MI355NDT_OK;
-  void fdf(const double* x, double& f, double* g) { const int r = gicp_fdf(h, "gicp_align", x, base, &f, g); if (r && !rc) rc = r; }
-  double f(const double* x) { double v = 0.0; const int r = gicp_fdf(h, "gicp_align", x, base, &v, nullptr); if (r && !rc) rc = r; return v; }
-  void df(const double* x, double* g) { const int r = gicp_fdf(h, "gicp_align", x, base, nullptr, g); if (r && !rc) rc = r; }
+// The outer loop of computeTransformation (:415-504) with its BFGS driver, over an evaluator of the two device requests:
+//   int match(const float* G, const float* T, int* m)                        one matching pass with transformation_ = T; *m = the matches
+//   int sums(const double x[6], const float* base, double sums[GC_SUMS])     the thirteen sums at applyState(base, x)
+// (a non-zero return ends the align with that code).  The single-pair surface evaluates on the spot (GicpEvalNow); a slot of
+// mi355ndt_gicp_batch_align posts the request to the lockstep round (ndt_host_gicp_batch.hpp).  One copy, so both give the same bytes.
+template <typename Eval>
+struct GicpFunctor {                               // OptimizationFunctorWithIndices over the sums; a failed evaluation is remembered
+  Eval& ev; const float* base; int m; int rc = MI355NDT_OK;
+  void eval(const double* x, double* f, double* g) {
+    double sums[GC_SUMS];
+    const int r = ev.sums(x, base, sums);
+    if (r) { if (!rc) rc = r; for (int k = 0; k < GC_SUMS; k++) sums[k] = 0.0; }
+    gicp_fdf_sums(sums, m, x, f, g);
+  }
+  void fdf(const double* x, double& f, double* g) { eval(x, &f, g); }
+  double f(const double* x) { double v = 0.0; eval(x, &v, nullptr); return v; }
+  void df(const double* x, double* g) { eval(x, nullptr, g); }
 };
 
-int mi355ndt_gicp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355ndt_gicp_result* result) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  NOT_IN_STREAM(h);
-  if (!guess_colmajor || !result) return MI355NDT_ERR_BAD_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  auto& gc = h->gicp;
-  const mi355ndt_gicp_params& p = gc.prm;
-  const float* G = guess_colmajor;
+template <typename Eval>
+static int gicp_outer(Eval& ev, const mi355ndt_gicp_params& p, const float* G, float F[16], mi355ndt_gicp_result* result) {
   float T[16], prev[16];
   memcpy(T, GICP_IDENTITY, sizeof T);
   memcpy(prev, T, sizeof T);
-  int nr = 0, status = gicp_bfgs::NotStarted;
+  int nr = 0, status = gicp_bfgs::NotStarted, m = 0;
   bool converged = false;
   double delta = 0.0;
-  gc.have_final = false;
   while (!converged) {                            // computeTransformation (:415-504)
-    int rc = gicp_match(h, "gicp_align", G, T);
+    int rc = ev.match(G, T, &m);
     if (rc) return rc;
     memcpy(prev, T, sizeof T);
-    if (gc.n_matched < 4) break;                  // NotEnoughPointsException (:197-202): caught, the loop ends unconverged
+    if (m < 4) break;                             // NotEnoughPointsException (:197-202): caught, the loop ends unconverged
     double x[6] = {(double)T[12], (double)T[13], (double)T[14],                         // (:204-210) angles in f64 from the f32 entries
                    atan2((double)T[1 * 4 + 2], (double)T[2 * 4 + 2]), asin(-(double)T[0 * 4 + 2]), atan2((double)T[0 * 4 + 1], (double)T[0])};
-    GicpFunctor fn{h, G};
-    gicp_bfgs::BFGS<GicpFunctor> bfgs(fn);
+    GicpFunctor<Eval> fn{ev, G, m};
+    gicp_bfgs::BFGS<GicpFunctor<Eval>> bfgs(fn);
     int inner = 0;
     status = gicp_bfgs::minimize(bfgs, x, 1e-2, p.max_inner_iterations, &inner);
     if (fn.rc) return fn.rc;
@@ -366,16 +390,54 @@ int mi355ndt_gicp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355nd
       memcpy(prev, T, sizeof T);
     }
   }
-  float* F = gc.final_cm;                         // final = [R_t R_g | t_t + t_g] (:508-511)
-  memcpy(F, GICP_IDENTITY, sizeof T);
+  memcpy(F, GICP_IDENTITY, sizeof T);             // final = [R_t R_g | t_t + t_g] (:508-511)
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) F[c * 4 + r] = (prev[0 * 4 + r] * G[c * 4 + 0] + prev[1 * 4 + r] * G[c * 4 + 1]) + prev[2 * 4 + r] * G[c * 4 + 2];
     F[3 * 4 + r] = prev[3 * 4 + r] + G[3 * 4 + r];
   }
-  gc.have_final = true;
   memcpy(result->final_colmajor, F, sizeof T);
   result->converged = converged ? 1 : 0; result->iterations = nr; result->inner_status = status;
-  result->n_matched = gc.n_matched; result->delta = delta;
+  result->n_matched = m; result->delta = delta;
+  return MI355NDT_OK;
+}
+
+// the single-pair surface's evaluator: each request is launched and waited for where it is made
+struct GicpEvalNow {
+  mi355ndt_handle* h;
+  int match(const float* G, const float* T, int* m) { const int rc = gicp_match(h, "gicp_align", G, T); *m = h->gicp.n_matched; return rc; }
+  int sums(const double* x, const float* base, double* sums) { return gicp_sums(h, "gicp_align", x, base, sums); }
+};
+
+int mi355ndt_gicp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355ndt_gicp_result* result) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!guess_colmajor || !result) return MI355NDT_ERR_BAD_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  auto& gc = h->gicp;
+  gc.have_final = false;
+  GicpEvalNow ev{h};
+  mi355ndt_gicp_result r;
+  const int rc = gicp_outer(ev, gc.prm, guess_colmajor, gc.final_cm, &r);
+  if (rc) return rc;
+  gc.have_final = true;
+  *result = r;
+  return MI355NDT_OK;
+}
+
+// a cloud moved by F (column-major) into the caller's records
+static int gicp_move_out(mi355ndt_handle* h, const GicpView& S, const float* F, void* out_pts, size_t out_stride_bytes) {
+  auto& gc = h->gicp;
+  if (S.n == 0) return MI355NDT_OK;
+  HIPCHK(h, gc.moved.reserve(3 * S.n));
+  GcCost a;
+  memcpy(a.Tx, F, sizeof a.Tx); memcpy(a.B, F, sizeof a.B);
+  k_gc_move<<<(unsigned)((S.n + 255) / 256), 256, 0, h->stream>>>(S.rows, S.pitch, (int)S.n, a, gc.moved);
+  HIPCHK(h, hipGetLastError());
+  std::vector<float> tmp(3 * S.n);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), gc.moved, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned char* o = (unsigned char*)out_pts;
+  for (size_t i = 0; i < S.n; i++) memcpy(o + i * out_stride_bytes, &tmp[3 * i], 12);
   return MI355NDT_OK;
 }
 
@@ -389,16 +451,5 @@ int mi355ndt_gicp_get_aligned(mi355ndt_handle* h, void* out_pts, size_t out_stri
   GicpView S;
   int rc = gicp_view(h, MI355NDT_GICP_SOURCE, "gicp_get_aligned", &S);
   if (rc) return rc;
-  if (S.n == 0) return MI355NDT_OK;
-  HIPCHK(h, gc.moved.reserve(3 * S.n));
-  GcCost a;
-  memcpy(a.Tx, gc.final_cm, sizeof a.Tx); memcpy(a.B, gc.final_cm, sizeof a.B);
-  k_gc_move<<<(unsigned)((S.n + 255) / 256), 256, 0, h->stream>>>(S.rows, S.pitch, (int)S.n, a, gc.moved);
-  HIPCHK(h, hipGetLastError());
-  std::vector<float> tmp(3 * S.n);
-  HIPCHK(h, hipMemcpyAsync(tmp.data(), gc.moved, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  unsigned char* o = (unsigned char*)out_pts;
-  for (size_t i = 0; i < S.n; i++) memcpy(o + i * out_stride_bytes, &tmp[3 * i], 12);
-  return MI355NDT_OK;
+  return gicp_move_out(h, S, gc.final_cm, out_pts, out_stride_bytes);
 }

@@ -1,4 +1,4 @@
-"""Loop-closure verification on the batch surface.
+"""Loop-closure verification on the batch surfaces (NDT: verify_candidates; GICP: verify_candidates_gicp).
 
 The reference's loop detector (include/global_graph/loop_detector.hpp) verifies the candidate keyframes of a new keyframe one by one: the
 new keyframe is the target, every candidate in turn is the source, aligned from the guess `new.inverse() * candidate` (z zeroed) and
@@ -100,6 +100,49 @@ def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range
         (engine.batch_set_source_keyframe if is_id(s) else engine.batch_set_source)(k, s)
     res = engine.batch_align(G[slots])
     sc, _ = engine.batch_fitness_scores(max_range)
+    converged, scores, finals = [False] * K, [DBL_MAX] * K, [None] * K
+    for k, c in enumerate(slots):
+        converged[c], scores[c], finals[c] = res[k]["converged"], float(sc[k]), res[k]["final"]
+    if bow is None:
+        return select_matching(converged, scores, finals, thresh)
+    return select_matching_and_bow(converged, scores, finals, bow, thresh)
+
+
+def verify_candidates_gicp(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
+    """verify_candidates for registration_method = GICP_OMP: the same arguments, the same tuple.  The target becomes the GICP surface's
+    target, candidate k the source of slot k of ONE gicp_batch_align (the K optimisers advance in lockstep: mi355ndt_gicp_batch_align),
+    then ONE keyframe_fitness_scores([target] * K, candidates, finals, max_range) -- getFitnessScore at each final transformation, the
+    kd-tree over the target -- and select_matching / select_matching_and_bow as they are.  Host clouds become keyframes for the call
+    (keyframe_add) and are released afterwards.  The engine's GICP parameters (gicp_set_params) are the registration's."""
+    K = len(candidates)
+    if K == 0:
+        return None, None, DBL_MAX, 0
+    G = np.asarray(guesses, np.float32)
+    if G.shape != (K, 4, 4):
+        raise ValueError(f"guesses must be [{K},4,4]")
+    slots = list(range(K)) if bow is None else list(dict.fromkeys(int(c) for _, c in bow))
+    if not slots:
+        return None, None, DBL_MAX, 0
+    is_id = lambda c: isinstance(c, (int, np.integer))
+    own = []
+
+    def resident(c):
+        if is_id(c):
+            return int(c)
+        own.append(engine.keyframe_add(ndt._as_points(c)))
+        return own[-1]
+    try:
+        tgt = resident(target)
+        ids = [resident(candidates[c]) for c in slots]
+        engine.gicp_set_target(keyframe=tgt)
+        engine.gicp_batch_reserve(len(slots))
+        for k, i in enumerate(ids):
+            engine.gicp_batch_set_source(k, keyframe=i)
+        res = engine.gicp_batch_align(G[slots])
+        sc, _ = engine.keyframe_fitness_scores([tgt] * len(slots), ids, [r["final"] for r in res], max_range)
+    finally:
+        for i in own:
+            engine.keyframe_release(i)
     converged, scores, finals = [False] * K, [DBL_MAX] * K, [None] * K
     for k, c in enumerate(slots):
         converged[c], scores[c], finals[c] = res[k]["converged"], float(sc[k]), res[k]["final"]

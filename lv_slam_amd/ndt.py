@@ -121,7 +121,10 @@ SYMBOLS = [
     "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
     "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
     "mi355ndt_gicp_get_aligned",
+    "mi355ndt_gicp_batch_reserve", "mi355ndt_gicp_batch_set_source", "mi355ndt_gicp_batch_set_source_keyframe", "mi355ndt_gicp_batch_align",
+    "mi355ndt_gicp_batch_get_aligned", "mi355ndt_gicp_batch_stats",
 ]
+GICP_BATCH_MAX = 64            # MI355NDT_GICP_BATCH_MAX: slots of one mi355ndt_gicp_batch_align
 GICP_TARGET, GICP_SOURCE = 0, 1  # mi355ndt_gicp_covariances' role
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
 OPT_DEBUG_ASYNC_ABORT = 3      # mi355ndt_option (test hook): the wave that claims this position of ring 0 gives up -> the batch is re-run in rounds
@@ -183,6 +186,12 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_gicp_cost.argtypes = [vp, vp, vp, C.POINTER(C.c_double), vp]
     L.mi355ndt_gicp_align.argtypes = [vp, vp, C.POINTER(GicpResult)]
     L.mi355ndt_gicp_get_aligned.argtypes = [vp, vp, sz]
+    L.mi355ndt_gicp_batch_reserve.argtypes = [vp, i]
+    L.mi355ndt_gicp_batch_set_source.argtypes = [vp, i, vp, sz, sz]
+    L.mi355ndt_gicp_batch_set_source_keyframe.argtypes = [vp, i, i]
+    L.mi355ndt_gicp_batch_align.argtypes = [vp, vp, vp]
+    L.mi355ndt_gicp_batch_get_aligned.argtypes = [vp, i, vp, sz]
+    L.mi355ndt_gicp_batch_stats.argtypes = [vp, C.POINTER(i), vp]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
@@ -309,6 +318,7 @@ class Engine:
             raise NDTError(rc, "mi355ndt_create")
         self._keep = []
         self._gicp_n = [0, 0]                       # points of the GICP surface's target and source
+        self._gicp_batch_n = []                     # points of the GICP batch's slots
 
     def close(self):
         if getattr(self, "h", None):
@@ -562,7 +572,7 @@ class Engine:
                                                             inliers.ctypes.data_as(C.c_void_p)), "keyframe_fitness_scores")
         return scores[:E], inliers[:E]
 
-    # -- GICP (pclomp::GeneralizedIterativeClosestPoint, registration_method = GICP_OMP): one pair, synchronous
+    # -- GICP (pclomp::GeneralizedIterativeClosestPoint, registration_method = GICP_OMP): one pair, synchronous (the batch form follows)
     def gicp_set_params(self, p: GicpParams):
         self._chk(self.lib.mi355ndt_gicp_set_params(self.h, C.byref(p)), "gicp_set_params")
 
@@ -623,6 +633,49 @@ class Engine:
         if len(out):
             self._chk(self.lib.mi355ndt_gicp_get_aligned(self.h, out.ctypes.data_as(C.c_void_p), 12), "gicp_get_aligned")
         return out
+
+    # -- GICP, all candidates of a loop check in one lockstep batch (the target and the parameters are the single-pair surface's)
+    def gicp_batch_reserve(self, n_slots: int):
+        self._chk(self.lib.mi355ndt_gicp_batch_reserve(self.h, int(n_slots)), "gicp_batch_reserve")
+        self._gicp_batch_n = [0] * int(n_slots)
+
+    def gicp_batch_set_source(self, slot: int, cloud=None, keyframe=None):
+        """candidate `slot`: a host cloud, or a resident keyframe by id (its index and covariances stay with the keyframe)"""
+        if keyframe is not None:
+            self._chk(self.lib.mi355ndt_gicp_batch_set_source_keyframe(self.h, int(slot), int(keyframe)), "gicp_batch_set_source_keyframe")
+            n = self.keyframe_get(int(keyframe), fetch=False)
+        else:
+            a = _as_points(cloud)
+            self._chk(self.lib.mi355ndt_gicp_batch_set_source(self.h, int(slot), a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0]), "gicp_batch_set_source")
+            n = a.shape[0]
+        self._gicp_batch_n[int(slot)] = int(n)
+
+    def gicp_batch_align(self, guesses) -> list:
+        """one lockstep align of every slot from guesses [K,4,4]: gicp_align's dict per slot, the same bytes as the single-pair surface gives"""
+        K = len(self._gicp_batch_n)
+        G = np.asarray(guesses, np.float32)
+        if G.shape != (K, 4, 4):
+            raise ValueError(f"guesses must be [{K},4,4]")
+        g = np.ascontiguousarray(np.transpose(G, (0, 2, 1))).reshape(max(K, 1), 16) if K else np.zeros((1, 16), np.float32)
+        res = (GicpResult * max(K, 1))()
+        self._chk(self.lib.mi355ndt_gicp_batch_align(self.h, g.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)), "gicp_batch_align")
+        return [dict(final=np.array(r.final_colmajor, np.float32).reshape(4, 4).T.copy(), converged=bool(r.converged), iterations=r.iterations,
+                     inner_status=r.inner_status, n_matched=r.n_matched, delta=r.delta) for r in res[:K]]
+
+    def gicp_batch_get_aligned(self, slot: int) -> np.ndarray:
+        if not 0 <= int(slot) < len(self._gicp_batch_n):
+            self._chk(self.lib.mi355ndt_gicp_batch_get_aligned(self.h, int(slot), np.zeros(3, np.float32).ctypes.data_as(C.c_void_p), 12), "gicp_batch_get_aligned")
+        out = np.zeros((self._gicp_batch_n[int(slot)], 3), np.float32)
+        if len(out):
+            self._chk(self.lib.mi355ndt_gicp_batch_get_aligned(self.h, int(slot), out.ctypes.data_as(C.c_void_p), 12), "gicp_batch_get_aligned")
+        return out
+
+    def gicp_batch_stats(self):
+        """(rounds, requests[K]) of the last batch align: waits on the device; device requests (matching passes + cost evaluations) per slot"""
+        K = len(self._gicp_batch_n)
+        rounds, req = C.c_int(0), np.zeros(max(K, 1), np.int32)
+        self._chk(self.lib.mi355ndt_gicp_batch_stats(self.h, C.byref(rounds), req.ctypes.data_as(C.c_void_p)), "gicp_batch_stats")
+        return rounds.value, req[:K].copy()
 
     # -- parity hooks
     def derivatives(self, p):

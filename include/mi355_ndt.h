@@ -286,7 +286,8 @@ int mi355ndt_batch_set_target(mi355ndt_handle* h, int pair, const void* pts, siz
 int mi355ndt_batch_set_source(mi355ndt_handle* h, int pair, const void* pts, size_t n, size_t stride_bytes);
 /* A whole batch of host clouds in one call: pairs first_pair .. first_pair + n - 1, one pointer and one point count per cloud
  * (`targets` or `sources` may be NULL to upload only the other side), records `stride_bytes` apart; n_threads staging threads
- * of the engine's own (<= 0: 8) share the pairs.  Same asynchrony as the per-cloud calls. */
+ * of the engine's own (<= 0: 8) share the pairs.  Same asynchrony as the per-cloud calls.  Every pair's arguments are checked before anything
+ * is staged: a NULL pointer with a count, a stride below 12 or a count above what was reserved returns MI355NDT_ERR_BAD_ARG with the batch unchanged. */
 int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const void* const* targets, const size_t* target_counts,
                               const void* const* sources, const size_t* source_counts, size_t stride_bytes, int n_threads);
 /* zero-copy: use device-resident SoA buffers laid out [pair][3][pitch] (x row, y row, z row of `pitch`

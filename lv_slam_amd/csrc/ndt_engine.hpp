@@ -1,5 +1,6 @@
 // ndt_engine.hpp -- the engine behind a handle: StreamCtx / StreamState / mi355ndt_handle, the error and state macros, the constants, and the
-// one home of every decision about a configuration that more than one surface takes (neighbor_K, is_pca_kd, async_served, launch_slots, ...).
+// one home of every decision about a configuration that more than one surface takes (neighbor_K, async_served, launch_slots, ...) and of the
+// two writers of the slots' cloud bookkeeping (cloud_changed, clouds_reset).
 #pragma once
 
 // ------------------------------------------------------------------------------------ host side
@@ -112,11 +113,9 @@ struct mi355ndt_handle {
   int *d_tgt_cnt = nullptr, *d_src_cnt = nullptr;   // views: d_tgt_cnt_own / d_src_cnt_own or the stream context's input block
   std::vector<int> h_tgt_cnt, h_src_cnt;
   std::vector<int> up_tgt_cnt, up_src_cnt;        // what d_tgt_cnt / d_src_cnt currently hold (uploads are skipped when unchanged)
-  bool targets_built = false, have_target = false, have_source = false;
+  bool have_target = false, have_source = false;  // written by cloud_changed / clouds_reset (below) alone, with the host counts
+  GridsBuilt built{};                             // what the resident grids hold (ndt_grid_state.hpp): filled at the end of build_targets_impl, asked by ensure_grids
   bool aligned_once = false;                      // d_state / d_results hold the outcome of an align of the CURRENT batch
-  bool icov64_built = false;                      // ... and the f64 inverse covariances computeHessian reads (live More-Thuente)
-  bool cent_built = false;                        // last target build also produced the f32 leaf centroids (KDTREE mode)
-  float grid_resolution = 0.f;                    // leaf size the resident grids were built with (setResolution without a source keeps them: ndt_omp.h:126-136)
 
   // build workspace
   unsigned* d_minmax = nullptr;                  // view: a slice of d_word_off (zeroed together before every build)
@@ -130,14 +129,13 @@ struct mi355ndt_handle {
   DevBuf<unsigned> d_seg_start; DevBuf<double> d_sums;
   DevBuf<unsigned> d_heads, d_head_cnt;          // k_mark's run heads per slice
   DevBuf<float> d_cent; DevBuf<double> d_icov64;
-  DevBuf<int> d_kdw; bool kdw_built = false;     // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
+  DevBuf<int> d_kdw;                             // per-leaf weights for ndt_pca + KDTREE (dead leaves included)
   DevBuf<float4> d_sorted; bool leaf_sorted = false;   // MI355NDT_LEAF_SORTED: the sorted order as points (k_sorted_points)
   DevBuf<unsigned> d_rs_hist, d_rs_offs;         // segmented radix sort: tile histograms / offsets
-  int last_cb = 0;
   // fitness scores (one pair or a batch, fit_scores): the block partials; the occupied-cell index of every target (ndt_fitness.hpp), built on the
   // first call after a target build; the launch's item table and transforms
   DevBuf<double> d_fit;
-  DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns; bool fit_index_ready = false;
+  DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns;
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
   // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)
   DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0;
@@ -200,7 +198,7 @@ struct mi355ndt_handle {
   unsigned debug_abort_pos = 0xFFFFFFFFu;         // MI355NDT_OPT_DEBUG_ASYNC_ABORT (test hook): the wave that claims this position of ring 0 gives up
   unsigned debug_ring_mask = 0xFFu;               // MI355NDT_OPT_DEBUG_ASYNC_RINGS (test hook): rings whose workgroups take part
   int arith = 0;                                  // MI355NDT_OPT_ARITH: 0 = the reference recipe's arithmetic, one rounding per operation; 1 = tolerance arithmetic (ndt_sweep.hpp: eval_hit_fast)
-  DevBuf<VoxelRecF> d_recs_fast; bool recs_fast_built = false;   // ... and the records its sweeps read (k_voxels writes them beside d_recs)
+  DevBuf<VoxelRecF> d_recs_fast;                  // ... and the records its sweeps read (k_voxels writes them beside d_recs)
   int f32_sum_order = 0;                          // MI355NDT_OPT_F32_SUM_ORDER: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
   double gauss_last[3] = {0, 0, 0};               // gauss_d1_/d2_/d3_ as the constructor / the last computeTransformation left them (calculateScore reads them)
   DevBuf<float> d_score_pts; DevBuf<double> d_score_part;   // calculateScore workspace
@@ -252,7 +250,6 @@ struct mi355ndt_handle {
   bool counts_preloaded = false;                  // the parent has put this batch's point counts (and guesses) on the device already
   bool build_stamped = false;                    // stream mode + profiling: build times come from stamps in the launch's status slot, not from events
   bool word_off_cleared = false;                 // stream mode: k_stream_inputs has cleared d_word_off for the next build (no fill)
-  size_t last_total_words = 0;                    // of the last synchronous build
 
   // stream mode: the session (null outside mi355ndt_stream_begin ... mi355ndt_stream_end) and the options it starts with
   std::unique_ptr<StreamState> ss;
@@ -333,15 +330,32 @@ static int check_params(const mi355ndt_params& p) {
   return MI355NDT_OK;
 }
 
-// impl2:888: the More-Thuente loop (and computeHessian after it) runs iff !(step_max - step_min > 0), step_min = eps/2
-static bool mt_is_live(const mi355ndt_params& p) { return !((p.step_size - p.trans_epsilon / 2) > 0); }
-// MI355NDT_OPT_ARITH = 1 is served for DIRECT1 / DIRECT7 with the dead More-Thuente loop (every configuration lv_slam ships); every other configuration
-// ignores the option altogether: exact kernels, ordered leaf sums, the exact records alone
-static bool fast_served(const mi355ndt_handle* h) {
-  return h->arith == 1 && (h->prm.neighbor_mode == MI355NDT_DIRECT1 || h->prm.neighbor_mode == MI355NDT_DIRECT7) && !mt_is_live(h->prm);
+// does the tolerance arithmetic (MI355NDT_OPT_ARITH = 1) serve this engine's configuration?  (mt_is_live, is_pca_kd, grid_extras: ndt_grid_state.hpp)
+static bool fast_served(const mi355ndt_handle* h) { return grid_extras(h->prm, h->arith).recs_fast; }
+
+// "Do the grids serve this call?" -- asked by ensure_grids (ndt_host_build.hpp) and nowhere else; it builds the wanted flavour when they do not.
+//   GRIDS_ANY     any valid grid will do (the fitness scores read the base records alone); none: this configuration's is built
+//   GRIDS_CONFIG  what this configuration's sweeps read (the aligns, the derivative hooks, mi355ndt_set_params)
+//   GRIDS_LIVE    the flavour of a live More-Thuente loop, f32 centroids + f64 inverse covariances (calculateScore, computeHessian)
+enum GridWant { GRIDS_ANY, GRIDS_CONFIG, GRIDS_LIVE };
+static int ensure_grids(mi355ndt_handle* h, GridWant want);
+// A slot's cloud changed: `n` consecutive slots of one side from `first_pair` now hold counts[0 .. n) points.  A new target leaves the grids
+// describing a cloud that is gone.  (Under up_mtx: mi355ndt_batch_set_target / _source may run on several threads, distinct pairs.)
+template <typename N>
+static void cloud_changed(mi355ndt_handle* h, bool tgt, int first_pair, int n, const N* counts) {
+  std::lock_guard<std::mutex> lk(h->up_mtx);
+  std::vector<int>& cnt = tgt ? h->h_tgt_cnt : h->h_src_cnt;
+  for (int k = 0; k < n; k++) cnt[(size_t)(first_pair + k)] = (int)counts[k];
+  (tgt ? h->have_target : h->have_source) = true;
+  if (tgt) h->built.valid = false;
 }
-// ndt_pca + KDTREE: order-dependent weights -- its own per-leaf weights from the build (d_kdw), its own sweep kernel (ndt_sweep_kd.hpp)
-static bool is_pca_kd(const mi355ndt_params& p) { return p.neighbor_mode == MI355NDT_KDTREE && p.variant == MI355NDT_VARIANT_PCA; }
+static void cloud_changed(mi355ndt_handle* h, bool tgt, int pair, size_t count) { cloud_changed(h, tgt, pair, 1, &count); }
+// The slots of a side hold nothing any more (their rows were re-allocated, the batch got another shape, an alias ended).
+static void clouds_reset(mi355ndt_handle* h, bool tgt, bool src) {
+  std::lock_guard<std::mutex> lk(h->up_mtx);
+  if (tgt) { std::fill(h->h_tgt_cnt.begin(), h->h_tgt_cnt.end(), 0); h->have_target = false; h->built.valid = false; }
+  if (src) { std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0); h->have_source = false; }
+}
 // May an align of this configuration be ONE persistent launch (ndt_async.hpp)?  Asked by mi355ndt_batch_align and by mi355ndt_stream_begin.
 static bool async_served(const mi355ndt_handle* h) { return h->async_align && !mt_is_live(h->prm) && !is_pca_kd(h->prm); }
 // algorithmic bytes of sweeping `points` points: every point is streamed (12 B) and probes K table words

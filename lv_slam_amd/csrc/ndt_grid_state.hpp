@@ -1,0 +1,38 @@
+// ndt_grid_state.hpp -- the record of what the resident target grids hold (GridsBuilt), the one statement of what a configuration needs of
+// them (grid_extras) and the one question asked of the record (grids_serve).  Nothing of HIP in this file: it compiles into the library's
+// host side and into tests/cpp/grid_state_main.cpp.
+#pragma once
+#include "mi355_ndt.h"
+
+// impl2:888: the More-Thuente loop (and computeHessian after it) runs iff !(step_max - step_min > 0), step_min = eps/2
+static inline bool mt_is_live(const mi355ndt_params& p) { return !((p.step_size - p.trans_epsilon / 2) > 0); }
+// ndt_pca + KDTREE: order-dependent weights -- its own per-leaf weights from the build (d_kdw), its own sweep kernel (ndt_sweep_kd.hpp)
+static inline bool is_pca_kd(const mi355ndt_params& p) { return p.neighbor_mode == MI355NDT_KDTREE && p.variant == MI355NDT_VARIANT_PCA; }
+
+// what a target build can make beside the base records (grid descriptors, bitmap words, the exact voxel records)
+struct GridExtras {
+  bool cent;        // f32 leaf centroids: the KDTREE probe, computeHessian, calculateScore
+  bool icov64;      // f64 inverse covariances: computeHessian, calculateScore
+  bool kdw;         // per-leaf weights of ndt_pca + KDTREE (dead leaves included)
+  bool recs_fast;   // the tolerance arithmetic's records (and, without centroids, its tree leaf sums)
+};
+// What a configuration needs: a pure function of (parameters, MI355NDT_OPT_ARITH, live).  live: "as if the More-Thuente loop were live", the
+// flavour calculateScore and computeHessian read whatever the configuration.  MI355NDT_OPT_ARITH = 1 is served for DIRECT1 / DIRECT7 with the dead
+// More-Thuente loop (every configuration lv_slam ships); every other configuration ignores the option altogether: exact kernels, ordered leaf
+// sums, the exact records alone.
+static inline GridExtras grid_extras(const mi355ndt_params& p, int arith, bool live = false) {
+  const bool mt_live = live || mt_is_live(p), direct_1_7 = p.neighbor_mode == MI355NDT_DIRECT1 || p.neighbor_mode == MI355NDT_DIRECT7;
+  return {p.neighbor_mode == MI355NDT_KDTREE || mt_live, mt_live, is_pca_kd(p), arith == 1 && direct_1_7 && !mt_live};
+}
+
+struct GridsBuilt {
+  bool valid;                   // the grids describe the target clouds the slots hold now
+  GridExtras made;              // what the last build made beside the base records
+  float leaf;                   // leaf size it used (setResolution without a source keeps the grids: ndt_omp.h:126-136)
+  int cb;                       // cell-key bits it sorted
+  size_t total_words;           // bitmap words of all its grids (a planned build of the stream: its plan's)
+  bool fit_index;               // the fitness scores' occupied-cell index has been built over it (ndt_fitness.hpp)
+};
+static inline bool grids_serve(const GridsBuilt& b, const GridExtras& need) {
+  return b.valid && (b.made.cent || !need.cent) && (b.made.icov64 || !need.icov64) && (b.made.kdw || !need.kdw) && (b.made.recs_fast || !need.recs_fast);
+}

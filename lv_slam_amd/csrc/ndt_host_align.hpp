@@ -110,11 +110,10 @@ static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt
 static int batch_align_impl(mi355ndt_handle* h, const float* guesses, mi355ndt_result* out) {
   if (!guesses || !out) return MI355NDT_ERR_BAD_ARG;
   if (h->n_pairs <= 0 || !h->d_tgt || !h->d_src) return MI355NDT_ERR_STATE;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
   const bool mt_live = mt_is_live(h->prm);                       // impl2:888: More-Thuente loop + computeHessian are live
-  if (!h->targets_built || (mt_live && !h->icov64_built) || (is_pca_kd(h->prm) && !h->kdw_built) || (fast_served(h) && !h->recs_fast_built)) { int rc = mi355ndt_batch_build_targets(h); if (rc) return rc; }
-  int rc = prep_align_ws(h);
+  int rc = ensure_grids(h, GRIDS_CONFIG);
+  if (rc) return rc;
+  rc = prep_align_ws(h);
   if (rc) return rc;
   const int B = h->n_pairs;
   hipStream_t s = h->stream;
@@ -255,12 +254,8 @@ static int set_single(mi355ndt_handle* h, bool tgt, const void* pts, size_t n, s
   NOT_IN_STREAM(h);
   if ((!pts && n) || (n && stride < 12) || n >= (1u << 31)) return MI355NDT_ERR_BAD_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = ensure_single(h, tgt, n);
-  if (rc) return rc;
-  rc = tgt ? mi355ndt_batch_set_target(h, 0, pts, n, stride) : mi355ndt_batch_set_source(h, 0, pts, n, stride);
-  if (rc) return rc;
-  (tgt ? h->have_target : h->have_source) = true;
-  return MI355NDT_OK;
+  const int rc = ensure_single(h, tgt, n);
+  return rc ? rc : batch_set_side(h, tgt, 0, pts, n, stride);
 }
 int mi355ndt_set_target(mi355ndt_handle* h, const void* pts, size_t n, size_t stride) {
   const int rc = set_single(h, true, pts, n, stride);
@@ -292,7 +287,6 @@ int mi355ndt_promote_source_to_target(mi355ndt_handle* h) {
   if (rc) return rc;
   rc = rows_into_slot(h, true, 0, h->d_src_own, h->src_pitch, m);
   if (rc) return rc;
-  h->h_tgt_cnt[0] = (int)m; h->have_target = true; h->targets_built = false;
   h->P.cloud_promotions++;
   return mi355ndt_batch_build_targets(h);
 }

@@ -1,9 +1,10 @@
 // ndt_host_build.hpp -- the target build's host side: workspace, the one wait for the grid sizes (or the stream's plan instead), the kernel chain
-// of ndt_build.hpp / ndt_segsort.hpp.
+// of ndt_build.hpp / ndt_segsort.hpp; ensure_grids, through which every surface that reads the grids asks for them.
 #pragma once
 
 // ---- target build -----------------------------------------------------------------------------
-static int build_targets_impl(mi355ndt_handle* h) {
+// `make`: what to build beside the base records (ndt_grid_state.hpp).  h->built is filled here, at the end, and nowhere else.
+static int build_targets_impl(mi355ndt_handle* h, const GridExtras make) {
   if (h->n_pairs <= 0 || !h->d_tgt) return MI355NDT_ERR_STATE;
   HIPCHK(h, hipSetDevice(h->device));
   { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
@@ -36,6 +37,7 @@ static int build_targets_impl(mi355ndt_handle* h) {
   const bool build_events = h->prof && !(h->build_stamped && h->async_build);   // (the stream's builds are stamped by the kernels around them)
   if (build_events) HIPCHK(h, ev_begin(h, h->ev_build));
   const int gx = (int)((pitch + 255) / 256);
+  h->built.valid = false;                         // (the kernels below overwrite what it describes: an error exit leaves no valid-looking grids)
   if (!h->word_off_cleared) HIPCHK(h, hipMemsetAsync(h->d_word_off, 0, (2 + 6 * (size_t)h->cap_pairs) * sizeof(unsigned), s));   // (stream mode: k_stream_inputs did)
   h->word_off_cleared = false;
   k_minmax<<<dim3(std::max(1, std::min((gx + 3) / 4 / MM_ILP, 64)), B), 256, 0, s>>>(h->d_tgt, pitch, h->d_tgt_cnt, h->d_minmax);
@@ -55,23 +57,13 @@ static int build_targets_impl(mi355ndt_handle* h) {
     total_words = h->h_pin_u[0];
     cb = std::max(1, ceil_log2(h->h_pin_u[1] + 1u));   // cell field: every cell index + the all-ones "not binned" value
     if (h->async_build) cb = std::max(cb, h->plan_cb);        // (a wider field sorts the same order: the plan only ever grows)
-    h->last_total_words = total_words;
     if (h->d_bstat) HIPCHK(h, hipMemsetAsync(h->d_bstat + 3, 0, sizeof(unsigned), s));
   }
   if (total_words > h->d_words.cap) HIPCHK(h, h->d_words.reserve(std::max(total_words, (size_t)1024)));
   if (total_words) HIPCHK(h, hipMemsetAsync(h->d_words, 0, total_words * sizeof(BitWord), s));
-  const bool mt_live = mt_is_live(h->prm);
-  const bool want_cent = h->prm.neighbor_mode == MI355NDT_KDTREE || mt_live;   // f32 leaf centroids: KDTREE probe, computeHessian
-  h->cent_built = want_cent;
-  h->icov64_built = mt_live;
-  if (mt_live) HIPCHK(h, h->d_icov64.reserve(h->d_recs.cap * 9));
-  // the tolerance arithmetic's records and tree leaf sums only where its sweeps are served (DIRECT1 / DIRECT7, dead More-Thuente loop): every other
-  // configuration ignores the option altogether -- ordered sums, the exact records alone, results word for word those of the option off
-  const bool fast_recs = fast_served(h);
+  const bool want_cent = make.cent, fast_recs = make.recs_fast, want_kdw = make.kdw;
+  if (make.icov64) HIPCHK(h, h->d_icov64.reserve(h->d_recs.cap * 9));
   if (fast_recs) HIPCHK(h, h->d_recs_fast.reserve(h->d_recs.cap));
-  h->recs_fast_built = fast_recs;
-  const bool want_kdw = is_pca_kd(h->prm);
-  h->kdw_built = want_kdw;
   if (want_kdw) HIPCHK(h, h->d_kdw.reserve(h->d_recs.cap));
   {
     unsigned *ka = h->d_keys_a, *kb = h->d_keys_b;
@@ -97,6 +89,9 @@ static int build_targets_impl(mi355ndt_handle* h) {
     k_rank<<<B, 1024, 0, s>>>(h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, h->d_seg_start);
     // leaf-sum workgroups per target: 64 keeps ~4 targets (3 MB of points) in flight per XCD, inside its 4 MB L2
     const int lb = std::max(1, std::min((int)((rpp + LS_WAVES - 1) / LS_WAVES), 64));
+    auto leafsum = [&](auto kern, const unsigned* vals) {
+      kern<<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, vals, h->d_grid, h->d_seg_start, h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
+    };
     if (fast_recs && !want_cent && !h->leaf_sorted) {      // tolerance arithmetic: the leaf sums as a tree (ndt_build.hpp)
       k_leafsum_tree<<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, h->d_vals_b, h->d_grid, h->d_seg_start, h->d_sums, h->d_vox_idx, h->d_vox_n, cb, lb, B);
     } else if (h->leaf_sorted) {
@@ -104,19 +99,12 @@ static int build_targets_impl(mi355ndt_handle* h) {
       HIPCHK(h, h->d_sorted.reserve(total));
       const int gb = std::max(1, std::min((int)((pitch + 256 * RUN_ILP - 1) / (256 * RUN_ILP)), 64));
       k_sorted_points<<<xcd_grid(gb, B), 256, 0, s>>>(h->d_tgt, pitch, h->d_vals_b, h->d_sorted, gb, B);
-      const unsigned* sp = reinterpret_cast<const unsigned*>(h->d_sorted.p);
-      if (want_cent) k_leafsum<unsigned, true, true><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, sp, h->d_grid, h->d_seg_start,
-                                                                                            h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
-      else k_leafsum<unsigned, false, true><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, sp, h->d_grid, h->d_seg_start,
-                                                                                  h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
-    } else if (want_cent) k_leafsum<unsigned, true><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, h->d_vals_b, h->d_grid, h->d_seg_start,
-                                                                                    h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
-    else k_leafsum<unsigned, false><<<xcd_grid(lb, B), 64 * LS_WAVES, 0, s>>>(h->d_tgt, pitch, kb, h->d_vals_b, h->d_grid, h->d_seg_start,
-                                                                          h->d_sums, h->d_vox_idx, h->d_vox_n, cb, h->d_cent, lb, B);
+      leafsum(want_cent ? k_leafsum<unsigned, true, true> : k_leafsum<unsigned, false, true>, reinterpret_cast<const unsigned*>(h->d_sorted.p));
+    } else leafsum(want_cent ? k_leafsum<unsigned, true> : k_leafsum<unsigned, false>, h->d_vals_b);
   }
   k_voxels<<<dim3((unsigned)((rpp + 255) / 256), B), 256, 0, s>>>(h->d_grid, h->d_sums, h->d_recs, h->d_vox_n,
                                                                   h->prm.min_covar_eigvalue_mult, h->prm.variant == MI355NDT_VARIANT_PCA,
-                                                                  mt_live ? h->d_icov64 : nullptr, want_kdw ? h->d_kdw : nullptr, fast_recs ? h->d_recs_fast : nullptr);
+                                                                  make.icov64 ? h->d_icov64 : nullptr, want_kdw ? h->d_kdw : nullptr, fast_recs ? h->d_recs_fast : nullptr);
   HIPCHK(h, hipGetLastError());
   if (h->prof) {
     if (build_events) HIPCHK(h, ev_end(h, h->ev_build));
@@ -125,18 +113,25 @@ static int build_targets_impl(mi355ndt_handle* h) {
     // B_build: minmax 12 + binning 12 + key write 12 + sort r/w + grouped gather 16 per point (+ records)
     h->P.build_alg_bytes += pts * (12 + 12 + 4 + 16);
   }
-  h->targets_built = true;
-  h->grid_resolution = h->prm.resolution;
-  h->fit_index_ready = false;
-  h->last_cb = cb;
+  h->built = GridsBuilt{true, make, h->prm.resolution, cb, total_words, false};
   return compute_enqueued(h);                     // asynchronous: a later upload into these rows has to wait for the kernels above
 }
 
-int mi355ndt_batch_build_targets(mi355ndt_handle* h) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+static int build_targets(mi355ndt_handle* h, const GridExtras make) {
   NOT_IN_STREAM(h);
-  const int rc = build_targets_impl(h);
+  const int rc = build_targets_impl(h, make);
   // an error exit may leave kernels queued that still read the cloud rows: later uploads have to wait for them all the same
   if (rc != MI355NDT_OK && h->ev_compute) (void)compute_enqueued(h);
   return rc;
+}
+int mi355ndt_batch_build_targets(mi355ndt_handle* h) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  return build_targets(h, grid_extras(h->prm, h->arith));
+}
+
+static int ensure_grids(mi355ndt_handle* h, GridWant want) {
+  HIPCHK(h, hipSetDevice(h->device));             // the prologue of every call that reads the grids: the engine's device, the uploads so far
+  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }   // in front of the compute stream (the cloud rows are read as well)
+  const GridExtras make = grid_extras(h->prm, h->arith, want == GRIDS_LIVE);
+  return grids_serve(h->built, want == GRIDS_ANY ? GridExtras{} : make) ? (int)MI355NDT_OK : build_targets(h, make);
 }

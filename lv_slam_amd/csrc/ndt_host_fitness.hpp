@@ -18,9 +18,7 @@ static void fit_reduce(const double* part, int nblk, double* score, long long* n
 // their arguments and the handle's state.  Per pair: the block partials of k_fitness_batch (a grid) or k_fitness_brute_batch (none), summed
 // on the host in block order from 0.0; no point to score on either side, or none finite in the target (GRID_EMPTY): (DBL_MAX, 0), no launch.
 static int fit_scores(mi355ndt_handle* h, const float* T, double max_range, double* scores, long long* n_inliers) {
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
-  if (!h->targets_built) { int rc = mi355ndt_batch_build_targets(h); if (rc) return rc; }
+  { int rc = ensure_grids(h, GRIDS_ANY); if (rc) return rc; }
   const int B = h->n_pairs;
   const size_t tp = h->tgt_pitch;
   hipStream_t s = h->stream;
@@ -46,16 +44,16 @@ static int fit_scores(mi355ndt_handle* h, const float* T, double max_range, doub
     part0[b] = n_part;
     n_part += nblk[b];
   }
-  if (any_ok && !h->fit_index_ready) {
+  if (any_ok && !h->built.fit_index) {
     HIPCHK(h, h->d_fwords.reserve(total_words));
     HIPCHK(h, h->d_fruns.reserve((size_t)B * (tp + 1)));
     HIPCHK(h, hipMemsetAsync(h->d_fwords, 0, total_words * sizeof(BitWord), s));
     const dim3 pg((unsigned)((tp + 255) / 256), (unsigned)B);
-    k_fit_mark<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->last_cb);
+    k_fit_mark<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->built.cb);
     k_fit_rank<<<B, 1024, 0, s>>>(h->d_grid, h->d_fwords);
-    k_fit_runs<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->d_fruns, h->last_cb);
+    k_fit_runs<<<pg, 256, 0, s>>>(h->d_keys_b, tp, h->d_grid, h->d_fwords, h->d_fruns, h->built.cb);
     HIPCHK(h, hipGetLastError());
-    h->fit_index_ready = true;
+    h->built.fit_index = true;
   }
   // item tables of the two launches: a grid -> k_fitness_batch, no grid (a target without one has no leaf size either) -> k_fitness_brute_batch
   std::vector<int> tab, tab_brute;
@@ -133,20 +131,13 @@ int mi355ndt_calculate_score(mi355ndt_handle* h, const void* pts, size_t n, size
   if (!score || (!pts && n) || (n && stride < 12) || n >= (1u << 31)) return MI355NDT_ERR_BAD_ARG;
   if (h->n_pairs != 1 || !h->have_target || h->h_tgt_cnt[0] <= 0) return MI355NDT_ERR_STATE;
   if (n == 0) { *score = std::nan(""); return MI355NDT_OK; }                     // 0 / 0 in the reference
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
-  if (!h->targets_built || !h->cent_built || !h->icov64_built) {                // f32 centroids + f64 inverse covariances: the "live" build flavour
-    const mi355ndt_params keep = h->prm;
-    h->prm.step_size = 0; h->prm.trans_epsilon = 0;
-    const int rc = mi355ndt_batch_build_targets(h);
-    h->prm = keep;
-    if (rc) return rc;
-  }
+  int rc = ensure_grids(h, GRIDS_LIVE);
+  if (rc) return rc;
   const size_t pitch = (n + 63) & ~(size_t)63;
   HIPCHK(h, h->d_score_pts.reserve(3 * pitch));
   const int blocks = (int)((n + SCORE_THREADS - 1) / SCORE_THREADS);
   HIPCHK(h, h->d_score_part.reserve((size_t)blocks));
-  int rc = upload_cloud(h, h->d_score_pts, pitch, 0, pts, n, stride);
+  rc = upload_cloud(h, h->d_score_pts, pitch, 0, pts, n, stride);
   if (rc) return rc;
   rc = uploads_before_compute(h);
   if (rc) return rc;

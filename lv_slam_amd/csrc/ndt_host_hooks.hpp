@@ -60,10 +60,8 @@ static int run_hook_sweep(mi355ndt_handle* h, double* score, double g[6], double
 static int hook_ready(mi355ndt_handle* h) {
   h->ev_last_fresh = false;
   if (h->n_pairs < 1 || !h->have_target || !h->have_source) return MI355NDT_ERR_STATE;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rcu = uploads_before_compute(h); if (rcu) return rcu; }
-  if (!h->targets_built || (is_pca_kd(h->prm) && !h->kdw_built) || (fast_served(h) && !h->recs_fast_built)) { int rc = mi355ndt_batch_build_targets(h); if (rc) return rc; }
-  return prep_align_ws(h);
+  const int rc = ensure_grids(h, GRIDS_CONFIG);
+  return rc ? rc : prep_align_ws(h);
 }
 
 int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, double g[6], double H[36], long long* hits) {
@@ -84,14 +82,8 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!p || !H) return MI355NDT_ERR_BAD_ARG;
   int rc = hook_ready(h);
+  if (rc == MI355NDT_OK) rc = ensure_grids(h, GRIDS_LIVE);        // (the grid may have been built for a configuration that never needs the Hessian's inputs)
   if (rc) return rc;
-  if (!h->cent_built || !h->icov64_built) {                       // the grid was built for a configuration that never needs it
-    const mi355ndt_params keep = h->prm;
-    h->prm.step_size = 0; h->prm.trans_epsilon = 0;               // "live" build flavour: centroids + f64 inverse covariances
-    rc = mi355ndt_batch_build_targets(h);
-    h->prm = keep;
-    if (rc) return rc;
-  }
   h->fine_it = 0; h->rows_per_pair = h->items_per_pair = h->chunks_per_pair * QUARTERS; h->pts_per_chunk = CHUNK_PTS;   // k_hessian writes batch-mode rows
   double* dp = (double*)h->d_hook.p;
   HIPCHK(h, hipMemcpyAsync(dp, p, 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -128,14 +120,19 @@ int mi355ndt_derivatives_T(mi355ndt_handle* h, const float T[16], const float Rj
   return run_hook_sweep(h, score, g, H, hits);
 }
 
+// the descriptor of a pair's resident grid, for the two getters below
+static int read_grid_desc(mi355ndt_handle* h, int pair, GridDesc& g) {
+  if (!h->built.valid) return MI355NDT_ERR_STATE;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(&g, h->d_grid + pair, sizeof g, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MI355NDT_OK;
+}
 int mi355ndt_get_grid(mi355ndt_handle* h, int pair, int min_b[3], int max_b[3], int div_b[3], int* n_voxels) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (pair < 0 || pair >= h->n_pairs) return MI355NDT_ERR_BAD_ARG;
-  if (!h->targets_built) return MI355NDT_ERR_STATE;
-  HIPCHK(h, hipSetDevice(h->device));
   GridDesc g;
-  HIPCHK(h, hipMemcpyAsync(&g, h->d_grid + pair, sizeof g, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = read_grid_desc(h, pair, g)) return rc;
   for (int a = 0; a < 3; a++) {
     if (min_b) min_b[a] = g.min_b[a];
     if (max_b) max_b[a] = g.max_b[a];
@@ -148,11 +145,8 @@ int mi355ndt_get_grid(mi355ndt_handle* h, int pair, int min_b[3], int max_b[3], 
 int mi355ndt_get_voxels(mi355ndt_handle* h, int pair, mi355ndt_voxel* out, size_t capacity) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (pair < 0 || pair >= h->n_pairs || (!out && capacity)) return MI355NDT_ERR_BAD_ARG;
-  if (!h->targets_built) return MI355NDT_ERR_STATE;
-  HIPCHK(h, hipSetDevice(h->device));
   GridDesc g;
-  HIPCHK(h, hipMemcpyAsync(&g, h->d_grid + pair, sizeof g, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = read_grid_desc(h, pair, g)) return rc;
   size_t n = std::min((size_t)g.n_voxels, capacity);
   if (n == 0) return MI355NDT_OK;
   std::vector<VoxelRec> r(n);

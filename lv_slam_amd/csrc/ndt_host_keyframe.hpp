@@ -197,7 +197,7 @@ int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int*
 }
 
 // A resident keyframe into a slot of the engine's own batch rows, device to device: what mi355ndt_batch_set_target / _source do with a host
-// cloud (the slot's rows zero-filled up to the pitch), with the bookkeeping of mi355ndt_use_prefiltered.
+// cloud (the slot's rows zero-filled up to the pitch).
 static int batch_set_side_keyframe(mi355ndt_handle* h, bool tgt, int pair, int id) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   NOT_IN_STREAM(h);
@@ -207,15 +207,8 @@ static int batch_set_side_keyframe(mi355ndt_handle* h, bool tgt, int pair, int i
   const size_t dp = tgt ? h->tgt_pitch : h->src_pitch;
   if (kf->n > dp) { h->err = "batch_set_*_keyframe: the keyframe has more points than mi355ndt_batch_reserve made room for"; return MI355NDT_ERR_BAD_ARG; }
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = rows_into_slot(h, tgt, pair, kf->rows, kf->pitch, kf->n);
-  if (rc) return rc;
-  {
-    std::lock_guard<std::mutex> lk(h->up_mtx);
-    (tgt ? h->h_tgt_cnt : h->h_src_cnt)[(size_t)pair] = (int)kf->n;
-    if (tgt) h->targets_built = false;
-    (tgt ? h->have_target : h->have_source) = true;
-  }
-  return compute_enqueued(h);                     // a later upload into these rows waits for the copies
+  const int rc = rows_into_slot(h, tgt, pair, kf->rows, kf->pitch, kf->n);
+  return rc ? rc : compute_enqueued(h);                    // a later upload into these rows waits for the copies
 }
 int mi355ndt_batch_set_target_keyframe(mi355ndt_handle* h, int pair, int id) { return batch_set_side_keyframe(h, true, pair, id); }
 int mi355ndt_batch_set_source_keyframe(mi355ndt_handle* h, int pair, int id) { return batch_set_side_keyframe(h, false, pair, id); }

@@ -190,14 +190,13 @@ int mi355ndt_set_params(mi355ndt_handle* h, const mi355ndt_params* p) {
   const bool regrid = (old.resolution != p->resolution && !keep_grid) || old.variant != p->variant ||
                       old.min_points_per_voxel != p->min_points_per_voxel ||
                       old.min_covar_eigvalue_mult != p->min_covar_eigvalue_mult ||
-                      ((p->neighbor_mode == MI355NDT_KDTREE || mt_is_live(*p)) && !h->cent_built) ||   // centroids the build skipped
-                      (mt_is_live(*p) && !h->icov64_built) ||
-                      (is_pca_kd(*p) && !h->kdw_built);
-  if (regrid && h->targets_built) {
-    h->targets_built = false;
-    rc = mi355ndt_batch_build_targets(h);     // setResolution -> init() (ndt_omp.h:126-136)
+                      !grids_serve(h->built, grid_extras(*p, 0));   // centroids, f64 inverse covariances or kd weights the build skipped (arith 0: the
+                                                                    // tolerance arithmetic's records are left to the next align)
+  if (regrid && h->built.valid) {
+    h->built.valid = false;
+    rc = ensure_grids(h, GRIDS_CONFIG);       // setResolution -> init() (ndt_omp.h:126-136)
     if (rc) h->prm = old;                     // the grids were not rebuilt: keep the parameters they were (last) built with;
-    return rc;                                // targets_built stays false, so the next align re-voxelises
+    return rc;                                // built.valid stays false, so the next align re-voxelises
   }
   return MI355NDT_OK;
 }

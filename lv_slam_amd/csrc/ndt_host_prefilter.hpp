@@ -62,10 +62,5 @@ int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role) {
   if (rc) return rc;
   rc = rows_into_slot(h, role == 2, 0, h->d_pf_out, h->pf_pitch, m);
   if (rc) return rc;
-  if (role == 2) {
-    h->h_tgt_cnt[0] = (int)m; h->have_target = true; h->targets_built = false;
-    return mi355ndt_batch_build_targets(h);
-  }
-  h->h_src_cnt[0] = (int)m; h->have_source = true;
-  return compute_enqueued(h);
+  return role == 2 ? mi355ndt_batch_build_targets(h) : compute_enqueued(h);
 }

@@ -29,10 +29,9 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
   rc = mi355ndt_batch_set_clouds(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, 0);
   if (rc) return rc;
   h->d_src = h->d_tgt_own; h->src_pitch = h->tgt_pitch;
-  for (int k = 0; k < n_frames; k++) h->h_src_cnt[k] = h->h_tgt_cnt[k];
-  h->have_source = true;
-  struct Unalias { mi355ndt_handle* h; ~Unalias() { h->d_src = h->d_src_own; h->src_pitch = h->own_src_pitch; std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0);
-                                                     h->have_source = false; h->d_grid_of_use = nullptr; h->aligned_once = false;
+  cloud_changed(h, false, 0, n_frames, counts);
+  struct Unalias { mi355ndt_handle* h; ~Unalias() { h->d_src = h->d_src_own; h->src_pitch = h->own_src_pitch; clouds_reset(h, false, true);
+                                                     h->d_grid_of_use = nullptr; h->aligned_once = false;
                                                      if (h->ev_compute) (void)compute_enqueued(h); } } unalias{h};   // (error exits too: later uploads wait for what was enqueued)
   for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));     // (upload time is reported on its own)
   const auto t_up1 = std::chrono::steady_clock::now();

@@ -17,8 +17,8 @@ static size_t stream_partials(const StreamState& ss) { return (size_t)ss.max_pai
 // A build of context engine `e` that waited for its sizes teaches the stream its plan: key width and pool words the later builds run
 // against without waiting (with headroom: scans of one drive vary by a few per cent).  The plan only ever grows.
 static void stream_learn_plan(StreamState& ss, const mi355ndt_handle* e) {
-  ss.plan_cb = std::max(ss.plan_cb, e->last_cb);
-  ss.plan_words = std::max(ss.plan_words, e->last_total_words + e->last_total_words / 4 + 1024);
+  ss.plan_cb = std::max(ss.plan_cb, e->built.cb);
+  ss.plan_words = std::max(ss.plan_words, e->built.total_words + e->built.total_words / 4 + 1024);
 }
 int mi355ndt_stream_end(mi355ndt_handle* h) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
@@ -54,7 +54,7 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
   ss.sync_only = !async_served(h);
   // the grids a streamed launch reads are the contexts' (built at prm.resolution); whatever single-registration grid the parent still holds
   // -- possibly one a setResolution without a source left at another leaf size (ndt_omp.h:126-136) -- is no part of the stream
-  h->targets_built = false; h->grid_resolution = 0.f; h->recs_fast_built = false;
+  h->built = GridsBuilt{};
   SweepConst sc;
   make_sweep_const(h, sc);
   const int slots = launch_slots(h, sc, fast_served(h));

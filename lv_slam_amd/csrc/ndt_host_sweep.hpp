@@ -75,7 +75,7 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
   sc.pca = h->prm.variant == MI355NDT_VARIANT_PCA;
   // the lookup divides by the GRID's leaf size (voxel_grid_covariance_omp_impl.hpp:379-381), which is resolution_ except after a setResolution
   // that found no source and therefore left the grid alone (ndt_omp.h:126-136); the Gauss constants and the kd radius follow resolution_
-  const float leaf = (h->targets_built && h->grid_resolution > 0.f) ? h->grid_resolution : h->prm.resolution;
+  const float leaf = (h->built.valid && h->built.leaf > 0.f) ? h->built.leaf : h->prm.resolution;
   { int ex; float mant = std::frexp(leaf, &ex); sc.leaf_pow2 = (mant == 0.5f) && ex > -100 && ex < 100; sc.inv_leaf = 1.0f / leaf; }
   sc.kd_r2 = (float)((double)h->prm.resolution * (double)h->prm.resolution);   // KdTreeFLANN::radiusSearch: float(radius * radius)
   build_offsets(h->prm.neighbor_mode, sc);
@@ -91,7 +91,7 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
 // loop -- every configuration lv_slam ships; the other searches and the live line search keep the exact kernels), else the f32 sum order.
 static int sweep_ord(const mi355ndt_handle* h, const SweepConst& sc) {
   // (a stream's parent handle owns no grids: its contexts' engines build them, with the option as it stood at mi355ndt_stream_begin)
-  if (fast_served(h) && (h->recs_fast_built || h->ss)) return 2;
+  if (fast_served(h) && (h->built.made.recs_fast || h->ss)) return 2;
   return h->f32_sum_order;
 }
 static const VoxelRec* sweep_recs(const mi355ndt_handle* h, const SweepConst& sc) {

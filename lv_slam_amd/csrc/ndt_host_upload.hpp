@@ -11,7 +11,7 @@ static int ensure_pair_arrays(mi355ndt_handle* h, int n_pairs) {
   // the arrays are released and re-created one by one: until all of them exist again the engine holds no batch at all
   // (a failure half way must not leave cap_pairs vouching for freed or undersized buffers)
   h->cap_pairs = 0; h->n_pairs = 0; h->d_tgt_cnt = h->d_src_cnt = nullptr; h->d_guess = nullptr;
-  h->targets_built = false; h->have_target = false; h->have_source = false; h->aligned_once = false;
+  clouds_reset(h, true, true); h->aligned_once = false;
   HIPCHK(h, h->d_tgt_cnt_own.realloc_exact(n_pairs)); h->d_tgt_cnt = h->d_tgt_cnt_own;
   HIPCHK(h, h->d_src_cnt_own.realloc_exact(n_pairs)); h->d_src_cnt = h->d_src_cnt_own;
   h->up_tgt_cnt.clear(); h->up_src_cnt.clear();       // fresh device arrays: nothing uploaded yet
@@ -43,9 +43,7 @@ static int alloc_side(mi355ndt_handle* h, bool tgt, int n_pairs, size_t pitch) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, buf.realloc_exact((size_t)n_pairs * 3 * pitch));
   own_pitch = pitch; own_pairs = n_pairs;
-  std::vector<int>& cnt = tgt ? h->h_tgt_cnt : h->h_src_cnt;
-  std::fill(cnt.begin(), cnt.end(), 0);
-  if (tgt) { h->targets_built = false; h->have_target = false; } else { h->have_source = false; }
+  clouds_reset(h, tgt, !tgt);
   return MI355NDT_OK;
 }
 
@@ -60,13 +58,10 @@ int mi355ndt_batch_reserve(mi355ndt_handle* h, int n_pairs, size_t max_tgt, size
   int rc = ensure_pair_arrays(h, n_pairs);
   if (rc) return rc;
   if (n_pairs != h->n_pairs || h->d_tgt != h->d_tgt_own || h->d_src != h->d_src_own) {
-    std::fill(h->h_tgt_cnt.begin(), h->h_tgt_cnt.end(), 0);
-    std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0);
-    h->targets_built = false; h->have_target = false; h->have_source = false; h->aligned_once = false;
+    clouds_reset(h, true, true); h->aligned_once = false;
   }
   rc = alloc_side(h, true, n_pairs, tp);
-  if (rc) return rc;
-  rc = alloc_side(h, false, n_pairs, sp);
+  if (rc == MI355NDT_OK) rc = alloc_side(h, false, n_pairs, sp);
   if (rc) return rc;
   h->n_pairs = n_pairs;
   h->tgt_pitch = tp; h->src_pitch = sp;
@@ -217,7 +212,7 @@ static int upload_items_grouped(mi355ndt_handle* h, const std::vector<UpItem>& i
 }
 
 // m points of device SoA rows (pitch src_pitch) into a pair slot of the engine's own batch rows, device to device, the slot's rows
-// zero-filled up to their pitch as an upload leaves them.  The caller does the bookkeeping (counts, flags, compute_enqueued or a build).
+// zero-filled up to their pitch as an upload leaves them, and recorded (cloud_changed).  The caller follows with compute_enqueued or a build.
 static int rows_into_slot(mi355ndt_handle* h, bool tgt, int pair, const float* rows, size_t src_pitch, size_t m) {
   int rc = uploads_before_compute(h);             // an earlier upload into these rows must not land after the copies (and one into `rows` has to have landed)
   if (rc) return rc;
@@ -226,6 +221,7 @@ static int rows_into_slot(mi355ndt_handle* h, bool tgt, int pair, const float* r
   HIPCHK(h, hipMemsetAsync(dst, 0, 3 * dp * sizeof(float), h->stream));
   for (int a = 0; a < 3; a++)
     if (m) HIPCHK(h, hipMemcpyAsync(dst + a * dp, rows + a * src_pitch, m * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  cloud_changed(h, tgt, pair, m);
   return MI355NDT_OK;
 }
 
@@ -235,12 +231,8 @@ static int batch_set_side(mi355ndt_handle* h, bool tgt, int pair, const void* pt
   if (pair < 0 || pair >= h->n_pairs || (tgt ? h->d_tgt != h->d_tgt_own : h->d_src != h->d_src_own)) return MI355NDT_ERR_BAD_ARG;
   if (hipError_t e = hipSetDevice(h->device)) { std::lock_guard<std::mutex> lk(h->up_mtx); h->err = std::string("hipSetDevice: ") + hipGetErrorString(e); return MI355NDT_ERR_HIP; }
   int rc = upload_cloud(h, tgt ? h->d_tgt_own : h->d_src_own, tgt ? h->tgt_pitch : h->src_pitch, pair, pts, n, stride);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->up_mtx);
-  (tgt ? h->h_tgt_cnt : h->h_src_cnt)[pair] = (int)n;
-  if (tgt) h->targets_built = false;
-  (tgt ? h->have_target : h->have_source) = true;
-  return MI355NDT_OK;
+  if (rc == MI355NDT_OK) cloud_changed(h, tgt, pair, n);
+  return rc;
 }
 int mi355ndt_batch_set_target(mi355ndt_handle* h, int pair, const void* pts, size_t n, size_t stride) { return batch_set_side(h, true, pair, pts, n, stride); }
 int mi355ndt_batch_set_source(mi355ndt_handle* h, int pair, const void* pts, size_t n, size_t stride) { return batch_set_side(h, false, pair, pts, n, stride); }
@@ -253,7 +245,15 @@ int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const v
   if (n <= 0 || first_pair < 0 || first_pair + n > h->n_pairs || (!targets && !sources) || (targets && !target_counts) || (sources && !source_counts))
     return MI355NDT_ERR_BAD_ARG;
   if (h->d_tgt != h->d_tgt_own || h->d_src != h->d_src_own) return MI355NDT_ERR_BAD_ARG;
+  // every pair's arguments before any staging thread starts (what upload_items checks per group): a refused call changes nothing
+  for (int k = 0; k < n; k++) {
+    const size_t tn = targets ? target_counts[k] : 0, sn = sources ? source_counts[k] : 0;
+    if ((tn && (!targets[k] || tn > h->tgt_pitch)) || (sn && (!sources[k] || sn > h->src_pitch)) || ((tn || sn) && stride < 12)) return MI355NDT_ERR_BAD_ARG;
+  }
   HIPCHK(h, hipSetDevice(h->device));
+  // recorded BEFORE the uploads begin: a HIP failure half way then leaves no valid-looking grids over rows that already hold new points
+  if (targets) cloud_changed(h, true, first_pair, n, target_counts);
+  if (sources) cloud_changed(h, false, first_pair, n, source_counts);
   const int nt = std::max(1, std::min(n_threads > 0 ? n_threads : 8, n));
   // the engine's own threads stage next to the GPU -- but only on CPUs the CALLER may use: the NUMA node's CPUs intersected with the
   // calling thread's affinity mask (a taskset / cgroup-restricted process keeps its restriction); an empty intersection = no pinning
@@ -284,18 +284,7 @@ int mi355ndt_batch_set_clouds(mi355ndt_handle* h, int first_pair, int n, const v
     }
     return (int)MI355NDT_OK;
   };
-  const int rc = staging_threads(nt, work);
-  if (rc) return rc;
-  {
-    std::lock_guard<std::mutex> lk(h->up_mtx);
-    for (int k = 0; k < n; k++) {
-      if (targets) h->h_tgt_cnt[(size_t)(first_pair + k)] = (int)target_counts[k];
-      if (sources) h->h_src_cnt[(size_t)(first_pair + k)] = (int)source_counts[k];
-    }
-    if (targets) { h->targets_built = false; h->have_target = true; }
-    if (sources) h->have_source = true;
-  }
-  return MI355NDT_OK;
+  return staging_threads(nt, work);
 }
 
 int mi355ndt_batch_bind_device(mi355ndt_handle* h, int n_pairs, const float* d_t, const int* tc, size_t tp,
@@ -311,9 +300,7 @@ int mi355ndt_batch_bind_device(mi355ndt_handle* h, int n_pairs, const float* d_t
   h->n_pairs = n_pairs;
   h->d_tgt = d_t; h->d_src = d_s;
   h->tgt_pitch = tp; h->src_pitch = sp;
-  for (int b = 0; b < n_pairs; b++) { h->h_tgt_cnt[b] = tc[b]; h->h_src_cnt[b] = scnt[b]; }
-  h->targets_built = false;
-  h->have_target = h->have_source = true;
+  cloud_changed(h, true, 0, n_pairs, tc); cloud_changed(h, false, 0, n_pairs, scnt);
   h->aligned_once = false;
   return MI355NDT_OK;
 }

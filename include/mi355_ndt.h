@@ -105,7 +105,7 @@ typedef struct mi355ndt_profile {
   long long stream_launches; /* stream mode: persistent launches (one per submitted batch + flushes) */
   long long stream_carried;  /* stream mode: pairs handed over from one launch to the next (stragglers that finished under a later batch) */
   long long stream_redone;   /* stream mode: batches re-run synchronously (build plan exceeded, or a launch gave up) */
-  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter / map_cloud: its non-empty keyframes / window_keyframe: its non-empty scans / keyframe_add), counted always */
+  long long cloud_uploads;   /* host clouds staged and sent over PCIe (set_target / set_source / batch_set_* / calculate_score / prefilter / batch_prefilter / map_cloud: its non-empty keyframes / window_keyframe: its non-empty scans / keyframe_add), counted always */
   long long cloud_upload_bytes;
   long long cloud_transfers;  /* host-to-device transfers those clouds travelled in (mi355ndt_batch_set_clouds / stream_submit_host send up to eight clouds per transfer) */
   long long cloud_promotions; /* mi355ndt_promote_source_to_target calls (device-to-device instead of an upload) */
@@ -251,7 +251,10 @@ enum mi355ndt_option {
   /* Cell size, in millimetres, of the spatial index mi355ndt_prefilter_outliers builds over the prefilter result in every call (default 100,
    * the keyframe option's default until the timing tool's sweep has been run on a GPU: DESIGN.md 8), doubled by the keyframe option's rule.
    * The search is exact for any cell: no result bit depends on the option, only the time. */
-  MI355NDT_OPT_OUTLIER_CELL_MM = 10
+  MI355NDT_OPT_OUTLIER_CELL_MM = 10,
+  /* Raw clouds per group of mi355ndt_batch_prefilter (0, the default: as many as keep the engine's scratch under its 2 GiB budget, 4096 at the
+   * most).  No result word depends on the option, only the time and the scratch; it exists so that a test can force several groups. */
+  MI355NDT_OPT_PREFILTER_GROUP = 11
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);
@@ -422,6 +425,53 @@ int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t str
                        void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
 /* install the last prefilter result as the registration source (role 1) or target (role 2) without a host round trip */
 int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
+
+/* ---- prefilter of whole batches: raw scans straight into the batch slots ------------------------------- */
+/* The nodelet's parameters.  With use_transform every raw point is first moved by T = transform_colmajor (4x4 f32, column-major), the
+ * nodelet's base_link move (prefiltering_nodelet.cpp:100-115: pcl_ros::transformPointCloud, which casts the tf transform to float and calls
+ * PCL 1.8.1's pcl::transformPointCloud(in, out, Eigen::Matrix4f)):  (float)(((T(a,0) x + T(a,1) y) + T(a,2) z) + T(a,3)),  every product and sum
+ * a separately rounded f32 operation; a point with a non-finite coordinate is not moved and is dropped by the filter.  The rule is PCL's as
+ * restated here, unpinned. */
+typedef struct mi355ndt_prefilter_params {
+  int    use_distance_filter;           /* 1 */
+  double distance_near, distance_far;   /* 1.0, 100.0: the nodelet's in-code defaults (prefiltering_nodelet.cpp:83-85) */
+  float  downsample_resolution;         /* 0.1; <= 0: no down-sampling */
+  int    use_transform;                 /* 0 */
+  float  transform_colmajor[16];        /* identity */
+} mi355ndt_prefilter_params;
+int mi355ndt_prefilter_params_default(mi355ndt_prefilter_params* p);
+
+/* Like mi355ndt_batch_set_clouds, but every cloud is RAW and goes through the prefilter (mi355ndt_prefilter's rules, bit for bit) on its way
+ * into its slot: the clouds are staged into the engine's scratch, filtered there group by group -- every stage one launch for all clouds of a
+ * group, one wait for the device per group, none per cloud -- and emitted into the slots' own rows, whose tails are zeroed as an upload leaves
+ * them.  mi355ndt_batch_reserve comes first; its two sizes are capacities for the FILTERED clouds, a raw count may exceed them (each below
+ * 2^30).  Either side may be NULL (with its counts); p == NULL: the defaults above.  target_counts_out / source_counts_out (may be NULL)
+ * receive the filtered counts.  mi355ndt_batch_build_targets / mi355ndt_batch_align follow as after mi355ndt_batch_set_clouds.
+ * A leaf too small for some cloud's extent is no error: that cloud goes in as its kept points, in input order, and mi355ndt_last_error names
+ * the first such slot.  MI355NDT_ERR_STATE in stream mode.  MI355NDT_ERR_BAD_ARG, every argument checked before anything is staged and
+ * the batch unchanged: device buffers bound, a NULL cloud with a count, a stride below 12, a NaN resolution, a NaN in the transform, slots
+ * outside the batch.  MI355NDT_ERR_BAD_ARG also for a filtered cloud that does not fit its slot: mi355ndt_last_error names the first such
+ * slot, and every slot the call touched is recorded as empty.  The resident prefilter result, the keyframes and their indexes are left as
+ * they were.  MI355NDT_OPT_PREFILTER_GROUP. */
+int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n,
+                             const void* const* targets, const size_t* target_counts,
+                             const void* const* sources, const size_t* source_counts, size_t stride_bytes,
+                             const mi355ndt_prefilter_params* p,
+                             size_t* target_counts_out, size_t* source_counts_out /* either may be NULL */);
+
+/* the points a batch slot holds (role 1 = source, 2 = target) as x,y,z records, whatever route filled the slot; waits for pending uploads
+ * and kernels.  out_pts == NULL: the count alone.  MI355NDT_ERR_BAD_ARG for a bad slot or role and for a capacity below the count;
+ * MI355NDT_ERR_STATE in stream mode. */
+int mi355ndt_batch_get_cloud(mi355ndt_handle* h, int pair, int role, void* out_pts, size_t out_capacity,
+                             size_t out_stride_bytes, size_t* n_out);
+
+/* mi355ndt_sequence_run over RAW scans: the same call with the batch prefilter in front, no scan downloaded in between.  The batch is
+ * reserved for the raw counts.  stats->upload_ms covers the staging of the raw scans, *prefilter_ms (may be NULL) the prefilter's kernels
+ * (HIP events); filtered_counts (may be NULL): n_frames filtered counts.  A frame that is empty after the prefilter is MI355NDT_ERR_BAD_ARG. */
+int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride_bytes,
+                              const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_seq_params* policy,
+                              mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats,
+                              size_t* filtered_counts /* may be NULL */, double* prefilter_ms /* may be NULL */);
 
 /* replaces PrefilteringNodelet::outlier_removal (prefiltering_nodelet.cpp:128, 150-161), the nodelet's last stage, over the RESIDENT
  * prefilter result, in place: the survivors keep their order, the result's count and rows are updated, and mi355ndt_use_prefiltered

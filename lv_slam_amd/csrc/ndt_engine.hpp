@@ -49,13 +49,13 @@ struct StreamState {
 };
 
 // ---- scratch of the sort-and-compact chain: stage clouds -> extremes -> grid -> keys -> one-segment radix sort -> run heads -> exclusive
-// scan -> emit -> count.  The prefilter, its outlier removal, the map cloud (both routes), the window map and the cloud index builds
+// scan -> emit -> count.  The prefilter, the batch prefilter (K clouds at once, a segment each), the outlier removal, the map cloud (both routes), the window map and the cloud index builds
 // (kfi_build_rows: the keyframe fitness scores, GICP) share this one instance; results (d_pf_out, the keyframe store, the indexes) are not in it.
 // Sharing is safe because
 //   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;
 //   * every user waits for the stream before it returns, except mi355ndt_window_keyframe, whose trailing k_kf_emit still reads x, keys, vals,
 //     flag and pos: only kernels on h->stream write those, so stream order covers it as well;
-//   * `in` alone is written from the copy streams: its readers (k_pf_*, k_mc_transform, k_kf_window) have finished when their call returns,
+//   * `in` alone is written from the copy streams: its readers (k_pf_*, k_pfb_*, k_mc_transform, k_kf_window) have finished when their call returns,
 //     and uploads_before_compute / compute_enqueued order the uploads against the compute stream as they do for the batch rows;
 //   * the pinned blocks are written by the host only at the start of a call, after vs_reserve has waited out a copy that may still read
 //     them (`pending`), and read by the host only after the call's own wait.
@@ -142,6 +142,7 @@ struct mi355ndt_handle {
   // outlier removal over it (mi355ndt_prefilter_outliers): the index rebuilt by every call, dist[] and its pinned twin
   CloudIndex ol_index; DevBuf<float> d_ol_dist; PinBuf<float> h_ol_dist;
   int ol_cell_mm = 100;                           // MI355NDT_OPT_OUTLIER_CELL_MM
+  int pf_group = 0;                               // MI355NDT_OPT_PREFILTER_GROUP: raw clouds per group of mi355ndt_batch_prefilter (0: by the scratch budget)
   VoxelScratch vs;                                // scratch of the prefilter, the map cloud, the window map and the keyframe index builds
   // keyframe store (mi355ndt_keyframe_*, mi355ndt_window_keyframe): every keyframe owns its rows -- [3 or 4][pitch] floats, x, y, z and, when
   // carried, the intensity; pitch = count rounded up to 64, the tail zeroed -- under an id that is never given out twice

@@ -256,6 +256,11 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
     h->ol_cell_mm = value;
     return MI355NDT_OK;
   }
+  if (option == MI355NDT_OPT_PREFILTER_GROUP) {
+    if (value < 0 || value > 4096) return MI355NDT_ERR_BAD_ARG;
+    h->pf_group = value;
+    return MI355NDT_OK;
+  }
   return MI355NDT_ERR_BAD_ARG;
 }
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
@@ -271,5 +276,6 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (option == MI355NDT_OPT_STREAM_RESERVE) { *value = h->s_reserve_opt; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_KF_FITNESS_CELL_MM) { *value = h->kff_cell_mm; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_OUTLIER_CELL_MM) { *value = h->ol_cell_mm; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_PREFILTER_GROUP) { *value = h->pf_group; return MI355NDT_OK; }
   return MI355NDT_ERR_BAD_ARG;
 }

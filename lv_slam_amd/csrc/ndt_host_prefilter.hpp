@@ -64,3 +64,187 @@ int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role) {
   if (rc) return rc;
   return role == 2 ? mi355ndt_batch_build_targets(h) : compute_enqueued(h);
 }
+
+// ---- whole batches of raw scans into the batch slots (ndt_prefilter_batch.hpp) -------------------------------------------------------------
+int mi355ndt_prefilter_params_default(mi355ndt_prefilter_params* p) {
+  if (!p) return MI355NDT_ERR_BAD_ARG;
+  memset(p, 0, sizeof *p);
+  p->use_distance_filter = 1; p->distance_near = 1.0; p->distance_far = 100.0;   // prefiltering_nodelet.cpp:83-85
+  p->downsample_resolution = 0.1f;
+  for (int a = 0; a < 4; a++) p->transform_colmajor[5 * a] = 1.f;
+  return MI355NDT_OK;
+}
+
+// The scratch of a group of K raw clouds of pitch rp, per raw point: rows 12 B + keep 1 + two key and two id arrays (sort ping-pong) 16 + flag 4
+// + pos 4 + the sort's tile histograms and offsets 2 x (2048 words per 4096-point tile) = 4: 41 B.  Groups are cut so that K * rp * 41 stays
+// under 2 GiB: 399 clouds of 131,072 points, 52 M raw points, whatever their number in the call.  (At most PFB_GROUP_MAX clouds: the per-cloud
+// words stay small beside the per-point ones.)
+#define PFB_POINT_BYTES    41
+#define PFB_SCRATCH_BUDGET ((size_t)2 << 30)
+#define PFB_GROUP_MAX      4096
+
+// kernels_ms (may be null): the time of the prefilter's kernels, HIP events around every group's chain, summed
+static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const void* const* targets, const size_t* target_counts,
+                                const void* const* sources, const size_t* source_counts, size_t stride, const mi355ndt_prefilter_params* prm,
+                                size_t* target_counts_out, size_t* source_counts_out, double* kernels_ms) {
+  // every argument before anything is staged: a refused call changes nothing
+  if (n <= 0 || first_pair < 0 || first_pair + n > h->n_pairs || (!targets && !sources) || (targets && !target_counts) || (sources && !source_counts))
+    return MI355NDT_ERR_BAD_ARG;
+  if (h->d_tgt != h->d_tgt_own || h->d_src != h->d_src_own) return MI355NDT_ERR_BAD_ARG;
+  mi355ndt_prefilter_params p;
+  if (prm) p = *prm; else (void)mi355ndt_prefilter_params_default(&p);
+  if (std::isnan(p.downsample_resolution)) return MI355NDT_ERR_BAD_ARG;
+  if (p.use_transform) for (float v : p.transform_colmajor) if (std::isnan(v)) return MI355NDT_ERR_BAD_ARG;
+  struct Raw { bool tgt; int pair; const void* pts; size_t n; };
+  std::vector<Raw> raw;                                 // pair after pair, the target before the source: "the first slot that ..." follows this order
+  size_t maxn = 0;
+  for (int k = 0; k < n; k++)
+    for (int side = 0; side < 2; side++) {
+      const void* const* cl = side == 0 ? targets : sources;
+      if (!cl) continue;
+      const size_t c = (side == 0 ? target_counts : source_counts)[k];
+      if (c && (!cl[k] || stride < 12 || c >= (1u << 30))) return MI355NDT_ERR_BAD_ARG;
+      raw.push_back(Raw{side == 0, first_pair + k, cl[k], c});
+      maxn = std::max(maxn, c);
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const float leaf = p.downsample_resolution;
+  const int downsample = leaf > 0.f;
+  PfbMove mv;
+  memset(&mv, 0, sizeof mv);
+  mv.on = p.use_transform != 0;
+  for (int a = 0; a < 3; a++) for (int c = 0; c < 4; c++) mv.m[4 * a + c] = p.transform_colmajor[4 * c + a];
+  const int n_raw = (int)raw.size();
+  const size_t rp = std::max((size_t)64, (maxn + 63) & ~(size_t)63);
+  int group = h->pf_group > 0 ? h->pf_group : (int)std::min((size_t)PFB_GROUP_MAX, std::max((size_t)1, PFB_SCRATCH_BUDGET / (PFB_POINT_BYTES * rp)));
+  group = std::min(std::min(group, PFB_GROUP_MAX), n_raw);
+  const int tiles = (int)((rp + RS_TILE - 1) / RS_TILE);  // of one cloud: sort tiles = scan chunks (RS_TILE == PF_SCAN_CHUNK)
+  static_assert(RS_TILE == PF_SCAN_CHUNK, "one tile count serves the sort and the scan");
+  VoxelScratch& w = h->vs;
+  VsNeed need;
+  need.clouds = (size_t)group; need.pitch = (size_t)group * rp; need.in = 3 * need.pitch;
+  need.tab = (size_t)group * sizeof(PfbItem); need.stat = PFB_RES_WORDS(group);
+  int rc = vs_reserve(h, need);
+  if (rc) return rc;
+  // until the counts are known the touched slots hold nothing: an error half way leaves no valid-looking cloud or grid over rows being rewritten
+  const std::vector<int> zeros((size_t)n, 0);
+  if (targets) cloud_changed(h, true, first_pair, n, zeros.data());
+  if (sources) cloud_changed(h, false, first_pair, n, zeros.data());
+  HipEvent ev[2];
+  if (kernels_ms) { *kernels_ms = 0.0; for (auto& e : ev) HIPCHK(h, e.create(hipEventDefault)); }
+  std::vector<int> counts((size_t)n_raw, 0);
+  int first_overflow = INT_MAX, first_small = INT_MAX;
+  const RsPlan plan = rs_plan(31);
+  for (int g0 = 0; g0 < n_raw; g0 += group) {
+    const int K = std::min(group, n_raw - g0);
+    if (w.pending) { HIPCHK(h, hipStreamSynchronize(s)); w.pending = false; }
+    PfbItem* tab = (PfbItem*)(unsigned char*)w.h_tab;
+    std::vector<UpItem> up((size_t)K);
+    for (int k = 0; k < K; k++) {
+      const Raw& r = raw[(size_t)(g0 + k)];
+      const size_t dp = r.tgt ? h->tgt_pitch : h->src_pitch;
+      tab[k] = PfbItem{(r.tgt ? h->d_tgt_own : h->d_src_own) + (size_t)r.pair * 3 * dp, (unsigned long long)dp, (int)r.n, g0 + k};
+      up[(size_t)k] = UpItem{w.in, rp, k, r.pts, r.n, stride};
+    }
+    w.pending = true;
+    HIPCHK(h, hipMemcpyAsync(w.tab, w.h_tab, (size_t)K * sizeof(PfbItem), hipMemcpyHostToDevice, s));
+    rc = upload_items_grouped(h, up);
+    if (rc) return rc;
+    rc = uploads_before_compute(h);
+    if (rc) return rc;
+    if (g0 == 0) {
+      // the rows behind a count are zero, as an upload leaves them: the touched slots are one contiguous range per side
+      if (targets) HIPCHK(h, hipMemsetAsync(h->d_tgt_own + (size_t)first_pair * 3 * h->tgt_pitch, 0, (size_t)n * 3 * h->tgt_pitch * sizeof(float), s));
+      if (sources) HIPCHK(h, hipMemsetAsync(h->d_src_own + (size_t)first_pair * 3 * h->src_pitch, 0, (size_t)n * 3 * h->src_pitch * sizeof(float), s));
+    }
+    if (kernels_ms) HIPCHK(h, hipEventRecord(ev[0], s));
+    const PfbItem* items = (const PfbItem*)(unsigned char*)w.tab;
+    int* res = w.stat;
+    const size_t seg = (size_t)K * rp;             // (the sort's second key / id arrays start here)
+    const unsigned* keys = w.keys; const unsigned* vals = w.vals;
+    k_pfb_begin<<<(6 * K + 255) / 256, 256, 0, s>>>(w.mm, res, K);
+    const int fx = std::max(1, std::min(tiles * (RS_TILE / 256) / 4, 32));   // flag workgroups per cloud: four points per thread and pass, 32 at the most
+    k_pfb_flag<<<xcd_grid(fx, K), 256, 0, s>>>(w.in, rp, items, K, fx, p.use_distance_filter, p.distance_near, p.distance_far, mv, w.keep, w.mm);
+    if (downsample) {
+      k_pfb_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, leaf, w.grid, items, K, res);
+      k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys);
+      unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
+      for (int ps = 0; ps < plan.passes; ps++) {
+        rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0);
+        std::swap(ka, kb); std::swap(va, vb);
+      }
+      keys = ka; vals = va;
+    }
+    k_pfb_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(keys, w.keep, rp, items, K, tiles, w.grid, downsample, w.flag);
+    k_pfb_scan_totals<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, tiles, K);
+    k_pfb_scan_offsets<<<K, 1024, 0, s>>>(w.tmp, tiles, items, K, res);
+    k_pfb_scan_apply<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, w.pos, tiles, K);
+    k_pfb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.flag, w.pos, w.grid, downsample, items, K, tiles);
+    if (kernels_ms) HIPCHK(h, hipEventRecord(ev[1], s));
+    rc = compute_enqueued(h);                      // the next group's uploads into the scratch wait for these kernels
+    if (rc) return rc;
+    // the group's one wait: K counts and the two "first cloud that ..." words
+    int* ret = w.h_ret;
+    HIPCHK(h, hipMemcpyAsync(ret, res, PFB_RES_WORDS(K) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    w.pending = false;
+    HIPCHK(h, hipGetLastError());
+    if (kernels_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, ev[0], ev[1])); *kernels_ms += ms; }
+    for (int k = 0; k < K; k++) counts[(size_t)(g0 + k)] = ret[k];
+    first_overflow = std::min(first_overflow, ret[K]);
+    first_small = std::min(first_small, ret[K + 1]);
+  }
+  if (first_overflow != INT_MAX) {                  // (the touched slots stay recorded as empty)
+    const Raw& r = raw[(size_t)first_overflow];
+    h->err = "batch prefilter: the filtered " + std::string(r.tgt ? "target" : "source") + " of slot " + std::to_string(r.pair) + " has " +
+             std::to_string(counts[(size_t)first_overflow]) + " points, more than its slot holds (" + std::to_string(r.tgt ? h->tgt_pitch : h->src_pitch) +
+             "): reserve the batch for the filtered clouds";
+    return MI355NDT_ERR_BAD_ARG;
+  }
+  for (int j = 0; j < n_raw; j++) {
+    const Raw& r = raw[(size_t)j];
+    cloud_changed(h, r.tgt, r.pair, (size_t)counts[(size_t)j]);
+    size_t* out = r.tgt ? target_counts_out : source_counts_out;
+    if (out) out[r.pair - first_pair] = (size_t)counts[(size_t)j];
+  }
+  if (first_small != INT_MAX) {
+    const Raw& r = raw[(size_t)first_small];
+    const std::string what = std::string(r.tgt ? "target" : "source") + " of slot " + std::to_string(r.pair);
+    h->err = "batch prefilter: leaf size too small for the extent of the " + what + ", voxel indices would overflow; " + what + " not down-sampled";
+  }
+  return MI355NDT_OK;
+}
+
+int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n, const void* const* targets, const size_t* target_counts,
+                             const void* const* sources, const size_t* source_counts, size_t stride, const mi355ndt_prefilter_params* p,
+                             size_t* target_counts_out, size_t* source_counts_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  const int rc = batch_prefilter_impl(h, first_pair, n, targets, target_counts, sources, source_counts, stride, p, target_counts_out, source_counts_out, nullptr);
+  // an error exit may leave copies and kernels queued that still use the scratch and the slot rows: later uploads wait for them all the same
+  if (rc != MI355NDT_OK && rc != MI355NDT_ERR_BAD_ARG && h->ev_compute) (void)compute_enqueued(h);
+  return rc;
+}
+
+// the points a batch slot holds, whatever route filled it
+int mi355ndt_batch_get_cloud(mi355ndt_handle* h, int pair, int role, void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (pair < 0 || pair >= h->n_pairs || (role != 1 && role != 2) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
+  const bool tgt = role == 2;
+  const float* base = tgt ? h->d_tgt : h->d_src;
+  const size_t pitch = tgt ? h->tgt_pitch : h->src_pitch;
+  const size_t m = (size_t)(tgt ? h->h_tgt_cnt : h->h_src_cnt)[(size_t)pair];
+  *n_out = m;
+  if (!out_pts || m == 0) return MI355NDT_OK;
+  if (m > out_capacity || !base) return MI355NDT_ERR_BAD_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));   // pending uploads and kernels
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::vector<float> tmp(3 * m);
+  for (int a = 0; a < 3; a++)
+    HIPCHK(h, hipMemcpy(tmp.data() + (size_t)a * m, base + (size_t)pair * 3 * pitch + (size_t)a * pitch, m * sizeof(float), hipMemcpyDeviceToHost));
+  rows_to_records(tmp.data(), m, 3, m, out_pts, out_stride, -1);
+  return MI355NDT_OK;
+}

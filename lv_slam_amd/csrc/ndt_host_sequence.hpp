@@ -8,33 +8,30 @@ int mi355ndt_set_latency_mode(mi355ndt_handle* h, int on) {
   return MI355NDT_OK;
 }
 
-int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
-                          const double* stamps, const mi355ndt_seq_params* policy,
-                          mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  NOT_IN_STREAM(h);
+// what both sequence runs ask of the handle and of their common arguments
+static int sequence_args(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride, const double* stamps,
+                         mi355ndt_seq_frame* out_frames, size_t count_limit, size_t* maxn) {
   if (n_frames < 1 || n_frames > MAX_PAIRS || !clouds || !counts || !stamps || !out_frames || stride < 12) return MI355NDT_ERR_BAD_ARG;
   if (mt_is_live(h->prm) || (h->prm.neighbor_mode != MI355NDT_DIRECT1 && h->prm.neighbor_mode != MI355NDT_DIRECT7)) {
     h->err = "sequence mode serves DIRECT1 / DIRECT7 with step_size > transformation_epsilon / 2 (every configuration lv_slam ships)";
     return MI355NDT_ERR_UNSUPPORTED;
   }
-  size_t maxn = 0;
-  for (int k = 0; k < n_frames; k++) { if (counts[k] == 0 || counts[k] >= (1u << 31) || !clouds[k]) return MI355NDT_ERR_BAD_ARG; maxn = std::max(maxn, counts[k]); }
-  HIPCHK(h, hipSetDevice(h->device));
-  const auto t_up0 = std::chrono::steady_clock::now();
-  // every frame is a TARGET slot (its voxel grid is built: it may become a keyframe) and, through the same rows, the SOURCE of its own
-  // align: one cloud buffer serves both sides
-  int rc = mi355ndt_batch_reserve(h, n_frames, maxn, 64);
-  if (rc) return rc;
-  rc = mi355ndt_batch_set_clouds(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, 0);
-  if (rc) return rc;
+  *maxn = 0;
+  for (int k = 0; k < n_frames; k++) { if (counts[k] == 0 || counts[k] >= count_limit || !clouds[k]) return MI355NDT_ERR_BAD_ARG; *maxn = std::max(*maxn, counts[k]); }
+  return MI355NDT_OK;
+}
+
+// The run itself, from the point where the n_frames frames sit in target slots 0 .. n_frames - 1 of the engine's own batch (recorded with their
+// counts); upload_ms: what getting them there took.
+static int sequence_tracked(mi355ndt_handle* h, int n_frames, const double* stamps, const mi355ndt_seq_params* policy,
+                            mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats, double upload_ms) {
+  int rc;
+  const std::vector<int> counts(h->h_tgt_cnt.begin(), h->h_tgt_cnt.begin() + n_frames);
   h->d_src = h->d_tgt_own; h->src_pitch = h->tgt_pitch;
-  cloud_changed(h, false, 0, n_frames, counts);
+  cloud_changed(h, false, 0, n_frames, counts.data());
   struct Unalias { mi355ndt_handle* h; ~Unalias() { h->d_src = h->d_src_own; h->src_pitch = h->own_src_pitch; clouds_reset(h, false, true);
                                                      h->d_grid_of_use = nullptr; h->aligned_once = false;
                                                      if (h->ev_compute) (void)compute_enqueued(h); } } unalias{h};   // (error exits too: later uploads wait for what was enqueued)
-  for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));     // (upload time is reported on its own)
-  const auto t_up1 = std::chrono::steady_clock::now();
   const bool keep_prof = h->prof;
   struct ProfBack { mi355ndt_handle* h; bool v; ~ProfBack() { h->prof = v; } } profback{h, keep_prof};   // (every exit restores it)
   h->prof = false;
@@ -114,11 +111,60 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
     float b_ms = 0, t_ms = 0;
     HIPCHK(h, hipEventElapsedTime(&b_ms, ev[0], ev[1]));
     HIPCHK(h, hipEventElapsedTime(&t_ms, ev[1], ev[2]));
-    stats->upload_ms = std::chrono::duration<double, std::milli>(t_up1 - t_up0).count();
+    stats->upload_ms = upload_ms;
     stats->build_ms = b_ms;
     stats->track_ms = t_ms;
     stats->aligns = n_frames > 1 ? n_frames : 0;
     stats->update_launches = h->h_seq_flags[1];
   }
   return compute_enqueued(h);
+}
+
+int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
+                          const double* stamps, const mi355ndt_seq_params* policy,
+                          mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  size_t maxn = 0;
+  int rc = sequence_args(h, n_frames, clouds, counts, stride, stamps, out_frames, (size_t)1 << 31, &maxn);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_up0 = std::chrono::steady_clock::now();
+  // every frame is a TARGET slot (its voxel grid is built: it may become a keyframe) and, through the same rows, the SOURCE of its own
+  // align: one cloud buffer serves both sides
+  rc = mi355ndt_batch_reserve(h, n_frames, maxn, 64);
+  if (rc) return rc;
+  rc = mi355ndt_batch_set_clouds(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, 0);
+  if (rc) return rc;
+  for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));     // (upload time is reported on its own)
+  const auto t_up1 = std::chrono::steady_clock::now();
+  return sequence_tracked(h, n_frames, stamps, policy, out_frames, out_results, stats, std::chrono::duration<double, std::milli>(t_up1 - t_up0).count());
+}
+
+// the same over RAW scans: the batch prefilter puts the frames into their slots (sized for the raw counts: a filtered cloud is no larger)
+int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
+                              const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_seq_params* policy,
+                              mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats,
+                              size_t* filtered_counts, double* prefilter_ms) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  size_t maxn = 0;
+  int rc = sequence_args(h, n_frames, clouds, counts, stride, stamps, out_frames, (size_t)1 << 30, &maxn);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_up0 = std::chrono::steady_clock::now();
+  rc = mi355ndt_batch_reserve(h, n_frames, maxn, 64);
+  if (rc) return rc;
+  std::vector<size_t> filtered((size_t)n_frames, 0);
+  double kernels_ms = 0.0;
+  rc = batch_prefilter_impl(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, pf, filtered.data(), nullptr, &kernels_ms);
+  if (rc) { if (rc != MI355NDT_ERR_BAD_ARG && h->ev_compute) (void)compute_enqueued(h); return rc; }
+  const auto t_up1 = std::chrono::steady_clock::now();
+  if (filtered_counts) std::copy(filtered.begin(), filtered.end(), filtered_counts);
+  if (prefilter_ms) *prefilter_ms = kernels_ms;
+  for (int k = 0; k < n_frames; k++)
+    if (filtered[(size_t)k] == 0) { h->err = "sequence run: frame " + std::to_string(k) + " is empty after the prefilter"; return MI355NDT_ERR_BAD_ARG; }
+  // staging and kernels alternate group by group inside the prefilter: what the host clock saw of it, less the kernels' own time, is the staging
+  const double up_ms = std::max(0.0, std::chrono::duration<double, std::milli>(t_up1 - t_up0).count() - kernels_ms);
+  return sequence_tracked(h, n_frames, stamps, policy, out_frames, out_results, stats, up_ms);
 }

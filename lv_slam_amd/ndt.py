@@ -86,6 +86,12 @@ class GicpResult(C.Structure):
                 ("delta", C.c_double)]
 
 
+class PrefilterParams(C.Structure):
+    """mi355ndt_prefilter_params: PrefilteringNodelet's distance filter, VoxelGrid leaf and base_link move."""
+    _fields_ = [("use_distance_filter", C.c_int), ("distance_near", C.c_double), ("distance_far", C.c_double), ("downsample_resolution", C.c_float),
+                ("use_transform", C.c_int), ("transform_colmajor", C.c_float * 16)]
+
+
 class SeqParams(C.Structure):
     _fields_ = [("keyframe_delta_trans", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double)]
 
@@ -118,6 +124,7 @@ SYMBOLS = [
     "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
     "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
     "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers",
+    "mi355ndt_prefilter_params_default", "mi355ndt_batch_prefilter", "mi355ndt_batch_get_cloud", "mi355ndt_sequence_run_raw",
     "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
     "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
     "mi355ndt_gicp_get_aligned",
@@ -137,6 +144,7 @@ OPT_F32_SUM_ORDER = 1          # mi355ndt_option: 0 = (t0 + t1) + t2 (canonical)
 OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch align's last sweep of a pair evaluates the score alone, 0 = all 43 sums; same bits
 OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
 OPT_OUTLIER_CELL_MM = 10       # mi355ndt_option: cell size [mm] of the index prefilter_outliers builds over the prefilter result in every call (default 100); no result bit depends on it
+OPT_PREFILTER_GROUP = 11      # mi355ndt_option: raw clouds per group of batch_prefilter (0, the default: by the engine's scratch budget); no result word depends on it
 OUTLIER_STATISTICAL = 1        # pcl::StatisticalOutlierRemoval, the prefiltering nodelet's in-code default
 OUTLIER_RADIUS = 2             # pcl::RadiusOutlierRemoval (the reference builds it and never runs it)
 
@@ -175,6 +183,10 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
     L.mi355ndt_outlier_params_default.argtypes = [C.POINTER(OutlierParams)]
     L.mi355ndt_prefilter_outliers.argtypes = [vp, C.POINTER(OutlierParams), vp, vp, sz, sz, C.POINTER(sz), C.POINTER(OutlierStats)]
+    L.mi355ndt_prefilter_params_default.argtypes = [C.POINTER(PrefilterParams)]
+    L.mi355ndt_batch_prefilter.argtypes = [vp, i, i, vp, vp, vp, vp, sz, C.POINTER(PrefilterParams), vp, vp]
+    L.mi355ndt_batch_get_cloud.argtypes = [vp, i, i, vp, sz, sz, C.POINTER(sz)]
+    L.mi355ndt_sequence_run_raw.argtypes = [vp, i, vp, vp, sz, vp, C.POINTER(PrefilterParams), C.POINTER(SeqParams), vp, vp, C.POINTER(SeqStats), vp, vp]
     L.mi355ndt_gicp_params_default.argtypes = [C.POINTER(GicpParams)]
     L.mi355ndt_gicp_set_params.argtypes = [vp, C.POINTER(GicpParams)]
     L.mi355ndt_gicp_set_target.argtypes = [vp, vp, sz, sz]
@@ -298,6 +310,35 @@ def _colmajor(M) -> np.ndarray:
     if M.shape != (4, 4):
         raise ValueError("transform must be 4x4")
     return np.ascontiguousarray(M.T).ravel()      # column-major flattening (Eigen::Matrix4f layout)
+
+
+def _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform) -> PrefilterParams:
+    """The keywords of Engine.batch_prefilter / sequence_run_raw as a PrefilterParams (no library call: a bad transform is refused here)."""
+    p = PrefilterParams(int(bool(use_distance_filter)), float(distance_near), float(distance_far), float(downsample_resolution), 0)
+    t = np.eye(4, dtype=np.float32) if transform is None else transform
+    p.transform_colmajor[:] = [float(v) for v in _colmajor(t)]
+    p.use_transform = int(transform is not None)
+    return p
+
+
+def _cloud_table(clouds, widen=False):
+    """A list of clouds as (kept arrays, pointers uint64[n], counts uint64[n], the records' one stride).  The C calls take one stride: with
+    `widen`, clouds of narrower records are copied into records as wide as the widest; without it, differing strides are refused."""
+    arrs = [_as_points(c) for c in clouds]
+    widths = {a.shape[1] for a in arrs if a.shape[0]} or {3}
+    if len(widths) != 1:
+        if not widen:
+            raise ValueError("all clouds of a call must share one record stride")
+        wide = max(widths)
+        arrs = [a if a.shape[1] == wide or not a.shape[0] else np.concatenate([a, np.zeros((a.shape[0], wide - a.shape[1]), np.float32)], axis=1) for a in arrs]
+    return (arrs, np.array([a.ctypes.data if a.shape[0] else 0 for a in arrs], np.uint64), np.array([a.shape[0] for a in arrs], np.uint64),
+            4 * max(widths))
+
+
+def _seq_frames_out(out, res) -> list:
+    return [dict(odom=np.array(f.odom_colmajor, np.float64).reshape(4, 4).T.copy(), tf_s2k=np.array(f.tf_s2k_colmajor, np.float32).reshape(4, 4).T.copy(),
+                 trans_probability=f.trans_probability, test=(f.dx, f.da, f.dt), key_id=f.key_id, new_keyframe=bool(f.new_keyframe),
+                 iterations=f.iterations, converged=bool(f.converged), aligns=f.aligns, result=_result_dict(r)) for f, r in zip(out, res)]
 
 
 def _result_dict(r: Result) -> dict:
@@ -751,6 +792,36 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         self._chk(self.lib.mi355ndt_batch_set_clouds(self.h, first_pair, n, ptr(tp), ptr(tc), ptr(sp), ptr(sc), stride, threads), "batch_set_clouds")
 
+    def batch_prefilter(self, targets, sources, first_pair=0, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1,
+                        use_distance_filter=True, transform=None):
+        """mi355ndt_batch_prefilter: lists of RAW clouds ([N,>=3], x,y,z first; either list may be None) through PrefilteringNodelet's distance
+        filter and VoxelGrid down-sampling (Engine.prefilter's rules and keyword defaults) into the batch slots first_pair ...; batch_reserve
+        comes first, sized for the FILTERED clouds.  transform: a 4x4 applied to every raw point first (the nodelet's base_link move).
+        Returns (target counts, source counts) after the filter, None for a side not given."""
+        if targets is None and sources is None:
+            raise ValueError("give targets, sources or both")
+        if targets is not None and sources is not None and len(targets) != len(sources):
+            raise ValueError("one source per target")
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
+        n = len(targets if targets is not None else sources)
+        both = _cloud_table(list(targets or []) + list(sources or []), widen=True)     # (one stride for the whole call)
+        nt = len(targets) if targets is not None else 0
+        tabs = [None if targets is None else (both[1][:nt].copy(), both[2][:nt].copy()), None if sources is None else (both[1][nt:].copy(), both[2][nt:].copy())]
+        outs = [None if t is None else np.zeros(max(n, 1), np.uint64) for t in tabs]
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        tt, ts = tabs
+        self._chk(self.lib.mi355ndt_batch_prefilter(self.h, int(first_pair), n, ptr(tt and tt[0]), ptr(tt and tt[1]), ptr(ts and ts[0]), ptr(ts and ts[1]),
+                                                    both[3], C.byref(prm), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
+        return tuple(None if o is None else [int(c) for c in o[:n]] for o in outs)
+
+    def batch_get_cloud(self, pair: int, target: bool) -> np.ndarray:
+        """The points batch slot `pair` holds on its target (or source) side, [M,3] f32, whatever route filled it."""
+        role, m = 2 if target else 1, C.c_size_t()
+        self._chk(self.lib.mi355ndt_batch_get_cloud(self.h, int(pair), role, None, 0, 12, C.byref(m)), "batch_get_cloud")
+        out = np.zeros((m.value, 3), np.float32)
+        self._chk(self.lib.mi355ndt_batch_get_cloud(self.h, int(pair), role, out.ctypes.data_as(C.c_void_p), m.value, 12, C.byref(m)), "batch_get_cloud")
+        return out
+
     def batch_bind_device(self, d_targets_ptr: int, target_counts, target_pitch: int, d_sources_ptr: int, source_counts, source_pitch: int):
         """Zero-copy device buffers laid out [pair][3][pitch] float32.  The caller keeps them alive."""
         tc = np.ascontiguousarray(target_counts, np.int32)
@@ -860,10 +931,10 @@ class Engine:
         """Opt-in fine-grained sweep for small batches (a single registration above all); see mi355ndt_set_latency_mode."""
         self._chk(self.lib.mi355ndt_set_latency_mode(self.h, int(on)), "set_latency_mode")
 
-    def sequence_run(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0):
+    def sequence_run(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0, raw_records=False):
         """mi355ndt_sequence_run: a run of frames tracked on the device the way ScanMatchingOdomNodelet::matching_s2k tracks them
         (scan_matching_odom_nodelet.cpp:192-261).  frames: list of [N,>=3] float arrays (x,y,z first); stamps: seconds.
-        Returns (list of per-frame dicts, stats dict)."""
+        Returns (list of per-frame dicts, stats dict); raw_records=True returns the (SeqFrame * n, Result * n) arrays in place of the dicts."""
         clouds = [_as_points(f) for f in frames]
         n = len(clouds)
         strides = {c.strides[0] for c in clouds if c.shape[0]} or {12}       # (numpy gives empty arrays zero strides)
@@ -879,10 +950,29 @@ class Engine:
         self._chk(self.lib.mi355ndt_sequence_run(self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), strides.pop(),
                                                  st.ctypes.data_as(C.c_void_p), C.byref(sp), C.cast(out, C.c_void_p), C.cast(res, C.c_void_p),
                                                  C.byref(stats)), "sequence_run")
-        frames_out = [dict(odom=np.array(f.odom_colmajor, np.float64).reshape(4, 4).T.copy(), tf_s2k=np.array(f.tf_s2k_colmajor, np.float32).reshape(4, 4).T.copy(),
-                           trans_probability=f.trans_probability, test=(f.dx, f.da, f.dt), key_id=f.key_id, new_keyframe=bool(f.new_keyframe),
-                           iterations=f.iterations, converged=bool(f.converged), aligns=f.aligns, result=_result_dict(r)) for f, r in zip(out, res)]
-        return frames_out, {k: getattr(stats, k) for k, _ in SeqStats._fields_}
+        return ((out, res) if raw_records else _seq_frames_out(out, res)), {k: getattr(stats, k) for k, _ in SeqStats._fields_}
+
+    def sequence_run_raw(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0,
+                         distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None, raw_records=False):
+        """mi355ndt_sequence_run_raw: sequence_run over RAW scans, the batch prefilter (batch_prefilter's keywords) in front and no scan
+        downloaded in between.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
+        returns the (SeqFrame * n, Result * n) arrays in place of the dicts."""
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
+        clouds, ptrs, cnts, stride = _cloud_table(frames)
+        n = len(clouds)
+        st = np.ascontiguousarray(stamps, np.float64)
+        if len(st) != n:
+            raise ValueError("one stamp per frame")
+        sp = SeqParams(keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time)
+        out, res, stats = (SeqFrame * n)(), (Result * n)(), SeqStats()
+        filtered, pf_ms = np.zeros(max(n, 1), np.uint64), C.c_double()
+        self._chk(self.lib.mi355ndt_sequence_run_raw(self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride,
+                                                     st.ctypes.data_as(C.c_void_p), C.byref(prm), C.byref(sp), C.cast(out, C.c_void_p),
+                                                     C.cast(res, C.c_void_p), C.byref(stats), filtered.ctypes.data_as(C.c_void_p), C.byref(pf_ms)),
+                  "sequence_run_raw")
+        sd = {k: getattr(stats, k) for k, _ in SeqStats._fields_}
+        sd["prefilter_ms"] = pf_ms.value
+        return ((out, res) if raw_records else _seq_frames_out(out, res)), sd, [int(c) for c in filtered[:n]]
 
     # -- profiling
     def profile_enable(self, on=True):

@@ -684,6 +684,85 @@ int mi355ndt_gicp_batch_align(mi355ndt_handle* h, const float* guesses_colmajor,
 int mi355ndt_gicp_batch_get_aligned(mi355ndt_handle* h, int slot, void* out_pts, size_t out_stride_bytes);
 int mi355ndt_gicp_batch_stats(mi355ndt_handle* h, int* rounds, int* requests);
 
+/* ---- ICP: pcl::IterativeClosestPoint (registration_method = ICP) -------------------------------------------------- */
+/* replaces pcl::IterativeClosestPoint as select_registration_method sets it up for registration_method = ICP
+ * (src/global_graph/registrations.cpp:21-29: transformation_epsilon 0.01, maximum_iterations 64, use_reciprocal_correspondences false):
+ * point-to-point ICP, one pair at a time, synchronously, here; all candidates of a loop check in one batch below (mi355ndt_icp_batch_*).
+ * PCL is not part of the reference tree: computeTransformation, CorrespondenceEstimation, TransformationEstimationSVD (Eigen::umeyama
+ * without scaling) and DefaultConvergenceCriteria are RESTATED AS RECALLED from PCL 1.8 (tools/icp_ref.py; parity unpinned,
+ * INTEGRATION.md).  One iteration is one device round trip -- the working cloud is moved by the last estimate, matched against the target's
+ * index and summed (two launches, one wait) -- and the host runs a 3x3 Jacobi SVD in f64 and the criteria on one small record.
+ * What the engine fixes because PCL's is not reproducible or not observable: a tie in the nearest-point search goes to the lower point id;
+ * d2 = (dx*dx + dy*dy) + dz*dz in f32; a correspondence is kept iff (double)d2 <= corr_dist_threshold^2; a source point that is not
+ * finite, or whose moved copy is not finite, matches nothing; the centroid and covariance sums are f64 sums of f64 products of the f32
+ * coordinates over a fixed tree (Eigen's are f32, in an order nobody can observe); the SVD is the engine's own (ndt_math.hpp jacobi_svd3).
+ * PCL's slip is reproduced: the convergence test compares the SQUARED translation of an iteration with the unsquared
+ * transformation_epsilon.  ICP reports hasConverged() = true at the iteration cap; so does this.
+ * mi355ndt_icp_params_default gives pcl::Registration's constructor values: transformation_epsilon 0, max_iterations 10,
+ * euclidean_fitness_epsilon -DBL_MAX, corr_dist_threshold sqrt(DBL_MAX), min_number_correspondences 3, use_reciprocal_correspondences 0.
+ * use_reciprocal_correspondences != 0 is refused (it needs a search over the moving cloud every iteration: not served).
+ * Clouds: host records or resident keyframes by id, as the GICP surface takes them; the target's one spatial index is the one the fitness
+ * scores and GICP search (built here if they have not built it); a source needs none.  A keyframe source is never written: the working
+ * cloud is the surface's own buffer.
+ *   mi355ndt_icp_correspondences: one step on a fresh working cloud T (guess p) (two f32 products; T NULL: identity): idx (may be NULL)
+ *     the target index per source point, -1 = none; d2 (may be NULL) the f32 squared distances, 0 where unmatched; sums (may be NULL)
+ *     sixteen f64 over the matches, p the moved source point, q its target point: sum p [0..2], sum q [3..5], sum q_r p_c [6 + 3 r + c],
+ *     sum d2 [15]; *m the matches.
+ *   mi355ndt_icp_align: align(output, guess).  state: how the loop ended (mi355ndt_icp_state); matches and mse: of the last iteration.
+ *   mi355ndt_icp_get_aligned: the working cloud after the last iteration's move (PCL's `output`), x, y, z into records of out_stride_bytes.
+ * Errors: MI355NDT_ERR_STATE in stream mode and with a cloud unset; MI355NDT_ERR_BAD_ARG with a mi355ndt_last_error text for a NaN or
+ * negative transformation_epsilon or corr_dist_threshold, a NaN euclidean_fitness_epsilon, a negative max_iterations or
+ * min_number_correspondences, reciprocal correspondences, an empty cloud, a released keyframe.  The GICP and NDT surfaces, the batch, the
+ * grids, the keyframes' rows and the other workspaces of the handle are left as they were. */
+enum mi355ndt_icp_state {
+  MI355NDT_ICP_NOT_CONVERGED = 0, MI355NDT_ICP_ITERATIONS = 1, MI355NDT_ICP_TRANSFORM = 2, MI355NDT_ICP_ABS_MSE = 3, MI355NDT_ICP_REL_MSE = 4,
+  MI355NDT_ICP_NO_CORRESPONDENCES = 5
+};
+typedef struct mi355ndt_icp_params {
+  double transformation_epsilon;         /* setTransformationEpsilon         0        */
+  int    max_iterations;                 /* setMaximumIterations             10       */
+  double euclidean_fitness_epsilon;      /* setEuclideanFitnessEpsilon       -DBL_MAX */
+  double corr_dist_threshold;            /* setMaxCorrespondenceDistance     sqrt(DBL_MAX) */
+  int    min_number_correspondences;     /* (no setter in PCL 1.8)           3        */
+  int    use_reciprocal_correspondences; /* setUseReciprocalCorrespondences  0; != 0 is refused */
+} mi355ndt_icp_params;
+typedef struct mi355ndt_icp_result {
+  float  final_colmajor[16];      /* getFinalTransformation() */
+  int    converged;               /* hasConverged() */
+  int    iterations;              /* nr_iterations_ */
+  int    state;                   /* mi355ndt_icp_state */
+  int    matches;                 /* correspondences of the last iteration */
+  double mse;                     /* their mean squared distance (0 with none) */
+} mi355ndt_icp_result;
+int mi355ndt_icp_params_default(mi355ndt_icp_params* p);
+int mi355ndt_icp_set_params(mi355ndt_handle* h, const mi355ndt_icp_params* p);
+int mi355ndt_icp_set_target(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_icp_set_source(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_icp_set_target_keyframe(mi355ndt_handle* h, int id);
+int mi355ndt_icp_set_source_keyframe(mi355ndt_handle* h, int id);
+int mi355ndt_icp_correspondences(mi355ndt_handle* h, const float* guess_colmajor, const float* T_colmajor, int* idx, float* d2, double* sums, int* m);
+int mi355ndt_icp_align(mi355ndt_handle* h, const float* guess_colmajor, mi355ndt_icp_result* result);
+int mi355ndt_icp_get_aligned(mi355ndt_handle* h, void* out_pts, size_t out_stride_bytes);
+
+/* ---- ICP, every candidate of a loop check in one batch ---------------------------------------------------------------- */
+/* The target is the one mi355ndt_icp_set_target / _set_target_keyframe set, the parameters are the handle's mi355ndt_icp_params; candidate
+ * k is the source of slot k.  ICP has no inner optimiser, so the batch is one loop on the calling thread (no worker threads): every round
+ * ONE table copy, ONE step launch, ONE final launch and ONE wait serve all slots that have not ended, then each slot's SVD and criteria
+ * run on the host; a slot that ended drops out of the table.  results[k] and mi355ndt_icp_batch_get_aligned(k) are, byte for byte, what
+ * mi355ndt_icp_set_source* + mi355ndt_icp_align(guess k) + mi355ndt_icp_get_aligned give for that source against the same target.
+ *   mi355ndt_icp_batch_reserve: 1..MI355NDT_ICP_BATCH_MAX slots; drops the earlier slots.
+ *   mi355ndt_icp_batch_stats: of the last batch align -- *rounds = the waits on the device = the largest iteration count of a slot,
+ *     requests[k] (n_slots; may be NULL) = the steps slot k took.
+ * Errors: as the single-pair surface's; a slot out of range and n_slots out of range are MI355NDT_ERR_BAD_ARG; after a failed round nothing
+ * more is launched and the first error is returned. */
+#define MI355NDT_ICP_BATCH_MAX MI355NDT_GICP_BATCH_MAX
+int mi355ndt_icp_batch_reserve(mi355ndt_handle* h, int n_slots);
+int mi355ndt_icp_batch_set_source(mi355ndt_handle* h, int slot, const void* pts, size_t n, size_t stride_bytes);
+int mi355ndt_icp_batch_set_source_keyframe(mi355ndt_handle* h, int slot, int id);
+int mi355ndt_icp_batch_align(mi355ndt_handle* h, const float* guesses_colmajor, mi355ndt_icp_result* results);
+int mi355ndt_icp_batch_get_aligned(mi355ndt_handle* h, int slot, void* out_pts, size_t out_stride_bytes);
+int mi355ndt_icp_batch_stats(mi355ndt_handle* h, int* rounds, int* requests);
+
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);
 int mi355ndt_profile_reset(mi355ndt_handle* h);

@@ -8,6 +8,9 @@
 //                   BFGS optimiser and the outer loop on the host: ndt_gicp.hpp, gicp_bfgs.hpp, ndt_host_gicp.hpp)
 //   GICP batch    : k_gc_cov per cloud -> [table copy -> k_gc_match_batch -> k_gc_cost_batch -> k_gc_cost_final_batch]*, one round for all
 //                   candidates of a loop check (gicp_lockstep.hpp, ndt_host_gicp_batch.hpp)
+//   ICP           : [k_icp_step -> k_icp_final]*, one round trip per iteration (pcl::IterativeClosestPoint; the 3x3 SVD, the criteria and
+//                   the loop on the host: ndt_icp.hpp, icp_outer.hpp, ndt_host_icp.hpp); the batch: [table copy -> k_icp_step_batch ->
+//                   k_icp_final_batch]* for all candidates of a loop check (ndt_host_icp_batch.hpp)
 //   align         : k_init_state -> k_sweep -> [k_update -> k_sweep]*      (computeTransformation +
 //                   computeDerivatives + computeStepLengthMT, include/ndt_omp/ndt_omp_impl2.hpp:87-188, 196-305, 841-1003;
 //                   step_size <= eps/2 only: [k_update -> k_hessian -> k_update -> k_sweep]*, impl2:622-714, 920-1000)
@@ -61,6 +64,8 @@
 #include "ndt_gicp.hpp"
 #include "gicp_bfgs.hpp"
 #include "gicp_lockstep.hpp"
+#include "ndt_icp.hpp"
+#include "icp_outer.hpp"
 #include "ndt_sequence.hpp"
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
@@ -92,5 +97,7 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result
 #include "ndt_host_gicp.hpp"       // GICP: covariances, correspondences, cost, BFGS driver, align
 #include "ndt_host_gicp_batch.hpp" // GICP: all candidates of a loop check in one lockstep batch
+#include "ndt_host_icp.hpp"        // ICP: correspondences, align (the estimate, the criteria and the loop: icp_outer.hpp)
+#include "ndt_host_icp_batch.hpp"  // ICP: all candidates of a loop check in one batch, one loop on the calling thread
 #include "ndt_host_sequence.hpp"   // latency mode, sequence run
 #include "ndt_host_stream.hpp"     // stream mode

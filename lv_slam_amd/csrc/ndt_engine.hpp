@@ -181,6 +181,33 @@ struct mi355ndt_handle {
     PinBuf<GcSlot> h_tab; DevBuf<GcSlot> d_tab;
     int rounds = 0; std::vector<int> requests;      // of the last batch align
   } gicp_batch;
+  // ICP surface (mi355ndt_icp_*, ndt_host_icp.hpp): parameters, the two clouds (a target's index is its side's or its keyframe's; a source
+  // needs none), the working cloud W ([3][pitch], the surface's own: a keyframe source is never written) with its correspondences, the
+  // step's chunk partials and match counter, the mapped record the host reads after every step, the last run (its final transformation
+  // and the estimate W has not been moved by yet)
+  struct IcpWork {
+    DevBuf<float> W, d2; DevBuf<int> idx; DevBuf<double> part;
+    size_t n = 0, pitch = 0;                        // of the cloud W holds
+    bool have_final = false; IcpRun run;
+  };
+  struct Icp {
+    mi355ndt_icp_params prm{0.0, 10, -DBL_MAX, 1.3407807929942596e154, 3, 0};
+    GicpSide side[2];
+    IcpWork work;
+    DevBuf<int> m; DevBuf<float> moved;
+    PinBuf<double> h_rec; double* d_rec = nullptr;   // (h_rec is mapped; d_rec: the device's view)
+  } icp;
+  // ICP batch (mi355ndt_icp_batch_*, ndt_host_icp_batch.hpp): the candidates of one loop check against the surface's target.  A slot is a
+  // source side with a working cloud of its own; the slots share one block of match counters, one mapped block of records and the round's
+  // table (pinned twin -> device).
+  struct IcpBatch {
+    struct Slot { GicpSide side; IcpWork work; };
+    std::vector<Slot> slot;
+    DevBuf<int> m;
+    PinBuf<double> h_rec; double* d_rec = nullptr;
+    PinBuf<IcpSlot> h_tab; DevBuf<IcpSlot> d_tab;
+    int rounds = 0; std::vector<int> requests;      // of the last batch align
+  } icp_batch;
   float last_final[16] = {1,0,0,0, 0,1,0,0, 0,0,1,0, 0,0,0,1};
   PinBuf<unsigned> h_pin_u;                      // pinned scratch (2 unsigned)
 

@@ -27,7 +27,8 @@
 //      Rm(r,c) += (double)(B p)_r * temp_c, B = the base transformation.
 //    The tree is fixed by the source index alone: 256 consecutive points per chunk -- 64 lanes by shuffle-xor 32, 16, ... 1, then the chunk's
 //    four wave sums in wave order -- then chunk c into slot c % 256 in ascending c, then the 256 slots by halving (slot t += slot t + s,
-//    s = 128 ... 1).  No float atomics.  The record (13 sums, m) is written into mapped host memory.
+//    s = 128 ... 1).  No float atomics.  The record (13 sums, m) is written into mapped host memory.  The two halves of the tree are
+//    templates on the number of sums (gc_chunk_tree, gc_slot_tree): the ICP step (ndt_icp.hpp) sums sixteen over the same tree.
 // 4. k_gc_match_batch + k_gc_cost_batch + k_gc_cost_final_batch -- stages 2 and 3 for every slot of mi355ndt_gicp_batch_align that waits for
 //    one, in one round.  The per-thread bodies of 2 and 3 are __device__ functions (gc_match_body, gc_cost_body, gc_final_body) which the
 //    single-pair and the batch kernels both instantiate; see section 4 below.
@@ -165,6 +166,43 @@ __global__ void __launch_bounds__(256) k_gc_match(const float* __restrict__ src,
   gc_match_body(src, spitch, n_src, tgt, a, c1, c2, idx, maha, m, (int)blockIdx.x);
 }
 
+// ---- the fixed-order tree of NS f64 sums (the GICP cost: 13; the ICP step, ndt_icp.hpp: 16) -------------------------------
+// gc_chunk_tree: a chunk's 256 lanes -> part[chunk][NS]: 64 lanes by shuffle-xor 32, 16, ... 1, then the four wave sums in wave order.  The
+// WHOLE workgroup of GC_CHUNK threads calls it (a lane without a term brings zeros).
+template <int NS>
+__device__ __forceinline__ void gc_chunk_tree(double (&v)[NS], double* __restrict__ part, int chunk) {
+  __shared__ double ws[GC_CHUNK / 64][NS];
+#pragma unroll
+  for (int k = 0; k < NS; k++)
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < NS; k++) ws[threadIdx.x >> 6][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    const int k = threadIdx.x;
+    part[(size_t)chunk * NS + k] = ((ws[0][k] + ws[1][k]) + ws[2][k]) + ws[3][k];
+  }
+}
+// gc_slot_tree: one cloud's chunks -> rec[0 .. NS - 1], by one workgroup of 256: chunk c into slot c % 256 in ascending c, then the 256
+// slots by halving
+template <int NS>
+__device__ __forceinline__ void gc_slot_tree(const double* __restrict__ part, int n_chunks, double* rec) {
+  __shared__ double sm[256];
+  for (int k = 0; k < NS; k++) {
+    double s = 0.0;
+    for (int c = threadIdx.x; c < n_chunks; c += 256) s += part[(size_t)c * NS + k];
+    __syncthreads();
+    sm[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) rec[k] = sm[0];
+  }
+}
+
 // ---- 3. cost sweep ---------------------------------------------------------------------------------------------
 struct GcCost { float Tx[16], B[16]; };            // applyState(base, x) and the base transformation, column-major
 
@@ -172,7 +210,6 @@ struct GcCost { float Tx[16], B[16]; };            // applyState(base, x) and th
 __device__ __forceinline__ void gc_cost_body(const float* __restrict__ src, size_t spitch, int n_src, const float* __restrict__ tgt, size_t tpitch,
                                              const int* __restrict__ idx, const double* __restrict__ maha, const GcCost& a, double* __restrict__ part,
                                              int chunk) {
-  __shared__ double ws[GC_CHUNK / 64][GC_SUMS];
   const int i = chunk * GC_CHUNK + threadIdx.x;
   double v[GC_SUMS];
 #pragma unroll
@@ -200,17 +237,7 @@ __device__ __forceinline__ void gc_cost_body(const float* __restrict__ src, size
 #pragma unroll
       for (int c = 0; c < 3; c++) v[4 + 3 * r + c] = bp[r] * temp[c];
   }
-#pragma unroll
-  for (int k = 0; k < GC_SUMS; k++)
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < GC_SUMS; k++) ws[threadIdx.x >> 6][k] = v[k];
-  __syncthreads();
-  if (threadIdx.x < GC_SUMS) {
-    const int k = threadIdx.x;
-    part[(size_t)chunk * GC_SUMS + k] = ((ws[0][k] + ws[1][k]) + ws[2][k]) + ws[3][k];
-  }
+  gc_chunk_tree<GC_SUMS>(v, part, chunk);
 }
 
 __global__ void __launch_bounds__(GC_CHUNK) k_gc_cost(const float* __restrict__ src, size_t spitch, int n_src, const float* __restrict__ tgt, size_t tpitch,
@@ -219,21 +246,7 @@ __global__ void __launch_bounds__(GC_CHUNK) k_gc_cost(const float* __restrict__ 
 }
 
 // one cloud's tree over its chunks' partials, by one workgroup of 256: rec[0 .. 12] = the sums
-__device__ __forceinline__ void gc_final_body(const double* __restrict__ part, int n_chunks, double* rec) {
-  __shared__ double sm[256];
-  for (int k = 0; k < GC_SUMS; k++) {
-    double s = 0.0;
-    for (int c = threadIdx.x; c < n_chunks; c += 256) s += part[(size_t)c * GC_SUMS + k];
-    __syncthreads();
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) rec[k] = sm[0];
-  }
-}
+__device__ __forceinline__ void gc_final_body(const double* __restrict__ part, int n_chunks, double* rec) { gc_slot_tree<GC_SUMS>(part, n_chunks, rec); }
 
 // the chunks' partials -> the record: rec[0 .. 12] = the sums, rec[13] = m
 __global__ void __launch_bounds__(256) k_gc_cost_final(const double* __restrict__ part, int n_chunks, const int* __restrict__ m, double* rec) {

@@ -88,14 +88,11 @@ static int gicp_view(mi355ndt_handle* h, int role, const char* where, GicpView* 
   return gicp_view_side(h, h->gicp.side[role], where, role == MI355NDT_GICP_TARGET ? ": no target cloud is set" : ": no source cloud is set", v);
 }
 
-// the side's index (first use of the cloud) and its covariances for the current (k_correspondences, gicp_epsilon); waits for the device
-static int gicp_prepare(mi355ndt_handle* h, const char* where, const GicpView& v) {
+// the side's index, built at the first use of the cloud (the ICP surface stops here: ndt_host_icp.hpp); waits for the device
+static int gicp_prepare_index(mi355ndt_handle* h, const GicpView& v) {
   CloudIndex& ix = *v.index;
   GicpCache& c = *v.cache;
-  const int K = h->gicp.prm.k_correspondences;
-  const double eps = h->gicp.prm.gicp_epsilon;
   hipStream_t s = h->stream;
-  if (v.n == 0) { h->err = std::string(where) + ": k_correspondences exceeds the cloud's searchable points (an empty cloud)"; return MI355NDT_ERR_BAD_ARG; }
   if (ix.status == CloudIndex::NO_INDEX) {
     int rc = uploads_before_compute(h);           // (a keyframe_add's transfer may still be on its way)
     if (rc) return rc;
@@ -112,6 +109,21 @@ static int gicp_prepare(mi355ndt_handle* h, const char* where, const GicpView& v
     w.pending = false;
     HIPCHK(h, hipGetLastError());
     kfi_built(ix, w.h_ret, 0);
+  }
+  return MI355NDT_OK;
+}
+
+// the side's index and its covariances for the current (k_correspondences, gicp_epsilon); waits for the device
+static int gicp_prepare(mi355ndt_handle* h, const char* where, const GicpView& v) {
+  CloudIndex& ix = *v.index;
+  GicpCache& c = *v.cache;
+  const int K = h->gicp.prm.k_correspondences;
+  const double eps = h->gicp.prm.gicp_epsilon;
+  hipStream_t s = h->stream;
+  if (v.n == 0) { h->err = std::string(where) + ": k_correspondences exceeds the cloud's searchable points (an empty cloud)"; return MI355NDT_ERR_BAD_ARG; }
+  {
+    const int rc = gicp_prepare_index(h, v);
+    if (rc) return rc;
   }
   if (c.k != K || c.eps != eps) {
     if (K > ix.n_fin) {

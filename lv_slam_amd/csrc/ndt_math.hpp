@@ -458,4 +458,84 @@ __device__ inline bool lu_solve6(const double* H, const double b[6], double x[6]
   return lu_accept(hF2, invF2);
 }
 
+// A = U diag(S) V' for a 3x3 f64 matrix (row-major), on the HOST: the SVD behind the ICP surface's rigid estimate (icp_outer.hpp), where
+// the reference runs Eigen::JacobiSVD<Matrix3d> inside Eigen::umeyama.  A two-sided Jacobi with Eigen's conventions as svd_solve6 keeps
+// them: the work matrix is A / max|A_ij| (a zero matrix gives U = V = I, S = 0), singular values come out non-negative and descending, U
+// and V are orthogonal whatever the rank (both are products of plane rotations, then sign flips of U's columns and column swaps of both).
+// Each (p, q) plane: a left rotation makes the 2x2 block symmetric, a Jacobi rotation diagonalises it; a block whose off-diagonal entries
+// are within 2 eps of the largest diagonal entry met so far (or below DBL_MIN) is left alone; sweeps until one rotates nothing.  Not a
+// transcription of Eigen's real_2x2_jacobi_svd: the last bits are the engine's (tools/icp_ref.py restates it operation for operation).
+inline void jacobi_svd3(const double A[9], double U[9], double S[3], double V[9]) {
+  double M[3][3], u[3][3], v[3][3], scale = 0.0;
+  for (int i = 0; i < 9; i++) scale = fabs(A[i]) > scale ? fabs(A[i]) : scale;
+  if (scale == 0.0) scale = 1.0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) { M[i][j] = A[3 * i + j] / scale; u[i][j] = v[i][j] = (i == j) ? 1.0 : 0.0; }
+  double maxdiag = 0.0;
+  for (int i = 0; i < 3; i++) maxdiag = fabs(M[i][i]) > maxdiag ? fabs(M[i][i]) : maxdiag;
+  for (int sweep = 0; sweep < 60; sweep++) {
+    bool rotated = false;
+    for (int p = 1; p < 3; p++)
+      for (int q = 0; q < p; q++) {
+        double thr = 2.0 * DBL_EPSILON * maxdiag;
+        if (thr < DBL_MIN) thr = DBL_MIN;
+        const double off = fabs(M[p][q]) > fabs(M[q][p]) ? fabs(M[p][q]) : fabs(M[q][p]);
+        if (!(off > thr)) continue;
+        rotated = true;
+        // rows/columns (q, p), q < p: the block [[a, b], [c, d]] = [[M(q,q), M(q,p)], [M(p,q), M(p,p)]]
+        const double a = M[q][q], b = M[q][p], c = M[p][q], d = M[p][p];
+        double c1 = 1.0, s1 = 0.0;                   // R1 = [[c1, s1], [-s1, c1]]: R1 * block is symmetric
+        const double t = a + d, dd = c - b;
+        if (dd != 0.0) {
+          const double w = t / dd, tmp = sqrt(1.0 + w * w);
+          s1 = 1.0 / tmp; c1 = w / tmp;
+        }
+        const double x = c1 * a + s1 * c, y = c1 * b + s1 * d, z = -s1 * b + c1 * d;   // the symmetric block [[x, y], [y, z]]
+        double cj = 1.0, sj = 0.0;                   // J = [[cj, sj], [-sj, cj]]: J' * symmetric * J is diagonal
+        if (y != 0.0) {
+          const double tau = (x - z) / (2.0 * y), w = sqrt(1.0 + tau * tau);
+          const double tj = -1.0 / (tau >= 0.0 ? tau + w : tau - w);
+          cj = 1.0 / sqrt(1.0 + tj * tj); sj = tj * cj;
+        }
+        const double cl = cj * c1 + sj * s1, sl = cj * s1 - sj * c1;   // L = J' R1 = [[cl, sl], [-sl, cl]]
+        for (int j = 0; j < 3; j++) {                // M <- L M (rows q, p)
+          const double mq = M[q][j], mp = M[p][j];
+          M[q][j] = cl * mq + sl * mp; M[p][j] = -sl * mq + cl * mp;
+        }
+        for (int i = 0; i < 3; i++) {                // M <- M J, V <- V J (columns q, p); U <- U L'
+          const double mq = M[i][q], mp = M[i][p];
+          M[i][q] = cj * mq - sj * mp; M[i][p] = sj * mq + cj * mp;
+          const double vq = v[i][q], vp = v[i][p];
+          v[i][q] = cj * vq - sj * vp; v[i][p] = sj * vq + cj * vp;
+          const double uq = u[i][q], up = u[i][p];
+          u[i][q] = cl * uq + sl * up; u[i][p] = -sl * uq + cl * up;
+        }
+        maxdiag = fabs(M[q][q]) > maxdiag ? fabs(M[q][q]) : maxdiag;
+        maxdiag = fabs(M[p][p]) > maxdiag ? fabs(M[p][p]) : maxdiag;
+      }
+    if (!rotated) break;
+  }
+  double s[3];
+  for (int j = 0; j < 3; j++) {                      // non-negative singular values: the sign goes into U's column
+    s[j] = fabs(M[j][j]);
+    if (M[j][j] < 0.0)
+      for (int i = 0; i < 3; i++) u[i][j] = -u[i][j];
+  }
+  for (int j = 0; j < 2; j++) {                      // descending: the largest of the tail (the first of equal ones) to position j
+    int k = j;
+    for (int l = j + 1; l < 3; l++) k = s[l] > s[k] ? l : k;
+    if (k != j) {
+      const double ts = s[j]; s[j] = s[k]; s[k] = ts;
+      for (int i = 0; i < 3; i++) {
+        const double tu = u[i][j]; u[i][j] = u[i][k]; u[i][k] = tu;
+        const double tv = v[i][j]; v[i][j] = v[i][k]; v[i][k] = tv;
+      }
+    }
+  }
+  for (int i = 0; i < 3; i++) {
+    S[i] = s[i] * scale;
+    for (int j = 0; j < 3; j++) { U[3 * i + j] = u[i][j]; V[3 * i + j] = v[i][j]; }
+  }
+}
+
 }  // namespace ndtm

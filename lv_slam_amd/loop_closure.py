@@ -114,6 +114,21 @@ def verify_candidates_gicp(engine: ndt.Engine, target, candidates, guesses, max_
     then ONE keyframe_fitness_scores([target] * K, candidates, finals, max_range) -- getFitnessScore at each final transformation, the
     kd-tree over the target -- and select_matching / select_matching_and_bow as they are.  Host clouds become keyframes for the call
     (keyframe_add) and are released afterwards.  The engine's GICP parameters (gicp_set_params) are the registration's."""
+    return _verify_on_slots(engine, engine.gicp_set_target, engine.gicp_batch_reserve, engine.gicp_batch_set_source, engine.gicp_batch_align,
+                            target, candidates, guesses, max_range, thresh, bow)
+
+
+def verify_candidates_icp(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
+    """verify_candidates for registration_method = ICP: the same arguments, the same tuple.  The target becomes the ICP surface's target,
+    candidate k the source of slot k of ONE icp_batch_align (mi355ndt_icp_batch_align: one round trip per iteration for all candidates
+    that have not ended), then ONE keyframe_fitness_scores and the two selection rules as they are.  The engine's ICP parameters
+    (icp_set_params) are the registration's."""
+    return _verify_on_slots(engine, engine.icp_set_target, engine.icp_batch_reserve, engine.icp_batch_set_source, engine.icp_batch_align,
+                            target, candidates, guesses, max_range, thresh, bow)
+
+
+def _verify_on_slots(engine, set_target, batch_reserve, batch_set_source, batch_align, target, candidates, guesses, max_range, thresh, bow):
+    """the body verify_candidates_gicp and verify_candidates_icp share: the surface's four calls differ, nothing else"""
     K = len(candidates)
     if K == 0:
         return None, None, DBL_MAX, 0
@@ -134,11 +149,11 @@ def verify_candidates_gicp(engine: ndt.Engine, target, candidates, guesses, max_
     try:
         tgt = resident(target)
         ids = [resident(candidates[c]) for c in slots]
-        engine.gicp_set_target(keyframe=tgt)
-        engine.gicp_batch_reserve(len(slots))
+        set_target(keyframe=tgt)
+        batch_reserve(len(slots))
         for k, i in enumerate(ids):
-            engine.gicp_batch_set_source(k, keyframe=i)
-        res = engine.gicp_batch_align(G[slots])
+            batch_set_source(k, keyframe=i)
+        res = batch_align(G[slots])
         sc, _ = engine.keyframe_fitness_scores([tgt] * len(slots), ids, [r["final"] for r in res], max_range)
     finally:
         for i in own:

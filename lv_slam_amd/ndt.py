@@ -86,6 +86,17 @@ class GicpResult(C.Structure):
                 ("delta", C.c_double)]
 
 
+class IcpParams(C.Structure):
+    """mi355ndt_icp_params: pcl::IterativeClosestPoint's parameters (pcl::Registration's constructor values)."""
+    _fields_ = [("transformation_epsilon", C.c_double), ("max_iterations", C.c_int), ("euclidean_fitness_epsilon", C.c_double),
+                ("corr_dist_threshold", C.c_double), ("min_number_correspondences", C.c_int), ("use_reciprocal_correspondences", C.c_int)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("final_colmajor", C.c_float * 16), ("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("matches", C.c_int),
+                ("mse", C.c_double)]
+
+
 class PrefilterParams(C.Structure):
     """mi355ndt_prefilter_params: PrefilteringNodelet's distance filter, VoxelGrid leaf and base_link move."""
     _fields_ = [("use_distance_filter", C.c_int), ("distance_near", C.c_double), ("distance_far", C.c_double), ("downsample_resolution", C.c_float),
@@ -130,7 +141,13 @@ SYMBOLS = [
     "mi355ndt_gicp_get_aligned",
     "mi355ndt_gicp_batch_reserve", "mi355ndt_gicp_batch_set_source", "mi355ndt_gicp_batch_set_source_keyframe", "mi355ndt_gicp_batch_align",
     "mi355ndt_gicp_batch_get_aligned", "mi355ndt_gicp_batch_stats",
+    "mi355ndt_icp_params_default", "mi355ndt_icp_set_params", "mi355ndt_icp_set_target", "mi355ndt_icp_set_source", "mi355ndt_icp_set_target_keyframe",
+    "mi355ndt_icp_set_source_keyframe", "mi355ndt_icp_correspondences", "mi355ndt_icp_align", "mi355ndt_icp_get_aligned",
+    "mi355ndt_icp_batch_reserve", "mi355ndt_icp_batch_set_source", "mi355ndt_icp_batch_set_source_keyframe", "mi355ndt_icp_batch_align",
+    "mi355ndt_icp_batch_get_aligned", "mi355ndt_icp_batch_stats",
 ]
+ICP_BATCH_MAX = 64             # MI355NDT_ICP_BATCH_MAX: slots of one mi355ndt_icp_batch_align
+ICP_STATES = ["NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES"]   # mi355ndt_icp_state
 GICP_BATCH_MAX = 64            # MI355NDT_GICP_BATCH_MAX: slots of one mi355ndt_gicp_batch_align
 GICP_TARGET, GICP_SOURCE = 0, 1  # mi355ndt_gicp_covariances' role
 OPT_ASYNC_ALIGN = 2            # mi355ndt_option: 1 (default) = one persistent launch per batch align, 0 = lockstep (update, sweep) rounds; same bits
@@ -204,6 +221,21 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_gicp_batch_align.argtypes = [vp, vp, vp]
     L.mi355ndt_gicp_batch_get_aligned.argtypes = [vp, i, vp, sz]
     L.mi355ndt_gicp_batch_stats.argtypes = [vp, C.POINTER(i), vp]
+    L.mi355ndt_icp_params_default.argtypes = [C.POINTER(IcpParams)]
+    L.mi355ndt_icp_set_params.argtypes = [vp, C.POINTER(IcpParams)]
+    L.mi355ndt_icp_set_target.argtypes = [vp, vp, sz, sz]
+    L.mi355ndt_icp_set_source.argtypes = [vp, vp, sz, sz]
+    L.mi355ndt_icp_set_target_keyframe.argtypes = [vp, i]
+    L.mi355ndt_icp_set_source_keyframe.argtypes = [vp, i]
+    L.mi355ndt_icp_correspondences.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(i)]
+    L.mi355ndt_icp_align.argtypes = [vp, vp, C.POINTER(IcpResult)]
+    L.mi355ndt_icp_get_aligned.argtypes = [vp, vp, sz]
+    L.mi355ndt_icp_batch_reserve.argtypes = [vp, i]
+    L.mi355ndt_icp_batch_set_source.argtypes = [vp, i, vp, sz, sz]
+    L.mi355ndt_icp_batch_set_source_keyframe.argtypes = [vp, i, i]
+    L.mi355ndt_icp_batch_align.argtypes = [vp, vp, vp]
+    L.mi355ndt_icp_batch_get_aligned.argtypes = [vp, i, vp, sz]
+    L.mi355ndt_icp_batch_stats.argtypes = [vp, C.POINTER(i), vp]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
@@ -297,6 +329,22 @@ def default_gicp_params(**kw) -> GicpParams:
     return p
 
 
+def default_icp_params(**kw) -> IcpParams:
+    """pcl::Registration's constructor values as pcl::IterativeClosestPoint starts with them, `kw` overriding fields."""
+    p = IcpParams()
+    load_library().mi355ndt_icp_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"no ICP parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _icp_result_dict(r: IcpResult) -> dict:
+    return dict(final=np.array(r.final_colmajor, np.float32).reshape(4, 4).T.copy(), converged=bool(r.converged), iterations=r.iterations,
+                state=r.state, matches=r.matches, mse=r.mse)
+
+
 def _as_points(cloud) -> np.ndarray:
     """Accept [N,3]/[N,4+] float arrays (PCL-like records: x,y,z first); returns C-contiguous f32."""
     a = np.asarray(cloud)
@@ -360,6 +408,8 @@ class Engine:
         self._keep = []
         self._gicp_n = [0, 0]                       # points of the GICP surface's target and source
         self._gicp_batch_n = []                     # points of the GICP batch's slots
+        self._icp_n = [0, 0]                        # points of the ICP surface's target and source
+        self._icp_batch_n = []                      # points of the ICP batch's slots
 
     def close(self):
         if getattr(self, "h", None):
@@ -716,6 +766,94 @@ class Engine:
         K = len(self._gicp_batch_n)
         rounds, req = C.c_int(0), np.zeros(max(K, 1), np.int32)
         self._chk(self.lib.mi355ndt_gicp_batch_stats(self.h, C.byref(rounds), req.ctypes.data_as(C.c_void_p)), "gicp_batch_stats")
+        return rounds.value, req[:K].copy()
+
+    # -- ICP (pcl::IterativeClosestPoint, registration_method = ICP): one pair, synchronous (the batch form follows)
+    def icp_set_params(self, p: IcpParams):
+        self._chk(self.lib.mi355ndt_icp_set_params(self.h, C.byref(p)), "icp_set_params")
+
+    def _icp_set(self, role: int, cloud=None, kid=None):
+        name = "icp_set_target" if role == GICP_TARGET else "icp_set_source"
+        if kid is not None:
+            fn = self.lib.mi355ndt_icp_set_target_keyframe if role == GICP_TARGET else self.lib.mi355ndt_icp_set_source_keyframe
+            self._chk(fn(self.h, int(kid)), name + "_keyframe")
+            n = self.keyframe_get(int(kid), fetch=False)
+        else:
+            a = _as_points(cloud)
+            fn = self.lib.mi355ndt_icp_set_target if role == GICP_TARGET else self.lib.mi355ndt_icp_set_source
+            self._chk(fn(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0]), name)
+            n = a.shape[0]
+        self._icp_n[role] = int(n)
+
+    def icp_set_target(self, cloud=None, keyframe=None):
+        """the target cloud: a host cloud, or a resident keyframe by id (searched through the keyframe's one index)"""
+        self._icp_set(GICP_TARGET, cloud, keyframe)
+
+    def icp_set_source(self, cloud=None, keyframe=None):
+        """the source cloud: a host cloud, or a resident keyframe by id (never written: the working cloud is the surface's own)"""
+        self._icp_set(GICP_SOURCE, cloud, keyframe)
+
+    def icp_correspondences(self, guess, T=None):
+        """one step on a fresh working cloud T (guess p): (idx [n] int32, -1 = none; d2 [n] f32, 0 where unmatched; sums [16] f64; m)"""
+        n = self._icp_n[GICP_SOURCE]
+        g = _colmajor(guess)
+        t = _colmajor(T) if T is not None else None
+        idx, d2, sums, m = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32), np.zeros(16, np.float64), C.c_int(0)
+        self._chk(self.lib.mi355ndt_icp_correspondences(self.h, g.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p) if t is not None else None,
+                                                        idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p),
+                                                        C.byref(m)), "icp_correspondences")
+        return idx[:n], d2[:n], sums, m.value
+
+    def icp_align(self, guess) -> dict:
+        """align(output, guess): final, converged, iterations, state (mi355ndt_icp_state; names: ICP_STATES), matches, mse"""
+        g = _colmajor(guess)
+        r = IcpResult()
+        self._chk(self.lib.mi355ndt_icp_align(self.h, g.ctypes.data_as(C.c_void_p), C.byref(r)), "icp_align")
+        return _icp_result_dict(r)
+
+    def icp_get_aligned(self) -> np.ndarray:
+        out = np.zeros((max(self._icp_n[GICP_SOURCE], 1), 3), np.float32)
+        self._chk(self.lib.mi355ndt_icp_get_aligned(self.h, out.ctypes.data_as(C.c_void_p), 12), "icp_get_aligned")
+        return out[: self._icp_n[GICP_SOURCE]]
+
+    # -- ICP, all candidates of a loop check in one batch (the target and the parameters are the single-pair surface's)
+    def icp_batch_reserve(self, n_slots: int):
+        self._chk(self.lib.mi355ndt_icp_batch_reserve(self.h, int(n_slots)), "icp_batch_reserve")
+        self._icp_batch_n = [0] * int(n_slots)
+
+    def icp_batch_set_source(self, slot: int, cloud=None, keyframe=None):
+        """candidate `slot`: a host cloud, or a resident keyframe by id"""
+        if keyframe is not None:
+            self._chk(self.lib.mi355ndt_icp_batch_set_source_keyframe(self.h, int(slot), int(keyframe)), "icp_batch_set_source_keyframe")
+            n = self.keyframe_get(int(keyframe), fetch=False)
+        else:
+            a = _as_points(cloud)
+            self._chk(self.lib.mi355ndt_icp_batch_set_source(self.h, int(slot), a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0]), "icp_batch_set_source")
+            n = a.shape[0]
+        self._icp_batch_n[int(slot)] = int(n)
+
+    def icp_batch_align(self, guesses) -> list:
+        """one batch align of every slot from guesses [K,4,4]: icp_align's dict per slot, the same bytes as the single-pair surface gives"""
+        K = len(self._icp_batch_n)
+        G = np.asarray(guesses, np.float32)
+        if G.shape != (K, 4, 4):
+            raise ValueError(f"guesses must be [{K},4,4]")
+        g = np.ascontiguousarray(np.transpose(G, (0, 2, 1))).reshape(max(K, 1), 16) if K else np.zeros((1, 16), np.float32)
+        res = (IcpResult * max(K, 1))()
+        self._chk(self.lib.mi355ndt_icp_batch_align(self.h, g.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)), "icp_batch_align")
+        return [_icp_result_dict(r) for r in res[:K]]
+
+    def icp_batch_get_aligned(self, slot: int) -> np.ndarray:
+        n = self._icp_batch_n[int(slot)] if 0 <= int(slot) < len(self._icp_batch_n) else 0
+        out = np.zeros((max(n, 1), 3), np.float32)
+        self._chk(self.lib.mi355ndt_icp_batch_get_aligned(self.h, int(slot), out.ctypes.data_as(C.c_void_p), 12), "icp_batch_get_aligned")
+        return out[:n]
+
+    def icp_batch_stats(self):
+        """(rounds, requests[K]) of the last batch align: waits on the device; steps per slot"""
+        K = len(self._icp_batch_n)
+        rounds, req = C.c_int(0), np.zeros(max(K, 1), np.int32)
+        self._chk(self.lib.mi355ndt_icp_batch_stats(self.h, C.byref(rounds), req.ctypes.data_as(C.c_void_p)), "icp_batch_stats")
         return rounds.value, req[:K].copy()
 
     # -- parity hooks

@@ -508,6 +508,32 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
                                 void* out_pts, size_t out_capacity, size_t out_stride_bytes,
                                 size_t* n_out, mi355ndt_outlier_stats* stats /* may be NULL */);
 
+/* PrefilteringNodelet::outlier_removal over the clouds that batch slots first_pair .. first_pair + n - 1 hold, in place, whatever route
+ * filled them.  sides: bit 0 = sources, bit 1 = targets.  Rules and params: mi355ndt_prefilter_outliers', word for word per cloud -- the
+ * NOTE on RADIUS included: the reference builds that filter and never runs it.  One launch chain serves all clouds of a group (groups are cut
+ * as mi355ndt_batch_prefilter cuts them, MI355NDT_OPT_PREFILTER_GROUP), the f64 statistics are formed on the device in index order, and the
+ * call waits for the device once per group: no dist[] crosses PCIe.  Per cloud: the survivors keep their order, the slot's rows behind the
+ * new count are zero as an upload leaves them, the slot's count is updated (a touched target invalidates the resident grids), and
+ * mi355ndt_batch_build_targets / mi355ndt_batch_align follow unchanged.  An empty slot stays empty and its stats are zeros; for RADIUS all
+ * stats are zeros.  target_counts_out / source_counts_out (n each, either may be NULL) receive the counts of the sides asked for;
+ * target_stats / source_stats (n each, either may be NULL) their statistics.  MI355NDT_ERR_STATE in stream mode.  MI355NDT_ERR_BAD_ARG,
+ * every argument checked before anything is enqueued and every slot, count and grid left as it was: device buffers bound, sides outside
+ * 1..3, slots outside the batch, a side that has never been given a cloud, and every parameter mi355ndt_prefilter_outliers refuses (the same
+ * texts behind "batch_remove_outliers:").  The resident prefilter result and its index, the keyframes and their indexes, the map-cloud and
+ * window workspaces are left as they were.  MI355NDT_OPT_OUTLIER_CELL_MM.  The rules are PCL 1.8's and FLANN's as restated in
+ * tools/outlier_ref.py, unpinned. */
+int mi355ndt_batch_remove_outliers(mi355ndt_handle* h, int first_pair, int n, int sides, const mi355ndt_outlier_params* p /* NULL: defaults */,
+                                   size_t* target_counts_out, size_t* source_counts_out,          /* either may be NULL */
+                                   mi355ndt_outlier_stats* target_stats, mi355ndt_outlier_stats* source_stats /* n each; either may be NULL */);
+
+/* mi355ndt_sequence_run_raw with the nodelet's third stage behind the batch prefilter: outlier != NULL runs mi355ndt_batch_remove_outliers
+ * over the frames' slots before the sequence (outlier == NULL: mi355ndt_sequence_run_raw itself).  filtered_counts are the counts after
+ * both stages, *prefilter_ms covers both stages' kernels, and a frame that is empty after both stages is MI355NDT_ERR_BAD_ARG. */
+int mi355ndt_sequence_run_raw_outliers(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride_bytes,
+                                       const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_outlier_params* outlier,
+                                       const mi355ndt_seq_params* policy, mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results,
+                                       mi355ndt_seq_stats* stats, size_t* filtered_counts /* may be NULL */, double* prefilter_ms /* may be NULL */);
+
 /* ---- map cloud: the global graph's map (MapCloudGenerator::generate) ------------------------------------ */
 /* replaces MapCloudGenerator::generate(keyframes, resolution) (src/global_graph/map_cloud_generator.cpp:17-55), which
  * GlobalGraphNodelet::optimization_timer_callback (global_graph_nodelet.cpp:725-745) and save_map_service (:1036-1046) call

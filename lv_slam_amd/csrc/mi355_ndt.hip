@@ -61,6 +61,7 @@
 #include "ndt_keyframe.hpp"
 #include "ndt_kffitness.hpp"
 #include "ndt_outlier.hpp"
+#include "ndt_outlier_batch.hpp"
 #include "ndt_gicp.hpp"
 #include "gicp_bfgs.hpp"
 #include "gicp_lockstep.hpp"
@@ -94,7 +95,7 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_mapcloud.hpp"   // map cloud
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id
 #include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
-#include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result
+#include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result and over batch slots
 #include "ndt_host_gicp.hpp"       // GICP: covariances, correspondences, cost, BFGS driver, align
 #include "ndt_host_gicp_batch.hpp" // GICP: all candidates of a loop check in one lockstep batch
 #include "ndt_host_icp.hpp"        // ICP: correspondences, align (the estimate, the criteria and the loop: icp_outer.hpp)

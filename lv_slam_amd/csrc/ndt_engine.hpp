@@ -49,7 +49,7 @@ struct StreamState {
 };
 
 // ---- scratch of the sort-and-compact chain: stage clouds -> extremes -> grid -> keys -> one-segment radix sort -> run heads -> exclusive
-// scan -> emit -> count.  The prefilter, the batch prefilter (K clouds at once, a segment each), the outlier removal, the map cloud (both routes), the window map and the cloud index builds
+// scan -> emit -> count.  The prefilter, the batch prefilter (K clouds at once, a segment each), the outlier removal (the batch form: K staged clouds in `x`, their index pools in `out`), the map cloud (both routes), the window map and the cloud index builds
 // (kfi_build_rows: the keyframe fitness scores, GICP) share this one instance; results (d_pf_out, the keyframe store, the indexes) are not in it.
 // Sharing is safe because
 //   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;

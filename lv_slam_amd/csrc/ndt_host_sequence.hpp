@@ -141,16 +141,18 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
   return sequence_tracked(h, n_frames, stamps, policy, out_frames, out_results, stats, std::chrono::duration<double, std::milli>(t_up1 - t_up0).count());
 }
 
-// the same over RAW scans: the batch prefilter puts the frames into their slots (sized for the raw counts: a filtered cloud is no larger)
-int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
-                              const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_seq_params* policy,
-                              mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats,
-                              size_t* filtered_counts, double* prefilter_ms) {
+// the same over RAW scans: the batch prefilter puts the frames into their slots (sized for the raw counts: a filtered cloud is no larger);
+// outlier != NULL: the nodelet's third stage follows over the same slots (the frames are target slots; the run aliases them as sources)
+int mi355ndt_sequence_run_raw_outliers(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
+                                       const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_outlier_params* outlier,
+                                       const mi355ndt_seq_params* policy, mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results,
+                                       mi355ndt_seq_stats* stats, size_t* filtered_counts, double* prefilter_ms) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   NOT_IN_STREAM(h);
   size_t maxn = 0;
   int rc = sequence_args(h, n_frames, clouds, counts, stride, stamps, out_frames, (size_t)1 << 30, &maxn);
   if (rc) return rc;
+  if (outlier) { rc = outlier_params_check(h, *outlier, "batch_remove_outliers"); if (rc) return rc; }
   HIPCHK(h, hipSetDevice(h->device));
   const auto t_up0 = std::chrono::steady_clock::now();
   rc = mi355ndt_batch_reserve(h, n_frames, maxn, 64);
@@ -159,6 +161,12 @@ int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* cons
   double kernels_ms = 0.0;
   rc = batch_prefilter_impl(h, 0, n_frames, clouds, counts, nullptr, nullptr, stride, pf, filtered.data(), nullptr, &kernels_ms);
   if (rc) { if (rc != MI355NDT_ERR_BAD_ARG && h->ev_compute) (void)compute_enqueued(h); return rc; }
+  if (outlier) {
+    double outlier_ms = 0.0;
+    rc = batch_outliers_impl(h, 0, n_frames, 2, outlier, filtered.data(), nullptr, nullptr, nullptr, &outlier_ms);
+    if (rc) { if (rc != MI355NDT_ERR_BAD_ARG && h->ev_compute) (void)compute_enqueued(h); return rc; }
+    kernels_ms += outlier_ms;
+  }
   const auto t_up1 = std::chrono::steady_clock::now();
   if (filtered_counts) std::copy(filtered.begin(), filtered.end(), filtered_counts);
   if (prefilter_ms) *prefilter_ms = kernels_ms;
@@ -167,4 +175,12 @@ int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* cons
   // staging and kernels alternate group by group inside the prefilter: what the host clock saw of it, less the kernels' own time, is the staging
   const double up_ms = std::max(0.0, std::chrono::duration<double, std::milli>(t_up1 - t_up0).count() - kernels_ms);
   return sequence_tracked(h, n_frames, stamps, policy, out_frames, out_results, stats, up_ms);
+}
+
+int mi355ndt_sequence_run_raw(mi355ndt_handle* h, int n_frames, const void* const* clouds, const size_t* counts, size_t stride,
+                              const double* stamps, const mi355ndt_prefilter_params* pf, const mi355ndt_seq_params* policy,
+                              mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats,
+                              size_t* filtered_counts, double* prefilter_ms) {
+  return mi355ndt_sequence_run_raw_outliers(h, n_frames, clouds, counts, stride, stamps, pf, nullptr, policy, out_frames, out_results, stats,
+                                            filtered_counts, prefilter_ms);
 }

@@ -50,9 +50,8 @@ struct KfiView {
   __device__ __forceinline__ int n_fin() const { return reinterpret_cast<const KfiHead*>(gd)->n_fin; }
 };
 
-// the cell rule; stat_out[0] = the status, for the host (two words per index built in a call, fetched with the call's results; the second:
-// the searchable points, cleared here for k_kfi_gather)
-__global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max_cells, KfiHead* head, int* stat_out) {
+// the cell rule over one cloud's six extreme words (k_kfi_grid below; k_olb_grid for K clouds at once, ndt_outlier_batch.hpp)
+__device__ __forceinline__ GridDesc kfi_cell_rule(const unsigned* __restrict__ mm, float cell0, int max_cells) {
   GridDesc g;
   memset(&g, 0, sizeof g);
   g.leaf = cell0;
@@ -81,6 +80,12 @@ __global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max
       break;
     }
   }
+  return g;
+}
+// ... for one cloud; stat_out[0] = the status, for the host (two words per index built in a call, fetched with the call's results; the
+// second: the searchable points, cleared here for k_kfi_gather)
+__global__ void k_kfi_grid(const unsigned* __restrict__ mm, float cell0, int max_cells, KfiHead* head, int* stat_out) {
+  const GridDesc g = kfi_cell_rule(mm, cell0, max_cells);
   head->gd = g;
   stat_out[0] = g.status;
   stat_out[1] = 0;

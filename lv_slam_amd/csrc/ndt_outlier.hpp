@@ -139,23 +139,24 @@ __device__ __forceinline__ bool knn_fill(const KfiView& v, unsigned j, float max
 }
 
 // One lane per searchable point.  method STATISTICAL: dist[id]; RADIUS: keep[id].  The caller has zeroed both; non-searchable points keep
-// their zero.  Both kernels are launched and the cloud's status picks the one that works.
+// their zero.  Both kernels are launched and the cloud's status picks the one that works.  blk: the workgroup's block of OL_LANES queries
+// within its cloud (the K-cloud launch of ndt_outlier_batch.hpp takes it from its item table).
 template <int CAP, bool LATTICE>
-__device__ __forceinline__ void ol_knn(const KfiView& v, int method, int K, float r2, float* dist, int* keep) {
+__device__ __forceinline__ void ol_knn(const KfiView& v, unsigned blk, int method, int K, float r2, float* dist, int* keep) {
   __shared__ float lst[CAP][OL_LANES];
   if (v.gd->status != (LATTICE ? GRID_OK : GRID_CAP)) return;
   if (method == OL_STATISTICAL && v.n_fin() < K + 1) return;   // nearestKSearch(mean_k + 1) comes back short: dist = 0, not valid
   OlList<CAP> list;
   list.init(lst, K);
   unsigned id;
-  if (!knn_fill<LATTICE, true>(v, blockIdx.x * OL_LANES + threadIdx.x, method == OL_RADIUS ? r2 : __int_as_float(0x7f800000), list, id)) return;
+  if (!knn_fill<LATTICE, true>(v, blk * OL_LANES + threadIdx.x, method == OL_RADIUS ? r2 : __int_as_float(0x7f800000), list, id)) return;
   if (method == OL_STATISTICAL) dist[id] = list.mean_distance();
   else keep[id] = (list.full() && list.worst < r2) ? 1 : 0;
 }
 template <int CAP>
-__global__ void __launch_bounds__(OL_LANES) k_ol_knn(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, true>(v, method, K, r2, dist, keep); }
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, true>(v, blockIdx.x, method, K, r2, dist, keep); }
 template <int CAP>
-__global__ void __launch_bounds__(OL_LANES) k_ol_knn_brute(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, false>(v, method, K, r2, dist, keep); }
+__global__ void __launch_bounds__(OL_LANES) k_ol_knn_brute(KfiView v, int method, int K, float r2, float* dist, int* keep) { ol_knn<CAP, false>(v, blockIdx.x, method, K, r2, dist, keep); }
 
 // STATISTICAL: removed iff (double)dist > threshold (a NaN threshold removes nothing); positions past n: 0
 __global__ void __launch_bounds__(256) k_ol_flag(const float* __restrict__ dist, int n, size_t pitch, double threshold, int* flag) {

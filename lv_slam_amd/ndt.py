@@ -134,7 +134,7 @@ SYMBOLS = [
     "mi355ndt_window_keyframe", "mi355ndt_keyframe_add", "mi355ndt_keyframe_get", "mi355ndt_keyframe_release", "mi355ndt_keyframe_count",
     "mi355ndt_map_cloud_keyframes", "mi355ndt_batch_set_target_keyframe", "mi355ndt_batch_set_source_keyframe",
     "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
-    "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers",
+    "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers", "mi355ndt_batch_remove_outliers", "mi355ndt_sequence_run_raw_outliers",
     "mi355ndt_prefilter_params_default", "mi355ndt_batch_prefilter", "mi355ndt_batch_get_cloud", "mi355ndt_sequence_run_raw",
     "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
     "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
@@ -200,6 +200,9 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_use_prefiltered.argtypes = [vp, i]
     L.mi355ndt_outlier_params_default.argtypes = [C.POINTER(OutlierParams)]
     L.mi355ndt_prefilter_outliers.argtypes = [vp, C.POINTER(OutlierParams), vp, vp, sz, sz, C.POINTER(sz), C.POINTER(OutlierStats)]
+    L.mi355ndt_batch_remove_outliers.argtypes = [vp, i, i, i, C.POINTER(OutlierParams), vp, vp, vp, vp]
+    L.mi355ndt_sequence_run_raw_outliers.argtypes = [vp, i, vp, vp, sz, vp, C.POINTER(PrefilterParams), C.POINTER(OutlierParams), C.POINTER(SeqParams), vp, vp,
+                                                     C.POINTER(SeqStats), vp, vp]
     L.mi355ndt_prefilter_params_default.argtypes = [C.POINTER(PrefilterParams)]
     L.mi355ndt_batch_prefilter.argtypes = [vp, i, i, vp, vp, vp, vp, sz, C.POINTER(PrefilterParams), vp, vp]
     L.mi355ndt_batch_get_cloud.argtypes = [vp, i, i, vp, sz, sz, C.POINTER(sz)]
@@ -367,6 +370,26 @@ def _prefilter_params(distance_near, distance_far, downsample_resolution, use_di
     p.transform_colmajor[:] = [float(v) for v in _colmajor(t)]
     p.use_transform = int(transform is not None)
     return p
+
+
+_OUTLIER_KEYS = ("method", "mean_k", "stddev_mul", "radius", "min_neighbors")
+
+
+def _outlier_params(method="STATISTICAL", mean_k=20, stddev_mul=1.0, radius=0.8, min_neighbors=2) -> OutlierParams:
+    """The keywords of Engine.batch_remove_outliers as an OutlierParams (no library call)."""
+    if isinstance(method, str):                    # (an unknown name becomes 0, which the library refuses with its own message)
+        method = {"STATISTICAL": OUTLIER_STATISTICAL, "RADIUS": OUTLIER_RADIUS}.get(method.upper(), 0)
+    return OutlierParams(int(method), int(mean_k), float(stddev_mul), float(radius), int(min_neighbors))
+
+
+def _outlier_dict(outlier) -> OutlierParams:
+    """The `outlier` dict of Engine.batch_prefilter / sequence_run_raw (empty: the nodelet's in-code defaults); an unknown key is refused here."""
+    if not isinstance(outlier, dict):
+        raise ValueError("outlier must be a dict of batch_remove_outliers' keywords (may be empty)")
+    unknown = sorted(set(outlier) - set(_OUTLIER_KEYS))
+    if unknown:
+        raise ValueError(f"outlier: unknown key(s) {unknown}; known: {list(_OUTLIER_KEYS)}")
+    return _outlier_params(**outlier)
 
 
 def _cloud_table(clouds, widen=False):
@@ -931,15 +954,18 @@ class Engine:
         self._chk(self.lib.mi355ndt_batch_set_clouds(self.h, first_pair, n, ptr(tp), ptr(tc), ptr(sp), ptr(sc), stride, threads), "batch_set_clouds")
 
     def batch_prefilter(self, targets, sources, first_pair=0, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1,
-                        use_distance_filter=True, transform=None):
+                        use_distance_filter=True, transform=None, outlier=None):
         """mi355ndt_batch_prefilter: lists of RAW clouds ([N,>=3], x,y,z first; either list may be None) through PrefilteringNodelet's distance
         filter and VoxelGrid down-sampling (Engine.prefilter's rules and keyword defaults) into the batch slots first_pair ...; batch_reserve
         comes first, sized for the FILTERED clouds.  transform: a 4x4 applied to every raw point first (the nodelet's base_link move).
+        outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the nodelet's third stage runs
+        over the same slots and sides right after, and the counts returned are those after both stages.
         Returns (target counts, source counts) after the filter, None for a side not given."""
         if targets is None and sources is None:
             raise ValueError("give targets, sources or both")
         if targets is not None and sources is not None and len(targets) != len(sources):
             raise ValueError("one source per target")
+        oprm = None if outlier is None else _outlier_dict(outlier)
         prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
         n = len(targets if targets is not None else sources)
         both = _cloud_table(list(targets or []) + list(sources or []), widen=True)     # (one stride for the whole call)
@@ -950,7 +976,37 @@ class Engine:
         tt, ts = tabs
         self._chk(self.lib.mi355ndt_batch_prefilter(self.h, int(first_pair), n, ptr(tt and tt[0]), ptr(tt and tt[1]), ptr(ts and ts[0]), ptr(ts and ts[1]),
                                                     both[3], C.byref(prm), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
+        if oprm is not None:
+            self._chk(self.lib.mi355ndt_batch_remove_outliers(self.h, int(first_pair), n, (2 if targets is not None else 0) | (1 if sources is not None else 0),
+                                                              C.byref(oprm), ptr(outs[0]), ptr(outs[1]), None, None), "batch_remove_outliers")
         return tuple(None if o is None else [int(c) for c in o[:n]] for o in outs)
+
+    def batch_remove_outliers(self, first_pair=0, n=None, targets=True, sources=True, method="STATISTICAL", mean_k=20, stddev_mul=1.0, radius=0.8,
+                              min_neighbors=2, return_stats=False):
+        """mi355ndt_batch_remove_outliers: PrefilteringNodelet::outlier_removal over the clouds batch slots first_pair .. first_pair + n - 1
+        hold (n=None: to the end of the batch), in place, whatever route filled them -- prefilter_outliers' rules and keywords per cloud
+        ("RADIUS" is the filter the reference builds and never runs: prefiltering_nodelet.cpp:71-78), all clouds of a group in one launch
+        chain.  Returns (target counts, source counts), None for a side not asked for; with return_stats also (target stats, source stats):
+        per cloud a dict n_in, n_valid, mean, stddev, threshold (zeros for RADIUS and for an empty slot)."""
+        sides = (2 if targets else 0) | (1 if sources else 0)
+        if not sides:
+            raise ValueError("give targets, sources or both")
+        prm = _outlier_params(method, mean_k, stddev_mul, radius, min_neighbors)
+        first_pair = int(first_pair)
+        if n is None:
+            n = self.lib.mi355ndt_batch_size(self.h) - first_pair
+        n = int(n)
+        m = max(n, 1)
+        cnt = [np.zeros(m, np.uint64) if targets else None, np.zeros(m, np.uint64) if sources else None]
+        st = [(OutlierStats * m)() if targets and return_stats else None, (OutlierStats * m)() if sources and return_stats else None]
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        sp = lambda a: None if a is None else C.cast(a, C.c_void_p)
+        self._chk(self.lib.mi355ndt_batch_remove_outliers(self.h, first_pair, n, sides, C.byref(prm), ptr(cnt[0]), ptr(cnt[1]), sp(st[0]), sp(st[1])),
+                  "batch_remove_outliers")
+        counts = tuple(None if c is None else [int(v) for v in c[:n]] for c in cnt)
+        if not return_stats:
+            return counts
+        return counts + tuple(None if a is None else [{k: getattr(a[j], k) for k, _ in OutlierStats._fields_} for j in range(n)] for a in st)
 
     def batch_get_cloud(self, pair: int, target: bool) -> np.ndarray:
         """The points batch slot `pair` holds on its target (or source) side, [M,3] f32, whatever route filled it."""
@@ -1091,11 +1147,15 @@ class Engine:
         return ((out, res) if raw_records else _seq_frames_out(out, res)), {k: getattr(stats, k) for k, _ in SeqStats._fields_}
 
     def sequence_run_raw(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0,
-                         distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None, raw_records=False):
+                         distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None, raw_records=False,
+                         outlier=None):
         """mi355ndt_sequence_run_raw: sequence_run over RAW scans, the batch prefilter (batch_prefilter's keywords) in front and no scan
-        downloaded in between.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
+        downloaded in between.  outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the
+        nodelet's third stage runs between the prefilter and the run (mi355ndt_sequence_run_raw_outliers); the filtered counts and
+        prefilter_ms then cover both stages.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
         returns the (SeqFrame * n, Result * n) arrays in place of the dicts."""
         prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
+        oprm = None if outlier is None else _outlier_dict(outlier)
         clouds, ptrs, cnts, stride = _cloud_table(frames)
         n = len(clouds)
         st = np.ascontiguousarray(stamps, np.float64)
@@ -1104,10 +1164,12 @@ class Engine:
         sp = SeqParams(keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time)
         out, res, stats = (SeqFrame * n)(), (Result * n)(), SeqStats()
         filtered, pf_ms = np.zeros(max(n, 1), np.uint64), C.c_double()
-        self._chk(self.lib.mi355ndt_sequence_run_raw(self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride,
-                                                     st.ctypes.data_as(C.c_void_p), C.byref(prm), C.byref(sp), C.cast(out, C.c_void_p),
-                                                     C.cast(res, C.c_void_p), C.byref(stats), filtered.ctypes.data_as(C.c_void_p), C.byref(pf_ms)),
-                  "sequence_run_raw")
+        head = (self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride, st.ctypes.data_as(C.c_void_p), C.byref(prm))
+        tail = (C.byref(sp), C.cast(out, C.c_void_p), C.cast(res, C.c_void_p), C.byref(stats), filtered.ctypes.data_as(C.c_void_p), C.byref(pf_ms))
+        if oprm is None:
+            self._chk(self.lib.mi355ndt_sequence_run_raw(*head, *tail), "sequence_run_raw")
+        else:
+            self._chk(self.lib.mi355ndt_sequence_run_raw_outliers(*head, C.byref(oprm), *tail), "sequence_run_raw_outliers")
         sd = {k: getattr(stats, k) for k, _ in SeqStats._fields_}
         sd["prefilter_ms"] = pf_ms.value
         return ((out, res) if raw_records else _seq_frames_out(out, res)), sd, [int(c) for c in filtered[:n]]

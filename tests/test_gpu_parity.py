@@ -585,7 +585,7 @@ def test_batch_matches_single_and_oracle():
 
 def test_many_pairs_with_one_very_large_grid():
     """Many pairs AND one very large grid (25 cell bits next to 9 bits' worth of pairs).  The sort key is the cell index alone and no
-    pass leaves a target's segment, so the batch's widest grid only sets the digit plan (three 9-bit passes here instead of two
+    pass leaves a target's segment, so the batch's widest grid only sets the digit plan (three 10-bit passes here instead of two
     10-bit ones) for every segment.  Same voxels as the oracle, same alignment as a single-pair engine."""
     rng = np.random.default_rng(11)
     t0, s0, _ = synth.make_pair(30, 64, n_beams=32)

@@ -431,15 +431,53 @@ int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
  * nodelet's base_link move (prefiltering_nodelet.cpp:100-115: pcl_ros::transformPointCloud, which casts the tf transform to float and calls
  * PCL 1.8.1's pcl::transformPointCloud(in, out, Eigen::Matrix4f)):  (float)(((T(a,0) x + T(a,1) y) + T(a,2) z) + T(a,3)),  every product and sum
  * a separately rounded f32 operation; a point with a non-finite coordinate is not moved and is dropped by the filter.  The rule is PCL's as
- * restated here, unpinned. */
+ * restated here, unpinned.
+ * With use_angle_calibration (mi355ndt_prefilter_params_ex) every point is then turned by angle_calibration_rad about the normalised p x (0,0,1)
+ * (vertical_angle_calibration, :183-220): in f64, Eigen 3.3's cross, normalize (a point on the z axis keeps a zero axis and is scaled by
+ * cos), AngleAxisd::toRotationMatrix and 3x3 product restated operation for operation, no FMA, the result cast to f32; a point with a
+ * non-finite coordinate is left as it is.  The gate and the centroids see the moved and calibrated points.
+ * downsample_method = MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID is pcl::ApproximateVoxelGrid (PCL 1.8.1 approximate_voxel_grid.hpp, x, y, z only):
+ * inv = 1.0f / leaf; cell = (int)floor(coord * inv), the product f32; a history table of 512 entries indexed by
+ * (ix * 7171 + iy * 3079 + iz * 4231) & 511, walked in input order; a point whose entry holds another cell flushes it -- f32 sum / (float)count
+ * is appended to the output --; after the last point the non-empty entries are flushed in table order.  A cell can appear more than once and
+ * the output can be as large as the input.  Non-finite points are dropped, gate or no gate.  A cloud with a kept point whose
+ * |floor(coord * inv)| >= 2^31 is left un-down-sampled under the "leaf too small" rule below.  Both rules as restated in
+ * tools/prefilter_options_ref.py, unpinned. */
+enum { MI355NDT_DOWNSAMPLE_VOXELGRID = 0, MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID = 1 };
 typedef struct mi355ndt_prefilter_params {
   int    use_distance_filter;           /* 1 */
+  int    extended;                      /* 0.  MI355NDT_PREFILTER_EXTENDED: this struct is the `base` of the mi355ndt_prefilter_params_ex below.  The
+                                           word lies where the compiler's padding lay: size and offsets of this struct are what they were */
   double distance_near, distance_far;   /* 1.0, 100.0: the nodelet's in-code defaults (prefiltering_nodelet.cpp:83-85) */
   float  downsample_resolution;         /* 0.1; <= 0: no down-sampling */
   int    use_transform;                 /* 0 */
   float  transform_colmajor[16];        /* identity */
 } mi355ndt_prefilter_params;
 int mi355ndt_prefilter_params_default(mi355ndt_prefilter_params* p);
+
+/* The nodelet's remaining parameters, behind the struct above: mi355ndt_prefilter_params keeps its 96 bytes, so a caller built against it
+ * goes on working unchanged, and every function that takes a `const mi355ndt_prefilter_params*` (mi355ndt_batch_prefilter,
+ * mi355ndt_sequence_run_raw, mi355ndt_sequence_run_raw_outliers, mi355ndt_prefilter_p) also takes `&ex.base` of this one: when
+ * base.extended == MI355NDT_PREFILTER_EXTENDED the three fields behind `base` are read, with any other value they are not looked at and
+ * the defaults hold (VOXELGRID, no calibration).  mi355ndt_prefilter_params_ex_default fills `base` as mi355ndt_prefilter_params_default
+ * does, sets base.extended and the three defaults. */
+#define MI355NDT_PREFILTER_EXTENDED 0x50467832   /* "PFx2" */
+typedef struct mi355ndt_prefilter_params_ex {
+  mi355ndt_prefilter_params base;       /* base.extended = MI355NDT_PREFILTER_EXTENDED */
+  int    downsample_method;             /* MI355NDT_DOWNSAMPLE_VOXELGRID; base.downsample_resolution <= 0 is "NONE" whatever the method */
+  int    use_angle_calibration;         /* 0 (prefiltering_nodelet.cpp:88) */
+  double angle_calibration_rad;         /* 0.11 * M_PI / 180, the reference's constant (:190) */
+} mi355ndt_prefilter_params_ex;
+int mi355ndt_prefilter_params_ex_default(mi355ndt_prefilter_params_ex* p);
+
+/* mi355ndt_prefilter with the nodelet's whole parameter set (p: a mi355ndt_prefilter_params or the base of a mi355ndt_prefilter_params_ex;
+ * NULL: the defaults): the base_link move, the calibration, the gate and the
+ * down-sampling method of p, by the batch surface's kernels over this one cloud.  The result stays resident exactly as after
+ * mi355ndt_prefilter -- mi355ndt_use_prefiltered and mi355ndt_prefilter_outliers follow unchanged --, and with the default method and no
+ * calibration its words are mi355ndt_prefilter's.  A leaf too small for the cloud is no error: the kept points go out in input order and
+ * mi355ndt_last_error says so.  MI355NDT_ERR_BAD_ARG for what mi355ndt_prefilter and mi355ndt_batch_prefilter refuse. */
+int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes, const mi355ndt_prefilter_params* p,
+                         void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
 
 /* Like mi355ndt_batch_set_clouds, but every cloud is RAW and goes through the prefilter (mi355ndt_prefilter's rules, bit for bit) on its way
  * into its slot: the clouds are staged into the engine's scratch, filtered there group by group -- every stage one launch for all clouds of a
@@ -449,8 +487,8 @@ int mi355ndt_prefilter_params_default(mi355ndt_prefilter_params* p);
  * receive the filtered counts.  mi355ndt_batch_build_targets / mi355ndt_batch_align follow as after mi355ndt_batch_set_clouds.
  * A leaf too small for some cloud's extent is no error: that cloud goes in as its kept points, in input order, and mi355ndt_last_error names
  * the first such slot.  MI355NDT_ERR_STATE in stream mode.  MI355NDT_ERR_BAD_ARG, every argument checked before anything is staged and
- * the batch unchanged: device buffers bound, a NULL cloud with a count, a stride below 12, a NaN resolution, a NaN in the transform, slots
- * outside the batch.  MI355NDT_ERR_BAD_ARG also for a filtered cloud that does not fit its slot: mi355ndt_last_error names the first such
+ * the batch unchanged: device buffers bound, a NULL cloud with a count, a stride below 12, a NaN resolution, a NaN in the transform, an unknown
+ * downsample_method, a non-finite angle_calibration_rad, slots outside the batch.  MI355NDT_ERR_BAD_ARG also for a filtered cloud that does not fit its slot: mi355ndt_last_error names the first such
  * slot, and every slot the call touched is recorded as empty.  The resident prefilter result, the keyframes and their indexes are left as
  * they were.  MI355NDT_OPT_PREFILTER_GROUP. */
 int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n,

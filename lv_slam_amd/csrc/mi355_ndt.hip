@@ -17,7 +17,7 @@
 // Build: __graft_entry__.build() compiles three translation units side by side and links them: this file, mi355_ndt_ord1.hip (the kernel
 // instantiations of the second f32 sum order) and mi355_ndt_fast.hip (those of the tolerance arithmetic); -DNDT_SINGLE_TU builds everything
 // from this file alone.
-// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp (the Newton control they call: ndt_newton.hpp) / ndt_hessian.hpp / ndt_upload.hpp / ndt_pose_record.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_prefilter_batch.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
+// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp (the Newton control they call: ndt_newton.hpp) / ndt_hessian.hpp / ndt_upload.hpp / ndt_pose_record.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_prefilter_batch.hpp / ndt_prefilter_approx.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
 // C-ABI lives in ndt_engine.hpp and the ndt_host_*.hpp headers listed at the end of this file, one per surface.  It stays ONE translation unit
 // (the non-template kernels of the headers would collide across units).  Data layout in HBM: DESIGN.md.  Built with -ffp-contract=off: every
 // f32/f64 step of the reference recipe is a separately rounded operation.
@@ -57,6 +57,7 @@
 #include "ndt_fitness.hpp"
 #include "ndt_prefilter.hpp"
 #include "ndt_prefilter_batch.hpp"
+#include "ndt_prefilter_approx.hpp"
 #include "ndt_mapcloud.hpp"
 #include "ndt_keyframe.hpp"
 #include "ndt_kffitness.hpp"

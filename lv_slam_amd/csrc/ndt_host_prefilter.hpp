@@ -74,14 +74,97 @@ int mi355ndt_prefilter_params_default(mi355ndt_prefilter_params* p) {
   for (int a = 0; a < 4; a++) p->transform_colmajor[5 * a] = 1.f;
   return MI355NDT_OK;
 }
+int mi355ndt_prefilter_params_ex_default(mi355ndt_prefilter_params_ex* p) {
+  if (!p) return MI355NDT_ERR_BAD_ARG;
+  memset(p, 0, sizeof *p);
+  (void)mi355ndt_prefilter_params_default(&p->base);
+  p->base.extended = MI355NDT_PREFILTER_EXTENDED;
+  p->downsample_method = MI355NDT_DOWNSAMPLE_VOXELGRID;
+  p->use_angle_calibration = 0; p->angle_calibration_rad = 0.11 * M_PI / 180;      // :88, :190
+  return MI355NDT_OK;
+}
 
 // The scratch of a group of K raw clouds of pitch rp, per raw point: rows 12 B + keep 1 + two key and two id arrays (sort ping-pong) 16 + flag 4
 // + pos 4 + the sort's tile histograms and offsets 2 x (2048 words per 4096-point tile) = 4: 41 B.  Groups are cut so that K * rp * 41 stays
 // under 2 GiB: 399 clouds of 131,072 points, 52 M raw points, whatever their number in the call.  (At most PFB_GROUP_MAX clouds: the per-cloud
-// words stay small beside the per-point ones.)
+// words stay small beside the per-point ones.)  APPROX_VOXELGRID uses the same arrays; what it needs on top -- 512 bucket words per cloud
+// behind the flags and the positions -- is in its pitch (pfb_pitch), so the same 41 B per position size its groups.
 #define PFB_POINT_BYTES    41
 #define PFB_SCRATCH_BUDGET ((size_t)2 << 30)
 #define PFB_GROUP_MAX      4096
+
+// What a prefilter chain does to every cloud of a group, decided once per call from the nodelet's parameters.
+struct PfbChain {
+  int use_df; double dnear, dfar;
+  float leaf; int downsample, approx;              // downsample: leaf > 0; approx: APPROX_VOXELGRID and downsample
+  PfbMove mv; PfCal cal;
+};
+// From the caller's parameters (NULL: the defaults; a mi355ndt_prefilter_params, or the base of a mi355ndt_prefilter_params_ex when it says
+// so): every parameter a call refuses, before anything is staged
+static int pfb_chain(const mi355ndt_prefilter_params* prm, PfbChain* c) {
+  mi355ndt_prefilter_params_ex x;
+  (void)mi355ndt_prefilter_params_ex_default(&x);
+  if (prm && prm->extended == MI355NDT_PREFILTER_EXTENDED) x = *(const mi355ndt_prefilter_params_ex*)prm;
+  else if (prm) x.base = *prm;
+  const mi355ndt_prefilter_params& p = x.base;
+  if (std::isnan(p.downsample_resolution)) return MI355NDT_ERR_BAD_ARG;
+  if (p.use_transform) for (float v : p.transform_colmajor) if (std::isnan(v)) return MI355NDT_ERR_BAD_ARG;
+  if (x.downsample_method != MI355NDT_DOWNSAMPLE_VOXELGRID && x.downsample_method != MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID) return MI355NDT_ERR_BAD_ARG;
+  if (!std::isfinite(x.angle_calibration_rad)) return MI355NDT_ERR_BAD_ARG;     // (NaN, and the infinities whose sine is one)
+  memset(c, 0, sizeof *c);
+  c->use_df = p.use_distance_filter; c->dnear = p.distance_near; c->dfar = p.distance_far;
+  c->leaf = p.downsample_resolution;
+  c->downsample = c->leaf > 0.f;
+  c->approx = c->downsample && x.downsample_method == MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID;
+  c->mv.on = p.use_transform != 0;
+  for (int a = 0; a < 3; a++) for (int k = 0; k < 4; k++) c->mv.m[4 * a + k] = p.transform_colmajor[4 * k + a];
+  c->cal.on = x.use_angle_calibration != 0;
+  c->cal.sn = std::sin(x.angle_calibration_rad); c->cal.cs = std::cos(x.angle_calibration_rad);
+  return MI355NDT_OK;
+}
+// the pitch of a group whose largest raw cloud has maxn points
+static size_t pfb_pitch(const PfbChain& c, size_t maxn) {
+  return std::max((size_t)64, (maxn + 63) & ~(size_t)63) + (c.approx ? (size_t)PFA_BUCKETS : 0);
+}
+// The chain over the K clouds staged in the scratch (rows in w.in at pitch rp, their items in w.tab): every stage one launch, the filtered
+// points into the items' rows, the result words (PFB_RES_WORDS) in w.stat.  Nothing waits.
+static void pfb_enqueue(hipStream_t s, VoxelScratch& w, const PfbChain& c, int K, size_t rp) {
+  const int tiles = (int)((rp + RS_TILE - 1) / RS_TILE);  // of one cloud: sort tiles = scan chunks (RS_TILE == PF_SCAN_CHUNK)
+  static_assert(RS_TILE == PF_SCAN_CHUNK, "one tile count serves the sort and the scan");
+  const PfbItem* items = (const PfbItem*)(unsigned char*)w.tab;
+  int* res = w.stat;
+  const size_t seg = (size_t)K * rp;               // (the sort's second key / id arrays start here)
+  const unsigned* keys = w.keys; const unsigned* vals = w.vals;
+  k_pfb_begin<<<(6 * K + 255) / 256, 256, 0, s>>>(w.mm, res, K);
+  const int fx = std::max(1, std::min(tiles * (RS_TILE / 256) / 4, 32));   // flag workgroups per cloud: four points per thread and pass, 32 at the most
+  k_pfb_flag<<<xcd_grid(fx, K), 256, 0, s>>>(w.in, rp, items, K, fx, c.use_df, c.dnear, c.dfar, c.mv, c.cal, w.keep, w.mm);
+  if (c.approx) {
+    k_pfa_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
+    k_pfa_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys, w.flag);
+    const RsPlan plan = rs_plan(10);               // 513 key values: one pass
+    rs_pass(s, plan.bits, w.keys, w.vals, w.keys + seg, w.vals + seg, rp, 0, w.hist, w.offs, tiles, K, true);
+    keys = w.keys + seg; vals = w.vals + seg;
+    k_pfa_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.keep, items, K, tiles, w.grid, w.flag);
+  } else {
+    if (c.downsample) {
+      const RsPlan plan = rs_plan(31);
+      k_pfb_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
+      k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys);
+      unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
+      for (int ps = 0; ps < plan.passes; ps++) {
+        rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0);
+        std::swap(ka, kb); std::swap(va, vb);
+      }
+      keys = ka; vals = va;
+    }
+    k_pfb_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(keys, w.keep, rp, items, K, tiles, w.grid, c.downsample, w.flag);
+  }
+  k_pfb_scan_totals<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, tiles, K);
+  k_pfb_scan_offsets<<<K, 1024, 0, s>>>(w.tmp, tiles, items, K, res);
+  k_pfb_scan_apply<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, w.pos, tiles, K);
+  if (c.approx) k_pfa_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.keep, w.flag, w.pos, w.grid, items, K, tiles);
+  else k_pfb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.flag, w.pos, w.grid, c.downsample, items, K, tiles);
+}
 
 // kernels_ms (may be null): the time of the prefilter's kernels, HIP events around every group's chain, summed
 static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const void* const* targets, const size_t* target_counts,
@@ -91,10 +174,8 @@ static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const
   if (n <= 0 || first_pair < 0 || first_pair + n > h->n_pairs || (!targets && !sources) || (targets && !target_counts) || (sources && !source_counts))
     return MI355NDT_ERR_BAD_ARG;
   if (h->d_tgt != h->d_tgt_own || h->d_src != h->d_src_own) return MI355NDT_ERR_BAD_ARG;
-  mi355ndt_prefilter_params p;
-  if (prm) p = *prm; else (void)mi355ndt_prefilter_params_default(&p);
-  if (std::isnan(p.downsample_resolution)) return MI355NDT_ERR_BAD_ARG;
-  if (p.use_transform) for (float v : p.transform_colmajor) if (std::isnan(v)) return MI355NDT_ERR_BAD_ARG;
+  PfbChain chain;
+  if (pfb_chain(prm, &chain)) return MI355NDT_ERR_BAD_ARG;
   struct Raw { bool tgt; int pair; const void* pts; size_t n; };
   std::vector<Raw> raw;                                 // pair after pair, the target before the source: "the first slot that ..." follows this order
   size_t maxn = 0;
@@ -109,18 +190,10 @@ static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const
     }
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const float leaf = p.downsample_resolution;
-  const int downsample = leaf > 0.f;
-  PfbMove mv;
-  memset(&mv, 0, sizeof mv);
-  mv.on = p.use_transform != 0;
-  for (int a = 0; a < 3; a++) for (int c = 0; c < 4; c++) mv.m[4 * a + c] = p.transform_colmajor[4 * c + a];
   const int n_raw = (int)raw.size();
-  const size_t rp = std::max((size_t)64, (maxn + 63) & ~(size_t)63);
+  const size_t rp = pfb_pitch(chain, maxn);
   int group = h->pf_group > 0 ? h->pf_group : (int)std::min((size_t)PFB_GROUP_MAX, std::max((size_t)1, PFB_SCRATCH_BUDGET / (PFB_POINT_BYTES * rp)));
   group = std::min(std::min(group, PFB_GROUP_MAX), n_raw);
-  const int tiles = (int)((rp + RS_TILE - 1) / RS_TILE);  // of one cloud: sort tiles = scan chunks (RS_TILE == PF_SCAN_CHUNK)
-  static_assert(RS_TILE == PF_SCAN_CHUNK, "one tile count serves the sort and the scan");
   VoxelScratch& w = h->vs;
   VsNeed need;
   need.clouds = (size_t)group; need.pitch = (size_t)group * rp; need.in = 3 * need.pitch;
@@ -135,7 +208,6 @@ static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const
   if (kernels_ms) { *kernels_ms = 0.0; for (auto& e : ev) HIPCHK(h, e.create(hipEventDefault)); }
   std::vector<int> counts((size_t)n_raw, 0);
   int first_overflow = INT_MAX, first_small = INT_MAX;
-  const RsPlan plan = rs_plan(31);
   for (int g0 = 0; g0 < n_raw; g0 += group) {
     const int K = std::min(group, n_raw - g0);
     if (w.pending) { HIPCHK(h, hipStreamSynchronize(s)); w.pending = false; }
@@ -159,28 +231,8 @@ static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const
       if (sources) HIPCHK(h, hipMemsetAsync(h->d_src_own + (size_t)first_pair * 3 * h->src_pitch, 0, (size_t)n * 3 * h->src_pitch * sizeof(float), s));
     }
     if (kernels_ms) HIPCHK(h, hipEventRecord(ev[0], s));
-    const PfbItem* items = (const PfbItem*)(unsigned char*)w.tab;
     int* res = w.stat;
-    const size_t seg = (size_t)K * rp;             // (the sort's second key / id arrays start here)
-    const unsigned* keys = w.keys; const unsigned* vals = w.vals;
-    k_pfb_begin<<<(6 * K + 255) / 256, 256, 0, s>>>(w.mm, res, K);
-    const int fx = std::max(1, std::min(tiles * (RS_TILE / 256) / 4, 32));   // flag workgroups per cloud: four points per thread and pass, 32 at the most
-    k_pfb_flag<<<xcd_grid(fx, K), 256, 0, s>>>(w.in, rp, items, K, fx, p.use_distance_filter, p.distance_near, p.distance_far, mv, w.keep, w.mm);
-    if (downsample) {
-      k_pfb_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, leaf, w.grid, items, K, res);
-      k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys);
-      unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
-      for (int ps = 0; ps < plan.passes; ps++) {
-        rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0);
-        std::swap(ka, kb); std::swap(va, vb);
-      }
-      keys = ka; vals = va;
-    }
-    k_pfb_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(keys, w.keep, rp, items, K, tiles, w.grid, downsample, w.flag);
-    k_pfb_scan_totals<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, tiles, K);
-    k_pfb_scan_offsets<<<K, 1024, 0, s>>>(w.tmp, tiles, items, K, res);
-    k_pfb_scan_apply<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, w.pos, tiles, K);
-    k_pfb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.flag, w.pos, w.grid, downsample, items, K, tiles);
+    pfb_enqueue(s, w, chain, K, rp);
     if (kernels_ms) HIPCHK(h, hipEventRecord(ev[1], s));
     rc = compute_enqueued(h);                      // the next group's uploads into the scratch wait for these kernels
     if (rc) return rc;
@@ -225,6 +277,54 @@ int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n, const vo
   // an error exit may leave copies and kernels queued that still use the scratch and the slot rows: later uploads wait for them all the same
   if (rc != MI355NDT_OK && rc != MI355NDT_ERR_BAD_ARG && h->ev_compute) (void)compute_enqueued(h);
   return rc;
+}
+
+// mi355ndt_prefilter with the nodelet's whole parameter set: the batch chain over a group of ONE cloud, emitted into the resident result
+int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t stride, const mi355ndt_prefilter_params* prm,
+                         void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  if ((!pts && n) || (n && stride < 12) || n >= (1u << 30) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
+  PfbChain chain;
+  if (pfb_chain(prm, &chain)) return MI355NDT_ERR_BAD_ARG;
+  *n_out = 0;
+  h->pf_count = 0;
+  if (n == 0) return MI355NDT_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t pitch = (n + 63) & ~(size_t)63, rp = pfb_pitch(chain, n);
+  VoxelScratch& w = h->vs;
+  VsNeed need;
+  need.pitch = rp; need.in = 3 * rp; need.tab = sizeof(PfbItem); need.stat = PFB_RES_WORDS(1);
+  int rc = vs_reserve(h, need);
+  if (rc) return rc;
+  if (3 * pitch > h->d_pf_out.cap) HIPCHK(h, hipStreamSynchronize(s));   // (the result buffer is re-allocated: no copy out of it may still run)
+  HIPCHK(h, h->d_pf_out.reserve(3 * pitch));
+  h->pf_pitch = pitch;
+  PfbItem* tab = (PfbItem*)(unsigned char*)w.h_tab;
+  tab[0] = PfbItem{h->d_pf_out, (unsigned long long)pitch, (int)n, 0};
+  w.pending = true;
+  HIPCHK(h, hipMemcpyAsync(w.tab, w.h_tab, sizeof(PfbItem), hipMemcpyHostToDevice, s));
+  rc = upload_cloud(h, w.in, rp, 0, pts, n, stride);
+  if (rc) return rc;
+  rc = uploads_before_compute(h);
+  if (rc) return rc;
+  pfb_enqueue(s, w, chain, 1, rp);
+  int* ret = w.h_ret;
+  HIPCHK(h, hipMemcpyAsync(ret, w.stat, PFB_RES_WORDS(1) * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  w.pending = false;
+  HIPCHK(h, hipGetLastError());
+  const size_t m = (size_t)ret[0];                // (at most n: the result's pitch holds it)
+  h->pf_count = (int)m;
+  *n_out = m;
+  if (ret[2] != INT_MAX) h->err = "prefilter: leaf size too small for the cloud's extent, voxel indices would overflow; cloud not down-sampled";
+  if (out_pts) {
+    if (m > out_capacity) return MI355NDT_ERR_BAD_ARG;
+    std::vector<float> tmp(3 * pitch);
+    HIPCHK(h, hipMemcpy(tmp.data(), h->d_pf_out, 3 * pitch * sizeof(float), hipMemcpyDeviceToHost));
+    rows_to_records(tmp.data(), pitch, 3, m, out_pts, out_stride, -1);
+  }
+  return MI355NDT_OK;
 }
 
 // the points a batch slot holds, whatever route filled it

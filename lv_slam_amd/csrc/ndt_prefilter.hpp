@@ -18,6 +18,30 @@ __device__ __forceinline__ bool pf_gate(float x, float y, float z, int use_df, d
   }
   return ok && finite3(x, y, z);
 }
+// PrefilteringNodelet::vertical_angle_calibration (:183-220): the point, widened to f64, turned by `delta` about the normalised p x (0,0,1) and
+// cast back to f32.  Eigen 3.3 restated operation for operation -- cross(), normalize() (squaredNorm; divided only when it is > 0, so a point on
+// the z axis keeps a zero axis and is scaled by cos(delta)), AngleAxisd::toRotationMatrix() and the 3x3 product --, every operation rounded on
+// its own, the terms that are zero kept: signed zeros come out as Eigen's.  sn, cs: sin(delta) and cos(delta), computed once on the host.
+// The caller leaves a point with a non-finite coordinate as it is (the gate drops it), the base_link move's rule.
+struct PfCal { int on; double sn, cs; };
+__device__ __forceinline__ void pf_calibrate(float& x, float& y, float& z, double sn, double cs) {
+  const double px = (double)x, py = (double)y, pz = (double)z;
+  double a0 = py * 1.0 - pz * 0.0, a1 = pz * 0.0 - px * 1.0, a2 = px * 0.0 - py * 0.0;   // p.cross((0,0,1))
+  const double s = (a0 * a0 + a1 * a1) + a2 * a2;
+  if (s > 0.0) { const double r = sqrt(s); a0 /= r; a1 /= r; a2 /= r; }                    // normalize()
+  const double s0 = sn * a0, s1 = sn * a1, s2 = sn * a2;                                   // sin_axis
+  const double k = 1.0 - cs, c0 = k * a0, c1 = k * a1, c2 = k * a2;                        // cos1_axis
+  double t = c0 * a1;
+  const double r01 = t - s2, r10 = t + s2;
+  t = c0 * a2;
+  const double r02 = t + s1, r20 = t - s1;
+  t = c1 * a2;
+  const double r12 = t - s0, r21 = t + s0;
+  const double r00 = c0 * a0 + cs, r11 = c1 * a1 + cs, r22 = c2 * a2 + cs;
+  x = (float)((r00 * px + r01 * py) + r02 * pz);
+  y = (float)((r10 * px + r11 * py) + r12 * pz);
+  z = (float)((r20 * px + r21 * py) + r22 * pz);
+}
 // a thread's extremes (f2ord order) into the six words of its cloud: wave reduction, one atomic per wave and word
 struct PfExt {
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};

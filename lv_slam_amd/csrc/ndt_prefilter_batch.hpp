@@ -27,9 +27,9 @@ __global__ void __launch_bounds__(256) k_pfb_begin(int* mm, int* res, int K) {
 
 // Flag: the move (pcl::transformPointCloud(in, out, Eigen::Matrix4f) of PCL 1.8.1: every product and sum a separately rounded f32 operation;
 // a point with a non-finite coordinate is left as it is and fails the finite test), written back to the rows -- the centroids sum moved points --,
-// then the gate and the cloud's extremes.
+// then the vertical-angle calibration (pf_calibrate) under the same rule, then the gate and the cloud's extremes: cloud_callback's order.
 __global__ void __launch_bounds__(256) k_pfb_flag(float* X, size_t rp, const PfbItem* __restrict__ items, int K, int nx, int use_df, double dnear,
-                                                  double dfar, const PfbMove mv, unsigned char* keep, int* mm) {
+                                                  double dfar, const PfbMove mv, const PfCal cal, unsigned char* keep, int* mm) {
   int b, bx;
   if (!xcd_map(nx, K, bx, b)) return;
   const int n = items[b].n;
@@ -38,13 +38,16 @@ __global__ void __launch_bounds__(256) k_pfb_flag(float* X, size_t rp, const Pfb
   PfExt ext;
   for (int i = bx * 256 + (int)threadIdx.x; i < n; i += nx * 256) {
     float x = Xb[i], y = Xb[rp + i], z = Xb[2 * rp + i];
-    if (mv.on && finite3(x, y, z)) {
+    const bool fin = finite3(x, y, z);
+    if (mv.on && fin) {
       const float tx = ((mv.m[0] * x + mv.m[1] * y) + mv.m[2] * z) + mv.m[3];
       const float ty = ((mv.m[4] * x + mv.m[5] * y) + mv.m[6] * z) + mv.m[7];
       const float tz = ((mv.m[8] * x + mv.m[9] * y) + mv.m[10] * z) + mv.m[11];
       x = tx; y = ty; z = tz;
-      Xb[i] = x; Xb[rp + i] = y; Xb[2 * rp + i] = z;
     }
+    const bool turn = cal.on && finite3(x, y, z);                    // (a move may have taken the point out of f32's range)
+    if (turn) pf_calibrate(x, y, z, cal.sn, cal.cs);
+    if ((mv.on && fin) || turn) { Xb[i] = x; Xb[rp + i] = y; Xb[2 * rp + i] = z; }
     const bool ok = pf_gate(x, y, z, use_df, dnear, dfar);
     kp[i] = ok ? 1 : 0;
     if (ok) ext.take(x, y, z);

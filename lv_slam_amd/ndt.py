@@ -11,6 +11,7 @@ loading fails loudly if the library is missing, construction fails if no GPU is 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import numpy as np
 
@@ -98,9 +99,16 @@ class IcpResult(C.Structure):
 
 
 class PrefilterParams(C.Structure):
-    """mi355ndt_prefilter_params: PrefilteringNodelet's distance filter, VoxelGrid leaf and base_link move."""
-    _fields_ = [("use_distance_filter", C.c_int), ("distance_near", C.c_double), ("distance_far", C.c_double), ("downsample_resolution", C.c_float),
-                ("use_transform", C.c_int), ("transform_colmajor", C.c_float * 16)]
+    """mi355ndt_prefilter_params: PrefilteringNodelet's distance filter, VoxelGrid leaf and base_link move (`extended` lies where the
+    compiler's padding lay: the layout is what it was)."""
+    _fields_ = [("use_distance_filter", C.c_int), ("extended", C.c_int), ("distance_near", C.c_double), ("distance_far", C.c_double),
+                ("downsample_resolution", C.c_float), ("use_transform", C.c_int), ("transform_colmajor", C.c_float * 16)]
+
+
+class PrefilterParamsEx(C.Structure):
+    """mi355ndt_prefilter_params_ex: the nodelet's down-sampling method and vertical-angle calibration behind a PrefilterParams whose
+    `extended` says so; every call that takes a PrefilterParams pointer takes byref(ex.base)."""
+    _fields_ = [("base", PrefilterParams), ("downsample_method", C.c_int), ("use_angle_calibration", C.c_int), ("angle_calibration_rad", C.c_double)]
 
 
 class SeqParams(C.Structure):
@@ -136,6 +144,7 @@ SYMBOLS = [
     "mi355ndt_keyframe_fitness_scores", "mi355ndt_inf_params_default", "mi355ndt_information_matrix",
     "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers", "mi355ndt_batch_remove_outliers", "mi355ndt_sequence_run_raw_outliers",
     "mi355ndt_prefilter_params_default", "mi355ndt_batch_prefilter", "mi355ndt_batch_get_cloud", "mi355ndt_sequence_run_raw",
+    "mi355ndt_prefilter_p", "mi355ndt_prefilter_params_ex_default",
     "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
     "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
     "mi355ndt_gicp_get_aligned",
@@ -162,6 +171,10 @@ OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch a
 OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
 OPT_OUTLIER_CELL_MM = 10       # mi355ndt_option: cell size [mm] of the index prefilter_outliers builds over the prefilter result in every call (default 100); no result bit depends on it
 OPT_PREFILTER_GROUP = 11      # mi355ndt_option: raw clouds per group of batch_prefilter (0, the default: by the engine's scratch budget); no result word depends on it
+PREFILTER_EXTENDED = 0x50467832  # MI355NDT_PREFILTER_EXTENDED: PrefilterParams.extended of the base of a PrefilterParamsEx
+DOWNSAMPLE_VOXELGRID = 0       # pcl::VoxelGrid, the prefiltering nodelet's default downsample_method
+DOWNSAMPLE_APPROX_VOXELGRID = 1  # pcl::ApproximateVoxelGrid
+ANGLE_CALIBRATION_RAD = 0.11 * math.pi / 180   # vertical_angle_calibration's constant (prefiltering_nodelet.cpp:190)
 OUTLIER_STATISTICAL = 1        # pcl::StatisticalOutlierRemoval, the prefiltering nodelet's in-code default
 OUTLIER_RADIUS = 2             # pcl::RadiusOutlierRemoval (the reference builds it and never runs it)
 
@@ -204,6 +217,8 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_sequence_run_raw_outliers.argtypes = [vp, i, vp, vp, sz, vp, C.POINTER(PrefilterParams), C.POINTER(OutlierParams), C.POINTER(SeqParams), vp, vp,
                                                      C.POINTER(SeqStats), vp, vp]
     L.mi355ndt_prefilter_params_default.argtypes = [C.POINTER(PrefilterParams)]
+    L.mi355ndt_prefilter_params_ex_default.argtypes = [C.POINTER(PrefilterParamsEx)]
+    L.mi355ndt_prefilter_p.argtypes = [vp, vp, sz, sz, C.POINTER(PrefilterParams), vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_batch_prefilter.argtypes = [vp, i, i, vp, vp, vp, vp, sz, C.POINTER(PrefilterParams), vp, vp]
     L.mi355ndt_batch_get_cloud.argtypes = [vp, i, i, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_sequence_run_raw.argtypes = [vp, i, vp, vp, sz, vp, C.POINTER(PrefilterParams), C.POINTER(SeqParams), vp, vp, C.POINTER(SeqStats), vp, vp]
@@ -363,13 +378,32 @@ def _colmajor(M) -> np.ndarray:
     return np.ascontiguousarray(M.T).ravel()      # column-major flattening (Eigen::Matrix4f layout)
 
 
-def _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform) -> PrefilterParams:
-    """The keywords of Engine.batch_prefilter / sequence_run_raw as a PrefilterParams (no library call: a bad transform is refused here)."""
-    p = PrefilterParams(int(bool(use_distance_filter)), float(distance_near), float(distance_far), float(downsample_resolution), 0)
+_DOWNSAMPLE_METHODS = {"VOXELGRID": DOWNSAMPLE_VOXELGRID, "APPROX_VOXELGRID": DOWNSAMPLE_APPROX_VOXELGRID}
+
+
+def _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method="VOXELGRID",
+                      angle_calibration=False) -> PrefilterParamsEx:
+    """The keywords of Engine.batch_prefilter / sequence_run_raw / prefilter_p as a PrefilterParamsEx, whose `base` the calls are given (no
+    library call: a bad transform, an unknown downsample_method and a non-finite calibration angle are refused here).  downsample_method:
+    the nodelet's strings ("NONE" is downsample_resolution <= 0); angle_calibration: False, True (the reference's 0.11 degrees) or the
+    angle in radians."""
+    if downsample_method not in _DOWNSAMPLE_METHODS:
+        raise ValueError(f"downsample_method must be one of {list(_DOWNSAMPLE_METHODS)} (no down-sampling: downsample_resolution <= 0)")
+    switch = isinstance(angle_calibration, (bool, np.bool_))
+    rad = ANGLE_CALIBRATION_RAD if switch else float(angle_calibration)
+    if not math.isfinite(rad):
+        raise ValueError("angle_calibration must be False, True or a finite angle in radians")
+    x = PrefilterParamsEx()
+    p = x.base
+    p.use_distance_filter, p.extended = int(bool(use_distance_filter)), PREFILTER_EXTENDED
+    p.distance_near, p.distance_far, p.downsample_resolution = float(distance_near), float(distance_far), float(downsample_resolution)
     t = np.eye(4, dtype=np.float32) if transform is None else transform
     p.transform_colmajor[:] = [float(v) for v in _colmajor(t)]
     p.use_transform = int(transform is not None)
-    return p
+    x.downsample_method = _DOWNSAMPLE_METHODS[downsample_method]
+    x.use_angle_calibration = int(bool(angle_calibration)) if switch else 1
+    x.angle_calibration_rad = rad
+    return x
 
 
 _OUTLIER_KEYS = ("method", "mean_k", "stddev_mul", "radius", "min_neighbors")
@@ -530,6 +564,19 @@ class Engine:
                                               int(use_distance_filter), float(distance_near), float(distance_far),
                                               float(downsample_resolution), out.ctypes.data_as(C.c_void_p) if fetch else None,
                                               a.shape[0], 12, C.byref(n_out)), "prefilter")
+        self._pf_count = n_out.value
+        return out[: n_out.value].copy() if fetch else n_out.value
+
+    def prefilter_p(self, cloud, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None,
+                    downsample_method="VOXELGRID", angle_calibration=False, fetch=True):
+        """mi355ndt_prefilter_p: prefilter with the nodelet's whole parameter set (batch_prefilter's keywords) over one cloud.  The result is
+        resident as after prefilter: use_prefiltered and prefilter_outliers follow.  Returns the filtered [M,3] cloud (M when fetch=False)."""
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
+        a = _as_points(cloud)
+        n_out = C.c_size_t()
+        out = np.zeros((a.shape[0], 3), np.float32) if fetch else None
+        self._chk(self.lib.mi355ndt_prefilter_p(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0] if a.shape[0] else 12, C.byref(prm.base),
+                                                out.ctypes.data_as(C.c_void_p) if fetch else None, a.shape[0], 12, C.byref(n_out)), "prefilter_p")
         self._pf_count = n_out.value
         return out[: n_out.value].copy() if fetch else n_out.value
 
@@ -954,10 +1001,13 @@ class Engine:
         self._chk(self.lib.mi355ndt_batch_set_clouds(self.h, first_pair, n, ptr(tp), ptr(tc), ptr(sp), ptr(sc), stride, threads), "batch_set_clouds")
 
     def batch_prefilter(self, targets, sources, first_pair=0, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1,
-                        use_distance_filter=True, transform=None, outlier=None):
+                        use_distance_filter=True, transform=None, outlier=None, downsample_method="VOXELGRID", angle_calibration=False):
         """mi355ndt_batch_prefilter: lists of RAW clouds ([N,>=3], x,y,z first; either list may be None) through PrefilteringNodelet's distance
         filter and VoxelGrid down-sampling (Engine.prefilter's rules and keyword defaults) into the batch slots first_pair ...; batch_reserve
         comes first, sized for the FILTERED clouds.  transform: a 4x4 applied to every raw point first (the nodelet's base_link move).
+        downsample_method: "VOXELGRID" or "APPROX_VOXELGRID" (pcl::ApproximateVoxelGrid: a cell may come out more than once, a slot may need
+        as many points as the raw cloud has); angle_calibration: False, True (the nodelet's 0.11 degrees) or radians -- the nodelet's
+        vertical_angle_calibration, after the move and before the gate.
         outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the nodelet's third stage runs
         over the same slots and sides right after, and the counts returned are those after both stages.
         Returns (target counts, source counts) after the filter, None for a side not given."""
@@ -966,7 +1016,7 @@ class Engine:
         if targets is not None and sources is not None and len(targets) != len(sources):
             raise ValueError("one source per target")
         oprm = None if outlier is None else _outlier_dict(outlier)
-        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
         n = len(targets if targets is not None else sources)
         both = _cloud_table(list(targets or []) + list(sources or []), widen=True)     # (one stride for the whole call)
         nt = len(targets) if targets is not None else 0
@@ -975,7 +1025,7 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         tt, ts = tabs
         self._chk(self.lib.mi355ndt_batch_prefilter(self.h, int(first_pair), n, ptr(tt and tt[0]), ptr(tt and tt[1]), ptr(ts and ts[0]), ptr(ts and ts[1]),
-                                                    both[3], C.byref(prm), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
+                                                    both[3], C.byref(prm.base), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
         if oprm is not None:
             self._chk(self.lib.mi355ndt_batch_remove_outliers(self.h, int(first_pair), n, (2 if targets is not None else 0) | (1 if sources is not None else 0),
                                                               C.byref(oprm), ptr(outs[0]), ptr(outs[1]), None, None), "batch_remove_outliers")
@@ -1148,13 +1198,13 @@ class Engine:
 
     def sequence_run_raw(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0,
                          distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None, raw_records=False,
-                         outlier=None):
+                         outlier=None, downsample_method="VOXELGRID", angle_calibration=False):
         """mi355ndt_sequence_run_raw: sequence_run over RAW scans, the batch prefilter (batch_prefilter's keywords) in front and no scan
         downloaded in between.  outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the
         nodelet's third stage runs between the prefilter and the run (mi355ndt_sequence_run_raw_outliers); the filtered counts and
         prefilter_ms then cover both stages.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
         returns the (SeqFrame * n, Result * n) arrays in place of the dicts."""
-        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform)
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
         oprm = None if outlier is None else _outlier_dict(outlier)
         clouds, ptrs, cnts, stride = _cloud_table(frames)
         n = len(clouds)
@@ -1164,7 +1214,7 @@ class Engine:
         sp = SeqParams(keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time)
         out, res, stats = (SeqFrame * n)(), (Result * n)(), SeqStats()
         filtered, pf_ms = np.zeros(max(n, 1), np.uint64), C.c_double()
-        head = (self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride, st.ctypes.data_as(C.c_void_p), C.byref(prm))
+        head = (self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride, st.ctypes.data_as(C.c_void_p), C.byref(prm.base))
         tail = (C.byref(sp), C.cast(out, C.c_void_p), C.cast(res, C.c_void_p), C.byref(stats), filtered.ctypes.data_as(C.c_void_p), C.byref(pf_ms))
         if oprm is None:
             self._chk(self.lib.mi355ndt_sequence_run_raw(*head, *tail), "sequence_run_raw")

@@ -40,7 +40,7 @@ extern "C" {
 #define MI355NDT_ERR_GRID        (-4)  /* target grid unusable: reference int32 guard
                                           (voxel_grid_covariance_omp_impl.hpp:75-84) or engine cell cap */
 #define MI355NDT_ERR_NO_DEVICE   (-5)
-#define MI355NDT_ERR_UNSUPPORTED (-6)  /* reserved: every configuration of the reference classes is served at present */
+#define MI355NDT_ERR_UNSUPPORTED (-6)  /* a surface or configuration MI355NDT_OPT_POSE_MODEL = 1 does not serve (mi355ndt_last_error says which) */
 /* Positive: a warning that rides in mi355ndt_result.status, never a return code.  Set only under MI355NDT_OPT_ARITH = 1: the registration is of a kind the
  * tolerance arithmetic is not meant for -- fewer than MI355NDT_TOLERANCE_MIN_HITS (point, voxel) hits at the final pose (the Hessian of a handful of points:
  * ~1e-7 per f32 term times its condition number is no tolerance-level perturbation any more) or a run that stopped at the iteration cap (an oscillating run
@@ -254,7 +254,20 @@ enum mi355ndt_option {
   MI355NDT_OPT_OUTLIER_CELL_MM = 10,
   /* Raw clouds per group of mi355ndt_batch_prefilter (0, the default: as many as keep the engine's scratch under its 2 GiB budget, 4096 at the
    * most).  No result word depends on the option, only the time and the scratch; it exists so that a test can force several groups. */
-  MI355NDT_OPT_PREFILTER_GROUP = 11
+  MI355NDT_OPT_PREFILTER_GROUP = 11,
+  /* Which implementation of pclomp::NormalDistributionsTransform the aligns restate.  0 (default): include/ndt_omp/ndt_omp_impl2.hpp, the
+   * Lie-algebra variant lv_slam compiles -- every result word as without the option.  1: include/ndt_omp/ndt_omp_impl.hpp, the Euler-angle NDT
+   * of upstream ndt_omp and of PCL, which a host gets by changing the include line of src/ndt_omp/ndt_omp.cpp: the pose vector is
+   * p = [x y z roll pitch yaw], started from the f32 translation and f32 rotation().eulerAngles(0, 1, 2) of the guess (a guess with negative
+   * roll starts in the chart near roll = pi, as the reference does) and updated by p += delta_p; the point Jacobian and Hessian come from the
+   * tables j_ang / h_ang applied to the ORIGINAL point; the pose matrix and the incremental transformations are convertTransform in f32.
+   * Served under 1: mi355ndt_batch_align, mi355ndt_align, mi355ndt_derivatives (p read as [t; roll pitch yaw]), all four neighbour searches, both
+   * f32 sum orders, always through the lockstep (update, sweep) rounds.  MI355NDT_OPT_ARITH is ignored (the exact arithmetic runs, no warning
+   * status).  Refused with MI355NDT_ERR_UNSUPPORTED and a message, nothing changed: variant = PCA, the live More-Thuente configuration
+   * (step_size <= trans_epsilon / 2), mi355ndt_sequence_run*, mi355ndt_stream_begin, mi355ndt_compute_hessian, mi355ndt_derivatives_T.  Setting
+   * the option while a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  PCL's own f64 NormalDistributionsTransform
+   * (registration_method = NDT) is not this option: it stays unserved. */
+  MI355NDT_OPT_POSE_MODEL = 12
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);

@@ -9,6 +9,22 @@ static inline bool mt_is_live(const mi355ndt_params& p) { return !((p.step_size 
 // ndt_pca + KDTREE: order-dependent weights -- its own per-leaf weights from the build (d_kdw), its own sweep kernel (ndt_sweep_kd.hpp)
 static inline bool is_pca_kd(const mi355ndt_params& p) { return p.neighbor_mode == MI355NDT_KDTREE && p.variant == MI355NDT_VARIANT_PCA; }
 
+// ---- MI355NDT_OPT_POSE_MODEL: 0 = ndt_omp_impl2.hpp (the SE(3) tangent), 1 = ndt_omp_impl.hpp (Euler angles).  What model 1 is served for is
+// answered here and nowhere else: ndt_omp with the dead More-Thuente loop, the exact arithmetic (MI355NDT_OPT_ARITH is ignored), the plain lockstep
+// rounds -- never the one-launch align, the latency pump, a sequence run or a stream.
+enum { POSE_MODEL_SE3 = 0, POSE_MODEL_EULER = 1 };
+// the arithmetic option as the engine's builds and sweeps see it
+static inline int model_arith(int pose_model, int arith) { return pose_model == POSE_MODEL_EULER ? 0 : arith; }
+// may an align of this model leave the lockstep rounds (one persistent launch, fine items)?
+static inline bool model_leaves_rounds(int pose_model) { return pose_model != POSE_MODEL_EULER; }
+// null: this model serves the configuration; else why not (MI355NDT_ERR_UNSUPPORTED)
+static inline const char* model_refuses(const mi355ndt_params& p, int pose_model) {
+  if (pose_model != POSE_MODEL_EULER) return nullptr;
+  if (p.variant == MI355NDT_VARIANT_PCA) return "MI355NDT_OPT_POSE_MODEL = 1 serves variant = OMP alone (ndt_pca_impl.hpp has its weight commented out: it is ndt_omp's sweep)";
+  if (mt_is_live(p)) return "MI355NDT_OPT_POSE_MODEL = 1 does not serve the live More-Thuente configuration (step_size <= trans_epsilon / 2)";
+  return nullptr;
+}
+
 // what a target build can make beside the base records (grid descriptors, bitmap words, the exact voxel records)
 struct GridExtras {
   bool cent;        // f32 leaf centroids: the KDTREE probe, computeHessian, calculateScore

@@ -45,7 +45,7 @@ static int run_hook_sweep(mi355ndt_handle* h, double* score, double g[6], double
   int rc = launch_sweep(h, sc);
   if (rc) return rc;
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 0);
+                                    nullptr, 0, 0, 0, 1, 0, nullptr);
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -67,6 +67,8 @@ static int hook_ready(mi355ndt_handle* h) {
 int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, double g[6], double H[36], long long* hits) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!p) return MI355NDT_ERR_BAD_ARG;
+  // (model 1: p = [t; roll pitch yaw] -- the cloud is moved by convertTransform(p), the rows are taken from p: k_set_pose_p)
+  if (const char* why = model_refuses(h->prm, h->pose_model)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
   int rc = hook_ready(h);
   if (rc) return rc;
   double* dp = (double*)h->d_hook.p;
@@ -74,13 +76,14 @@ int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, d
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
   h->ctl_idx = 0;
-  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 0);
+  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 0, euler_rows_of(h));
   return run_hook_sweep(h, score, g, H, hits);
 }
 
 int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!p || !H) return MI355NDT_ERR_BAD_ARG;
+  NOT_EULER(h, "mi355ndt_compute_hessian");             // (impl.hpp:913: dead at the settings model 1 serves)
   int rc = hook_ready(h);
   if (rc == MI355NDT_OK) rc = ensure_grids(h, GRIDS_LIVE);        // (the grid may have been built for a configuration that never needs the Hessian's inputs)
   if (rc) return rc;
@@ -90,12 +93,12 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
   h->ctl_idx = 0;
-  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 1);
+  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 1, nullptr);
   SweepConst sc;
   make_sweep_const(h, sc);
   launch_hessian(h, sc);
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 2);
+                                    nullptr, 0, 0, 0, 1, 2, nullptr);
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -107,6 +110,7 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
 int mi355ndt_derivatives_T(mi355ndt_handle* h, const float T[16], const float Rj[9], double* score, double g[6], double H[36], long long* hits) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!T || !Rj) return MI355NDT_ERR_BAD_ARG;
+  NOT_EULER(h, "mi355ndt_derivatives_T");               // (the Euler model's sweep is a function of the pose vector: mi355ndt_derivatives)
   int rc = hook_ready(h);
   if (rc) return rc;
   float buf[25];

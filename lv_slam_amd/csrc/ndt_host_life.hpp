@@ -205,7 +205,12 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
   if (h->ss && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
-                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP)) NOT_IN_STREAM(h);
+                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL)) NOT_IN_STREAM(h);
+  if (option == MI355NDT_OPT_POSE_MODEL) {
+    if (value != POSE_MODEL_SE3 && value != POSE_MODEL_EULER) return MI355NDT_ERR_BAD_ARG;
+    h->pose_model = value;                       // (what model 1 serves: ndt_grid_state.hpp; grids built for the tolerance arithmetic are rebuilt by the next align)
+    return MI355NDT_OK;
+  }
   if (option == MI355NDT_OPT_F32_SUM_ORDER) {
     if (value != 0 && value != 1) return MI355NDT_ERR_BAD_ARG;
     h->f32_sum_order = value;
@@ -268,6 +273,7 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (!value) return MI355NDT_ERR_BAD_ARG;
   if (option == MI355NDT_OPT_F32_SUM_ORDER) { *value = h->f32_sum_order; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ARITH) { *value = h->arith; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_POSE_MODEL) { *value = h->pose_model; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) { *value = h->async_force ? 2 : (h->async_align ? 1 : 0); return MI355NDT_OK; }
   if (option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) { *value = h->score_only_last; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_ABORT) { *value = h->debug_abort_pos == 0xFFFFFFFFu ? -1 : (int)h->debug_abort_pos; return MI355NDT_OK; }

@@ -125,6 +125,7 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
                           mi355ndt_seq_frame* out_frames, mi355ndt_result* out_results, mi355ndt_seq_stats* stats) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   NOT_IN_STREAM(h);
+  NOT_EULER(h, "mi355ndt_sequence_run");
   size_t maxn = 0;
   int rc = sequence_args(h, n_frames, clouds, counts, stride, stamps, out_frames, (size_t)1 << 31, &maxn);
   if (rc) return rc;
@@ -149,6 +150,7 @@ int mi355ndt_sequence_run_raw_outliers(mi355ndt_handle* h, int n_frames, const v
                                        mi355ndt_seq_stats* stats, size_t* filtered_counts, double* prefilter_ms) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   NOT_IN_STREAM(h);
+  NOT_EULER(h, "mi355ndt_sequence_run");
   size_t maxn = 0;
   int rc = sequence_args(h, n_frames, clouds, counts, stride, stamps, out_frames, (size_t)1 << 30, &maxn);
   if (rc) return rc;

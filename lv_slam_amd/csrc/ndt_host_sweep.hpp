@@ -9,7 +9,9 @@
 //   * IT = 8: batch-mode items (and the one-launch align, which has no other); IT = 1 / 2: latency mode's fine items, DIRECT1 / DIRECT7 alone
 // ndt_ord1_list.hpp and ndt_fast_list.hpp spell out the ORD = 1 and ORD = 2 rows of this predicate as text (explicit instantiation needs
 // that): a change here is a change there.
+// Under MI355NDT_OPT_POSE_MODEL = 1: k_sweep<false, K, 8, false, ORD, 1> for the four K and ORD = 0 / 1 (euler_sweep_exists, launch_sweep_euler).
 constexpr int SWEEP_IT_BATCH = 8;
+constexpr bool euler_sweep_exists(int K, int ord) { return (K == 1 || K == 7 || K == 26 || K == 27) && (ord == 0 || ord == 1); }
 constexpr bool sweep_exists(bool pca, int K, int ord, int it) {
   if ((K != 1 && K != 7 && K != 26 && K != 27) || (pca && K == 27)) return false;
   if (ord < 0 || ord > 2 || (it != SWEEP_IT_BATCH && it != 1 && it != 2)) return false;
@@ -45,8 +47,9 @@ static int prep_align_ws(mi355ndt_handle* h) {
     const bool fine_served = sweep_exists(false, neighbor_K(h->prm.neighbor_mode), 0, h->fine_tiles);
     // "small": fewer batch-mode items than two per resident wave; a sequence run sweeps ONE pair at a time whatever the number of frames
     const bool small = h->seq_running || (long long)B * h->chunks_per_pair * QUARTERS < 4LL * h->n_cu * WAVES;
-    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small) ? h->fine_tiles : 0;
+    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small && model_leaves_rounds(h->pose_model)) ? h->fine_tiles : 0;
   }
+  if (h->pose_model == POSE_MODEL_EULER) HIPCHK(h, h->d_euler_rows.reserve((size_t)B * EULER_ROW_WORDS));
   if (h->fine_it) {
     const int item_pts = h->fine_it * 64;
     h->pts_per_chunk = 4 * item_pts;                                   // a block of the fine sweep = four items = one chunk, stored as ONE row
@@ -85,6 +88,7 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
   sc.rebase_block = 0;
   sc.d1f = (float)d1;
   sc.kq = (float)(-0.5 * (double)sc.d2f * 1.4426950408889634);   // exp(-d2 q / 2) = 2^(kq q)
+  sc.euler_rows = euler_rows_of(h);
 }
 
 // The arithmetic a sweep runs in: 2 = tolerance arithmetic (MI355NDT_OPT_ARITH = 1; instantiated for DIRECT1 / DIRECT7 with the dead More-Thuente
@@ -98,6 +102,22 @@ static const VoxelRec* sweep_recs(const mi355ndt_handle* h, const SweepConst& sc
   return sweep_ord(h, sc) == 2 ? reinterpret_cast<const VoxelRec*>(h->d_recs_fast.p) : h->d_recs;
 }
 
+// the Euler model's sweep: run-time (K, ord) -> its instantiation
+template <int K>
+static void launch_sweep_euler_k(mi355ndt_handle* h, const SweepConst& sc, int ord, dim3 grid, SweepCtl* ctl, SweepCtl* ctl_next) {
+  auto kern = ord == 1 ? k_sweep<false, K, SWEEP_IT_BATCH, false, 1, 1> : k_sweep<false, K, SWEEP_IT_BATCH, false, 0, 1>;
+  kern<<<grid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_partials, h->items_per_pair, h->d_active_list, ctl,
+                                              ctl_next, sc, h->d_cent, h->d_grid_of_use);
+}
+static int launch_sweep_euler(mi355ndt_handle* h, const SweepConst& sc, int ord, dim3 grid, SweepCtl* ctl, SweepCtl* ctl_next) {
+  if (sc.pca || h->fine_it || !euler_sweep_exists(sc.K, ord) || !sc.euler_rows) return MI355NDT_ERR_UNSUPPORTED;
+  if (sc.K == 1) launch_sweep_euler_k<1>(h, sc, ord, grid, ctl, ctl_next);
+  else if (sc.K == 7) launch_sweep_euler_k<7>(h, sc, ord, grid, ctl, ctl_next);
+  else if (sc.K == 26) launch_sweep_euler_k<26>(h, sc, ord, grid, ctl, ctl_next);
+  else launch_sweep_euler_k<27>(h, sc, ord, grid, ctl, ctl_next);
+  return MI355NDT_OK;
+}
+
 static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs = -1) {
   // persistent waves: SWEEP_WPE workgroups per CU pull (pair, chunk, quarter) items until the per-XCD queues are dry
   const int ord = sweep_ord(h, sc);
@@ -109,7 +129,10 @@ static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs 
     grid.x = (unsigned)std::max(1LL, std::min((long long)grid.x, (items + WAVES - 1) / WAVES));
     if (sc.rebase_block) grid.x += 1;              // + the workgroup that computes the next update's re-basing instead of sweeping
   }
-  if (!h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)
+  if (h->pose_model == POSE_MODEL_EULER) {
+    const int rc = launch_sweep_euler(h, sc, ord, grid, ctl, ctl_next);
+    if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_POSE_MODEL = 1"; return rc; }
+  } else if (!h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)
     const dim3 kdgrid((unsigned)h->chunks_per_pair, (unsigned)h->n_pairs);
     auto kd = ord == 1 ? k_sweep_pca_kd<1> : k_sweep_pca_kd<0>;
     kd<<<kdgrid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_cent, h->d_kdw, h->d_partials,

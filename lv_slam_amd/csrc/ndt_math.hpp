@@ -196,6 +196,103 @@ __device__ inline void pose_to_f32(const double p[6], float T[12], float Rj[9]) 
   }
 }
 
+// ---- the Euler-angle pose model (MI355NDT_OPT_POSE_MODEL = 1: include/ndt_omp/ndt_omp_impl.hpp) ------------------------------
+// p = [x y z roll pitch yaw].  f32 sines, cosines and arc tangents: the f64 function of the f32 argument, rounded to f32 (tools/ndt_euler_ref.py
+// does the same, so the two sides hold the same bits).
+__device__ inline float sin_f32(float a) { return (float)sin((double)a); }
+__device__ inline float cos_f32(float a) { return (float)cos((double)a); }
+__device__ inline float atan2_f32(float a, float b) { return (float)atan2((double)a, (double)b); }
+
+// Eigen 3.3 AngleAxisf(angle, unit axis).toRotationMatrix() (third-party, restated from its published form), row-major
+__device__ inline void aa_matrix_f32(const float angle, const int axis, float R[9]) {
+  const float ax[3] = {axis == 0 ? 1.f : 0.f, axis == 1 ? 1.f : 0.f, axis == 2 ? 1.f : 0.f};
+  const float sn = sin_f32(angle), c = cos_f32(angle);
+  const float sa[3] = {sn * ax[0], sn * ax[1], sn * ax[2]};
+  const float c1[3] = {(1.f - c) * ax[0], (1.f - c) * ax[1], (1.f - c) * ax[2]};
+  float tmp = c1[0] * ax[1];
+  R[1] = tmp - sa[2]; R[3] = tmp + sa[2];
+  tmp = c1[0] * ax[2];
+  R[2] = tmp + sa[1]; R[6] = tmp - sa[1];
+  tmp = c1[1] * ax[2];
+  R[5] = tmp - sa[0]; R[7] = tmp + sa[0];
+  for (int a = 0; a < 3; a++) R[a * 3 + a] = c1[a] * ax[a] + c;
+}
+__device__ inline void mul33_f32(const float A[9], const float B[9], float C[9]) {
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) C[r * 3 + c] = A[r * 3 + 0] * B[0 * 3 + c] + (A[r * 3 + 1] * B[1 * 3 + c] + A[r * 3 + 2] * B[2 * 3 + c]);
+}
+// convertTransform (ndt_omp.h:209-228; impl.hpp:146-149, 811-814): Translation3f * AngleAxisf(X) * AngleAxisf(Y) * AngleAxisf(Z) as Eigen 3.3
+// evaluates it in f32 -- the operations of mi355ndt_convert_transform.  T = 3x4 row-major [R|t].
+__device__ inline void euler_to_f32(const double x[6], float T[12]) {
+  float Rx[9], Ry[9], Rz[9], A[9], L[9];
+  aa_matrix_f32((float)x[3], 0, Rx); aa_matrix_f32((float)x[4], 1, Ry); aa_matrix_f32((float)x[5], 2, Rz);
+  mul33_f32(Rx, Ry, A);
+  mul33_f32(A, Rz, L);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) T[r * 4 + c] = L[r * 3 + c];
+    T[r * 4 + 3] = (float)x[r];
+  }
+}
+// ... the same matrix, 4x4 column-major (transformation_, final_transformation_)
+__device__ inline void euler_to_cm(const double x[6], float cm[16]) {
+  float T[12];
+  euler_to_f32(x, T);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 4; c++) cm[c * 4 + r] = T[r * 4 + c];
+    cm[r * 4 + 3] = 0.f;
+  }
+  cm[15] = 1.f;
+}
+// Eigen 3.3 MatrixBase::eulerAngles(0, 1, 2) of the rotation block of a column-major 4x4, f32 throughout (third-party, restated from its published
+// form; parity unpinned).  A rotation with negative roll comes back in the chart near roll = pi: the reference's behaviour.
+__device__ inline void euler_angles_012(const float G[16], float e[3]) {
+#define NDT_M(r, c) G[(c) * 4 + (r)]
+  float r0 = atan2_f32(NDT_M(1, 2), NDT_M(2, 2)), r1;
+  const float c2 = sqrtf(NDT_M(0, 0) * NDT_M(0, 0) + NDT_M(0, 1) * NDT_M(0, 1));
+  if (r0 > 0.f) { r0 -= 3.14159265358979323846f; r1 = atan2_f32(-NDT_M(0, 2), -c2); }
+  else r1 = atan2_f32(-NDT_M(0, 2), c2);
+  const float s1 = sin_f32(r0), c1 = cos_f32(r0);
+  const float r2 = atan2_f32(s1 * NDT_M(2, 0) - c1 * NDT_M(1, 0), c1 * NDT_M(1, 1) - s1 * NDT_M(2, 1));
+#undef NDT_M
+  e[0] = -r0; e[1] = -r1; e[2] = -r2;
+}
+// computeAngleDerivatives (impl.hpp:288-393): the eight rows of j_ang, then the fifteen of h_ang, three floats each.  sin / cos in f64, an angle
+// with |angle| < 10e-5 takes c = 1, s = 0, the rows are cast to f32.
+#define EULER_ROWS 23
+#define EULER_ROW_WORDS (3 * EULER_ROWS)
+__device__ inline void euler_rows(const double p[6], float rows[EULER_ROW_WORDS]) {
+  double cx, cy, cz, sx, sy, sz;
+  if (fabs(p[3]) < 10e-5) { cx = 1.0; sx = 0.0; } else { cx = cos(p[3]); sx = sin(p[3]); }
+  if (fabs(p[4]) < 10e-5) { cy = 1.0; sy = 0.0; } else { cy = cos(p[4]); sy = sin(p[4]); }
+  if (fabs(p[5]) < 10e-5) { cz = 1.0; sz = 0.0; } else { cz = cos(p[5]); sz = sin(p[5]); }
+  const double r[EULER_ROWS][3] = {
+    {(-sx * sz + cx * sy * cz), (-sx * cz - cx * sy * sz), (-cx * cy)},            // j_ang: a .. h (impl.hpp:338-345)
+    {(cx * sz + sx * sy * cz), (cx * cz - sx * sy * sz), (-sx * cy)},
+    {(-sy * cz), sy * sz, cy},
+    {sx * cy * cz, (-sx * cy * sz), sx * sy},
+    {(-cx * cy * cz), cx * cy * sz, (-cx * sy)},
+    {(-cy * sz), (-cy * cz), 0},
+    {(cx * cz - sx * sy * sz), (-cx * sz - sx * sy * cz), 0},
+    {(sx * cz + cx * sy * sz), (cx * sy * cz - sx * sz), 0},
+    {(-cx * sz - sx * sy * cz), (-cx * cz + sx * sy * sz), sx * cy},               // h_ang: a2 a3 b2 b3 c2 c3 d1 d2 d3 e1 e2 e3 f1 f2 f3 (impl.hpp:372-391)
+    {(-sx * sz + cx * sy * cz), (-cx * sy * sz - sx * cz), (-cx * cy)},
+    {(cx * cy * cz), (-cx * cy * sz), (cx * sy)},
+    {(sx * cy * cz), (-sx * cy * sz), (sx * sy)},
+    {(-sx * cz - cx * sy * sz), (sx * sz - cx * sy * cz), 0},
+    {(cx * cz - sx * sy * sz), (-sx * sy * cz - cx * sz), 0},
+    {(-cy * cz), (cy * sz), (sy)},
+    {(-sx * sy * cz), (sx * sy * sz), (sx * cy)},
+    {(cx * sy * cz), (-cx * sy * sz), (-cx * cy)},
+    {(sy * sz), (sy * cz), 0},
+    {(-sx * cy * sz), (-sx * cy * cz), 0},
+    {(cx * cy * sz), (cx * cy * cz), 0},
+    {(-cy * cz), (cy * sz), 0},
+    {(-cx * sz - sx * sy * cz), (-cx * cz + sx * sy * sz), 0},
+    {(-sx * sz + cx * sy * cz), (-cx * sy * sz - sx * cz), 0}};
+  for (int k = 0; k < EULER_ROWS; k++)
+    for (int a = 0; a < 3; a++) rows[3 * k + a] = (float)r[k][a];
+}
+
 // ---- exp of an f32 argument, evaluated in f64 and rounded to f32 (the canonical choice for impl2:581) ----------
 // Table-driven: x = n*ln2/64 + r, exp(x) = 2^(n>>6) * 2^((n&63)/64) * exp(r), |r| <= ln2/128, exp(r) - 1 by its degree-5 Taylor
 // polynomial (truncation 3.5e-17).  Total error < 1 ulp of f64, like the device library's exp, but 12 instead of 28 f64-rate

@@ -30,8 +30,28 @@ __device__ __forceinline__ ndtm::SE3 shfl_se3(const ndtm::SE3& e, int src) {
   return r;
 }
 
+// ---- the pose model (MI355NDT_OPT_POSE_MODEL) behind the one update body ------------------------------------------------
+// PM = 0: ndt_omp_impl2.hpp -- p is the tangent of SE(3), a step re-bases it (newton_rebase), T = float(exp(p)), Rj = its rotation.
+// PM = 1: ndt_omp_impl.hpp  -- p = [x y z roll pitch yaw], a step adds to it (impl.hpp:152), T = convertTransform(p) in f32 (impl.hpp:811-814),
+//         transformation_ = convertTransform(delta_p) (impl.hpp:146-149); whoever writes T writes the pair's 23 rows for the sweep that reads it
+//         (`rows`: the pair's slot of SweepConst::euler_rows).  Rj, reb_* and the re-basing are not used.
+// The sweep pose of a pair from its pose vector
+template <int PM>
+__device__ __forceinline__ void pose_to_sweep(const double x[6], PairState& S, float* rows) {
+  if constexpr (PM == 1) { ndtm::euler_to_f32(x, S.T); ndtm::euler_rows(x, rows); }
+  else ndtm::pose_to_f32(x, S.T, S.Rj);
+}
+// A step of length a_t along dir taken from p (PM = 1): pn = p + delta_p, inc = convertTransform(delta_p)
+__device__ inline void euler_step(const double p[6], const double dir[6], const double a_t, double pn[6], float inc_cm[16]) {
+  double dp[6];
+  for (int a = 0; a < 6; a++) { dp[a] = dir[a] * a_t; pn[a] = p[a] + dp[a]; }    // impl.hpp:143, 152
+  ndtm::euler_to_cm(dp, inc_cm);                                                 // impl.hpp:146-149
+}
+
 // computeTransformation's set-up for one pair (impl2:102-129): p = log(guess), first sweep moves the cloud by the f32 guess itself
-__device__ inline void init_pair_state(PairState& S, const float G[16] /* column-major */, int n_src, int grid_status) {
+// PM = 1 (impl.hpp:95-119): p = the f32 translation and f32 rotation().eulerAngles(0, 1, 2) of the guess, widened; the rows from that p
+template <int PM = 0>
+__device__ inline void init_pair_state(PairState& S, const float G[16] /* column-major */, int n_src, int grid_status, float* rows = nullptr) {
   double R[9], t[3];
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) { S.T[r * 4 + c] = G[c * 4 + r]; R[r * 3 + c] = (double)G[c * 4 + r]; }
@@ -39,9 +59,17 @@ __device__ inline void init_pair_state(PairState& S, const float G[16] /* column
     t[r] = (double)G[12 + r];
   }
   for (int a = 0; a < 16; a++) S.final_cm[a] = G[a];
-  ndtm::se3_log(ndtm::se3_from_Rt(R, t), S.p);
-  float Tdummy[12];
-  ndtm::pose_to_f32(S.p, Tdummy, S.Rj);
+  if constexpr (PM == 1) {
+    float e[3];
+    ndtm::euler_angles_012(G, e);
+    for (int a = 0; a < 3; a++) { S.p[a] = t[a]; S.p[3 + a] = (double)e[a]; }
+    for (int a = 0; a < 9; a++) S.Rj[a] = 0.f;
+    ndtm::euler_rows(S.p, rows);
+  } else {
+    ndtm::se3_log(ndtm::se3_from_Rt(R, t), S.p);
+    float Tdummy[12];
+    ndtm::pose_to_f32(S.p, Tdummy, S.Rj);
+  }
   S.it = 0; S.phase = PH_SWEEP0; S.converged = 0; S.sweeps = 1; S.a_t = 0; S.hits = 0; S.score = 0; S.mt_loops = 0; S.last_sweep = 0;
   for (int a = 0; a < 16; a++) S.inc_cm[a] = S.prev_inc_cm[a] = (a % 5 == 0) ? 1.f : 0.f;    // align(): transformation_ = previous_ = I
   S.n_src = n_src;
@@ -235,13 +263,15 @@ __device__ inline bool step_ends_pair(const int it, const double a_t, const doub
 // mt = 1: live case, called after a derivative sweep;  mt = 2: live case, called after the computeHessian pass.
 // score_only_last (one-launch align, MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): mark a scheduled step whose convergence test is decided already
 // (S.last_sweep), so that its sweep evaluates the score alone.
+// PM: the pose model (above); PM = 1 is served with mt = 0 alone, and `rows` is the pair's slot of the Euler rows.
+template <int PM = 0>
 __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res, double step_max, double eps, int max_iterations, int mt,
                                              volatile double* sol = nullptr /* non-null: the solve comes from newton_solve_side */,
                                              const bool rebased = false /* S.reb_pn / S.reb_inc hold the re-basing of this step already */,
-                                             const bool score_only_last = false) {
+                                             const bool score_only_last = false, float* rows = nullptr) {
   double pn[6];
   float inc[16];
-  const bool pre = (mt == 0) && (S.phase == PH_STEP) && !rebased;                // wave-uniform: nothing has been written yet
+  const bool pre = PM == 0 && (mt == 0) && (S.phase == PH_STEP) && !rebased;     // wave-uniform: nothing has been written yet
   if (pre) newton_rebase(S.p, S.dir, S.a_t, pn, inc);
   if ((threadIdx.x & 63) != 0) return NEWTON_DONE;
 
@@ -267,7 +297,9 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
   }
   if (S.phase == PH_HESS) S.phase = PH_STEP;
   if (S.phase == PH_STEP) {
-    if (rebased) {                                                               // computed after the previous update published its sweep (same operations)
+    if constexpr (PM == 1) {
+      euler_step(S.p, S.dir, S.a_t, pn, inc);
+    } else if (rebased) {                                                        // computed after the previous update published its sweep (same operations)
       for (int a = 0; a < 16; a++) inc[a] = S.reb_inc[a];
       for (int a = 0; a < 6; a++) pn[a] = S.reb_pn[a];
     } else if (!pre) {                                                           // live More-Thuente: this lane alone
@@ -303,7 +335,8 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     if (dphi0 >= 0 && dphi0 == 0) {
       // impl2:856-857: step length 0, nothing re-evaluated
       const double z[6] = {0, 0, 0, 0, 0, 0};
-      newton_rebase<false>(S.p, z, 0.0, pn, S.inc_cm);
+      if constexpr (PM == 1) euler_step(S.p, z, 0.0, pn, S.inc_cm);              // impl.hpp:771-772
+      else newton_rebase<false>(S.p, z, 0.0, pn, S.inc_cm);
       for (int a = 0; a < 6; a++) S.p[a] = pn[a];
       const bool conv = step_ends_pair(S.it, 0.0, eps, max_iterations);
       S.it++;
@@ -322,7 +355,7 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     S.last_sweep = (mt == 0 && score_only_last && step_ends_pair(S.it, a_t, eps, max_iterations)) ? 1 : 0;
     S.phi0 = -S.score;                                                           // impl2:846
     S.dphi0 = dphi0 >= 0 ? -dphi0 : dphi0;                                       // impl2:849, 860
-    ndtm::pose_to_f32(xt, S.T, S.Rj);                                            // impl2:900
+    pose_to_sweep<PM>(xt, S, rows);                                              // impl2:900 / impl.hpp:811-821
     pose_to_final(S);
     S.phase = PH_STEP;
     S.sweeps++;

@@ -16,6 +16,8 @@
   X __global__ void k_sweep<false, 7, 8, false, 1> NDT_SWEEP_ARGS_T;  X __global__ void k_sweep<true, 7, 8, false, 1> NDT_SWEEP_ARGS_T;   \
   X __global__ void k_sweep<false, 26, 8, false, 1> NDT_SWEEP_ARGS_T; X __global__ void k_sweep<true, 26, 8, false, 1> NDT_SWEEP_ARGS_T;  \
   X __global__ void k_sweep<false, 27, 8, false, 1> NDT_SWEEP_ARGS_T;                                                                      \
+  X __global__ void k_sweep<false, 1, 8, false, 1, 1> NDT_SWEEP_ARGS_T;  X __global__ void k_sweep<false, 7, 8, false, 1, 1> NDT_SWEEP_ARGS_T;  /* the Euler model (euler_sweep_exists) */ \
+  X __global__ void k_sweep<false, 26, 8, false, 1, 1> NDT_SWEEP_ARGS_T; X __global__ void k_sweep<false, 27, 8, false, 1, 1> NDT_SWEEP_ARGS_T; \
   X __global__ void k_sweep<false, 1, 1, true, 1> NDT_SWEEP_ARGS_T;   X __global__ void k_sweep<true, 1, 1, true, 1> NDT_SWEEP_ARGS_T;    \
   X __global__ void k_sweep<false, 1, 2, true, 1> NDT_SWEEP_ARGS_T;   X __global__ void k_sweep<true, 1, 2, true, 1> NDT_SWEEP_ARGS_T;    \
   X __global__ void k_sweep<false, 7, 1, true, 1> NDT_SWEEP_ARGS_T;   X __global__ void k_sweep<true, 7, 1, true, 1> NDT_SWEEP_ARGS_T;    \

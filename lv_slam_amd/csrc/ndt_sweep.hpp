@@ -114,6 +114,88 @@ __device__ __forceinline__ void eval_hit(const float u_in[3], const float r[3], 
 #undef NDT_ACC
 }
 
+// ------------------------------------------------------------------------------------ the Euler-angle pose model (PM = 1)
+// MI355NDT_OPT_POSE_MODEL = 1: the evaluation of include/ndt_omp/ndt_omp_impl.hpp.  updateDerivatives (impl.hpp:483-535) is impl2's, operation
+// for operation -- the same eval_prefix, the same sum3<ORD>, one rounding per f32 operation, the same 43 f64 sums -- but the point Jacobian and the
+// point Hessian are those of the f32 computePointDerivatives (impl.hpp:397-438): eight entries x . j_ang row and the six vectors a .. f = x . h_ang
+// rows, taken from the ORIGINAL point x (staged where eval_hit finds R x) and the pair's 23 rows `rw` (ndtm::euler_rows: wave-uniform, so they
+// arrive through scalar loads).  Structural zeros of the 4 x 6 / 24 x 6 patterns are skipped as in eval_hit: Jacobian entry (0, 3), the first
+// components of a, b, c, the fourth lane of every inner product.  ndt_omp only (ndt_pca_impl.hpp has the weight commented out), exact arithmetic only.
+// The rows are written by the launch before the sweep and by nobody during it: read through the constant address space, a wave-uniform
+// address makes every one of them a scalar load.
+typedef const __attribute__((address_space(4))) float* EulerRows;
+__device__ __forceinline__ EulerRows euler_rows_of_pair(const float* rows, const int b) {
+  return (EulerRows)(unsigned long long)(rows + (size_t)__builtin_amdgcn_readfirstlane(b) * EULER_ROW_WORDS);
+}
+template <typename Mid = NoHook, bool SAN = false, int ORD = 0>
+__device__ __forceinline__ void eval_hit_euler(const float u_in[3], const float x[3], const float C_in[9], const EulerRows rw,
+                                               const double d1, const float d2f, const bool ok_in, double acc[43],
+                                               const double* __restrict__ exp_tab, Mid mid = Mid()) {
+  float u[3] = {u_in[0], u_in[1], u_in[2]}, C[9];
+#pragma unroll
+  for (int a = 0; a < 9; a++) C[a] = C_in[a];
+  float y[3], e1, s_inc;
+  const bool ok = eval_prefix<ORD>(u, C, d1, d2f, ok_in, exp_tab, y, e1, s_inc);
+  float e = (float)((double)e1 * d1);                                            // impl.hpp:508
+  e = ok ? e : 0.f;
+  if (SAN) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) { u[a] = ok ? u[a] : 0.f; y[a] = ok ? y[a] : 0.f; }
+#pragma unroll
+    for (int a = 0; a < 9; a++) C[a] = ok ? C[a] : 0.f;
+  }
+  // x_j_ang = j_ang * x4 (impl.hpp:403): the Jacobian's columns 3..5 are (0, xj0, xj1), (xj2, xj3, xj4), (xj5, xj6, xj7) (impl.hpp:405-412)
+  float xj[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) xj[k] = sum3<ORD>(rw[3 * k] * x[0], rw[3 * k + 1] * x[1], rw[3 * k + 2] * x[2]);
+  // CJ = c_inv4 * point_gradient4 (impl.hpp:510): columns 0..2 are C itself
+  float CJ[3][6];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    CJ[a][0] = C[a * 3 + 0]; CJ[a][1] = C[a * 3 + 1]; CJ[a][2] = C[a * 3 + 2];
+    CJ[a][3] = C[a * 3 + 1] * xj[0] + C[a * 3 + 2] * xj[1];
+    CJ[a][4] = sum3<ORD>(C[a * 3 + 0] * xj[2], C[a * 3 + 1] * xj[3], C[a * 3 + 2] * xj[4]);
+    CJ[a][5] = sum3<ORD>(C[a * 3 + 0] * xj[5], C[a * 3 + 1] * xj[6], C[a * 3 + 2] * xj[7]);
+  }
+  float v[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) v[k] = sum3<ORD>(u[0] * CJ[0][k], u[1] * CJ[1][k], u[2] * CJ[2][k]);   // impl.hpp:511
+  acc[0] += (double)s_inc;
+#pragma unroll
+  for (int k = 0; k < 6; k++) acc[1 + k] += (double)(e * v[k]);                                  // impl.hpp:513
+  // x_h_ang = h_ang * x4 (impl.hpp:416) and z = (x_trans4 * c_inv4) * point_hessian block (impl.hpp:523): the blocks are a b c / b d e / c e f
+  // (impl.hpp:428-436), so six inner products serve the nine entries
+  float xh[15];
+#pragma unroll
+  for (int k = 0; k < 15; k++) xh[k] = sum3<ORD>(rw[24 + 3 * k] * x[0], rw[24 + 3 * k + 1] * x[1], rw[24 + 3 * k + 2] * x[2]);
+  const float za = y[1] * xh[0] + y[2] * xh[1];
+  const float zb = y[1] * xh[2] + y[2] * xh[3];
+  const float zc = y[1] * xh[4] + y[2] * xh[5];
+  const float zd = sum3<ORD>(y[0] * xh[6], y[1] * xh[7], y[2] * xh[8]);
+  const float ze = sum3<ORD>(y[0] * xh[9], y[1] * xh[10], y[2] * xh[11]);
+  const float zf = sum3<ORD>(y[0] * xh[12], y[1] * xh[13], y[2] * xh[14]);
+  const float Z[3][3] = {{za, zb, zc}, {zb, zd, ze}, {zc, ze, zf}};
+  __builtin_amdgcn_sched_barrier(0);
+  mid();
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      // JCJ[j][i] = (J^T CJ)(j,i) (impl.hpp:517)
+      float jcj;
+      if (j < 3) jcj = CJ[j][i];
+      else if (j == 3) jcj = xj[0] * CJ[1][i] + xj[1] * CJ[2][i];
+      else if (j == 4) jcj = sum3<ORD>(xj[2] * CJ[0][i], xj[3] * CJ[1][i], xj[4] * CJ[2][i]);
+      else jcj = sum3<ORD>(xj[5] * CJ[0][i], xj[6] * CJ[1][i], xj[7] * CJ[2][i]);
+      float t = ((-d2f) * v[i]) * v[j];
+      if (i >= 3 && j >= 3) t = t + Z[i - 3][j - 3];
+      const float h = e * (t + jcj);                                                           // impl.hpp:527-529
+      acc[7 + i * 6 + j] += (double)h;
+    }
+  }
+}
+
 // Score-only evaluation (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): eval_hit's prefix and the same term added to the same accumulator, for the
 // last sweep of an align, whose gradient and Hessian are never read.
 template <bool PCA, int ORD = 0>
@@ -457,8 +539,13 @@ struct BatchF { unsigned slot; float mh[3], ml[3], c[6]; int weight; float w; };
 // W_LATE (ndt_pca, K = 1: the hit's weight is the leaf's own, read with its record): widen it when the batch is evaluated, not when it is
 // fetched -- the same value either way, but two registers fewer across the mid-evaluation prefetch.  sweep_rows_d1 needs that (with the
 // widening at the fetch the pca / DIRECT1 headline lost 5 %, docs/experiments.md 10i); sweep_item widens at the fetch as it always did.
-template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false>
+// PM (MI355NDT_OPT_POSE_MODEL): 1 = hits are evaluated by eval_hit_euler -- the staged point's second half is the ORIGINAL point and `rw` the pair's
+// 23 rows (set by the item body; no member at all for PM = 0, whose kernels keep their register tables).
+struct NoRows {};
+template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0>
 struct HitQueue {
+  static_assert(PM == 0 || (PM == 1 && !PCA && ORD != 2 && !SO), "the Euler model: ndt_omp, exact arithmetic, full rows");
+  typename std::conditional<PM == 1, EulerRows, NoRows>::type rw;
   static constexpr bool KD = (K == 27), FAST = (ORD == 2), PCAQ = PCA && K > 1;
   static constexpr int NA = FAST ? NACC_F : 43;
   typedef typename std::conditional<FAST, float, double>::type AccT;
@@ -535,6 +622,7 @@ struct HitQueue {
       float u[3] = {(float)((double)xt0 - B.m0), (float)((double)xt1 - B.m1), (float)((double)xt2 - B.m2)};   // impl2:276-279, 574
       const double w = (W_LATE && !PCAQ) ? (PCA ? (double)B.weight : 1.0) : B.w;
       if constexpr (SO) { mid(); eval_score<PCA, ORD>(u, B.C, sc.d1, sc.d2f, w, live, acc[0], exp_tab); }
+      else if constexpr (PM == 1) eval_hit_euler<Mid, KD, ORD>(u, r, B.C, rw, sc.d1, sc.d2f, live, acc, exp_tab, mid);
       else eval_hit<PCA, Mid, KD, ORD>(u, r, B.C, sc.d1, sc.d2f, w, live, acc, exp_tab, mid);
     }
     nhits += PCAQ ? (unsigned)m : (unsigned)__popcll(__ballot(live));
@@ -571,7 +659,9 @@ struct HitQueue {
 
 // SO: score-only item (the pair's last sweep, PairState::last_sweep): the same probe stage, hit queue, 64-hit batches and ndt_pca weights; each
 // hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
-template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false>
+// PM = 1 (MI355NDT_OPT_POSE_MODEL, the lockstep rounds only): phase A stages the moved point and the ORIGINAL point, phase B is eval_hit_euler over
+// the pair's rows sc.euler_rows[b] (written by whoever wrote the pair's T: k_init_state, k_set_pose_p, newton_update).
+template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false, int PM = 0>
 __device__ __forceinline__ void sweep_item(const int b, const int rem, const float* __restrict__ src, const size_t pitch, const PairState* st,
                                            const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                            double* partials, const int rows_per_pair, const SweepConst& sc, const float* __restrict__ cent,
@@ -582,6 +672,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   constexpr bool FAST = (ORD == 2);                // tolerance arithmetic (eval_hit_fast): `recs` holds VoxelRecF records
   static_assert(!SO || (ASYNC && !FINE), "score-only items belong to the one-launch align");
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
+  static_assert(PM == 0 || (!PCA && !FAST && !ASYNC && !FINE && !SO), "the Euler model takes the lockstep rounds: ndt_omp, exact arithmetic, batch items");
   typedef SweepTune<PCA, K, ORD> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // ndt_pca's per-hit multiplier is the product of the hit's own weight and those of the point's LATER hits, known only in phase A.
@@ -593,7 +684,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   constexpr int Q_NEED = (IT / TP > 1 ? 64 : 0) + TP * (K < Q_GROUP ? K : Q_GROUP) * 64;
   constexpr int Q_CAP = FAST ? (Q_NEED <= 128 ? 128 : Q_NEED <= 256 ? 256 : Q_NEED <= 512 ? 512 : 1024) : ((K > 1 && K <= Q_GROUP) ? 1024 : 512);
   static_assert(Q_NEED <= Q_CAP, "hit queue");
-  typedef HitQueue<PCA, K, ORD, SO, Q_CAP> Queue;
+  typedef HitQueue<PCA, K, ORD, SO, Q_CAP, false, PM> Queue;
   auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 0>();
   auto& q_w = item_lds<typename Queue::QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
   // TP tiles of 64 points are probed together ("super-tile"): their point transforms, then ALL their bitmap loads, then all
@@ -624,7 +715,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
 #pragma unroll
     for (int a = 0; a < 12; a++) T[a] = S.T[a];
 #pragma unroll
-    for (int a = 0; a < 9; a++) Rj[a] = S.Rj[a];
+    for (int a = 0; a < 9; a++) Rj[a] = PM == 1 ? 0.f : S.Rj[a];               // (PM = 1: no Jacobian point, Rj is not read)
   }
   const float leaf = g.leaf;
   const int mb0 = g.min_b[0], mb1 = g.min_b[1], mb2 = g.min_b[2];
@@ -633,6 +724,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   {
     typename Queue::AccT acc[Queue::NA];
     Queue Q(acc, q_ent[wv], q_w[PCAQ ? wv : 0], stage[wv], R, sc, exp_tab, lane);
+    // a work item belongs to one pair: a wave-uniform index, so the 69 floats come through the scalar cache
+    if constexpr (PM == 1) Q.rw = euler_rows_of_pair(sc.euler_rows, b);
     const int wbase = rem * (IT * 64);
     if (wbase < n && grid_ok) {
       constexpr int NST = IT / TP;                            // super-tiles per item
@@ -670,7 +763,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           // a non-finite moved point (NaN pose: only reachable through a NaN More-Thuente trial value) has no neighbours;
           // the reference's float->int cast is undefined there
           ok = ok && finite3(xt[0], xt[1], xt[2]);
-          stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, r);
+          if constexpr (PM == 1) { const float xo[3] = {px, py, pz}; stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, xo); }
+          else stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, r);
           kx[p] = xt[0]; ky[p] = xt[1]; kz[p] = xt[2];
           // Branch-free probe stage.  Relative cell r = c - min_b; "inside the grid" (impl:382-392) is one unsigned
           // compare per axis; a probe that falls outside (or belongs to an invalid lane) is redirected to the grid's
@@ -873,7 +967,7 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   }
 }
 
-template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0>
+template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0, int PM = 0>
 __global__ void __launch_bounds__(SWEEP_THREADS, (SweepTune<PCA, K, ORD>::WPE))
 k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict__ st,
         const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
@@ -968,7 +1062,7 @@ k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict
       const int rem = item % items_per_pair;        // the pair's work item = its partial row
       TL_STAMP(0);
 
-      sweep_item<PCA, K, IT, FINE, ORD, false>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0, tl);
+      sweep_item<PCA, K, IT, FINE, ORD, false, false, PM>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0, tl);
       if (next_static) { round++; item = wx + round * xw; }
       else item = __builtin_amdgcn_readfirstlane(next_item);
     }

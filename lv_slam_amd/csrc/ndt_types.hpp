@@ -112,6 +112,9 @@ struct SweepConst {
   int    rebase_block;         // latency mode: the launch's LAST workgroup does not sweep -- it computes the re-basing of p the next Newton update starts with (ndt_sweep.hpp)
   // tolerance arithmetic (ORD = 2 instantiations only): d1 as f32, and kq = -d2 / 2 * log2(e): exp(-d2 q / 2) = 2^(kq q), one v_exp_f32
   float  d1f, kq;
+  // MI355NDT_OPT_POSE_MODEL = 1 only (else null): 69 floats per pair slot, the 8 rows of j_ang and the 15 of h_ang at the pose of the pair's pending
+  // sweep (ndtm::euler_rows).  An array of its own: the pose words of PairState stay where the one-launch align fetches them.
+  const float* euler_rows;
 };
 
 // Neighbour offsets in the reference's probe order.  DIRECT1: voxel_grid_covariance_omp_impl.hpp:441;

@@ -171,6 +171,8 @@ OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch a
 OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
 OPT_OUTLIER_CELL_MM = 10       # mi355ndt_option: cell size [mm] of the index prefilter_outliers builds over the prefilter result in every call (default 100); no result bit depends on it
 OPT_PREFILTER_GROUP = 11      # mi355ndt_option: raw clouds per group of batch_prefilter (0, the default: by the engine's scratch budget); no result word depends on it
+OPT_POSE_MODEL = 12           # mi355ndt_option: 0 (default) = ndt_omp_impl2.hpp, the SE(3) tangent; 1 = ndt_omp_impl.hpp, the Euler-angle pose model (lockstep rounds, ndt_omp, dead More-Thuente)
+POSE_MODELS = {"se3": 0, "euler": 1}
 PREFILTER_EXTENDED = 0x50467832  # MI355NDT_PREFILTER_EXTENDED: PrefilterParams.extended of the base of a PrefilterParamsEx
 DOWNSAMPLE_VOXELGRID = 0       # pcl::VoxelGrid, the prefiltering nodelet's default downsample_method
 DOWNSAMPLE_APPROX_VOXELGRID = 1  # pcl::ApproximateVoxelGrid
@@ -1244,11 +1246,19 @@ class NormalDistributionsTransform:
     Method names (including the reference's `setOulierRatio` spelling) follow ndt_omp.h:109-203 and
     pcl::Registration.  PCL-style error behaviour: no exceptions for a failed registration --
     `hasConverged()` reports it; exceptions are reserved for API misuse and HIP failures.
+
+    pose_model="se3" (default) is include/ndt_omp/ndt_omp_impl2.hpp, the implementation lv_slam compiles; pose_model="euler" is
+    include/ndt_omp/ndt_omp_impl.hpp, the Euler-angle NDT a host gets by changing the include line of src/ndt_omp/ndt_omp.cpp
+    (mi355ndt_set_option(MI355NDT_OPT_POSE_MODEL, 1): variant OMP, step_size > trans_epsilon / 2).
     """
 
-    def __init__(self, variant: int = VARIANT_OMP, device: int = 0):
+    def __init__(self, variant: int = VARIANT_OMP, device: int = 0, pose_model: str = "se3"):
+        if pose_model not in POSE_MODELS:
+            raise ValueError(f"pose_model must be one of {sorted(POSE_MODELS)}")
         self._prm = default_params(variant=variant)           # ctor defaults, ndt_omp_impl2.hpp:53-83
         self._eng = Engine(self._prm, device)
+        if POSE_MODELS[pose_model]:
+            self._eng.set_option(OPT_POSE_MODEL, POSE_MODELS[pose_model])
         self._final = np.eye(4, dtype=np.float32)
         self._converged = False
         self._nr_iterations = 0

@@ -432,7 +432,9 @@ int mi355ndt_sequence_run(mi355ndt_handle* h, int n_frames, const void* const* c
 /* replaces PrefilteringNodelet::distance_filter + downsample (src/lidar_odometry/prefiltering_nodelet.cpp:137-181,
  * launch/dlo_kitti.launch:30-36): keep near < |p| < far, then pcl::VoxelGrid centroid down-sampling with leaf
  * `downsample_resolution` (<= 0: none), output ordered by ascending voxel index.  The result stays on the GPU
- * (mi355ndt_use_prefiltered) and is copied to out_pts (x,y,z records, may be NULL) when it fits out_capacity. */
+ * (mi355ndt_use_prefiltered) and is copied to out_pts (x,y,z records, may be NULL) when it fits out_capacity.
+ * It is mi355ndt_prefilter_p (below) with these four parameters and the rest at their defaults -- no move, no
+ * calibration, VOXELGRID --: one implementation, the same words. */
 int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes,
                        int use_distance_filter, double distance_near, double distance_far, float downsample_resolution,
                        void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);

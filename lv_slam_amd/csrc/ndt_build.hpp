@@ -5,12 +5,6 @@
 #include "ndt_math.hpp"
 
 // ------------------------------------------------------------------------------------ target build
-// (the prefilter's one-cloud extremes, ndt_prefilter.hpp, are plain ints with an init launch)
-__global__ void k_minmax_init(int* mm, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n * 6) mm[i] = (i % 6) < 3 ? INT_MAX : INT_MIN;
-}
-
 // The six extremes of a target live as unsigned "the larger wins" words whose all-zero state means "no finite point yet", so that the
 // workspace memset that precedes every build is their initialisation: a maximum as ord ^ 0x80000000 (order-preserving int -> unsigned),
 // a minimum as the complement of that.  No finite float maps to 0 in either form (f2ord of a finite float is neither INT_MIN nor INT_MAX).

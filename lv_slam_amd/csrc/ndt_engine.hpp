@@ -55,7 +55,7 @@ struct StreamState {
 //   * every user enqueues its kernels, table copies and read-backs on h->stream, so stream order separates one user's work from the next's;
 //   * every user waits for the stream before it returns, except mi355ndt_window_keyframe, whose trailing k_kf_emit still reads x, keys, vals,
 //     flag and pos: only kernels on h->stream write those, so stream order covers it as well;
-//   * `in` alone is written from the copy streams: its readers (k_pf_*, k_pfb_*, k_mc_transform, k_kf_window) have finished when their call returns,
+//   * `in` alone is written from the copy streams: its readers (k_pfb_*, k_pfa_*, k_mc_transform, k_kf_window) have finished when their call returns,
 //     and uploads_before_compute / compute_enqueued order the uploads against the compute stream as they do for the batch rows;
 //   * the pinned blocks are written by the host only at the start of a call, after vs_reserve has waited out a copy that may still read
 //     them (`pending`), and read by the host only after the call's own wait.

@@ -22,8 +22,9 @@ static int kf_alloc(mi355ndt_handle* h, mi355ndt_handle::Keyframe& kf, size_t m,
 
 // ---- window map -> keyframe ------------------------------------------------------------------------
 // replaces the window accumulation and down-sampling of GlobalGraphNodelet::cloud_callback (global_graph_nodelet.cpp:202-244).  The scans go
-// up through the engine's staging as the map cloud's keyframes do; the call waits for the device twice -- the grid's status, as the
-// prefilter does, and the count, which sizes the keyframe's rows -- and returns with the emit kernel enqueued.
+// up through the engine's staging as the map cloud's keyframes do; between its own flag pass (k_kf_window) and its own emit the window is
+// the prefilter chain's one cloud (pfb_positions).  The call waits for the device once -- for the count, which sizes the keyframe's rows --
+// and returns with the emit kernel enqueued.
 int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const* scans, const size_t* counts, size_t stride_bytes,
                              int intensity_offset_bytes, const double* rel_poses, float leaf, int* id, size_t* n_out) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
@@ -50,15 +51,21 @@ int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const*
   VoxelScratch& w = h->vs;
   const size_t pitch = (n + 63) & ~(size_t)63;
   const int nblk = (int)((pitch + KF_CHUNK - 1) / KF_CHUNK);
-  const size_t at_tab = (size_t)K * 12 * sizeof(double);
+  const size_t at_tab = (size_t)K * 12 * sizeof(double), at_item = at_tab + (size_t)K * sizeof(KfScan);
+  static_assert(sizeof(KfScan) % 8 == 0, "the tables' layout");
+  PfbChain chain;                                 // the window as the prefilter chain's one cloud: no gate, VOXELGRID
+  memset(&chain, 0, sizeof chain);
+  chain.leaf = leaf; chain.downsample = leaf > 0.f;
   VsNeed need;
-  need.pitch = pitch; need.in = in_total; need.x = (size_t)ch * pitch; need.tab = at_tab + (size_t)K * sizeof(KfScan);
+  need.pitch = pitch; need.in = in_total; need.x = (size_t)ch * pitch; need.tab = at_item + sizeof(PfbItem); need.stat = PFB_RES_WORDS(1);
   int rc = vs_reserve(h, need);                   // (an earlier window's emit kernel may still run: it is waited for if anything grows)
   if (rc) return rc;
 
-  // poses ((w_odom.inverse() * odom_k).matrix(), column-major f64 -> row-major rows 0..2) and scan table, one pinned block, one copy
+  // poses ((w_odom.inverse() * odom_k).matrix(), column-major f64 -> row-major rows 0..2), scan table and the chain's item (nothing is emitted
+  // through it: a pitch no count exceeds), one pinned block, one copy
   double* T = (double*)(unsigned char*)w.h_tab;
   KfScan* tab = (KfScan*)((unsigned char*)w.h_tab + at_tab);
+  *(PfbItem*)((unsigned char*)w.h_tab + at_item) = PfbItem{nullptr, ~0ull, (int)n, 0};
   std::vector<UpItem> items;
   items.reserve((size_t)K);
   size_t start = 0, base = 0;
@@ -79,22 +86,21 @@ int mi355ndt_window_keyframe(mi355ndt_handle* h, int n_scans, const void* const*
 
   float* X = w.x;
   const int gx = (int)((pitch + 255) / 256);
-  k_minmax_init<<<1, 64, 0, s>>>(w.mm, 1);
+  const PfbItem* item = (const PfbItem*)((unsigned char*)w.tab + at_item);
+  k_pfb_begin<<<1, 256, 0, s>>>(w.mm, w.stat, 1);
   k_kf_window<<<nblk, KF_THREADS, 0, s>>>((const KfScan*)((unsigned char*)w.tab + at_tab), K, (const double*)(unsigned char*)w.tab, (int)n, pitch, ch, X, w.keep, w.mm);
-  VgHeads v;
-  rc = voxel_grid_heads(h, "window_keyframe", "window", X, pitch, n, leaf, &v);
-  if (rc) return rc;
+  const PfbSorted v = pfb_positions(s, w, chain, X, item, 1, pitch);
   HIPCHK(h, hipGetLastError());
-  int* ret = w.h_ret;                             // last scan position, last head flag
-  HIPCHK(h, hipMemcpyAsync(ret, w.pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(ret + 1, w.flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  int* ret = w.h_ret;                             // the count, the overflow word (never raised), the too-small word
+  HIPCHK(h, hipMemcpyAsync(ret, w.stat, PFB_RES_WORDS(1) * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   w.pending = false;
-  const size_t m = (size_t)ret[0] + (size_t)ret[1];
+  const size_t m = (size_t)ret[0];
+  if (ret[2] != INT_MAX) h->err = "window_keyframe: leaf size too small for the window's extent, voxel indices would overflow; window not down-sampled";
   rc = kf_alloc(h, kf, m, ch);
   if (rc) return rc;
   if (m) {
-    k_kf_emit<<<gx, 256, 0, s>>>(X, pitch, v.keys, v.vals, w.flag, w.pos, v.downsample, ch, kf.rows, kf.pitch, m);
+    k_kf_emit<<<gx, 256, 0, s>>>(X, pitch, v.keys, v.vals, w.flag, w.pos, w.grid, chain.downsample, ch, kf.rows, kf.pitch, m);
     HIPCHK(h, hipGetLastError());
   }
   *id = h->kf_next_id++;

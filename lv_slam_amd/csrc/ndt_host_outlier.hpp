@@ -112,13 +112,7 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
   const size_t m = (size_t)w.h_ret[0] + (size_t)w.h_ret[1];
   h->pf_count = (int)m;
   *n_out = m;
-  if (out_pts) {
-    if (m > out_capacity) return MI355NDT_ERR_BAD_ARG;
-    std::vector<float> tmp(3 * pitch);
-    HIPCHK(h, hipMemcpy(tmp.data(), rows, 3 * pitch * sizeof(float), hipMemcpyDeviceToHost));
-    rows_to_records(tmp.data(), pitch, 3, m, out_pts, out_stride, -1);
-  }
-  return MI355NDT_OK;
+  return pf_result_records(h, m, out_pts, out_capacity, out_stride);
 }
 
 // ---- the same stage over the clouds batch slots hold, K clouds per launch chain (ndt_outlier_batch.hpp) ---------------------------------
@@ -189,8 +183,7 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t rp_all = (maxn + 63) & ~(size_t)63;
-    int group = h->pf_group > 0 ? h->pf_group : (int)std::min((size_t)PFB_GROUP_MAX, std::max((size_t)1, PFB_SCRATCH_BUDGET / (OLB_POINT_BYTES * rp_all)));
-    group = std::min(std::min(group, PFB_GROUP_MAX), n_cl);
+    const int group = pfb_group_size(h, OLB_POINT_BYTES, rp_all, n_cl);
     // the groups: a group's segment pitch is its own largest count, and its k-NN table is made here, before anything is enqueued
     struct Grp { int g0, K; size_t rp; std::vector<int> tab; int gmax; };
     std::vector<Grp> groups;

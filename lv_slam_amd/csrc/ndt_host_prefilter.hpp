@@ -2,52 +2,14 @@
 // The result (d_pf_out) is the prefilter's own and stays until the next prefilter call; everything before it is the shared scratch (h->vs).
 #pragma once
 
-// replaces PrefilteringNodelet::distance_filter + downsample (prefiltering_nodelet.cpp:137-181)
-int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t stride,
-                       int use_distance_filter, double distance_near, double distance_far, float downsample_resolution,
-                       void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if ((!pts && n) || (n && stride < 12) || n >= (1u << 30) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
-  if (std::isnan(downsample_resolution)) return MI355NDT_ERR_BAD_ARG;
-  *n_out = 0;
-  h->pf_count = 0;
-  if (n == 0) return MI355NDT_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t pitch = (n + 63) & ~(size_t)63;
-  VoxelScratch& w = h->vs;
-  VsNeed need;
-  need.pitch = pitch; need.in = 3 * pitch;
-  int rc = vs_reserve(h, need);
-  if (rc) return rc;
-  if (3 * pitch > h->d_pf_out.cap) HIPCHK(h, hipStreamSynchronize(s));   // (the result buffer is re-allocated: no copy out of it may still run)
-  HIPCHK(h, h->d_pf_out.reserve(3 * pitch));
-  h->pf_pitch = pitch;
-  rc = upload_cloud(h, w.in, pitch, 0, pts, n, stride);
-  if (rc) return rc;
-  rc = uploads_before_compute(h);
-  if (rc) return rc;
-  const int gx = (int)((pitch + 255) / 256);
-  k_minmax_init<<<1, 64, 0, s>>>(w.mm, 1);
-  k_pf_flag<<<std::min(gx, 256), 256, 0, s>>>(w.in, pitch, (int)n, use_distance_filter, distance_near, distance_far, w.keep, w.mm);
-  VgHeads v;
-  rc = voxel_grid_heads(h, "prefilter", "cloud", w.in, pitch, n, downsample_resolution, &v);
-  if (rc) return rc;
-  k_pf_emit<<<gx, 256, 0, s>>>(w.in, pitch, v.keys, v.vals, w.flag, w.pos, v.downsample, h->d_pf_out, pitch);
-  int last_pos = 0, last_flag = 0;
-  HIPCHK(h, hipMemcpyAsync(&last_pos, w.pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(&last_flag, w.flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  const size_t m = (size_t)last_pos + (size_t)last_flag;
-  h->pf_count = (int)m;
-  *n_out = m;
-  if (out_pts) {
-    if (m > out_capacity) return MI355NDT_ERR_BAD_ARG;
-    std::vector<float> tmp(3 * pitch);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->d_pf_out, 3 * pitch * sizeof(float), hipMemcpyDeviceToHost));
-    rows_to_records(tmp.data(), pitch, 3, m, out_pts, out_stride, -1);
-  }
+// the first m points of the resident result into the caller's records (out_pts may be null: nothing is fetched)
+static int pf_result_records(mi355ndt_handle* h, size_t m, void* out_pts, size_t out_capacity, size_t out_stride) {
+  if (!out_pts) return MI355NDT_OK;
+  if (m > out_capacity) return MI355NDT_ERR_BAD_ARG;
+  const size_t pitch = h->pf_pitch;
+  std::vector<float> tmp(3 * pitch);
+  HIPCHK(h, hipMemcpy(tmp.data(), h->d_pf_out, 3 * pitch * sizeof(float), hipMemcpyDeviceToHost));
+  rows_to_records(tmp.data(), pitch, 3, m, out_pts, out_stride, -1);
   return MI355NDT_OK;
 }
 
@@ -126,30 +88,29 @@ static int pfb_chain(const mi355ndt_prefilter_params* prm, PfbChain* c) {
 static size_t pfb_pitch(const PfbChain& c, size_t maxn) {
   return std::max((size_t)64, (maxn + 63) & ~(size_t)63) + (c.approx ? (size_t)PFA_BUCKETS : 0);
 }
-// The chain over the K clouds staged in the scratch (rows in w.in at pitch rp, their items in w.tab): every stage one launch, the filtered
-// points into the items' rows, the result words (PFB_RES_WORDS) in w.stat.  Nothing waits.
-static void pfb_enqueue(hipStream_t s, VoxelScratch& w, const PfbChain& c, int K, size_t rp) {
+// The VoxelGrid middle of every chain, for K clouds whose rows X ([cloud][>= 3][rp]), keep flags (w.keep) and extremes (w.mm) are filled and
+// whose result words k_pfb_begin has set: grid, keys, the stable sort by voxel index (a cloud one segment), heads, the three scan kernels,
+// for both down-sampling methods.  It leaves the emit positions in w.pos, the counts in res[0, K), the overflow word in res[K] and the
+// too-small word in res[K + 1] (w.stat), and returns the sorted keys and point ids the emit kernel walks.  Nothing waits.
+struct PfbSorted { const unsigned *keys, *vals; };
+static PfbSorted pfb_positions(hipStream_t s, VoxelScratch& w, const PfbChain& c, const float* X, const PfbItem* items, int K, size_t rp) {
   const int tiles = (int)((rp + RS_TILE - 1) / RS_TILE);  // of one cloud: sort tiles = scan chunks (RS_TILE == PF_SCAN_CHUNK)
   static_assert(RS_TILE == PF_SCAN_CHUNK, "one tile count serves the sort and the scan");
-  const PfbItem* items = (const PfbItem*)(unsigned char*)w.tab;
   int* res = w.stat;
   const size_t seg = (size_t)K * rp;               // (the sort's second key / id arrays start here)
   const unsigned* keys = w.keys; const unsigned* vals = w.vals;
-  k_pfb_begin<<<(6 * K + 255) / 256, 256, 0, s>>>(w.mm, res, K);
-  const int fx = std::max(1, std::min(tiles * (RS_TILE / 256) / 4, 32));   // flag workgroups per cloud: four points per thread and pass, 32 at the most
-  k_pfb_flag<<<xcd_grid(fx, K), 256, 0, s>>>(w.in, rp, items, K, fx, c.use_df, c.dnear, c.dfar, c.mv, c.cal, w.keep, w.mm);
   if (c.approx) {
     k_pfa_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
-    k_pfa_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys, w.flag);
+    k_pfa_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, items, K, tiles, w.keep, w.grid, w.keys, w.flag);
     const RsPlan plan = rs_plan(10);               // 513 key values: one pass
     rs_pass(s, plan.bits, w.keys, w.vals, w.keys + seg, w.vals + seg, rp, 0, w.hist, w.offs, tiles, K, true);
     keys = w.keys + seg; vals = w.vals + seg;
-    k_pfa_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.keep, items, K, tiles, w.grid, w.flag);
+    k_pfa_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, keys, vals, w.keep, items, K, tiles, w.grid, w.flag);
   } else {
     if (c.downsample) {
       const RsPlan plan = rs_plan(31);
       k_pfb_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
-      k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, items, K, tiles, w.keep, w.grid, w.keys);
+      k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, items, K, tiles, w.keep, w.grid, w.keys);
       unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
       for (int ps = 0; ps < plan.passes; ps++) {
         rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0);
@@ -162,8 +123,26 @@ static void pfb_enqueue(hipStream_t s, VoxelScratch& w, const PfbChain& c, int K
   k_pfb_scan_totals<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, tiles, K);
   k_pfb_scan_offsets<<<K, 1024, 0, s>>>(w.tmp, tiles, items, K, res);
   k_pfb_scan_apply<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, w.pos, tiles, K);
-  if (c.approx) k_pfa_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.keep, w.flag, w.pos, w.grid, items, K, tiles);
-  else k_pfb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, keys, vals, w.flag, w.pos, w.grid, c.downsample, items, K, tiles);
+  return PfbSorted{keys, vals};
+}
+// The chain over the K clouds staged in the scratch (rows in w.in at pitch rp, their items in w.tab): every stage one launch, the filtered
+// points into the items' rows, the result words (PFB_RES_WORDS) in w.stat.  Nothing waits.
+static void pfb_enqueue(hipStream_t s, VoxelScratch& w, const PfbChain& c, int K, size_t rp) {
+  const int tiles = (int)((rp + RS_TILE - 1) / RS_TILE);
+  const PfbItem* items = (const PfbItem*)(unsigned char*)w.tab;
+  k_pfb_begin<<<(6 * K + 255) / 256, 256, 0, s>>>(w.mm, w.stat, K);
+  const int fx = std::max(1, std::min(tiles * (RS_TILE / 256) / 4, 32));   // flag workgroups per cloud: four points per thread and pass, 32 at the most
+  k_pfb_flag<<<xcd_grid(fx, K), 256, 0, s>>>(w.in, rp, items, K, fx, c.use_df, c.dnear, c.dfar, c.mv, c.cal, w.keep, w.mm);
+  const PfbSorted v = pfb_positions(s, w, c, w.in, items, K, rp);
+  if (c.approx) k_pfa_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, v.keys, v.vals, w.keep, w.flag, w.pos, w.grid, items, K, tiles);
+  else k_pfb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(w.in, rp, v.keys, v.vals, w.flag, w.pos, w.grid, c.downsample, items, K, tiles);
+}
+
+// how many clouds of pitch rp a group holds: the caller's own number (pf_group), else what the scratch budget allows at `point_bytes` per
+// position; never more than PFB_GROUP_MAX or the call's `clouds`
+static int pfb_group_size(const mi355ndt_handle* h, size_t point_bytes, size_t rp, int clouds) {
+  const int group = h->pf_group > 0 ? h->pf_group : (int)std::min((size_t)PFB_GROUP_MAX, std::max((size_t)1, PFB_SCRATCH_BUDGET / (point_bytes * rp)));
+  return std::min(std::min(group, PFB_GROUP_MAX), clouds);
 }
 
 // kernels_ms (may be null): the time of the prefilter's kernels, HIP events around every group's chain, summed
@@ -192,8 +171,7 @@ static int batch_prefilter_impl(mi355ndt_handle* h, int first_pair, int n, const
   hipStream_t s = h->stream;
   const int n_raw = (int)raw.size();
   const size_t rp = pfb_pitch(chain, maxn);
-  int group = h->pf_group > 0 ? h->pf_group : (int)std::min((size_t)PFB_GROUP_MAX, std::max((size_t)1, PFB_SCRATCH_BUDGET / (PFB_POINT_BYTES * rp)));
-  group = std::min(std::min(group, PFB_GROUP_MAX), n_raw);
+  const int group = pfb_group_size(h, PFB_POINT_BYTES, rp, n_raw);
   VoxelScratch& w = h->vs;
   VsNeed need;
   need.clouds = (size_t)group; need.pitch = (size_t)group * rp; need.in = 3 * need.pitch;
@@ -279,13 +257,9 @@ int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n, const vo
   return rc;
 }
 
-// mi355ndt_prefilter with the nodelet's whole parameter set: the batch chain over a group of ONE cloud, emitted into the resident result
-int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t stride, const mi355ndt_prefilter_params* prm,
+// One cloud into the resident result: the batch chain over a group of ONE cloud.  (The arguments have been checked.)
+static int prefilter_one(mi355ndt_handle* h, const void* pts, size_t n, size_t stride, const PfbChain& chain,
                          void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
-  if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  if ((!pts && n) || (n && stride < 12) || n >= (1u << 30) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
-  PfbChain chain;
-  if (pfb_chain(prm, &chain)) return MI355NDT_ERR_BAD_ARG;
   *n_out = 0;
   h->pf_count = 0;
   if (n == 0) return MI355NDT_OK;
@@ -318,13 +292,33 @@ int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t s
   h->pf_count = (int)m;
   *n_out = m;
   if (ret[2] != INT_MAX) h->err = "prefilter: leaf size too small for the cloud's extent, voxel indices would overflow; cloud not down-sampled";
-  if (out_pts) {
-    if (m > out_capacity) return MI355NDT_ERR_BAD_ARG;
-    std::vector<float> tmp(3 * pitch);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->d_pf_out, 3 * pitch * sizeof(float), hipMemcpyDeviceToHost));
-    rows_to_records(tmp.data(), pitch, 3, m, out_pts, out_stride, -1);
-  }
-  return MI355NDT_OK;
+  return pf_result_records(h, m, out_pts, out_capacity, out_stride);
+}
+
+// replaces PrefilteringNodelet::distance_filter + downsample (prefiltering_nodelet.cpp:137-181): mi355ndt_prefilter_p with plain parameters --
+// no move, no calibration, VOXELGRID
+int mi355ndt_prefilter(mi355ndt_handle* h, const void* pts, size_t n, size_t stride,
+                       int use_distance_filter, double distance_near, double distance_far, float downsample_resolution,
+                       void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  if ((!pts && n) || (n && stride < 12) || n >= (1u << 30) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
+  mi355ndt_prefilter_params p;
+  (void)mi355ndt_prefilter_params_default(&p);
+  p.use_distance_filter = use_distance_filter; p.distance_near = distance_near; p.distance_far = distance_far;
+  p.downsample_resolution = downsample_resolution;
+  PfbChain chain;
+  if (pfb_chain(&p, &chain)) return MI355NDT_ERR_BAD_ARG;        // (a NaN resolution)
+  return prefilter_one(h, pts, n, stride, chain, out_pts, out_capacity, out_stride, n_out);
+}
+
+// mi355ndt_prefilter with the nodelet's whole parameter set
+int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t stride, const mi355ndt_prefilter_params* prm,
+                         void* out_pts, size_t out_capacity, size_t out_stride, size_t* n_out) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  if ((!pts && n) || (n && stride < 12) || n >= (1u << 30) || !n_out || (out_pts && out_stride < 12)) return MI355NDT_ERR_BAD_ARG;
+  PfbChain chain;
+  if (pfb_chain(prm, &chain)) return MI355NDT_ERR_BAD_ARG;
+  return prefilter_one(h, pts, n, stride, chain, out_pts, out_capacity, out_stride, n_out);
 }
 
 // the points a batch slot holds, whatever route filled it

@@ -1,5 +1,6 @@
 // ndt_host_voxel.hpp -- what the prefilter, the map cloud, the window map and the keyframe index builds share on the host: growth of their one
-// scratch (VoxelScratch, ndt_engine.hpp), the exclusive scan, the VoxelGrid chain and the scatter of SoA rows into the caller's records.
+// scratch (VoxelScratch, ndt_engine.hpp), the exclusive scan and the scatter of SoA rows into the caller's records.  (The VoxelGrid chain
+// itself is pfb_positions, ndt_host_prefilter.hpp: one segmented chain for one cloud as for K.)
 #pragma once
 
 // what a call needs of the scratch: points (a multiple of 64: every per-point member follows from it), floats of in / x / out, bytes of the
@@ -37,36 +38,6 @@ static void exscan_ints(hipStream_t s, const int* flag, size_t pitch, unsigned* 
   k_pf_scan_totals<<<chunks, 1024, 0, s>>>(flag, pitch, tmp);
   k_pf_scan_offsets<<<1, 1024, 0, s>>>(tmp, chunks);
   k_pf_scan_apply<<<chunks, 1024, 0, s>>>(flag, pitch, tmp, pos);
-}
-
-// The VoxelGrid chain between the caller's flag kernel (vs.keep and vs.mm filled from the n points of X) and its emit kernel: grid, keys,
-// stable sort by voxel index (the whole cloud one segment, 31 key bits), run heads, emit positions in vs.pos.  It waits for the device once,
-// for the grid's status; a leaf too small for the extent (PCL: "Leaf size is too small for the input dataset") leaves the cloud as it is:
-// `who`'s `what` is not down-sampled, and h->err says so.  leaf <= 0: no down-sampling, no wait.
-struct VgHeads { const unsigned *keys, *vals; int downsample; };   // the sorted keys and point ids; 0: the kept points in input order
-static int voxel_grid_heads(mi355ndt_handle* h, const char* who, const char* what, const float* X, size_t pitch, size_t n, float leaf, VgHeads* out) {
-  VoxelScratch& w = h->vs;
-  hipStream_t s = h->stream;
-  const int gx = (int)((pitch + 255) / 256);
-  *out = VgHeads{w.keys, w.vals, leaf > 0.f};
-  if (out->downsample) {
-    k_pf_grid<<<1, 1, 0, s>>>(w.mm, leaf, w.grid);
-    PfGrid g;
-    HIPCHK(h, hipMemcpyAsync(&g, w.grid, sizeof g, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    w.pending = false;
-    if (g.status == 2) {
-      h->err = std::string(who) + ": leaf size too small for the " + what + "'s extent, voxel indices would overflow; " + what + " not down-sampled";
-      out->downsample = 0;
-    } else {
-      k_pf_keys<<<gx, 256, 0, s>>>(X, pitch, (int)n, w.keep, w.grid, w.keys, w.vals);
-      const RsSorted r = rs_sort_one_segment(s, 31, w.keys, w.vals, w.keys + pitch, w.vals + pitch, pitch, w.hist, w.offs);
-      out->keys = r.keys; out->vals = r.vals;
-    }
-  }
-  k_pf_heads<<<gx, 256, 0, s>>>(out->keys, w.keep, (int)n, pitch, out->downsample, w.flag);
-  exscan_ints(s, w.flag, pitch, w.tmp, w.pos);
-  return MI355NDT_OK;
 }
 
 // n points of host SoA rows (`ch` rows of `pitch` floats: x, y, z and, with ch = 4, the intensity) into the caller's records; ioff >= 0: the

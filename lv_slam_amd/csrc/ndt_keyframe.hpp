@@ -5,10 +5,12 @@
 // in scan order (:242), and the whole window goes through pcl::VoxelGrid(leaf) when it closes (:214-218).  The CPU restatement, with the
 // arithmetic step by step, is tools/window_map_ref.py.
 //   k_kf_window   ONE pass over the window: scan rows -> moved points (and intensity), SoA in window order, keep flags, f32 extremes
-//   k_pf_grid, k_pf_keys, rs_pass x 3, k_pf_heads, k_pf_scan_*   the prefilter's VoxelGrid machinery (ndt_prefilter.hpp), unchanged
+//   k_pfb_grid, k_pfb_keys, rs_pass x 3, k_pfb_heads, k_pfb_scan_*   the prefilter's segmented VoxelGrid chain (ndt_prefilter_batch.hpp), the
+//                 window its one cloud; the grid's status ("leaf too small") is decided and consumed on the device
 //   k_kf_emit     one centroid per occupied voxel, x, y, z and intensity, straight into the keyframe's own rows
 #pragma once
 #include "ndt_types.hpp"
+#include "ndt_prefilter.hpp"
 
 #define KF_CHUNK   1024              // window positions per workgroup of k_kf_window (four per lane)
 #define KF_THREADS 256
@@ -21,7 +23,7 @@ struct KfScan { const float* rows; unsigned start, pitch; };   // scan k: its x,
 // T: per scan the three upper rows of (w_odom.inverse() * odom_k).matrix(), row-major f64; scan 0 is the window's own frame and is taken as
 // it is (:206, :232).  A point with a non-finite coordinate is not moved (PCL skips it in a non-dense cloud) and is not kept; neither is a
 // point the move pushes out of f32's range: VoxelGrid drops both.  Positions n .. pitch are written as zeros, not kept.
-// mm: the ordered-int extremes of the kept points, reduced per wave before one atomic per wave and word (the k_pf_flag pattern).
+// mm: the ordered-int extremes of the kept points, reduced per wave before one atomic per wave and word (PfExt's pattern).
 __global__ void __launch_bounds__(KF_THREADS) k_kf_window(const KfScan* __restrict__ sc, int n_scans, const double* __restrict__ T, int n, size_t pitch,
                                                           int ch, float* X, unsigned char* keep, int* mm) {
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
@@ -69,11 +71,13 @@ __global__ void __launch_bounds__(KF_THREADS) k_kf_window(const KfScan* __restri
 // One lane per voxel head (or, without down-sampling, per kept point).  CentroidPoint<PointXYZI>: AccumulatorXYZ and AccumulatorIntensity add
 // the points of the voxel in f32, in input order (the stable sort keeps it), and divide by float(n).  The sums are order-bound, so a run
 // stays with its one lane however long it is.  Rows past the m emitted points, up to the keyframe's pitch, are zeroed here.
+// downsample: leaf > 0; a window whose grid says the leaf is too small is emitted as it is (k_pfb_emit's rule).
 __global__ void __launch_bounds__(256) k_kf_emit(const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ keys,
                                                  const unsigned* __restrict__ vals, const int* __restrict__ flag, const int* __restrict__ pos,
-                                                 int downsample, int ch, float* out, size_t out_pitch, size_t m) {
+                                                 const PfGrid* __restrict__ grid, int downsample, int ch, float* out, size_t out_pitch, size_t m) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= pitch) return;
+  downsample = downsample && grid->status == 0;
   if (i >= m && i < out_pitch)
     for (int c = 0; c < ch; c++) out[c * out_pitch + i] = 0.f;
   if (!flag[i]) return;

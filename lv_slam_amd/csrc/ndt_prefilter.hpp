@@ -7,8 +7,8 @@
 // launch/dlo_kitti.launch:30-36): keep points with near < |p| < far (f32 norm compared as double), then pcl::VoxelGrid
 // centroid downsample (PCL 1.8 voxel_grid.hpp applyFilter, CentroidPoint / AccumulatorXYZ: f32 sums, divided by the
 // count), output in ascending voxel index.  Same binning + stable sort machinery as the NDT target build.
-// The per-point pieces below are shared by the one-cloud kernels of this file and the segmented ones of ndt_prefilter_batch.hpp: the two surfaces
-// cannot drift.
+// This file holds the per-point pieces and the exclusive scan; the kernels that run them are the segmented ones of ndt_prefilter_batch.hpp, for
+// one cloud (mi355ndt_prefilter, mi355ndt_window_keyframe: a group of one) as for K.
 // the gate: near < |p| < far (f32 norm compared as double, :168) and the finite test (VoxelGrid skips non-finite points: is_dense = false, :175)
 __device__ __forceinline__ bool pf_gate(float x, float y, float z, int use_df, double dnear, double dfar) {
   bool ok = true;
@@ -62,18 +62,6 @@ struct PfExt {
   }
 };
 
-__global__ void __launch_bounds__(256) k_pf_flag(const float* __restrict__ X, size_t pitch, int n, int use_df, double dnear, double dfar,
-                                                 unsigned char* keep, int* mm) {
-  PfExt ext;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float x = X[i], y = X[pitch + i], z = X[2 * pitch + i];
-    const bool ok = pf_gate(x, y, z, use_df, dnear, dfar);
-    keep[i] = ok ? 1 : 0;
-    if (ok) ext.take(x, y, z);
-  }
-  ext.commit(mm);
-}
-
 struct PfGrid { int min_b[3], mul1, mul2, status; float inv_leaf; };   // status: 0 ok, 1 empty, 2 index overflow
 
 // the grid of one cloud from its six extremes
@@ -91,7 +79,6 @@ __device__ __forceinline__ PfGrid pf_make_grid(const int* __restrict__ mm, float
   g.mul2 = g.mul1 * (maxb[1] - g.min_b[1] + 1);
   return g;
 }
-__global__ void k_pf_grid(const int* __restrict__ mm, float leaf, PfGrid* out) { *out = pf_make_grid(mm, leaf); }
 
 // the 31-bit voxel key of position i (0x7FFFFFFF: not binned -- past the cloud, dropped by the gate, or the cloud has no usable grid)
 __device__ __forceinline__ unsigned pf_cell_key(const float* __restrict__ X, size_t pitch, int n, const unsigned char* __restrict__ keep,
@@ -105,25 +92,11 @@ __device__ __forceinline__ unsigned pf_cell_key(const float* __restrict__ X, siz
   }
   return cell;
 }
-__global__ void __launch_bounds__(256) k_pf_keys(const float* __restrict__ X, size_t pitch, int n, const unsigned char* __restrict__ keep,
-                                                 const PfGrid* __restrict__ pg, unsigned* keys, unsigned* vals) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int)pitch) return;
-  const PfGrid g = *pg;
-  keys[i] = pf_cell_key(X, pitch, n, keep, g, (size_t)i);
-  vals[i] = (unsigned)i;
-}
 
 // head of every occupied voxel's run (or, without down-sampling, every kept point)
 __device__ __forceinline__ int pf_is_head(const unsigned* __restrict__ keys, const unsigned char* __restrict__ keep, int n, int downsample, size_t i) {
   if (downsample) return keys[i] != 0x7FFFFFFFu && (i == 0 || keys[i - 1] != keys[i]);
   return i < (size_t)n && keep[i];
-}
-__global__ void __launch_bounds__(256) k_pf_heads(const unsigned* __restrict__ keys, const unsigned char* __restrict__ keep, int n, size_t pitch,
-                                                  int downsample, int* flag) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int)pitch) return;
-  flag[i] = pf_is_head(keys, keep, n, downsample, (size_t)i);
 }
 
 // what the head at position i emits: the voxel's centroid -- the f32 sum of its points in input order, divided by (float)count -- or, without
@@ -145,17 +118,6 @@ __device__ __forceinline__ void pf_emit_point(const float* __restrict__ X, size_
     sx = X[i]; sy = X[pitch + i]; sz = X[2 * pitch + i];
   }
 }
-__global__ void __launch_bounds__(256) k_pf_emit(const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ keys,
-                                                 const unsigned* __restrict__ vals, const int* __restrict__ flag, const int* __restrict__ pos,
-                                                 int downsample, float* out, size_t out_pitch) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int)pitch || !flag[i]) return;
-  float sx, sy, sz;
-  pf_emit_point(X, pitch, keys, vals, downsample, (size_t)i, sx, sy, sz);
-  const int o = pos[i];
-  out[o] = sx; out[out_pitch + o] = sy; out[2 * out_pitch + o] = sz;
-}
-
 
 // Exclusive prefix sum of n ints (the emit positions of the kept points / voxel heads): block totals of 4096-element chunks,
 // one block scanning those totals, then every chunk scans itself again on top of its offset.

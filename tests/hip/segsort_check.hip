@@ -1,6 +1,6 @@
 // TEST HELPER (tests/test_segsort_gpu.py): the stable segmented radix sort (ndt_segsort.hpp: k_rs_hist, k_rs_scan, k_rs_scatter behind rs_plan,
 // rs_pass, rs_sort_one_segment) and the exclusive scans that turn head flags into emit positions (ndt_prefilter.hpp: k_pf_scan_totals / _offsets /
-// _apply, k_pf_heads; ndt_prefilter_batch.hpp: k_pfb_scan_*, k_pfb_heads) on the device, alone.  It launches the library's own kernels through
+// _apply; ndt_prefilter_batch.hpp: k_pfb_scan_*, k_pfb_heads) on the device, alone.  It launches the library's own kernels through
 // the library's own host entry points and restates none of them; every comparison happens in the test, against numpy.
 //
 //   segsort_check plan                      no HIP call: prints "f bits passes" of rs_plan(f) for f = 0 .. 33
@@ -20,7 +20,7 @@
 //     kind 1: [nchunks] totals[nchunks]: k_pf_scan_offsets alone.                      out: TOTALS
 //     kind 2: [K] [chunks] [rp] K x {out_pitch n id} flags[K * rp]: the per-cloud chain after k_pfb_begin.   out: mm RES TOTALS POS
 //   mode 4, heads:   [K] [rp] [downsample] K x {n status} keys[K * rp] keep[K * rp] (one word per byte)
-//     k_pf_heads over every cloud on its own, then k_pfb_heads over all.               out: FLAGS_PF FLAGS_PFB
+//     k_pfb_heads over all clouds with every grid's status 0, then with the statuses given.   out: FLAGS_OK FLAGS_PFB
 // <out.u32>: the output buffers of every case in the order above, each as [n] [64 guard words] [n words] [64 guard words]; a buffer in capitals
 // is written whole, the others with n = 0 (their guard words only).  Every buffer is filled with 0xA5A5A5A5, guards included, before any
 // launch: a word the kernels did not write, or wrote outside their buffer, shows in the test.
@@ -235,11 +235,12 @@ static void case_heads(Reader& in, FILE* out) {
   Buf ditems(((size_t)K * sizeof(PfbItem) + 3) / 4), dgrid(((size_t)K * sizeof(PfGrid) + 3) / 4), dkeys(words), dkeep(keep.size() / 4), f1(words), f2(words);
   CK(hipMemcpy(ditems.p(), items.data(), items.size() * sizeof(PfbItem), hipMemcpyHostToDevice));
   CK(hipMemcpy(dgrid.p(), grid.data(), grid.size() * sizeof(PfGrid), hipMemcpyHostToDevice));
+  Buf dgrid0(dgrid.n);                                                           // the same clouds, every grid usable
+  CK(hipMemset(dgrid0.p(), 0, grid.size() * sizeof(PfGrid)));
   dkeys.put(keys, words);
   CK(hipMemcpy(dkeep.p(), keep.data(), keep.size(), hipMemcpyHostToDevice));
   const unsigned char* kp = (const unsigned char*)dkeep.p();
-  for (int b = 0; b < K; b++)
-    k_pf_heads<<<(unsigned)((rp + 255) / 256), 256>>>(dkeys.p() + (size_t)b * rp, kp + (size_t)b * rp, items[(size_t)b].n, rp, downsample, (int*)f1.p() + (size_t)b * rp);
+  k_pfb_heads<<<xcd_grid(tiles, K), 256>>>(dkeys.p(), kp, rp, (const PfbItem*)ditems.p(), K, tiles, (const PfGrid*)dgrid0.p(), downsample, (int*)f1.p());
   k_pfb_heads<<<xcd_grid(tiles, K), 256>>>(dkeys.p(), kp, rp, (const PfbItem*)ditems.p(), K, tiles, (const PfGrid*)dgrid.p(), downsample, (int*)f2.p());
   settle();
   f1.dump(out, true); f2.dump(out, true);

@@ -240,9 +240,12 @@ def test_single_surface():
     eng = ndt.Engine(ndt.default_params(**PRM))
     for cloud, kw in ((scan, {}), (c, dict(distance_near=1.0, distance_far=40.0, downsample_resolution=0.25)), (c, dict(downsample_resolution=0.0)),
                       (c[:0], {}), (c[:1], {})):
-        want = eng.prefilter(cloud, **kw)
+        want = O.prefilter(cloud, **{"leaf" if k == "downsample_resolution" else k: v for k, v in kw.items()})
+        plain = eng.prefilter(cloud, **kw)               # (the two entry points run one chain: each is held to the oracle, and to the other)
         got = eng.prefilter_p(cloud, **kw)
+        assert plain.tobytes() == want.tobytes() and plain.shape == want.shape
         assert got.tobytes() == want.tobytes() and got.shape == want.shape
+        assert got.tobytes() == plain.tobytes() and got.shape == plain.shape
     # the whole chain: the batch slot's words, resident for the third stage
     kw = dict(transform=T, angle_calibration=True, downsample_method=APPROX, downsample_resolution=0.2)
     got = eng.prefilter_p(c, **kw)
@@ -305,4 +308,84 @@ def test_argument_errors(monkeypatch):
     exp = O.prefilter(scan, 0.5, 100.0, 0.1, True)
     assert tc == [len(exp)] * 2 and eng.batch_get_cloud(1, True).tobytes() == exp.tobytes()
     monkeypatch.setattr(ndt, "_prefilter_params", make)
+    eng.close()
+
+
+# ---- mi355ndt_prefilter as a group of one: the 64-point pitch and the 4,096-point sort tile / scan chunk, where the segmented chain's tile
+# and chunk counts change
+GROUP_OF_ONE_N = (1, 63, 64, 65, 4095, 4096, 4097, 8193)
+GATE = (1.5, 3.5)
+LEAF_TOO_SMALL = "prefilter: leaf size too small for the cloud's extent, voxel indices would overflow; cloud not down-sampled"
+
+
+def clustered_cloud():
+    """8,193 points in clusters of four within a centimetre (voxels of several points from the first rows on), inside and outside the
+    1.5 .. 3.5 m gate, two rows not finite; row 0 passes the gate"""
+    rng = np.random.default_rng(20261020)
+    base = np.repeat(rng.uniform([-3.0, -3.0, -0.5], [3.0, 3.0, 0.5], (2049, 3)), 4, axis=0)
+    c = (base + rng.normal(0.0, 0.01, base.shape)).astype(np.float32)[:8193]
+    c[0] = [2.0, 0.5, 0.1]
+    c[5] = np.nan
+    c[40, 1] = np.inf
+    c.setflags(write=False)
+    return c
+
+
+def last_error(eng):
+    return (eng.lib.mi355ndt_last_error(eng.h) or b"").decode()
+
+
+@pytest.fixture(scope="module")
+def one_eng():
+    e = ndt.Engine(ndt.default_params(**PRM))
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("n", GROUP_OF_ONE_N)
+def test_plain_prefilter_at_pitch_and_tile_edges(one_eng, n):
+    c = clustered_cloud()[:n]
+    exp = {}
+    for gate in (True, False):
+        for leaf in (0.1, 0.0):
+            exp[gate, leaf] = O.prefilter(c, *GATE, leaf, gate)
+            got = one_eng.prefilter(c, *GATE, leaf, gate)
+            assert got.shape == exp[gate, leaf].shape and got.tobytes() == exp[gate, leaf].tobytes(), (n, gate, leaf)
+    if n > 1:                                             # the oracle's own answers are not trivial: the gate rejects, voxels hold several points
+        assert 0 < len(exp[True, 0.0]) < len(exp[False, 0.0]) <= n
+        assert len(exp[True, 0.1]) < len(exp[True, 0.0]) and len(exp[False, 0.1]) < len(exp[False, 0.0])
+    else:
+        assert len(exp[True, 0.1]) == 1
+
+
+def test_plain_prefilter_leaf_too_small():
+    rng = np.random.default_rng(9)
+    pts = rng.uniform(-120, 120, (4097, 3)).astype(np.float32)            # 2.4e6 cells of 1e-4 m per axis
+    eng = ndt.Engine(ndt.default_params(**PRM))
+    assert last_error(eng) == ""
+    got = eng.prefilter(pts, 0.5, 100.0, 1e-4, True)                      # (returns: the code is OK)
+    d = np.sqrt((pts[:, 0] * pts[:, 0] + pts[:, 1] * pts[:, 1]) + pts[:, 2] * pts[:, 2]).astype(np.float64)
+    kept = pts[(d > 0.5) & (d < 100.0)]
+    assert 0 < len(kept) < len(pts)
+    assert got.shape == kept.shape and got.tobytes() == kept.tobytes()    # the gated input in input order
+    assert got.tobytes() == O.prefilter(pts, 0.5, 100.0, 1e-4, True).tobytes()
+    assert last_error(eng) == LEAF_TOO_SMALL
+    eng.close()
+
+
+def test_resident_result_follows_each_call():
+    """one engine, large cloud, 1-point cloud, all-rejected cloud, large again: the count and the resident rows are those of the last call
+    (read back through the stage that consumes them, RADIUS outlier removal with min_neighbors = 0: every finite point stays)"""
+    c = clustered_cloud()
+    rng = np.random.default_rng(78)
+    inside = rng.uniform(-0.2, 0.2, (300, 3)).astype(np.float32)
+    eng = ndt.Engine(ndt.default_params(**PRM))
+    for cloud in (c, c[:1], inside, c[:4097]):
+        exp = O.prefilter(cloud, *GATE, 0.1, True)
+        got = eng.prefilter(cloud, *GATE, 0.1, True)
+        assert got.shape == exp.shape and got.tobytes() == exp.tobytes()
+        assert eng.prefilter(cloud, *GATE, 0.1, True, fetch=False) == len(exp)
+        resident = eng.prefilter_outliers(method="RADIUS", min_neighbors=0)
+        assert resident.shape == exp.shape and resident.tobytes() == exp.tobytes()
+    assert len(O.prefilter(inside, *GATE, 0.1, True)) == 0 and len(O.prefilter(c[:1], *GATE, 0.1, True)) == 1
     eng.close()

@@ -1,6 +1,6 @@
 """The two device building blocks under every voxel surface, alone, word for word against numpy: the stable segmented radix sort
 (lv_slam_amd/csrc/ndt_segsort.hpp: k_rs_hist, k_rs_scan, k_rs_scatter behind rs_plan, rs_pass, rs_sort_one_segment) and the exclusive scans
-that turn head flags into emit positions (ndt_prefilter.hpp: k_pf_scan_totals / _offsets / _apply, k_pf_heads; ndt_prefilter_batch.hpp:
+that turn head flags into emit positions (ndt_prefilter.hpp: k_pf_scan_totals / _offsets / _apply; ndt_prefilter_batch.hpp:
 k_pfb_scan_*, k_pfb_heads).  tests/hip/segsort_check.hip launches the library's own kernels through the library's own host entry points; the
 references below are numpy's stable argsort, bincount and cumsum.  Everything is integer work: every comparison is exact.
 
@@ -451,7 +451,8 @@ def test_heads_equal_the_two_branches_of_pf_is_head(tmp_path):
             kept = (np.arange(rp)[None, :] < np.array(ns)[:, None]) & (keep != 0)
             ds = np.array([downsample and s == 0 for s in status], bool)[:, None]
             want.append((f"heads, K {K}, rp {rp}, downsample {downsample}",
-                         [("k_pf_heads", (run_head if downsample else kept).astype(np.uint32)), ("k_pfb_heads", np.where(ds, run_head, kept).astype(np.uint32))]))
+                         [("k_pfb_heads, every grid usable", (run_head if downsample else kept).astype(np.uint32)),
+                          ("k_pfb_heads", np.where(ds, run_head, kept).astype(np.uint32))]))
     res = run_helper(tmp_path, 4, blobs)
     bad = []
     for name, arrays in want:

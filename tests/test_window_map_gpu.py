@@ -9,6 +9,7 @@ import pytest
 
 from conftest import ROOT
 from lv_slam_amd import ndt, synth
+from oracle import oracle_py as O
 
 pytestmark = pytest.mark.gpu
 
@@ -169,3 +170,62 @@ def test_bad_arguments(eng, drive):
     before = eng.keyframe_count()
     check(eng, [one], [np.eye(4)], 0.1)                           # the engine still works, and the failed calls left no keyframe
     assert eng.keyframe_count() == before
+
+
+# ---- the window as the prefilter chain's one cloud: totals at the 4,096-point sort tile / scan chunk, against the oracle's VoxelGrid over the
+# window written out in NumPy f64 (what tests/test_window_map_cpu.py holds the restatement to)
+LEAF_TOO_SMALL = "window_keyframe: leaf size too small for the window's extent, voxel indices would overflow; window not down-sampled"
+
+
+def clustered_records():
+    """4,097 records (x, y, z, intensity) in clusters of four within a centimetre -- voxels of several points, also across scans that barely
+    move --, three of them not finite"""
+    rng = np.random.default_rng(20261021)
+    base = np.repeat(rng.uniform([-3.0, -3.0, -0.5], [3.0, 3.0, 0.5], (1025, 3)), 4, axis=0)
+    r = np.concatenate([base + rng.normal(0.0, 0.01, base.shape), rng.uniform(0, 255, (len(base), 1))], axis=1).astype(np.float32)[:4097]
+    r[7, 0] = np.nan
+    r[2100, 2] = np.inf
+    r[4090, 1] = -np.inf
+    return r
+
+
+def small_poses(k):
+    out = []
+    for j in range(k):
+        a = 1e-3 * j
+        T = np.eye(4)
+        T[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        T[:3, 3] = [2e-3 * j, -1e-3 * j, 5e-4 * j]
+        out.append(T)
+    return out
+
+
+def check_oracle(eng, recs, rel, leaf):
+    """with and without intensity: x, y, z against the oracle, all four channels against the restatement; returns the oracle's cloud"""
+    from test_window_map_cpu import concat_f64
+    exp = O.prefilter(concat_f64(recs, rel), use_distance_filter=False, leaf=leaf)
+    got3 = check(eng, [r[:, :3] for r in recs], rel, leaf)
+    got4 = check(eng, recs, rel, leaf, intensity=True)
+    assert same_words(got3, exp) and same_words(got4[:, :3], exp)
+    return exp
+
+
+@pytest.mark.parametrize("total", (1, 4096, 4097))
+def test_window_totals_at_tile_edges_against_the_oracle(total):
+    r = clustered_records()[4097 - total:]                        # (the last record is finite: a window of one point keeps it)
+    eng = ndt.Engine()
+    assert (eng.lib.mi355ndt_last_error(eng.h) or b"") == b""
+    finite = int(np.isfinite(r[:, :3]).all(axis=1).sum())
+    splits = [(total,), (total // 2, total - total // 2), (total // 3, total // 3, total - 2 * (total // 3))]
+    if total == 4097:
+        splits.append((2000, 0, 2097))                            # one scan of the window is empty
+    for sizes in splits:
+        at = np.cumsum((0,) + sizes)
+        recs = [r[at[k]:at[k + 1]] for k in range(len(sizes))]
+        rel = small_poses(len(sizes))
+        exp = {leaf: check_oracle(eng, recs, rel, leaf) for leaf in (0.1, 0.0, 1e-4)}
+        assert len(exp[0.0]) == finite
+        if total > 1:                                             # not trivial: points dropped, voxels of several points, the 1e-4 m grid refused
+            assert finite < total and len(exp[0.1]) < finite and same_words(exp[1e-4], exp[0.0])
+            assert (eng.lib.mi355ndt_last_error(eng.h) or b"").decode() == LEAF_TOO_SMALL
+    eng.close()

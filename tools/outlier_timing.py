@@ -83,7 +83,7 @@ def kernel_stats(azimuth):
         for row in csv.DictReader(open(files[0])):
             name, ns = row.get("Name", ""), float(row.get("TotalDurationNs", 0) or 0)
             tot += ns
-            if name.startswith(("k_pf_", "k_minmax_init", "k_deint")) and "scan" not in name:
+            if name.startswith(("k_pfb_", "k_deint")):          # (the prefilter's own kernels; its sort passes count with the index build's)
                 pre += ns
             elif name.startswith(("k_kfi_", "k_minmax", "k_rs_", "k_fit_")):
                 build += ns

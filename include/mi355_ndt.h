@@ -40,7 +40,7 @@ extern "C" {
 #define MI355NDT_ERR_GRID        (-4)  /* target grid unusable: reference int32 guard
                                           (voxel_grid_covariance_omp_impl.hpp:75-84) or engine cell cap */
 #define MI355NDT_ERR_NO_DEVICE   (-5)
-#define MI355NDT_ERR_UNSUPPORTED (-6)  /* a surface or configuration MI355NDT_OPT_POSE_MODEL = 1 does not serve (mi355ndt_last_error says which) */
+#define MI355NDT_ERR_UNSUPPORTED (-6)  /* a surface or configuration MI355NDT_OPT_POSE_MODEL = 1 or MI355NDT_OPT_NDT_CLASS = 1 does not serve (mi355ndt_last_error says which) */
 /* Positive: a warning that rides in mi355ndt_result.status, never a return code.  Set only under MI355NDT_OPT_ARITH = 1: the registration is of a kind the
  * tolerance arithmetic is not meant for -- fewer than MI355NDT_TOLERANCE_MIN_HITS (point, voxel) hits at the final pose (the Hessian of a handful of points:
  * ~1e-7 per f32 term times its condition number is no tolerance-level perturbation any more) or a run that stopped at the iteration cap (an oscillating run
@@ -266,8 +266,24 @@ enum mi355ndt_option {
    * status).  Refused with MI355NDT_ERR_UNSUPPORTED and a message, nothing changed: variant = PCA, the live More-Thuente configuration
    * (step_size <= trans_epsilon / 2), mi355ndt_sequence_run*, mi355ndt_stream_begin, mi355ndt_compute_hessian, mi355ndt_derivatives_T.  Setting
    * the option while a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  PCL's own f64 NormalDistributionsTransform
-   * (registration_method = NDT) is not this option: it stays unserved. */
-  MI355NDT_OPT_POSE_MODEL = 12
+   * (registration_method = NDT) is not this option: it is MI355NDT_OPT_NDT_CLASS. */
+  MI355NDT_OPT_POSE_MODEL = 12,
+  /* Which class the aligns restate.  0 (default): pclomp::NormalDistributionsTransform -- every result word as without the option.  1:
+   * pcl::NormalDistributionsTransform<PointXYZI, PointXYZI>, PCL's own class, which select_registration_method (src/global_graph/registrations.cpp)
+   * hands out for registration_method = NDT and for every name it does not know.  It is the Euler-angle pose model (as MI355NDT_OPT_POSE_MODEL = 1:
+   * the same pose vector, start, step, convertTransform in f32 and convergence rule) with PCL's evaluation: one neighbourhood,
+   * radiusSearch(moved point, resolution) over the leaf centroids, and updateDerivatives in f64 from end to end -- the f32 moved point widened
+   * minus the leaf's f64 mean, the leaf's f64 inverse covariance, the f64 j_ang / h_ang rows applied to the original point, exp in f64.
+   * Under 1 neighbor_mode, MI355NDT_OPT_POSE_MODEL and MI355NDT_OPT_ARITH are not consulted (no warning status), and no result word depends on
+   * MI355NDT_OPT_F32_SUM_ORDER: the evaluation has no three-term f32 sum, and the point transform and the radius test are written in one order.
+   * Served under 1: mi355ndt_batch_align, mi355ndt_align, mi355ndt_derivatives (p read as [t; roll pitch yaw]), mi355ndt_get_fitness_score,
+   * mi355ndt_batch_fitness_scores, host clouds and keyframe ids as sources and targets; an align always goes through the lockstep (update, sweep)
+   * rounds.  Refused with MI355NDT_ERR_UNSUPPORTED and a message, nothing changed: variant = PCA, the live More-Thuente configuration
+   * (step_size <= trans_epsilon / 2), mi355ndt_sequence_run*, mi355ndt_stream_begin, mi355ndt_compute_hessian, mi355ndt_derivatives_T.  Setting
+   * the option while a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  A target that is resident without centroids
+   * or f64 inverse covariances is rebuilt by the next align.  PCL's single-threaded GeneralizedIterativeClosestPoint (registration_method = GICP)
+   * stays unserved. */
+  MI355NDT_OPT_NDT_CLASS = 13
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);

@@ -49,6 +49,31 @@ struct GridsBuilt {
   size_t total_words;           // bitmap words of all its grids (a planned build of the stream: its plan's)
   bool fit_index;               // the fitness scores' occupied-cell index has been built over it (ndt_fitness.hpp)
 };
+// ---- MI355NDT_OPT_NDT_CLASS: 0 = pclomp::NormalDistributionsTransform (the option above says which implementation), 1 =
+// pcl::NormalDistributionsTransform, PCL's own f64 class (registration_method = NDT, the factory's fall-back).  Class 1 is the Euler pose model
+// with one neighbourhood -- radiusSearch(point, resolution), whatever neighbor_mode says -- and an f64 evaluation (ndt_sweep.hpp: eval_hit_pcl)
+// that reads the leaves' f64 inverse covariances.  MI355NDT_OPT_POSE_MODEL and MI355NDT_OPT_ARITH are not consulted.  The overloads below take the
+// class; the ones above are the class-0 answers.
+enum { NDT_CLASS_OMP = 0, NDT_CLASS_PCL = 1 };
+// the pose model an align of this class runs
+static inline int class_model(int ndt_class, int pose_model) { return ndt_class == NDT_CLASS_PCL ? POSE_MODEL_EULER : pose_model; }
+// the neighbour search an align of this class runs
+static inline int class_neighbor_mode(int ndt_class, int neighbor_mode) { return ndt_class == NDT_CLASS_PCL ? (int)MI355NDT_KDTREE : neighbor_mode; }
+static inline int model_arith(int pose_model, int arith, int ndt_class) { return model_arith(class_model(ndt_class, pose_model), arith); }
+static inline bool model_leaves_rounds(int pose_model, int ndt_class) { return model_leaves_rounds(class_model(ndt_class, pose_model)); }
+static inline const char* model_refuses(const mi355ndt_params& p, int pose_model, int ndt_class) {
+  if (ndt_class != NDT_CLASS_PCL) return model_refuses(p, pose_model);
+  if (p.variant == MI355NDT_VARIANT_PCA) return "MI355NDT_OPT_NDT_CLASS = 1 serves variant = OMP alone (pcl::NormalDistributionsTransform has no weights)";
+  if (mt_is_live(p)) return "MI355NDT_OPT_NDT_CLASS = 1 does not serve the live More-Thuente configuration (step_size <= trans_epsilon / 2)";
+  return nullptr;
+}
+// what a configuration of this class needs: class 1 reads the centroids (its radius search) and the f64 inverse covariances (its evaluation)
+// whatever neighbor_mode says, and never the kd weights or the tolerance arithmetic's records
+static inline GridExtras grid_extras(const mi355ndt_params& p, int arith, bool live, int ndt_class) {
+  if (ndt_class != NDT_CLASS_PCL) return grid_extras(p, arith, live);
+  return {true, true, false, false};
+}
+
 static inline bool grids_serve(const GridsBuilt& b, const GridExtras& need) {
   return b.valid && (b.made.cent || !need.cent) && (b.made.icov64 || !need.icov64) && (b.made.kdw || !need.kdw) && (b.made.recs_fast || !need.recs_fast);
 }

@@ -126,12 +126,12 @@ static int build_targets(mi355ndt_handle* h, const GridExtras make) {
 }
 int mi355ndt_batch_build_targets(mi355ndt_handle* h) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
-  return build_targets(h, grid_extras(h->prm, model_arith(h->pose_model, h->arith)));
+  return build_targets(h, eff_extras(h));
 }
 
 static int ensure_grids(mi355ndt_handle* h, GridWant want) {
   HIPCHK(h, hipSetDevice(h->device));             // the prologue of every call that reads the grids: the engine's device, the uploads so far
   { int rcu = uploads_before_compute(h); if (rcu) return rcu; }   // in front of the compute stream (the cloud rows are read as well)
-  const GridExtras make = grid_extras(h->prm, model_arith(h->pose_model, h->arith), want == GRIDS_LIVE);
+  const GridExtras make = eff_extras(h, want == GRIDS_LIVE);
   return grids_serve(h->built, want == GRIDS_ANY ? GridExtras{} : make) ? (int)MI355NDT_OK : build_targets(h, make);
 }

@@ -45,7 +45,7 @@ static int run_hook_sweep(mi355ndt_handle* h, double* score, double g[6], double
   int rc = launch_sweep(h, sc);
   if (rc) return rc;
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 0, nullptr);
+                                    nullptr, 0, 0, 0, 1, 0, nullptr, nullptr);
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -68,7 +68,7 @@ int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, d
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!p) return MI355NDT_ERR_BAD_ARG;
   // (model 1: p = [t; roll pitch yaw] -- the cloud is moved by convertTransform(p), the rows are taken from p: k_set_pose_p)
-  if (const char* why = model_refuses(h->prm, h->pose_model)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
+  if (const char* why = model_refuses(h->prm, h->pose_model, h->ndt_class)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
   int rc = hook_ready(h);
   if (rc) return rc;
   double* dp = (double*)h->d_hook.p;
@@ -76,7 +76,7 @@ int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, d
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
   h->ctl_idx = 0;
-  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 0, euler_rows_of(h));
+  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 0, euler_rows_of(h), pcl_rows_of(h));
   return run_hook_sweep(h, score, g, H, hits);
 }
 
@@ -93,12 +93,12 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), h->stream));
   h->ctl_idx = 0;
-  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 1, nullptr);
+  k_set_pose_p<<<1, 1, 0, h->stream>>>(h->d_state, 0, dp, h->d_src_cnt, h->d_grid, h->d_active_list, h->d_ctl, 1, nullptr, nullptr);
   SweepConst sc;
   make_sweep_const(h, sc);
   launch_hessian(h, sc);
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 2, nullptr);
+                                    nullptr, 0, 0, 0, 1, 2, nullptr, nullptr);
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

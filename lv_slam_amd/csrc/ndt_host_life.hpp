@@ -185,12 +185,12 @@ int mi355ndt_set_params(mi355ndt_handle* h, const mi355ndt_params* p) {
   // re-made when a SOURCE cloud is set; without one it keeps its leaf size until the next setInputTarget, while the Gauss constants follow
   // the new value (impl2:93-100).  Reproduced for the DIRECT searches of the single-registration surface; a radius search over the grid
   // (KDTREE, live More-Thuente) is emulated by a 27-cell probe that needs radius <= leaf, so those re-voxelise as before (documented deviation).
-  const bool radius_search = p->neighbor_mode == MI355NDT_KDTREE || mt_is_live(*p);
+  const bool radius_search = class_neighbor_mode(h->ndt_class, p->neighbor_mode) == MI355NDT_KDTREE || mt_is_live(*p);
   const bool keep_grid = old.resolution != p->resolution && h->n_pairs == 1 && !h->have_source && !radius_search && h->d_tgt == h->d_tgt_own;
   const bool regrid = (old.resolution != p->resolution && !keep_grid) || old.variant != p->variant ||
                       old.min_points_per_voxel != p->min_points_per_voxel ||
                       old.min_covar_eigvalue_mult != p->min_covar_eigvalue_mult ||
-                      !grids_serve(h->built, grid_extras(*p, 0));   // centroids, f64 inverse covariances or kd weights the build skipped (arith 0: the
+                      !grids_serve(h->built, grid_extras(*p, 0, false, h->ndt_class));   // centroids, f64 inverse covariances or kd weights the build skipped (arith 0: the
                                                                     // tolerance arithmetic's records are left to the next align)
   if (regrid && h->built.valid) {
     h->built.valid = false;
@@ -205,7 +205,12 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
   if (h->ss && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
-                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL)) NOT_IN_STREAM(h);
+                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL || option == MI355NDT_OPT_NDT_CLASS)) NOT_IN_STREAM(h);
+  if (option == MI355NDT_OPT_NDT_CLASS) {
+    if (value != NDT_CLASS_OMP && value != NDT_CLASS_PCL) return MI355NDT_ERR_BAD_ARG;
+    h->ndt_class = value;                        // (what class 1 serves and needs of the grids: ndt_grid_state.hpp; the next align rebuilds what a resident target lacks)
+    return MI355NDT_OK;
+  }
   if (option == MI355NDT_OPT_POSE_MODEL) {
     if (value != POSE_MODEL_SE3 && value != POSE_MODEL_EULER) return MI355NDT_ERR_BAD_ARG;
     h->pose_model = value;                       // (what model 1 serves: ndt_grid_state.hpp; grids built for the tolerance arithmetic are rebuilt by the next align)
@@ -274,6 +279,7 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (option == MI355NDT_OPT_F32_SUM_ORDER) { *value = h->f32_sum_order; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ARITH) { *value = h->arith; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_POSE_MODEL) { *value = h->pose_model; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_NDT_CLASS) { *value = h->ndt_class; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) { *value = h->async_force ? 2 : (h->async_align ? 1 : 0); return MI355NDT_OK; }
   if (option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) { *value = h->score_only_last; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_ABORT) { *value = h->debug_abort_pos == 0xFFFFFFFFu ? -1 : (int)h->debug_abort_pos; return MI355NDT_OK; }

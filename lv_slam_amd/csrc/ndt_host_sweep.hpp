@@ -10,6 +10,7 @@
 // ndt_ord1_list.hpp and ndt_fast_list.hpp spell out the ORD = 1 and ORD = 2 rows of this predicate as text (explicit instantiation needs
 // that): a change here is a change there.
 // Under MI355NDT_OPT_POSE_MODEL = 1: k_sweep<false, K, 8, false, ORD, 1> for the four K and ORD = 0 / 1 (euler_sweep_exists, launch_sweep_euler).
+// Under MI355NDT_OPT_NDT_CLASS = 1: k_sweep<false, 27, 8, false, 0, 2> alone (the radius search, the f64 evaluation: launch_sweep).
 constexpr int SWEEP_IT_BATCH = 8;
 constexpr bool euler_sweep_exists(int K, int ord) { return (K == 1 || K == 7 || K == 26 || K == 27) && (ord == 0 || ord == 1); }
 constexpr bool sweep_exists(bool pca, int K, int ord, int it) {
@@ -47,9 +48,10 @@ static int prep_align_ws(mi355ndt_handle* h) {
     const bool fine_served = sweep_exists(false, neighbor_K(h->prm.neighbor_mode), 0, h->fine_tiles);
     // "small": fewer batch-mode items than two per resident wave; a sequence run sweeps ONE pair at a time whatever the number of frames
     const bool small = h->seq_running || (long long)B * h->chunks_per_pair * QUARTERS < 4LL * h->n_cu * WAVES;
-    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small && model_leaves_rounds(h->pose_model)) ? h->fine_tiles : 0;
+    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small && model_leaves_rounds(h->pose_model, h->ndt_class)) ? h->fine_tiles : 0;
   }
-  if (h->pose_model == POSE_MODEL_EULER) HIPCHK(h, h->d_euler_rows.reserve((size_t)B * EULER_ROW_WORDS));
+  if (eff_model(h) == POSE_MODEL_EULER) HIPCHK(h, h->d_euler_rows.reserve((size_t)B * EULER_ROW_WORDS));
+  if (h->ndt_class == NDT_CLASS_PCL) HIPCHK(h, h->d_pcl_rows.reserve((size_t)B * EULER_ROW_WORDS));
   if (h->fine_it) {
     const int item_pts = h->fine_it * 64;
     h->pts_per_chunk = 4 * item_pts;                                   // a block of the fine sweep = four items = one chunk, stored as ONE row
@@ -81,7 +83,7 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
   const float leaf = (h->built.valid && h->built.leaf > 0.f) ? h->built.leaf : h->prm.resolution;
   { int ex; float mant = std::frexp(leaf, &ex); sc.leaf_pow2 = (mant == 0.5f) && ex > -100 && ex < 100; sc.inv_leaf = 1.0f / leaf; }
   sc.kd_r2 = (float)((double)h->prm.resolution * (double)h->prm.resolution);   // KdTreeFLANN::radiusSearch: float(radius * radius)
-  build_offsets(h->prm.neighbor_mode, sc);
+  build_offsets(class_neighbor_mode(h->ndt_class, h->prm.neighbor_mode), sc);   // (class 1: always the radius search)
   sc.dyn_shift = h->dyn_shift >= 0 ? h->dyn_shift : (sc.K == 1 ? 3 : 2);
   sc.host_flags = nullptr;
   sc.seq_no = 0;
@@ -89,11 +91,15 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
   sc.d1f = (float)d1;
   sc.kq = (float)(-0.5 * (double)sc.d2f * 1.4426950408889634);   // exp(-d2 q / 2) = 2^(kq q)
   sc.euler_rows = euler_rows_of(h);
+  sc.pcl_rows = pcl_rows_of(h);
+  sc.icov64 = h->d_icov64.p;
+  sc.d2 = d2;
 }
 
 // The arithmetic a sweep runs in: 2 = tolerance arithmetic (MI355NDT_OPT_ARITH = 1; instantiated for DIRECT1 / DIRECT7 with the dead More-Thuente
 // loop -- every configuration lv_slam ships; the other searches and the live line search keep the exact kernels), else the f32 sum order.
 static int sweep_ord(const mi355ndt_handle* h, const SweepConst& sc) {
+  if (h->ndt_class == NDT_CLASS_PCL) return 0;    // (no three-term f32 sum in the f64 evaluation: MI355NDT_OPT_F32_SUM_ORDER moves no word)
   // (a stream's parent handle owns no grids: its contexts' engines build them, with the option as it stood at mi355ndt_stream_begin)
   if (fast_served(h) && (h->built.made.recs_fast || h->ss)) return 2;
   return h->f32_sum_order;
@@ -129,7 +135,14 @@ static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs 
     grid.x = (unsigned)std::max(1LL, std::min((long long)grid.x, (items + WAVES - 1) / WAVES));
     if (sc.rebase_block) grid.x += 1;              // + the workgroup that computes the next update's re-basing instead of sweeping
   }
-  if (h->pose_model == POSE_MODEL_EULER) {
+  if (h->ndt_class == NDT_CLASS_PCL) {             // pcl::NormalDistributionsTransform: one kernel -- the radius search, the f64 evaluation
+    if (sc.pca || h->fine_it || sc.K != 27 || !sc.pcl_rows || !sc.icov64 || !h->built.made.icov64 || !h->built.made.cent) {
+      h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_NDT_CLASS = 1";
+      return MI355NDT_ERR_UNSUPPORTED;
+    }
+    k_sweep<false, 27, SWEEP_IT_BATCH, false, 0, 2><<<grid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_partials,
+                                                                                           h->items_per_pair, h->d_active_list, ctl, ctl_next, sc, h->d_cent, h->d_grid_of_use);
+  } else if (h->pose_model == POSE_MODEL_EULER) {
     const int rc = launch_sweep_euler(h, sc, ord, grid, ctl, ctl_next);
     if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_POSE_MODEL = 1"; return rc; }
   } else if (!h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)

@@ -260,7 +260,9 @@ __device__ inline void euler_angles_012(const float G[16], float e[3]) {
 // with |angle| < 10e-5 takes c = 1, s = 0, the rows are cast to f32.
 #define EULER_ROWS 23
 #define EULER_ROW_WORDS (3 * EULER_ROWS)
-__device__ inline void euler_rows(const double p[6], float rows[EULER_ROW_WORDS]) {
+// (ROW = float: the rows the f32 computePointDerivatives reads; ROW = double: j_ang_a_ .. h_ang_f3_ as PCL's f64 overload reads them, impl.hpp:442-479)
+template <typename ROW>
+__device__ inline void euler_rows_as(const double p[6], ROW rows[EULER_ROW_WORDS]) {
   double cx, cy, cz, sx, sy, sz;
   if (fabs(p[3]) < 10e-5) { cx = 1.0; sx = 0.0; } else { cx = cos(p[3]); sx = sin(p[3]); }
   if (fabs(p[4]) < 10e-5) { cy = 1.0; sy = 0.0; } else { cy = cos(p[4]); sy = sin(p[4]); }
@@ -290,8 +292,10 @@ __device__ inline void euler_rows(const double p[6], float rows[EULER_ROW_WORDS]
     {(-cx * sz - sx * sy * cz), (-cx * cz + sx * sy * sz), 0},
     {(-sx * sz + cx * sy * cz), (-cx * sy * sz - sx * cz), 0}};
   for (int k = 0; k < EULER_ROWS; k++)
-    for (int a = 0; a < 3; a++) rows[3 * k + a] = (float)r[k][a];
+    for (int a = 0; a < 3; a++) rows[3 * k + a] = (ROW)r[k][a];
 }
+__device__ inline void euler_rows(const double p[6], float rows[EULER_ROW_WORDS]) { euler_rows_as<float>(p, rows); }
+__device__ inline void euler_rows64(const double p[6], double rows[EULER_ROW_WORDS]) { euler_rows_as<double>(p, rows); }
 
 // ---- exp of an f32 argument, evaluated in f64 and rounded to f32 (the canonical choice for impl2:581) ----------
 // Table-driven: x = n*ln2/64 + r, exp(x) = 2^(n>>6) * 2^((n&63)/64) * exp(r), |r| <= ln2/128, exp(r) - 1 by its degree-5 Taylor

@@ -35,10 +35,16 @@ __device__ __forceinline__ ndtm::SE3 shfl_se3(const ndtm::SE3& e, int src) {
 // PM = 1: ndt_omp_impl.hpp  -- p = [x y z roll pitch yaw], a step adds to it (impl.hpp:152), T = convertTransform(p) in f32 (impl.hpp:811-814),
 //         transformation_ = convertTransform(delta_p) (impl.hpp:146-149); whoever writes T writes the pair's 23 rows for the sweep that reads it
 //         (`rows`: the pair's slot of SweepConst::euler_rows).  Rj, reb_* and the re-basing are not used.
+//         `rows64` non-null (MI355NDT_OPT_NDT_CLASS = 1, PCL's f64 class): the rows are written as doubles there (SweepConst::pcl_rows) and
+//         `rows` is left alone -- the one difference the class makes on this side of the sweep.
+// the pair's rows at pose vector x, in the form its sweep reads
+__device__ __forceinline__ void write_pose_rows(const double x[6], float* rows, double* rows64) {
+  if (rows64) ndtm::euler_rows64(x, rows64); else ndtm::euler_rows(x, rows);
+}
 // The sweep pose of a pair from its pose vector
 template <int PM>
-__device__ __forceinline__ void pose_to_sweep(const double x[6], PairState& S, float* rows) {
-  if constexpr (PM == 1) { ndtm::euler_to_f32(x, S.T); ndtm::euler_rows(x, rows); }
+__device__ __forceinline__ void pose_to_sweep(const double x[6], PairState& S, float* rows, double* rows64 = nullptr) {
+  if constexpr (PM == 1) { ndtm::euler_to_f32(x, S.T); write_pose_rows(x, rows, rows64); }
   else ndtm::pose_to_f32(x, S.T, S.Rj);
 }
 // A step of length a_t along dir taken from p (PM = 1): pn = p + delta_p, inc = convertTransform(delta_p)
@@ -51,7 +57,8 @@ __device__ inline void euler_step(const double p[6], const double dir[6], const 
 // computeTransformation's set-up for one pair (impl2:102-129): p = log(guess), first sweep moves the cloud by the f32 guess itself
 // PM = 1 (impl.hpp:95-119): p = the f32 translation and f32 rotation().eulerAngles(0, 1, 2) of the guess, widened; the rows from that p
 template <int PM = 0>
-__device__ inline void init_pair_state(PairState& S, const float G[16] /* column-major */, int n_src, int grid_status, float* rows = nullptr) {
+__device__ inline void init_pair_state(PairState& S, const float G[16] /* column-major */, int n_src, int grid_status, float* rows = nullptr,
+                                       double* rows64 = nullptr) {
   double R[9], t[3];
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) { S.T[r * 4 + c] = G[c * 4 + r]; R[r * 3 + c] = (double)G[c * 4 + r]; }
@@ -64,7 +71,7 @@ __device__ inline void init_pair_state(PairState& S, const float G[16] /* column
     ndtm::euler_angles_012(G, e);
     for (int a = 0; a < 3; a++) { S.p[a] = t[a]; S.p[3 + a] = (double)e[a]; }
     for (int a = 0; a < 9; a++) S.Rj[a] = 0.f;
-    ndtm::euler_rows(S.p, rows);
+    write_pose_rows(S.p, rows, rows64);
   } else {
     ndtm::se3_log(ndtm::se3_from_Rt(R, t), S.p);
     float Tdummy[12];
@@ -268,7 +275,7 @@ template <int PM = 0>
 __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res, double step_max, double eps, int max_iterations, int mt,
                                              volatile double* sol = nullptr /* non-null: the solve comes from newton_solve_side */,
                                              const bool rebased = false /* S.reb_pn / S.reb_inc hold the re-basing of this step already */,
-                                             const bool score_only_last = false, float* rows = nullptr) {
+                                             const bool score_only_last = false, float* rows = nullptr, double* rows64 = nullptr) {
   double pn[6];
   float inc[16];
   const bool pre = PM == 0 && (mt == 0) && (S.phase == PH_STEP) && !rebased;     // wave-uniform: nothing has been written yet
@@ -355,7 +362,7 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     S.last_sweep = (mt == 0 && score_only_last && step_ends_pair(S.it, a_t, eps, max_iterations)) ? 1 : 0;
     S.phi0 = -S.score;                                                           // impl2:846
     S.dphi0 = dphi0 >= 0 ? -dphi0 : dphi0;                                       // impl2:849, 860
-    pose_to_sweep<PM>(xt, S, rows);                                              // impl2:900 / impl.hpp:811-821
+    pose_to_sweep<PM>(xt, S, rows, rows64);                                              // impl2:900 / impl.hpp:811-821
     pose_to_final(S);
     S.phase = PH_STEP;
     S.sweeps++;

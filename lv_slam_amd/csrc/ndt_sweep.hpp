@@ -196,6 +196,95 @@ __device__ __forceinline__ void eval_hit_euler(const float u_in[3], const float 
   }
 }
 
+// ------------------------------------------------------------------------------------ pcl::NormalDistributionsTransform (PM = 2)
+// MI355NDT_OPT_NDT_CLASS = 1: PCL's own class, which is impl.hpp with the f32 substitutions undone -- updateDerivatives in f64 from end to end
+// (the structure of impl.hpp:482-535, the terms updateHessian writes in f64 at impl.hpp:598-640) over the f64 computePointDerivatives
+// (impl.hpp:442-479).  u = the f32 moved point widened minus the leaf's f64 mean, C = the leaf's f64 inverse covariance (row-major; not assumed
+// symmetric), x = the ORIGINAL point widened, `rw` = the pair's 23 rows as doubles.
+//   e = d1 d2 exp(-d2 u'C u / 2), rejected as impl.hpp:504 rejects;  g_i += e u.(C J_i);
+//   H_ij += e (-d2 (u.C J_i)(u.C J_j) + u.(C Hp_ij) + J_j.(C J_i)), all 36 of them: nothing is mirrored, so the 43 sums keep the row layout and tree.
+// u.(C w) is evaluated as (u'C).w for every w (one row vector per hit instead of a matrix-vector product per term): the same number up to the
+// rounding of an f64 inner product, which is what the class is held to (1e-11 of the largest entry against tools/ndt_pcl_ref.py).  Inner products
+// are fused (fma): this body restates no f32 recipe whose roundings would have to be kept apart.
+// The eight Jacobian and fifteen Hessian-block entries depend on the point alone.  They are computed here, per hit, from x and the rows (69 scalar
+// loads + 69 f64 operations, about a fifth of a hit's arithmetic) and not once per point in phase A: staged, they would be 184 bytes a point,
+// 94 KB of LDS per workgroup at the two super-tile buffers of the K = 27 item -- more than two workgroups per CU can have.
+// The rows are wave-uniform and read through the constant address space: scalar loads on demand, no LDS, no vector register until an operation
+// needs the value as an operand.
+typedef const __attribute__((address_space(4))) double* PclRows;
+struct PclCtx { PclRows rows; const double* icov64; };     // the pair's rows; the f64 inverse covariances of the pair's target grid
+__device__ __forceinline__ PclRows pcl_rows_of_pair(const double* rows, const int b) {
+  return (PclRows)(unsigned long long)(rows + (size_t)__builtin_amdgcn_readfirstlane(b) * EULER_ROW_WORDS);
+}
+__device__ __forceinline__ double dot3(const double a0, const double b0, const double a1, const double b1, const double a2, const double b2) {
+  return fma(a2, b2, fma(a1, b1, a0 * b0));
+}
+template <typename Mid = NoHook>
+__device__ __forceinline__ void eval_hit_pcl(const double u_in[3], const float xf[3], const double C_in[9], const PclRows rw,
+                                             const double d1, const double d2, const bool ok_in, double acc[43], Mid mid = Mid()) {
+  double u[3] = {u_in[0], u_in[1], u_in[2]}, C[9];
+#pragma unroll
+  for (int a = 0; a < 9; a++) C[a] = C_in[a];
+  double uC[3];                                                                  // u' C
+#pragma unroll
+  for (int k = 0; k < 3; k++) uC[k] = dot3(u[0], C[k], u[1], C[3 + k], u[2], C[6 + k]);
+  const double e0 = exp(-d2 * dot3(uC[0], u[0], uC[1], u[1], uC[2], u[2]) / 2);
+  const double e1 = d2 * e0;
+  // (radiusSearch returns leaves without a usable inverse covariance as well: a rejected hit adds +0 to every sum, so its operands go first)
+  const bool ok = ok_in && !(e1 > 1.0 || e1 < 0.0 || e1 != e1);
+  const double e = ok ? e1 * d1 : 0.0;
+  acc[0] += ok ? -d1 * e0 : 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) { u[a] = ok ? u[a] : 0.0; uC[a] = ok ? uC[a] : 0.0; }
+#pragma unroll
+  for (int a = 0; a < 9; a++) C[a] = ok ? C[a] : 0.0;
+  const double x[3] = {(double)xf[0], (double)xf[1], (double)xf[2]};
+  // point_gradient_ columns 3..5: (0, xj0, xj1), (xj2, xj3, xj4), (xj5, xj6, xj7) (impl.hpp:446-453)
+  double xj[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) xj[k] = dot3(x[0], rw[3 * k], x[1], rw[3 * k + 1], x[2], rw[3 * k + 2]);
+  const double Jr[3][3] = {{0.0, xj[2], xj[5]}, {xj[0], xj[3], xj[6]}, {xj[1], xj[4], xj[7]}};   // rows of J's rotation columns
+  double v[6] = {uC[0], uC[1], uC[2], fma(uC[2], Jr[2][0], uC[1] * Jr[1][0]), dot3(uC[0], Jr[0][1], uC[1], Jr[1][1], uC[2], Jr[2][1]),
+                 dot3(uC[0], Jr[0][2], uC[1], Jr[1][2], uC[2], Jr[2][2])};
+#pragma unroll
+  for (int k = 0; k < 6; k++) acc[1 + k] = fma(e, v[k], acc[1 + k]);
+  // u.(C Hp_ij): the blocks are a b c / b d e / c e f (impl.hpp:460-477), a, b, c without a first component
+  double Z[3][3];
+  {
+    double xh[15];
+#pragma unroll
+    for (int k = 0; k < 15; k++) xh[k] = dot3(x[0], rw[24 + 3 * k], x[1], rw[24 + 3 * k + 1], x[2], rw[24 + 3 * k + 2]);
+    const double za = fma(uC[2], xh[1], uC[1] * xh[0]), zb = fma(uC[2], xh[3], uC[1] * xh[2]), zc = fma(uC[2], xh[5], uC[1] * xh[4]);
+    const double zd = dot3(uC[0], xh[6], uC[1], xh[7], uC[2], xh[8]), ze = dot3(uC[0], xh[9], uC[1], xh[10], uC[2], xh[11]);
+    const double zf = dot3(uC[0], xh[12], uC[1], xh[13], uC[2], xh[14]);
+    Z[0][0] = za; Z[0][1] = zb; Z[0][2] = zc; Z[1][0] = zb; Z[1][1] = zd; Z[1][2] = ze; Z[2][0] = zc; Z[2][1] = ze; Z[2][2] = zf;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  mid();
+  __builtin_amdgcn_sched_barrier(0);
+  // one row of H at a time: C J_i is three doubles that live for six terms (C J as a whole would be eighteen, for all thirty-six); the
+  // scheduling barrier between the rows keeps the compiler from interleaving them back into that
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    // C J_i: a column of C for a translation (J_i a unit vector); only the three rotation columns cost a product
+    double CJi[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+      CJi[a] = i < 3 ? C[a * 3 + i] : (i == 3 ? fma(C[a * 3 + 2], Jr[2][0], C[a * 3 + 1] * Jr[1][0])
+                                              : dot3(C[a * 3 + 0], Jr[0][i < 3 ? 0 : i - 3], C[a * 3 + 1], Jr[1][i < 3 ? 0 : i - 3], C[a * 3 + 2], Jr[2][i < 3 ? 0 : i - 3]));
+    const double dvi = -d2 * v[i];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      // J_j . (C J_i)
+      const int c = j < 3 ? 0 : j - 3;
+      double t = j < 3 ? CJi[j] : (j == 3 ? fma(Jr[2][0], CJi[2], Jr[1][0] * CJi[1]) : dot3(Jr[0][c], CJi[0], Jr[1][c], CJi[1], Jr[2][c], CJi[2]));
+      if (i >= 3 && j >= 3) t += Z[i - 3][j - 3];
+      acc[7 + i * 6 + j] = fma(e, fma(dvi, v[j], t), acc[7 + i * 6 + j]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // Score-only evaluation (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP): eval_hit's prefix and the same term added to the same accumulator, for the
 // last sweep of an align, whose gradient and Hessian are never read.
 template <bool PCA, int ORD = 0>
@@ -534,6 +623,7 @@ __device__ __forceinline__ T& item_lds() { __shared__ T v; return v; }
 // One batch of queued hits (one per lane): queue entry + the voxel record it points at, in registers.
 struct BatchX { unsigned slot; double m0, m1, m2; float C[9]; int weight; double w; };
 struct BatchF { unsigned slot; float mh[3], ml[3], c[6]; int weight; float w; };
+struct BatchD { unsigned slot; double m0, m1, m2; double C[9]; };            // PM = 2: the f64 mean and the f64 inverse covariance
 // `ent` / `qw` / `stage`: the wave's rows of the LDS queue (Q_CAP entries, a power of two), of its ndt_pca weights and of its staged points.
 // SO: hits are evaluated by eval_score / eval_score_fast (acc[0] alone).
 // W_LATE (ndt_pca, K = 1: the hit's weight is the leaf's own, read with its record): widen it when the batch is evaluated, not when it is
@@ -541,17 +631,20 @@ struct BatchF { unsigned slot; float mh[3], ml[3], c[6]; int weight; float w; };
 // widening at the fetch the pca / DIRECT1 headline lost 5 %, docs/experiments.md 10i); sweep_item widens at the fetch as it always did.
 // PM (MI355NDT_OPT_POSE_MODEL): 1 = hits are evaluated by eval_hit_euler -- the staged point's second half is the ORIGINAL point and `rw` the pair's
 // 23 rows (set by the item body; no member at all for PM = 0, whose kernels keep their register tables).
+// PM = 2 (MI355NDT_OPT_NDT_CLASS = 1, K = 27 alone): hits are evaluated by eval_hit_pcl -- the staged points as for PM = 1, `rw` the pair's rows as
+// doubles and the grid's f64 inverse covariances, which a batch fetches in place of the record's f32 ones.
 struct NoRows {};
 template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0>
 struct HitQueue {
-  static_assert(PM == 0 || (PM == 1 && !PCA && ORD != 2 && !SO), "the Euler model: ndt_omp, exact arithmetic, full rows");
-  typename std::conditional<PM == 1, EulerRows, NoRows>::type rw;
+  static_assert(PM == 0 || ((PM == 1 || PM == 2) && !PCA && ORD != 2 && !SO), "the Euler model: ndt_omp, exact arithmetic, full rows");
+  static_assert(PM != 2 || (K == 27 && ORD == 0), "PCL's class: the radius search, one instantiation");
+  typename std::conditional<PM == 1, EulerRows, typename std::conditional<PM == 2, PclCtx, NoRows>::type>::type rw;
   static constexpr bool KD = (K == 27), FAST = (ORD == 2), PCAQ = PCA && K > 1;
   static constexpr int NA = FAST ? NACC_F : 43;
   typedef typename std::conditional<FAST, float, double>::type AccT;
   // ndt_pca weight of a queued hit: the suffix product (f64: up to ~150^7) -- for DIRECT1 just the leaf's own integer weight
   typedef typename std::conditional<K == 1, int, AccT>::type QW;
-  typedef typename std::conditional<FAST, BatchF, BatchX>::type Batch;
+  typedef typename std::conditional<FAST, BatchF, typename std::conditional<PM == 2, BatchD, BatchX>::type>::type Batch;
   unsigned* const ent; QW* const qw; const float (*const stage)[6];
   const VoxelRec* const R; const SweepConst& sc; const double* const exp_tab;
   const int lane; const unsigned long long lt_mask;
@@ -594,6 +687,12 @@ struct HitQueue {
       if (!W_LATE) B.w = 1.f;
       if (PCAQ) B.w = (float)qw[(head + off + k) & (Q_CAP - 1)];
       else if (PCA && !W_LATE) B.w = (float)vr.weight;
+    } else if constexpr (PM == 2) {
+      const unsigned id = e & ((1u << ID_BITS) - 1);
+      const VoxelRec& vr = R[id];
+      B.m0 = vr.mean[0]; B.m1 = vr.mean[1]; B.m2 = vr.mean[2];
+#pragma unroll
+      for (int a = 0; a < 9; a++) B.C[a] = rw.icov64[(size_t)id * 9 + a];
     } else {
       const VoxelRec& vr = R[e & ((1u << ID_BITS) - 1)];
       B.m0 = vr.mean[0]; B.m1 = vr.mean[1]; B.m2 = vr.mean[2];
@@ -612,8 +711,12 @@ struct HitQueue {
     const float xt0 = sp[0], xt1 = sp[1], xt2 = sp[2];
     float r[3] = {sp[3], sp[4], sp[5]};
     // ndt_omp: leaves with nr_points = -1 (eigen / inverse failure) are not neighbours (impl:395): filtered here
-    const bool live = lane < m && (PCAQ || KD || B.weight != VOX_DEAD);
-    if constexpr (FAST) {
+    bool live = lane < m;
+    if constexpr (PM != 2) live = live && (PCAQ || KD || B.weight != VOX_DEAD);
+    if constexpr (PM == 2) {
+      const double u[3] = {(double)xt0 - B.m0, (double)xt1 - B.m1, (double)xt2 - B.m2};
+      eval_hit_pcl<Mid>(u, r, B.C, rw.rows, sc.d1, sc.d2, live, acc, mid);
+    } else if constexpr (FAST) {
       float u[3] = {(xt0 - B.mh[0]) - B.ml[0], (xt1 - B.mh[1]) - B.ml[1], (xt2 - B.mh[2]) - B.ml[2]};
       const float w = (W_LATE && !PCAQ) ? (PCA ? (float)B.weight : 1.f) : B.w;
       if constexpr (SO) { mid(); eval_score_fast<PCA>(u, B.c, sc.d1f, sc.d2f, sc.kq, w, live, acc[0]); }
@@ -639,7 +742,8 @@ struct HitQueue {
   // All full batches in the queue, software-pipelined: the next batch's record loads are issued in the middle of the
   // current batch's arithmetic (before its 36 Hessian terms), so their L2 latency is off the critical path.
   __device__ __forceinline__ void drain_full() {
-    if (!SweepTune<PCA, K, ORD>::PIPE) {           // plain: one batch after the other
+    // (PM = 2: the f64 evaluation is bound by its arithmetic, and the 25 registers of a second batch in flight are the ones it would spill)
+    if (PM == 2 || !SweepTune<PCA, K, ORD>::PIPE) {           // plain: one batch after the other
       while (count >= 64) drain(64);
       return;
     }
@@ -673,6 +777,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   static_assert(!SO || (ASYNC && !FINE), "score-only items belong to the one-launch align");
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
   static_assert(PM == 0 || (!PCA && !FAST && !ASYNC && !FINE && !SO), "the Euler model takes the lockstep rounds: ndt_omp, exact arithmetic, batch items");
+  static_assert(PM != 2 || (K == 27 && ORD == 0 && IT == 8), "PCL's class: the radius search, batch items");
   typedef SweepTune<PCA, K, ORD> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // ndt_pca's per-hit multiplier is the product of the hit's own weight and those of the point's LATER hits, known only in phase A.
@@ -715,7 +820,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
 #pragma unroll
     for (int a = 0; a < 12; a++) T[a] = S.T[a];
 #pragma unroll
-    for (int a = 0; a < 9; a++) Rj[a] = PM == 1 ? 0.f : S.Rj[a];               // (PM = 1: no Jacobian point, Rj is not read)
+    for (int a = 0; a < 9; a++) Rj[a] = PM != 0 ? 0.f : S.Rj[a];               // (PM = 1: no Jacobian point, Rj is not read)
   }
   const float leaf = g.leaf;
   const int mb0 = g.min_b[0], mb1 = g.min_b[1], mb2 = g.min_b[2];
@@ -726,6 +831,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
     Queue Q(acc, q_ent[wv], q_w[PCAQ ? wv : 0], stage[wv], R, sc, exp_tab, lane);
     // a work item belongs to one pair: a wave-uniform index, so the 69 floats come through the scalar cache
     if constexpr (PM == 1) Q.rw = euler_rows_of_pair(sc.euler_rows, b);
+    // (PM = 2: 69 doubles, too many to sit in scalar registers at once -- each is loaded where its operation needs it)
+    if constexpr (PM == 2) { Q.rw.rows = pcl_rows_of_pair(sc.pcl_rows, b); Q.rw.icov64 = sc.icov64 + (size_t)g.rec_off * 9; }
     const int wbase = rem * (IT * 64);
     if (wbase < n && grid_ok) {
       constexpr int NST = IT / TP;                            // super-tiles per item
@@ -763,7 +870,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           // a non-finite moved point (NaN pose: only reachable through a NaN More-Thuente trial value) has no neighbours;
           // the reference's float->int cast is undefined there
           ok = ok && finite3(xt[0], xt[1], xt[2]);
-          if constexpr (PM == 1) { const float xo[3] = {px, py, pz}; stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, xo); }
+          if constexpr (PM != 0) { const float xo[3] = {px, py, pz}; stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, xo); }
           else stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, r);
           kx[p] = xt[0]; ky[p] = xt[1]; kz[p] = xt[2];
           // Branch-free probe stage.  Relative cell r = c - min_b; "inside the grid" (impl:382-392) is one unsigned

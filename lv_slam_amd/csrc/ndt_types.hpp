@@ -115,6 +115,11 @@ struct SweepConst {
   // MI355NDT_OPT_POSE_MODEL = 1 only (else null): 69 floats per pair slot, the 8 rows of j_ang and the 15 of h_ang at the pose of the pair's pending
   // sweep (ndtm::euler_rows).  An array of its own: the pose words of PairState stay where the one-launch align fetches them.
   const float* euler_rows;
+  // MI355NDT_OPT_NDT_CLASS = 1 only (else null / unset): the same 23 rows as doubles (ndtm::euler_rows64), 69 per pair slot, the f64 inverse
+  // covariances of the leaves (9 doubles a record, beside d_recs) and gauss_d2_ unrounded.
+  const double* pcl_rows;
+  const double* icov64;
+  double d2;
 };
 
 // Neighbour offsets in the reference's probe order.  DIRECT1: voxel_grid_covariance_omp_impl.hpp:441;

@@ -11,12 +11,14 @@
 // p = SE3(R,t).log(); first sweep moves the cloud by the caller's f32 guess itself (impl2:102-129)
 // euler_rows: non-null = MI355NDT_OPT_POSE_MODEL 1 (impl.hpp:95-119), the pairs' row slots
 NDT_KERNEL void k_init_state(PairState* st, const float* __restrict__ guess_cm, const int* __restrict__ src_cnt,
-                             const GridDesc* __restrict__ gd, int n_pairs, int* active_list, SweepCtl* ctl, float* euler_rows) {
+                             const GridDesc* __restrict__ gd, int n_pairs, int* active_list, SweepCtl* ctl, float* euler_rows,
+                             double* pcl_rows /* non-null: MI355NDT_OPT_NDT_CLASS 1, the rows as doubles */) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n_pairs) return;
   active_list[b] = b;                            // the first sweep covers every pair
   if (b == 0) ctl->n_active = n_pairs;
-  if (euler_rows) init_pair_state<1>(st[b], guess_cm + (size_t)b * 16, src_cnt[b], gd[b].status, euler_rows + (size_t)b * EULER_ROW_WORDS);
+  if (euler_rows) init_pair_state<1>(st[b], guess_cm + (size_t)b * 16, src_cnt[b], gd[b].status, euler_rows + (size_t)b * EULER_ROW_WORDS,
+                                     pcl_rows ? pcl_rows + (size_t)b * EULER_ROW_WORDS : nullptr);
   else init_pair_state(st[b], guess_cm + (size_t)b * 16, src_cnt[b], gd[b].status);
 }
 
@@ -31,12 +33,12 @@ NDT_KERNEL void k_set_pose(PairState* st, int b, const float* __restrict__ T_cm,
 }
 // euler_rows: non-null = MI355NDT_OPT_POSE_MODEL 1, p = [t; roll pitch yaw]: the cloud is moved by convertTransform(p), the rows are taken from p
 NDT_KERNEL void k_set_pose_p(PairState* st, int b, const double* __restrict__ p, const int* __restrict__ src_cnt, const GridDesc* __restrict__ gd,
-                             int* active_list, SweepCtl* ctl, int for_hessian, float* euler_rows) {
+                             int* active_list, SweepCtl* ctl, int for_hessian, float* euler_rows, double* pcl_rows) {
   PairState& S = st[b];
   active_list[0] = b; ctl->n_active = 1;
   double pp[6];
   for (int a = 0; a < 6; a++) { pp[a] = p[a]; S.xt[a] = p[a]; }
-  if (euler_rows) pose_to_sweep<1>(pp, S, euler_rows + (size_t)b * EULER_ROW_WORDS);
+  if (euler_rows) pose_to_sweep<1>(pp, S, euler_rows + (size_t)b * EULER_ROW_WORDS, pcl_rows ? pcl_rows + (size_t)b * EULER_ROW_WORDS : nullptr);
   else pose_to_sweep<0>(pp, S, nullptr);
   S.phase = for_hessian ? PH_HESS : PH_SWEEP0; S.n_src = src_cnt[b]; S.grid_status = gd[b].status; S.it = 0; S.sweeps = 1; S.last_sweep = 0;
 }
@@ -201,7 +203,7 @@ template <bool SC1, bool STATE_FIRST, int PM = 0>
 __device__ __forceinline__ int update_block(const PairState* Sg, PairState& S, double (*sm)[NACC], volatile double* sol, const double* __restrict__ rows, int n_src,
                                             const int pts_per_chunk, const bool chunk_rows, mi355ndt_result* res, unsigned long long* hits_total,
                                             const double step_max, const double eps, const int max_iterations, const int reduce_only, const int mt, Timeline* tl,
-                                            float* pose_rows = nullptr) {
+                                            float* pose_rows = nullptr, double* pose_rows64 = nullptr) {
   state_to_lds<SC1>(S, Sg, threadIdx.x, UPD_THREADS);
   if (threadIdx.x == 0) sol[6] = 0.0;
   if (STATE_FIRST) {
@@ -225,21 +227,23 @@ __device__ __forceinline__ int update_block(const PairState* Sg, PairState& S, d
   if (reduce_only) return NEWTON_DONE;
   // (latency mode: the re-basing of p for this step was computed under the sweep, by its extra workgroup -- ndt_sweep.hpp; the tag says so)
   const bool rebased = mt == 0 && S.phase == PH_STEP && S.reb_tag == (long long)S.sweeps;
-  return newton_update<PM>(S, res, step_max, eps, max_iterations, mt, mt == 0 ? sol : nullptr, PM == 0 && rebased, false, pose_rows);
+  return newton_update<PM>(S, res, step_max, eps, max_iterations, mt, mt == 0 ? sol : nullptr, PM == 0 && rebased, false, pose_rows, pose_rows64);
 }
 
 // One block per pair.  `rows_per_pair` = stored rows per pair (the row stride).
 NDT_KERNEL void __launch_bounds__(UPD_THREADS, 2)
 k_update(PairState* st, const double* __restrict__ partials, int rows_per_pair, int pts_per_chunk, int chunk_rows, mi355ndt_result* results,
          int* active_counter, int* active_list, SweepCtl* ctl, unsigned long long* hits_total,
-         double step_max, double eps, int max_iterations, int reduce_only, int mt, float* euler_rows /* non-null: MI355NDT_OPT_POSE_MODEL 1 */) {
+         double step_max, double eps, int max_iterations, int reduce_only, int mt, float* euler_rows /* non-null: MI355NDT_OPT_POSE_MODEL 1 */,
+         double* pcl_rows /* non-null (with euler_rows): MI355NDT_OPT_NDT_CLASS 1 */) {
   __shared__ double sm[UPD_WAVES][NACC];
   __shared__ double sol[SOL_WORDS];
   __shared__ PairState S;
   const int b = blockIdx.x;
   const int rc = euler_rows
       ? update_block<false, true, 1>(&st[b], S, sm, sol, partials + (size_t)b * rows_per_pair * NACC, 0, pts_per_chunk, chunk_rows != 0, &results[b], hits_total,
-                                     step_max, eps, max_iterations, reduce_only, mt, nullptr, euler_rows + (size_t)b * EULER_ROW_WORDS)
+                                     step_max, eps, max_iterations, reduce_only, mt, nullptr, euler_rows + (size_t)b * EULER_ROW_WORDS,
+                                     pcl_rows ? pcl_rows + (size_t)b * EULER_ROW_WORDS : nullptr)
       : update_block<false, true>(&st[b], S, sm, sol, partials + (size_t)b * rows_per_pair * NACC, 0, pts_per_chunk, chunk_rows != 0, &results[b], hits_total,
                                   step_max, eps, max_iterations, reduce_only, mt, nullptr);
   if (rc == UPD_EXIT) return;

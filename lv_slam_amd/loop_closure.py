@@ -108,6 +108,15 @@ def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range
     return select_matching_and_bow(converged, scores, finals, bow, thresh)
 
 
+def verify_candidates_ndt(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
+    """verify_candidates for registration_method = NDT (pcl::NormalDistributionsTransform, the factory's fall-back): the same arguments, the
+    same tuple, on an engine whose MI355NDT_OPT_NDT_CLASS is 1 (registrations.select_registration_method makes one).  The batch surface serves
+    the class as it serves ndt_omp, so this is verify_candidates itself; the check only keeps a class-0 engine from answering for NDT."""
+    if engine.get_option(ndt.OPT_NDT_CLASS) != ndt.NDT_CLASSES["pcl"]:
+        raise ValueError("verify_candidates_ndt needs an engine with OPT_NDT_CLASS = 1")
+    return verify_candidates(engine, target, candidates, guesses, max_range, thresh, bow)
+
+
 def verify_candidates_gicp(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
     """verify_candidates for registration_method = GICP_OMP: the same arguments, the same tuple.  The target becomes the GICP surface's
     target, candidate k the source of slot k of ONE gicp_batch_align (the K optimisers advance in lockstep: mi355ndt_gicp_batch_align),

@@ -173,6 +173,8 @@ OPT_OUTLIER_CELL_MM = 10       # mi355ndt_option: cell size [mm] of the index pr
 OPT_PREFILTER_GROUP = 11      # mi355ndt_option: raw clouds per group of batch_prefilter (0, the default: by the engine's scratch budget); no result word depends on it
 OPT_POSE_MODEL = 12           # mi355ndt_option: 0 (default) = ndt_omp_impl2.hpp, the SE(3) tangent; 1 = ndt_omp_impl.hpp, the Euler-angle pose model (lockstep rounds, ndt_omp, dead More-Thuente)
 POSE_MODELS = {"se3": 0, "euler": 1}
+OPT_NDT_CLASS = 13            # mi355ndt_option: 0 (default) = pclomp::NormalDistributionsTransform; 1 = pcl::NormalDistributionsTransform, PCL's f64 class (registration_method = NDT): radius search, Euler pose vector, f64 evaluation
+NDT_CLASSES = {"omp": 0, "pcl": 1}
 PREFILTER_EXTENDED = 0x50467832  # MI355NDT_PREFILTER_EXTENDED: PrefilterParams.extended of the base of a PrefilterParamsEx
 DOWNSAMPLE_VOXELGRID = 0       # pcl::VoxelGrid, the prefiltering nodelet's default downsample_method
 DOWNSAMPLE_APPROX_VOXELGRID = 1  # pcl::ApproximateVoxelGrid
@@ -1250,15 +1252,35 @@ class NormalDistributionsTransform:
     pose_model="se3" (default) is include/ndt_omp/ndt_omp_impl2.hpp, the implementation lv_slam compiles; pose_model="euler" is
     include/ndt_omp/ndt_omp_impl.hpp, the Euler-angle NDT a host gets by changing the include line of src/ndt_omp/ndt_omp.cpp
     (mi355ndt_set_option(MI355NDT_OPT_POSE_MODEL, 1): variant OMP, step_size > trans_epsilon / 2).
+
+    ndt_class="omp" (default) is pclomp's class; ndt_class="pcl" is pcl::NormalDistributionsTransform, the class select_registration_method
+    hands out for registration_method = NDT (mi355ndt_set_option(MI355NDT_OPT_NDT_CLASS, 1)): the Euler pose vector, the radius search and an
+    f64 evaluation.  PCL's class has neither setNeighborhoodSearchMethod nor setNumThreads, and neither has this object then.
     """
 
-    def __init__(self, variant: int = VARIANT_OMP, device: int = 0, pose_model: str = "se3"):
+    _NOT_IN_PCL = ("setNeighborhoodSearchMethod", "setNumThreads")
+
+    def __getattribute__(self, name):
+        if name in NormalDistributionsTransform._NOT_IN_PCL and object.__getattribute__(self, "__dict__").get("_ndt_class") == "pcl":
+            raise AttributeError(f"pcl::NormalDistributionsTransform has no {name}")
+        return object.__getattribute__(self, name)
+
+    def __init__(self, variant: int = VARIANT_OMP, device: int = 0, pose_model: str = "se3", ndt_class: str = "omp", engine: "Engine | None" = None):
         if pose_model not in POSE_MODELS:
             raise ValueError(f"pose_model must be one of {sorted(POSE_MODELS)}")
+        if ndt_class not in NDT_CLASSES:
+            raise ValueError(f"ndt_class must be one of {sorted(NDT_CLASSES)}")
+        self._ndt_class = ndt_class
         self._prm = default_params(variant=variant)           # ctor defaults, ndt_omp_impl2.hpp:53-83
-        self._eng = Engine(self._prm, device)
+        if engine is None:
+            self._eng = Engine(self._prm, device)
+        else:                                                 # an engine the caller shares with other surfaces (its keyframe store, its stream)
+            self._eng = engine
+            self._eng.set_params(self._prm)
         if POSE_MODELS[pose_model]:
             self._eng.set_option(OPT_POSE_MODEL, POSE_MODELS[pose_model])
+        if NDT_CLASSES[ndt_class]:
+            self._eng.set_option(OPT_NDT_CLASS, NDT_CLASSES[ndt_class])
         self._final = np.eye(4, dtype=np.float32)
         self._converged = False
         self._nr_iterations = 0

@@ -110,8 +110,13 @@ typedef struct mi355ndt_profile {
   long long cloud_transfers;  /* host-to-device transfers those clouds travelled in (mi355ndt_batch_set_clouds / stream_submit_host send up to eight clouds per transfer) */
   long long cloud_promotions; /* mi355ndt_promote_source_to_target calls (device-to-device instead of an upload) */
   long long stream_reserved_slots; /* stream mode: workgroup slots the persistent launches leave to the next batch's build (the effective MI355NDT_OPT_STREAM_RESERVE; 0 = the build runs between the launches) */
-  long long stream_launch_slots;   /* stream mode: workgroups of one persistent launch (CUs x workgroups per CU - the reserved slots) */
+  long long stream_launch_slots;   /* stream mode: workgroups of one persistent launch (CUs x workgroups per CU - the reserved slots).  Both: of the last launch that
+                                      started a batch; before the first launch, what mi355ndt_stream_begin sized the session for (two workgroups per CU in the exact
+                                      arithmetic -- a launch that takes the three-wave body, MI355NDT_OPT_SWEEP_WAVES, reports its own 768-slot geometry) */
   long long score_only_sweeps;     /* sweeps of the one-launch align that evaluated the score alone (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) */
+  long long async_waves_per_simd;  /* the last persistent launch (one-launch align or stream launch; 0: none yet): waves per SIMD its kernel is built for
+                                      (2; 3 = the lean exact DIRECT7 body, MI355NDT_OPT_SWEEP_WAVES; 3 / 4 in the tolerance arithmetic) ... */
+  long long async_launch_slots;    /* ... and the workgroups it was launched with (CUs x waves per SIMD - the stream's reserved slots); not cleared by a reset */
 } mi355ndt_profile;
 
 typedef struct mi355ndt_handle mi355ndt_handle;
@@ -222,7 +227,8 @@ enum mi355ndt_option {
    * and the NEXT batch's target build runs on a stream of its own beside the launch instead of between two launches -- the build streams
    * through HBM, the launch saturates the vector ALUs.  Needs >= 3 contexts (a context is rebuilt one launch earlier, so its pairs are carried
    * through one launch less).  -1 (default): the environment variable MI355NDT_STREAM_RESERVE, else for DIRECT1 128 with clouds of up to 98,304 points and 96 beyond (launches that
-   * wait for their point stream leave the vector ALUs to the build: +5-10 %), for DIRECT7 with batches of up to 768 x 65,536 target points 64 (ndt_omp) / 32 (ndt_pca)
+   * wait for their point stream leave the vector ALUs to the build: +5-10 %), for DIRECT7 with batches of up to 768 x 65,536 target points 64 (ndt_omp; 96 of 768 slots where the launch runs
+   * the three-wave body, MI355NDT_OPT_SWEEP_WAVES) / 32 (ndt_pca)
    * (the launch pays for the slots in full, the whole build disappears under it: +4-6 % at 271 pairs, +22 % at 64) and 0 = off for every other search.  No result bit depends on it. */
   MI355NDT_OPT_STREAM_RESERVE = 5,
   /* Test hook, default 0xFF (off).  Bit x clear: the workgroups of a one-launch align that serve ring x leave at once, as if XCD x held no
@@ -283,7 +289,16 @@ enum mi355ndt_option {
    * the option while a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  A target that is resident without centroids
    * or f64 inverse covariances is rebuilt by the next align.  PCL's single-threaded GeneralizedIterativeClosestPoint (registration_method = GICP)
    * stays unserved. */
-  MI355NDT_OPT_NDT_CLASS = 13
+  MI355NDT_OPT_NDT_CLASS = 13,
+  /* Waves per SIMD of the exact (MI355NDT_OPT_ARITH = 0) ndt_omp / DIRECT7 item body in the one-launch align and the stream's launches.  2: the
+   * body with the mid-evaluation record prefetch and two-tile probe groups (245 VGPRs).  3: the lean body (168 VGPRs, no prefetch, one tile
+   * probed at a time), 768 instead of 512 workgroup slots.  0 (default): decided per launch on the host -- three waves where the records of
+   * the pairs in flight stay L2-resident, by an estimate from the leaf size and the points per target (ndt_host_sweep.hpp: async_lean), else
+   * two.  Every other configuration (ndt_pca, DIRECT1, DIRECT26, KDTREE, the tolerance arithmetic, the lockstep rounds, the Euler model,
+   * MI355NDT_OPT_NDT_CLASS = 1) ignores the option.  No result word depends on it: both bodies write the same rows bit for bit.  Setting it while
+   * a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  The environment variable MI355NDT_SWEEP_WAVES sets the
+   * default for engines created afterwards.  mi355ndt_profile.async_waves_per_simd reports what the last launch took. */
+  MI355NDT_OPT_SWEEP_WAVES = 14
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);
@@ -301,6 +316,13 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
  * i.e. the first sweep of align() where the cloud is moved by the caller's guess (impl2:102-129) */
 int mi355ndt_derivatives_T(mi355ndt_handle* h, const float T_colmajor[16], const float Rj_rowmajor[9],
                            double* score, double g[6], double H[36], long long* hits);
+/* The partial rows the last sweep of every pair of the bound batch left on the device: per pair *rows_per_pair rows of 44 doubles (score, g[6],
+ * H[36] row-major, hits) -- one row per work item of 512 source points in batch mode --, pair after pair, `capacity` doubles at the most
+ * (MI355NDT_ERR_BAD_ARG when the rows need more; `out` may be NULL to ask for *rows_per_pair alone).  A row's bits depend on the pair, the pose
+ * and the input order alone: never on the kernel, the launch geometry or the wave that ran the item.  A score-only last sweep
+ * (MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) writes a row's score and hits and leaves the sweep before it in the other 42 words.
+ * MI355NDT_ERR_STATE before the first align of the batch, and in stream mode. */
+int mi355ndt_get_partial_rows(mi355ndt_handle* h, double* out, size_t capacity, int* rows_per_pair);
 /* target grid of pair `pair`: bounds (min_b_, max_b_, div_b_) and searchable voxels in ascending idx order */
 int mi355ndt_get_grid(mi355ndt_handle* h, int pair, int min_b[3], int max_b[3], int div_b[3], int* n_voxels);
 int mi355ndt_get_voxels(mi355ndt_handle* h, int pair, mi355ndt_voxel* out, size_t capacity);

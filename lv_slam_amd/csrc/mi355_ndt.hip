@@ -72,6 +72,7 @@
 #include "ndt_async.hpp"
 #include "ndt_hostmem.hpp"
 #include "ndt_grid_state.hpp"
+#include "ndt_sweep_waves.hpp"
 #ifndef NDT_SINGLE_TU      // the ORD = 1 instantiations come from mi355_ndt_ord1.hip (built side by side with this file)
 #include "ndt_ord1_list.hpp"
 #include "ndt_fast_list.hpp"

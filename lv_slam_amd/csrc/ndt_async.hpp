@@ -279,8 +279,9 @@ NDT_KERNEL void k_stream_status(const AsyncCtl* __restrict__ ctl, const CtxStat*
 #define NDT_CTX_PARAMS(i) const float* __restrict__ src##i, size_t pitch##i, PairState* st##i, const GridDesc* __restrict__ gd##i, const BitWord* __restrict__ words##i, \
                           const VoxelRec* __restrict__ recs##i, double* partials##i, const int* __restrict__ src_cnt##i, unsigned* arrived##i, const float* __restrict__ cent##i
 #define NDT_CTX_SEL(f, ci) ((ci) == 0 ? f##0 : (ci) == 1 ? f##1 : (ci) == 2 ? f##2 : f##3)
-template <bool PCA, int K, int ORD>
-__global__ void __launch_bounds__(SWEEP_THREADS, (SweepTune<PCA, K, ORD>::WPE))
+// LEAN: the exact ndt_omp / DIRECT7 item body at three waves per SIMD (SweepTune, ndt_sweep.hpp); the host picks it per launch (async_lean).
+template <bool PCA, int K, int ORD, bool LEAN = false>
+__global__ void __launch_bounds__(SWEEP_THREADS, (SweepTune<PCA, K, ORD, LEAN>::WPE))
 k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, int ring_cap, AsyncCtl* ctl, SweepConst sc, unsigned long long* hits_total,
               double step_max, double eps, int max_iterations, int stop_thresh, unsigned debug_abort_pos, unsigned debug_ring_mask, int claim_items,
               NDT_CTX_PARAMS(0), NDT_CTX_PARAMS(1), NDT_CTX_PARAMS(2), NDT_CTX_PARAMS(3)) {
@@ -398,7 +399,7 @@ k_align_async(const AsyncTab* __restrict__ tab, int items_per_pair, int* ring, i
       } else {
 #pragma unroll 1
         for (int k = 0; k < CLAIM; k++)
-          sweep_item<PCA, K, 8, false, ORD, true, SO>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b, tl);
+          sweep_item<PCA, K, 8, false, ORD, true, SO, 0, LEAN>(b, rem + k, C.src, C.pitch, C.st, C.gd, C.words, C.recs, C.partials, I, sc, C.cent, nullptr, exp_tab, pose_w, n_b, b, tl);
       }
     };
     if (last) items(std::true_type()); else items(std::false_type());

@@ -198,19 +198,26 @@ __global__ void __launch_bounds__(256) k_mark(const KeyT* __restrict__ keys, siz
   if (lane == 0) head_cnt[(size_t)b * n_slices + q] = n;
 }
 // exclusive popcount prefix over the bitmap words of each target: voxel id = rank in ascending cell order.
-// One block of 16 waves per target; per round a wave owns 512 consecutive words as eight rows of 64 (lane = word: coalesced 16-byte
-// accesses), scans every row with shuffles and carries the row totals along; the 16 wave totals go through one small LDS scan.
-// A 0.5 m grid of ~21 k words takes 3 rounds.
+// One block of RANK_WAVES waves per target; per round a wave owns 512 consecutive words as eight rows of 64 (lane = word: coalesced 16-byte
+// accesses), scans every row with shuffles and carries the row totals along; the wave totals go through one small LDS scan.
+// A 0.5 m grid of ~21 k words takes 6 rounds.
+// Eight waves, not sixteen: a block then needs two waves per SIMD, 128 registers, and fits beside two resident workgroups of the lean one-launch
+// align (3 x 168 registers per SIMD, ndt_sweep.hpp: SweepTune) when the stream builds under a launch.  As sixteen waves of 61 registers it
+// needed 256 per SIMD: half a CU, which the two-wave launch's reserved slots are and the three-wave launch's are not -- the build then stood
+// still at this kernel until the launch ended (docs/experiments.md 10o).  Alone the kernel is no slower for it (35 us for 271 targets at 1 m, 42 before).
 #define RANK_ROWS 8
-__global__ void __launch_bounds__(1024) k_rank(GridDesc* gd, BitWord* words, const unsigned* __restrict__ heads, const unsigned* __restrict__ head_cnt,
-                                                 unsigned n_slices, unsigned slice_cap, unsigned* seg_start) {
+#define RANK_WAVES 8
+#define RANK_THREADS (64 * RANK_WAVES)
+__global__ void __launch_bounds__(RANK_THREADS) k_rank(GridDesc* gd, BitWord* words, const unsigned* __restrict__ heads, const unsigned* __restrict__ head_cnt,
+                                                         unsigned n_slices, unsigned slice_cap, unsigned* seg_start) {
   __shared__ unsigned wtot[17];
+  static_assert(RANK_WAVES <= 16, "wtot");
   const int b = blockIdx.x;
   BitWord* W = words + gd[b].word_off;
   const int nw = gd[b].nwords;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned base = 0;
-  for (int w0 = 0; w0 < nw; w0 += 1024 * RANK_ROWS) {
+  for (int w0 = 0; w0 < nw; w0 += RANK_THREADS * RANK_ROWS) {
     const int wbase = w0 + wv * 64 * RANK_ROWS;
     unsigned c[RANK_ROWS], ex[RANK_ROWS], run = 0;
 #pragma unroll
@@ -226,12 +233,12 @@ __global__ void __launch_bounds__(1024) k_rank(GridDesc* gd, BitWord* words, con
     if (lane == 0) wtot[wv] = run;
     __syncthreads();
     if (wv == 0) {
-      const unsigned v = lane < 16 ? wtot[lane] : 0u;
+      const unsigned v = lane < RANK_WAVES ? wtot[lane] : 0u;
       unsigned inc = v;
 #pragma unroll
-      for (int o = 1; o < 16; o <<= 1) { const unsigned t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-      if (lane < 16) wtot[lane] = inc - v;
-      if (lane == 15) wtot[16] = inc;
+      for (int o = 1; o < RANK_WAVES; o <<= 1) { const unsigned t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+      if (lane < RANK_WAVES) wtot[lane] = inc - v;
+      if (lane == RANK_WAVES - 1) wtot[16] = inc;
     }
     __syncthreads();
     const unsigned off = base + wtot[wv];
@@ -244,11 +251,11 @@ __global__ void __launch_bounds__(1024) k_rank(GridDesc* gd, BitWord* words, con
   // run start of voxel id = the id-th head of the target's slices (k_mark): exclusive scan of the slice counts, then every thread moves
   // the few heads of its slice
   unsigned hbase = 0;
-  for (unsigned q0 = 0; q0 < n_slices; q0 += 1024) {
+  for (unsigned q0 = 0; q0 < n_slices; q0 += RANK_THREADS) {
     const unsigned q = q0 + threadIdx.x;
     const unsigned c = q < n_slices ? head_cnt[(size_t)b * n_slices + q] : 0u;
     unsigned tot;
-    const unsigned ex = block_exscan<1024>(c, &tot, wtot);
+    const unsigned ex = block_exscan<RANK_THREADS>(c, &tot, wtot);
     const unsigned* H = heads + ((size_t)b * n_slices + q) * slice_cap;
     unsigned* S = seg_start + gd[b].rec_off + hbase + ex;
     for (unsigned k = 0; k < c; k++) S[k] = H[k];

@@ -43,6 +43,9 @@ struct StreamState {
   // Build under the launch: with reserve_wg > 0 the contexts' engines run their builds on build_stream, the persistent launches leave
   // that many workgroup slots free, and events order  launch j-2 done -> build of batch j -> launch j
   HipStream build_stream; int reserve_wg = 0, launch_slots = 0;
+  bool lean = false;                            // the last launch ran the lean item body (three waves per SIMD; decided per launch: stream_launch)
+  bool reserve_given = false;                   // MI355NDT_OPT_STREAM_RESERVE or MI355NDT_STREAM_RESERVE named the reserve (else the defaults, per geometry)
+  int last_reserve = 0, last_slots = 0;         // reserved slots and workgroups of the last launch that started a batch (before the first: the session's sizing)
   HipEvent ev_built[ASYNC_MAX_CTX], ev_launched[EV], ev_prepared[EV]; bool prep_first = true;
   PinBuf<volatile StreamStatus> h_status; StreamStatus* d_status = nullptr;   // mapped ring of per-launch status slots (k_stream_status); d_status: the device's view
   StreamCtx ctx[ASYNC_MAX_CTX];                 // (last: the contexts' engines are released before the stream they run on)
@@ -225,6 +228,8 @@ struct mi355ndt_handle {
   DevBuf<AsyncTab> d_atab;                        // the launch's context table (ndt_async.hpp)
   unsigned debug_abort_pos = 0xFFFFFFFFu;         // MI355NDT_OPT_DEBUG_ASYNC_ABORT (test hook): the wave that claims this position of ring 0 gives up
   unsigned debug_ring_mask = 0xFFu;               // MI355NDT_OPT_DEBUG_ASYNC_RINGS (test hook): rings whose workgroups take part
+  int sweep_waves = 0;                            // MI355NDT_OPT_SWEEP_WAVES: 0 = automatic (async_lean, ndt_host_sweep.hpp), 2, 3
+  int last_async_wpe = 0, last_async_grid = 0;    // the last persistent launch: its kernel's waves per SIMD, its workgroups (mi355ndt_profile)
   int arith = 0;                                  // MI355NDT_OPT_ARITH: 0 = the reference recipe's arithmetic, one rounding per operation; 1 = tolerance arithmetic (ndt_sweep.hpp: eval_hit_fast)
   DevBuf<VoxelRecF> d_recs_fast;                  // ... and the records its sweeps read (k_voxels writes them beside d_recs)
   int pose_model = 0;                             // MI355NDT_OPT_POSE_MODEL: 0 = ndt_omp_impl2.hpp (SE(3) tangent), 1 = ndt_omp_impl.hpp (Euler angles; ndt_grid_state.hpp says what it serves)
@@ -405,4 +410,5 @@ static bool async_served(const mi355ndt_handle* h) { return h->async_align && !m
 static double sweep_alg_bytes(double points, int K) { return points * (12.0 + 4.0 * K); }
 // resident workgroup slots of a sweep launch or a persistent launch; `fast`: the tolerance arithmetic's kernels serve it.  (Callers decide
 // `fast` by sweep_ord(...) == 2 or by fast_served(h); the two differ before the fast records are built: ndt_host_sweep.hpp, sweep_ord.)
-static int launch_slots(const mi355ndt_handle* h, const SweepConst& sc, bool fast) { return h->n_cu * sweep_wpe(sc.K, fast); }
+// `lean`: a persistent launch of the lean item body (async_lean, ndt_host_sweep.hpp): three slots per CU.
+static int launch_slots(const mi355ndt_handle* h, const SweepConst& sc, bool fast, bool lean = false) { return h->n_cu * sweep_wpe(sc.K, fast, lean); }

@@ -82,7 +82,7 @@ static int finish_align(mi355ndt_handle* h, const SweepConst& sc, int B, mi355nd
   return MI355NDT_OK;
 }
 
-static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt_result* out) {
+static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt_result* out, bool lean) {
   const int ring_cap = async_ring_cap(h, B);
   if (ring_cap == 0) return MI355NDT_ERR_UNSUPPORTED;
   // (a ring that cannot be allocated is no error of the align: the round-based path needs none)
@@ -101,6 +101,7 @@ static int align_async(mi355ndt_handle* h, const SweepConst& sc, int B, mi355ndt
   L.active_list = h->d_active_list; L.sweep_ctl = h->d_ctl;
   L.tab_dev = h->d_atab; L.ring = h->d_ring; L.ring_cap = ring_cap; L.ctl = h->d_actl; L.prev = nullptr;
   L.items_per_pair = h->items_per_pair; L.stop_thresh = 0; L.debug_abort_pos = h->debug_abort_pos; L.debug_ring_mask = h->debug_ring_mask;
+  L.lean = lean;
   int rc = launch_async(h, sc, L);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(h->h_pin_actl, h->d_actl, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));   // pub, fin, abort_, n_live, susp
@@ -129,9 +130,13 @@ static int batch_align_impl(mi355ndt_handle* h, const float* guesses, mi355ndt_r
   // One launch for the whole align (ndt_async.hpp) when the batch offers more work items than the GPU has resident waves.  A smaller batch
   // -- a single registration above all -- keeps the round-based kernels, whose flat dealing spreads a pair's items over every XCD: a ticket
   // is served by ONE ring (an eighth of the waves), which costs a lone 65,536-point pair 0.39 ms against 0.31 ms per align.
+  // (two or three waves per SIMD: decided here, once per launch, from the batch's largest target -- async_lean, ndt_host_sweep.hpp)
+  const int tgt_max = *std::max_element(h->h_tgt_cnt.begin(), h->h_tgt_cnt.begin() + B);
+  const bool lean = async_lean(h, sc, sweep_ord(h, sc), tgt_max > 0 ? (size_t)tgt_max : h->tgt_pitch);   // (counts the host never saw: the rows' pitch bounds them)
+  // (which path a batch takes does not follow that choice: "more work items than resident waves" is asked of the geometry every configuration has)
   const bool big_batch = (long long)B * h->items_per_pair > (long long)launch_slots(h, sc, sweep_ord(h, sc) == 2) * WAVES;
   if (async_served(h) && (big_batch || h->async_force) && !h->fine_it) {
-    rc = align_async(h, sc, B, out);                                // (prepares the pair states itself: k_async_prepare)
+    rc = align_async(h, sc, B, out, lean);                                // (prepares the pair states itself: k_async_prepare)
     if (rc != MI355NDT_ERR_UNSUPPORTED) return rc;                  // done, or failed.  (Not resident, no ring, or the launch gave up: the lockstep rounds below)
   }
   HIPCHK(h, hipMemsetAsync(h->d_ctl, 0, 2 * sizeof(SweepCtl), s));

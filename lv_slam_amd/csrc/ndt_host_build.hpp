@@ -86,7 +86,7 @@ static int build_targets_impl(mi355ndt_handle* h, const GridExtras make) {
     HIPCHK(h, h->d_heads.reserve((size_t)B * nsl * scap));
     HIPCHK(h, h->d_head_cnt.reserve((size_t)B * nsl));
     k_mark<unsigned><<<dim3((nsl + 3) / 4, B), 256, 0, s>>>(kb, pitch, h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, minpts, cb);
-    k_rank<<<B, 1024, 0, s>>>(h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, h->d_seg_start);
+    k_rank<<<B, RANK_THREADS, 0, s>>>(h->d_grid, h->d_words, h->d_heads, h->d_head_cnt, nsl, scap, h->d_seg_start);
     // leaf-sum workgroups per target: 64 keeps ~4 targets (3 MB of points) in flight per XCD, inside its 4 MB L2
     const int lb = std::max(1, std::min((int)((rpp + LS_WAVES - 1) / LS_WAVES), 64));
     auto leafsum = [&](auto kern, const unsigned* vals) {

@@ -39,6 +39,21 @@ int mi355ndt_get_incremental(mi355ndt_handle* h, int pair, float last[16], float
   return MI355NDT_OK;
 }
 
+int mi355ndt_get_partial_rows(mi355ndt_handle* h, double* out, size_t capacity, int* rows_per_pair) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!rows_per_pair) return MI355NDT_ERR_BAD_ARG;
+  if (h->n_pairs < 1 || !h->aligned_once || !h->d_partials || h->rows_per_pair < 1) return MI355NDT_ERR_STATE;
+  *rows_per_pair = h->rows_per_pair;
+  if (!out) return MI355NDT_OK;
+  const size_t need = (size_t)h->n_pairs * h->rows_per_pair * NACC;
+  if (capacity < need) return MI355NDT_ERR_BAD_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(out, h->d_partials, need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MI355NDT_OK;
+}
+
 static int run_hook_sweep(mi355ndt_handle* h, double* score, double g[6], double H[36], long long* hits) {
   SweepConst sc;
   make_sweep_const(h, sc);

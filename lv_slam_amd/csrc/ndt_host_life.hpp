@@ -108,6 +108,7 @@ int mi355ndt_create(const mi355ndt_params* params, int device, mi355ndt_handle**
   if (const char* e = std::getenv("MI355NDT_LEAF_SORTED")) h->leaf_sorted = std::atoi(e) != 0;
   if (const char* e = std::getenv("MI355NDT_FINE_TILES")) { const int v = std::atoi(e); if (v == 1 || v == 2) h->fine_tiles = v; }
   if (const char* e = std::getenv("MI355NDT_ARITH")) h->arith = std::atoi(e) == 1 ? 1 : 0;   // default of MI355NDT_OPT_ARITH for engines created afterwards (tools, A/B runs)
+  if (const char* e = std::getenv("MI355NDT_SWEEP_WAVES")) { const int v = std::atoi(e); if (v == 0 || v == 2 || v == 3) h->sweep_waves = v; }   // default of MI355NDT_OPT_SWEEP_WAVES (A/B runs)
   if (const char* e = std::getenv("MI355NDT_ASYNC")) { h->async_align = std::atoi(e) != 0; h->async_force = std::atoi(e) == 2; }
   if (const char* e = std::getenv("MI355NDT_SCORE_ONLY_LAST_SWEEP")) h->score_only_last = std::atoi(e) != 0;   // default of MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP (A/B runs)
   if (const char* e = std::getenv("MI355NDT_SWEEP_DYN_SHIFT")) { const int v = std::atoi(e); if (v >= 0 && v <= 30) h->dyn_shift = v; }
@@ -205,7 +206,8 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
   if (h->ss && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
-                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL || option == MI355NDT_OPT_NDT_CLASS)) NOT_IN_STREAM(h);
+                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL || option == MI355NDT_OPT_NDT_CLASS ||
+                       option == MI355NDT_OPT_SWEEP_WAVES)) NOT_IN_STREAM(h);
   if (option == MI355NDT_OPT_NDT_CLASS) {
     if (value != NDT_CLASS_OMP && value != NDT_CLASS_PCL) return MI355NDT_ERR_BAD_ARG;
     h->ndt_class = value;                        // (what class 1 serves and needs of the grids: ndt_grid_state.hpp; the next align rebuilds what a resident target lacks)
@@ -224,6 +226,11 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (option == MI355NDT_OPT_ARITH) {
     if (value != 0 && value != 1) return MI355NDT_ERR_BAD_ARG;
     h->arith = value;                            // (grids built before lack the records of the other arithmetic: the next align rebuilds them)
+    return MI355NDT_OK;
+  }
+  if (option == MI355NDT_OPT_SWEEP_WAVES) {
+    if (const int rc = sweep_waves_option_rc(false, value)) return rc;     // (a stream: refused above)
+    h->sweep_waves = value;                      // (no result word depends on it: which body serves a launch is decided per launch, async_lean)
     return MI355NDT_OK;
   }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) {
@@ -278,6 +285,7 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (!value) return MI355NDT_ERR_BAD_ARG;
   if (option == MI355NDT_OPT_F32_SUM_ORDER) { *value = h->f32_sum_order; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ARITH) { *value = h->arith; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_SWEEP_WAVES) { *value = h->sweep_waves; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_POSE_MODEL) { *value = h->pose_model; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_NDT_CLASS) { *value = h->ndt_class; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) { *value = h->async_force ? 2 : (h->async_align ? 1 : 0); return MI355NDT_OK; }

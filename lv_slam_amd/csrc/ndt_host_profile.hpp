@@ -87,9 +87,10 @@ int mi355ndt_profile_get(mi355ndt_handle* h, mi355ndt_profile* out) {
   unsigned long long hh[2] = {0, 0};              // (point, voxel) evaluations and score-only sweeps since the last reset, summed on the device
   HIPCHK(h, hipMemcpy(hh, h->d_hits, sizeof hh, hipMemcpyDeviceToHost));
   *out = h->P;
-  if (h->ss) { out->stream_reserved_slots = h->ss->reserve_wg; out->stream_launch_slots = h->ss->launch_slots; }
+  if (h->ss) { out->stream_reserved_slots = h->ss->last_reserve; out->stream_launch_slots = h->ss->last_slots; }
   out->sweep_hits += (long long)hh[0];
   out->sweep_alg_bytes += 64.0 * (double)hh[0];
   out->score_only_sweeps = (long long)hh[1];
+  out->async_waves_per_simd = h->last_async_wpe; out->async_launch_slots = h->last_async_grid;
   return MI355NDT_OK;
 }

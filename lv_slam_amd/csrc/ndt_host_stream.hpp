@@ -58,6 +58,8 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
   h->built = GridsBuilt{};
   SweepConst sc;
   make_sweep_const(h, sc);
+  // (the session is sized for the geometry every configuration has; whether a launch of exact ndt_omp / DIRECT7 runs the lean body on 768 slots
+  //  instead is decided launch by launch, from the batch that launch starts: stream_launch)
   const int slots = launch_slots(h, sc, fast_served(h));
   {
     const int iu = ss.items / (sc.K == 1 ? ASYNC_CLAIM(1) : sc.K == 7 ? 2 : 1);   // positions per ticket (DIRECT1: ndt_async.hpp; stream_launch: two DIRECT7 items per claim when pairs are handed over)
@@ -83,18 +85,23 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
     //    The smaller the batch, the more it is worth (a small build is a chain of short kernels, not throughput): 64 pairs 41.3 -> 50.6 k; at 1,536 pairs
     //    per batch the build no longer fits under its launch: exact +-0, tolerance arithmetic -6 % (DIRECT1 still +4 %) -- so only for batches up to
     //    768 x 65,536 target points.
+    //    The lean launch (three waves per SIMD, 768 slots, a slot = a third of a CU; chosen per launch: stream_launch): 96 = the same eighth of the GPU.  Swept on one box with
+    //    plain bench.py runs (docs/experiments.md 10o), r = 0 / 32 / 48 / 64 / 80 / 96 / 112 / 128 / 160: 64.0 / 65.2 / 64.6 / 67.1 / 66.9 / 68.4 / 68.4 /
+    //    68.4 / 66.9 k against 64.9 k for the two-wave launch at its 64 -- a plateau from 96 to 128, of which 96 leaves the launch the most slots.  Every
+    //    kernel of the build has to fit a third of a CU for that: k_rank (ndt_build.hpp) is an eight-wave block since.
     //  * ndt_pca / DIRECT7: 32 (same bound on the batch).  Until the build was made to start BEHIND the launch's prepare kernel (stream_submit) its first kernels
     //    raced the launch's own start and r >= 64 cost a third of the rate; since then config 5 (0.5 m, 128 x 131,072) r = 0 / 16 / 32 / 48 / 64 / 96: 19.1 /
     //    19.3 / 20.0 / 19.6 / 19.8 / 18.8 k, 271 x 65,536 at 1 m 34.9 -> 35.3 k, 64-pair batches 31.7 -> 35.3 k.
     //  * Everything else (DIRECT26, KDTREE): 0.
     const bool small_batch = (unsigned long long)max_pairs * (unsigned long long)max_tgt <= 768ull * 65536ull;
     int r = sc.K == 1 ? (max_tgt <= 98304 ? 128 : 96) : ((sc.K == 7 && small_batch) ? (sc.pca ? 32 : 64) : 0);
-    if (const char* e = std::getenv("MI355NDT_STREAM_RESERVE")) r = std::atoi(e);
-    if (h->s_reserve_opt >= 0) r = h->s_reserve_opt;
+    if (const char* e = std::getenv("MI355NDT_STREAM_RESERVE")) { r = std::atoi(e); ss.reserve_given = true; }
+    if (h->s_reserve_opt >= 0) { r = h->s_reserve_opt; ss.reserve_given = true; }
     r = std::max(0, std::min(r, slots / 2)) & ~7;
     if (n_contexts < 3) r = 0;                       // (the overlapped build needs its context free one launch earlier: at least three contexts)
     ss.reserve_wg = r;
     ss.launch_slots = std::max(8, slots - r);
+    ss.last_reserve = r; ss.last_slots = ss.launch_slots;       // (what the profile reports until the first launch says what it took)
   }
   ss.ring_cap = async_ring_cap(h, (long long)max_pairs + ASYNC_MAX_CARRY);
   if (ss.ring_cap == 0) ss.sync_only = true;
@@ -115,7 +122,7 @@ int mi355ndt_stream_begin(mi355ndt_handle* h, int n_contexts, int max_pairs, siz
     }
     rc = mi355ndt_set_stream(e, ss.reserve_wg > 0 ? ss.build_stream : h->stream);
     if (rc) return rc;
-    e->f32_sum_order = h->f32_sum_order; e->arith = h->arith; e->async_align = h->async_align; e->dyn_shift = h->dyn_shift; e->score_only_last = h->score_only_last;
+    e->sweep_waves = h->sweep_waves; e->f32_sum_order = h->f32_sum_order; e->arith = h->arith; e->async_align = h->async_align; e->dyn_shift = h->dyn_shift; e->score_only_last = h->score_only_last;
     e->async_build = true;
     e->ev_pool_target = 128;
     rc = ensure_pair_arrays(e, max_pairs);          // every per-pair array at its final size: no allocation, no wait inside submit
@@ -184,7 +191,18 @@ static int stream_launch(mi355ndt_handle* h, int new_ci, int n_new) {
   L.ctl = ss.d_ctl + (j & 1); L.prev = ss.drop_carry ? nullptr : ss.d_ctl + ((j + 1) & 1);
   // (the automatic threshold never hands over more than a quarter of the batch: a batch too small to fill the GPU has no bulk to hide stragglers under)
   L.items_per_pair = ss.items; L.stop_thresh = flush ? 0 : (ss.thresh_given ? ss.thresh : std::min(ss.thresh, n_new / 4)); L.debug_abort_pos = h->debug_abort_pos; L.debug_ring_mask = h->debug_ring_mask;
+  // Two or three waves per SIMD, launch by launch: the batch this launch starts says (its largest target; a flush runs what the launch before
+  // it ran).  A lean launch has 768 slots, a third of a CU each: a reserve the caller named is taken as named, the default becomes LEAN_RESERVE_WG
+  // -- the same eighth of the GPU as the two-wave launch's 64 -- wherever the two-wave default reserves at all.
+  if (!flush) {
+    const mi355ndt_handle* e = ss.ctx[new_ci].e.get();
+    const int tgt_max = *std::max_element(e->h_tgt_cnt.begin(), e->h_tgt_cnt.begin() + n_new);
+    ss.lean = async_lean(h, sc, sweep_ord(h, sc), tgt_max > 0 ? (size_t)tgt_max : ss.max_tgt);
+  }
+  L.lean = ss.lean;
   L.reserve_wg = flush ? 0 : ss.reserve_wg;
+  if (L.lean && !flush && !ss.reserve_given && ss.reserve_wg > 0) L.reserve_wg = LEAN_RESERVE_WG;
+  if (L.lean) L.reserve_wg = std::min(L.reserve_wg, launch_slots(h, sc, false, true) / 2) & ~7;
   L.ev_prepared = (ss.reserve_wg > 0 && ss.prep_first) ? ss.ev_prepared[j % StreamState::EV] : nullptr;
   // two DIRECT7 items per claim halve the hand-overs between items (+1.4-2 %); the coarser positions lengthen a launch's own tail, so only
   // where the tail is handed on (docs/experiments.md 10d)
@@ -195,6 +213,7 @@ static int stream_launch(mi355ndt_handle* h, int new_ci, int n_new) {
   int rc = launch_async(h, sc, L);
   if (rc) return rc;
   ss.drop_carry = false;
+  if (!flush) { ss.last_reserve = L.reserve_wg; ss.last_slots = h->last_async_grid; }
   const int slot = (int)(j % StreamState::EV);
   k_stream_status<<<1, 64, 0, s>>>(L.ctl, ss.d_stat, reinterpret_cast<volatile unsigned*>(ss.d_status + slot), (unsigned)(j + 1));
   HIPCHK(h, hipGetLastError());

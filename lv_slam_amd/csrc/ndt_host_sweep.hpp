@@ -9,6 +9,8 @@
 //   * IT = 8: batch-mode items (and the one-launch align, which has no other); IT = 1 / 2: latency mode's fine items, DIRECT1 / DIRECT7 alone
 // ndt_ord1_list.hpp and ndt_fast_list.hpp spell out the ORD = 1 and ORD = 2 rows of this predicate as text (explicit instantiation needs
 // that): a change here is a change there.
+// k_align_async alone has a fourth tag: <false, 7, ORD, true>, ORD = 0 / 1, the lean item body at three waves per SIMD (lean_exists, ndt_sweep_waves.hpp;
+// launch_async picks it when the launch's AsyncLaunch::lean says so).
 // Under MI355NDT_OPT_POSE_MODEL = 1: k_sweep<false, K, 8, false, ORD, 1> for the four K and ORD = 0 / 1 (euler_sweep_exists, launch_sweep_euler).
 // Under MI355NDT_OPT_NDT_CLASS = 1: k_sweep<false, 27, 8, false, 0, 2> alone (the radius search, the f64 evaluation: launch_sweep).
 constexpr int SWEEP_IT_BATCH = 8;
@@ -35,6 +37,16 @@ static int dispatch_sweep(bool pca, int K, int ord, int it, F&& f) {
   by_K(std::false_type{}); by_K(std::true_type{});
   return rc;
 }
+
+// ---- two or three waves per SIMD in a persistent launch (MI355NDT_OPT_SWEEP_WAVES) ----------------
+// Decided once per launch, on the host (a stream: by the batch the launch starts, stream_launch): ndt_sweep_waves.hpp has the rule and where its threshold comes from.
+// `ord`: the arithmetic of the launch's sweeps (sweep_ord); `tgt_pts`: the largest target of the batch.
+static_assert(sizeof(VoxelRec) == LEAN_REC_BYTES, "the record the estimate counts");
+static bool async_lean(const mi355ndt_handle* h, const SweepConst& sc, int ord, size_t tgt_pts) {
+  return async_served(h) && lean_exists(sc.pca != 0, sc.K, ord) && sweep_waves_choice(h->sweep_waves, h->prm, ord, tgt_pts) == 3;
+}
+// stream mode: the slots a lean launch leaves to the next batch's build -- of 768, a third of a CU each (mi355ndt_stream_begin has the sweep)
+constexpr int LEAN_RESERVE_WG = 96;
 
 // ---- sweeps -----------------------------------------------------------------------------------
 static int prep_align_ws(mi355ndt_handle* h) {
@@ -190,13 +202,14 @@ struct AsyncLaunch {
   unsigned long long* stamp_end = nullptr;       // stream mode + profiling: where k_async_prepare stamps the end of the build in front of it
   int claim_items = 1;                           // DIRECT7 items per claimed position (DIRECT1: always ASYNC_CLAIM(1) = 2; ndt_async.hpp)
   int reserve_wg = 0;
+  bool lean = false;                             // the lean item body, three waves per SIMD (async_lean: the caller decides, per launch)
   hipEvent_t ev_prepared = nullptr;              // stream mode, build beside the launch: recorded between the prepare kernel and the persistent launch
 };
 #define NDT_CTX_ARGS(i) L.tab.c[i].src, L.tab.c[i].pitch, L.tab.c[i].st, L.tab.c[i].gd, L.tab.c[i].words, L.tab.c[i].recs, L.tab.c[i].partials, L.tab.c[i].src_cnt, \
                         L.tab.c[i].arrived, L.tab.c[i].cent
-template <bool PCA, int K, int ORD>
+template <bool PCA, int K, int ORD, bool LEAN = false>
 static int launch_async_t(mi355ndt_handle* h, const SweepConst& sc, const AsyncLaunch& L) {
-  auto kern = k_align_async<PCA, K, ORD>;
+  auto kern = k_align_async<PCA, K, ORD, LEAN>;
   // (asked once per instantiation and device: the query sits between the prepare kernel and the launch, on the host's critical path)
   // (engines on several host threads come through here at once: the cached answer is an atomic, the query writes into a local)
   static std::atomic<int> per_cu_of_device[64];
@@ -205,7 +218,7 @@ static int launch_async_t(mi355ndt_handle* h, const SweepConst& sc, const AsyncL
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, SWEEP_THREADS, 0) != hipSuccess) { (void)hipGetLastError(); return MI355NDT_ERR_UNSUPPORTED; }
     per_cu_of_device[h->device & 63].store(per_cu, std::memory_order_relaxed);
   }
-  const int slots = launch_slots(h, sc, ORD == 2);
+  const int slots = launch_slots(h, sc, ORD == 2, LEAN);
   // Workgroup L serves ring L % 8 first, and the launch is sized to be resident as a whole.  Residency is no condition of correctness:
   // positions are claimed, a waiting wave serves the published positions of OTHER rings too (ndt_async.hpp: an XCD that holds no workgroup
   // of this launch -- another engine's launch fills it -- leaves no ticket unserved), a workgroup that starts late finds the launch over
@@ -217,6 +230,7 @@ static int launch_async_t(mi355ndt_handle* h, const SweepConst& sc, const AsyncL
   kern<<<grid, SWEEP_THREADS, 0, h->stream>>>(L.tab_dev, L.items_per_pair, L.ring, L.ring_cap, L.ctl, sc, h->prof ? h->d_hits : nullptr,
                                              h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations, L.stop_thresh, L.debug_abort_pos, L.debug_ring_mask, L.claim_items,
                                              NDT_CTX_ARGS(0), NDT_CTX_ARGS(1), NDT_CTX_ARGS(2), NDT_CTX_ARGS(3));
+  h->last_async_wpe = SweepTune<PCA, K, ORD, LEAN>::WPE; h->last_async_grid = (int)grid.x;
   return MI355NDT_OK;
 }
 // prepare kernel + the persistent launch on the engine's stream (HIP events around the launch when profiling)
@@ -231,6 +245,8 @@ static int launch_async(mi355ndt_handle* h, const SweepConst& sc, const AsyncLau
   if (h->prof) HIPCHK(h, ev_begin(h, h->ev_sweep));
   // (a one-launch align sweeps batch-mode items; ORD as the sweeps of this engine have it: sweep_ord)
   const int rc = dispatch_sweep(sc.pca != 0, sc.K, sweep_ord(h, sc), SWEEP_IT_BATCH, [&](auto P, auto KK, auto O, auto) {
+    if constexpr (lean_exists(decltype(P)::value, decltype(KK)::value, decltype(O)::value))
+      if (L.lean) return launch_async_t<false, 7, decltype(O)::value, true>(h, sc, L);
     return launch_async_t<decltype(P)::value, decltype(KK)::value, decltype(O)::value>(h, sc, L);
   });
   if (h->prof) HIPCHK(h, ev_end(h, h->ev_sweep));

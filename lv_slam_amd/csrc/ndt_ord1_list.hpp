@@ -26,4 +26,5 @@
   X __global__ void k_align_async<false, 1, 1> NDT_ASYNC_ARGS_T;  X __global__ void k_align_async<true, 1, 1> NDT_ASYNC_ARGS_T;           \
   X __global__ void k_align_async<false, 7, 1> NDT_ASYNC_ARGS_T;  X __global__ void k_align_async<true, 7, 1> NDT_ASYNC_ARGS_T;           \
   X __global__ void k_align_async<false, 26, 1> NDT_ASYNC_ARGS_T; X __global__ void k_align_async<true, 26, 1> NDT_ASYNC_ARGS_T;          \
-  X __global__ void k_align_async<false, 27, 1> NDT_ASYNC_ARGS_T;
+  X __global__ void k_align_async<false, 27, 1> NDT_ASYNC_ARGS_T;                                                                          \
+  X __global__ void k_align_async<false, 7, 1, true> NDT_ASYNC_ARGS_T;   /* the lean body (three waves per SIMD: MI355NDT_OPT_SWEEP_WAVES) */

@@ -485,15 +485,21 @@ struct SweepCtl {               // 9 ints; two of them alternate: the sweep that
 #ifndef FAST_PIPE
 #define FAST_PIPE 1
 #endif
-template <bool PCA, int K, int ORD = 0>
+// LEAN (MI355NDT_OPT_SWEEP_WAVES; exact ndt_omp / DIRECT7 in the one-launch align alone): the same item body register-allocated for three
+// waves per SIMD (168 VGPRs).  What it gives up for that: the mid-evaluation record prefetch, and the second tile of a probe group -- a
+// super-tile is still two tiles (the staging geometry, the partial drains at its boundaries), probed one tile at a time.  Rows keep their bits:
+// hits enter the queue in the same order, full batches leave it FIFO, the partial drains happen at the same boundaries with the same counts.
+template <bool PCA, int K, int ORD = 0, bool LEAN = false>
 struct SweepTune {
+  static_assert(!LEAN || (!PCA && K == 7 && (ORD == 0 || ORD == 1)), "the lean body: exact ndt_omp / DIRECT7");
   static constexpr bool FAST = (ORD == 2);
-  static constexpr int  WPE  = FAST ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE;                  // workgroups per CU = waves per SIMD
-  static constexpr bool PIPE = FAST ? (FAST_PIPE != 0) : true;                                       // fetch batch k+1's records in the middle of batch k
-  // tiles probed together (8 = the whole work item); tolerance arithmetic: small super-tiles keep the LDS of a workgroup under a quarter of the CU's
+  static constexpr int  WPE  = LEAN ? 3 : (FAST ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE);     // workgroups per CU = waves per SIMD
+  static constexpr bool PIPE = LEAN ? false : (FAST ? (FAST_PIPE != 0) : true);                      // fetch batch k+1's records in the middle of batch k
+  // tiles of a super-tile (8 = the whole work item); tolerance arithmetic: small super-tiles keep the LDS of a workgroup under a quarter of the CU's
   static constexpr int  TP   = FAST ? (K == 1 ? FAST_TP1 : FAST_TP7) : (K == 1 ? 8 : (K <= 7 ? 2 : 1));
+  static constexpr int  TPP  = LEAN ? 1 : TP;                                                        // ... of which that many are probed together
 };
-static inline int sweep_wpe(int K, bool fast = false) { return fast ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE; }
+static inline int sweep_wpe(int K, bool fast = false, bool lean = false) { return lean ? 3 : (fast ? (K == 1 ? FAST_WPE1 : FAST_WPE7) : SWEEP_WPE); }
 
 // IT = tiles of 64 points per work item.  8 is the batch mode described above (a wave-quarter of a 2048-point chunk).
 // FINE (latency mode): small items (IT = 1 or 2) dealt statically over ALL waves of the grid, for a sweep over one or a
@@ -634,7 +640,7 @@ struct BatchD { unsigned slot; double m0, m1, m2; double C[9]; };            // 
 // PM = 2 (MI355NDT_OPT_NDT_CLASS = 1, K = 27 alone): hits are evaluated by eval_hit_pcl -- the staged points as for PM = 1, `rw` the pair's rows as
 // doubles and the grid's f64 inverse covariances, which a batch fetches in place of the record's f32 ones.
 struct NoRows {};
-template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0>
+template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0, bool LEAN = false>
 struct HitQueue {
   static_assert(PM == 0 || ((PM == 1 || PM == 2) && !PCA && ORD != 2 && !SO), "the Euler model: ndt_omp, exact arithmetic, full rows");
   static_assert(PM != 2 || (K == 27 && ORD == 0), "PCL's class: the radius search, one instantiation");
@@ -743,7 +749,7 @@ struct HitQueue {
   // current batch's arithmetic (before its 36 Hessian terms), so their L2 latency is off the critical path.
   __device__ __forceinline__ void drain_full() {
     // (PM = 2: the f64 evaluation is bound by its arithmetic, and the 25 registers of a second batch in flight are the ones it would spill)
-    if (PM == 2 || !SweepTune<PCA, K, ORD>::PIPE) {           // plain: one batch after the other
+    if (PM == 2 || !SweepTune<PCA, K, ORD, LEAN>::PIPE) {           // plain: one batch after the other
       while (count >= 64) drain(64);
       return;
     }
@@ -765,7 +771,7 @@ struct HitQueue {
 // hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
 // PM = 1 (MI355NDT_OPT_POSE_MODEL, the lockstep rounds only): phase A stages the moved point and the ORIGINAL point, phase B is eval_hit_euler over
 // the pair's rows sc.euler_rows[b] (written by whoever wrote the pair's T: k_init_state, k_set_pose_p, newton_update).
-template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false, int PM = 0>
+template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false, int PM = 0, bool LEAN = false>
 __device__ __forceinline__ void sweep_item(const int b, const int rem, const float* __restrict__ src, const size_t pitch, const PairState* st,
                                            const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                            double* partials, const int rows_per_pair, const SweepConst& sc, const float* __restrict__ cent,
@@ -778,26 +784,32 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
   static_assert(PM == 0 || (!PCA && !FAST && !ASYNC && !FINE && !SO), "the Euler model takes the lockstep rounds: ndt_omp, exact arithmetic, batch items");
   static_assert(PM != 2 || (K == 27 && ORD == 0 && IT == 8), "PCL's class: the radius search, batch items");
-  typedef SweepTune<PCA, K, ORD> Tune;
+  static_assert(!LEAN || (ASYNC && !FINE && PM == 0 && IT == 8), "the lean body belongs to the one-launch align");
+  typedef SweepTune<PCA, K, ORD, LEAN> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // ndt_pca's per-hit multiplier is the product of the hit's own weight and those of the point's LATER hits, known only in phase A.
   // With one probe per point (DIRECT1) it is just the leaf's own weight, which phase B reads with the record anyway: no weight
   // load in the probe stage, no weight queue, dead leaves filtered in phase B exactly as for ndt_omp.
   constexpr bool PCAQ = PCA && K > 1;
   // per-wave hit queue: must hold a leftover (< 64) plus everything one probe group can push: TP tiles x min(K, Q_GROUP) probes x 64
-  constexpr int TP = Tune::TP < IT ? Tune::TP : IT;
+  constexpr int TPS = Tune::TP < IT ? Tune::TP : IT;         // tiles of a super-tile: the staging geometry and the partial drains
+  constexpr int TP = Tune::TPP < TPS ? Tune::TPP : TPS;      // tiles of a probe group (= the super-tile, except in the lean body)
+  constexpr int GPS = TPS / TP;                              // probe groups per super-tile
+  static_assert(TPS % TP == 0, "probe groups tile the super-tile");
   constexpr int Q_NEED = (IT / TP > 1 ? 64 : 0) + TP * (K < Q_GROUP ? K : Q_GROUP) * 64;
   constexpr int Q_CAP = FAST ? (Q_NEED <= 128 ? 128 : Q_NEED <= 256 ? 256 : Q_NEED <= 512 ? 512 : 1024) : ((K > 1 && K <= Q_GROUP) ? 1024 : 512);
   static_assert(Q_NEED <= Q_CAP, "hit queue");
-  typedef HitQueue<PCA, K, ORD, SO, Q_CAP, false, PM> Queue;
+  typedef HitQueue<PCA, K, ORD, SO, Q_CAP, false, PM, LEAN> Queue;
   auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 0>();
   auto& q_w = item_lds<typename Queue::QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
   // TP tiles of 64 points are probed together ("super-tile"): their point transforms, then ALL their bitmap loads, then all
   // their ballots -- the probe stage costs a few L2 round trips per super-tile, not per tile.  DIRECT1 has one probe per point
   // and ~0.9 hits, so it is probe-stage bound: 4 tiles at a time; DIRECT7: 2 (14 bitmap words in flight); the 26/27-cell
   // searches already have 7-probe groups inside one tile.
-  constexpr int NBUF = (IT / TP > 1) ? 2 : 1;   // a super-tile that is the whole item needs no second buffer
-  auto& stage = item_lds<float[WAVES][NBUF * 64 * TP][6], 2>();   // (two) super-tiles of staged points: x'(3), R x (3)
+  // The lean body probes ONE tile at a time and keeps everything else of the two-tile super-tile: the staging halves, and the boundaries at
+  // which the entries of the older half are drained.
+  constexpr int NBUF = (IT / TPS > 1) ? 2 : 1;   // a super-tile that is the whole item needs no second buffer
+  auto& stage = item_lds<float[WAVES][NBUF * 64 * TPS][6], 2>();   // (two) super-tiles of staged points: x'(3), R x (3)
 
   // FINE: the four waves of a block always hold the four rows of ONE chunk (items 4q .. 4q+3: static dealing, four waves per block, a
   // multiple of four items per pair), so the chunk level of k_update's tree -- ((r0 + r1) + r2) + r3 -- is added here through LDS and
@@ -835,7 +847,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
     if constexpr (PM == 2) { Q.rw.rows = pcl_rows_of_pair(sc.pcl_rows, b); Q.rw.icov64 = sc.icov64 + (size_t)g.rec_off * 9; }
     const int wbase = rem * (IT * 64);
     if (wbase < n && grid_ok) {
-      constexpr int NST = IT / TP;                            // super-tiles per item
+      constexpr int NST = IT / TP;                            // probe groups per item (= super-tiles, except in the lean body)
       const unsigned e0 = (unsigned)(xb0 - mb0), e1 = (unsigned)(xb1 - mb1), e2 = (unsigned)(xb2 - mb2);
       const unsigned empty_cell = (unsigned)(nwords - 1) << 6;
       // points of the next super-tile are fetched one super-tile ahead (HBM latency ~2 us would otherwise be exposed each time)
@@ -852,8 +864,12 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
         if (wbase + st * TP * 64 >= n) break;        // wave-uniform
         // the staging area holds two super-tiles: entries of super-tile st-2 must be gone before st overwrites their half
         // (only happens when hits are sparse; dense tiles are consumed by the regular 64-wide drains)
-        if (Q.old > 0) { __builtin_amdgcn_wave_barrier(); Q.drain(Q.old); }
-        Q.old = Q.count;
+        if (GPS == 1 || st % GPS == 0) {             // (a super-tile begins: always, except in the lean body)
+          if (Q.old > 0) { __builtin_amdgcn_wave_barrier(); Q.drain(Q.old); }
+          Q.old = Q.count;
+        }
+        // staging tile of tile p of this probe group: the super-tile's half, the group's place in it
+#define NDT_STAGE_TILE(p) (GPS == 1 ? (st & 1) * TP + (p) : ((st / GPS) & 1) * TPS + (st % GPS) * TP + (p))
         int r0[TP], r1[TP], r2[TP], cc[TP];
         bool valid[TP];
         float kx[TP], ky[TP], kz[TP];                // moved points (only the KDTREE distance test reads them again)
@@ -870,8 +886,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           // a non-finite moved point (NaN pose: only reachable through a NaN More-Thuente trial value) has no neighbours;
           // the reference's float->int cast is undefined there
           ok = ok && finite3(xt[0], xt[1], xt[2]);
-          if constexpr (PM != 0) { const float xo[3] = {px, py, pz}; stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, xo); }
-          else stage_point(stage[wv][((st & 1) * TP + p) * 64 + lane], xt, r);
+          if constexpr (PM != 0) { const float xo[3] = {px, py, pz}; stage_point(stage[wv][NDT_STAGE_TILE(p) * 64 + lane], xt, xo); }
+          else stage_point(stage[wv][NDT_STAGE_TILE(p) * 64 + lane], xt, r);
           kx[p] = xt[0]; ky[p] = xt[1]; kz[p] = xt[2];
           // Branch-free probe stage.  Relative cell r = c - min_b; "inside the grid" (impl:382-392) is one unsigned
           // compare per axis; a probe that falls outside (or belongs to an invalid lane) is redirected to the grid's
@@ -926,7 +942,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           }
 #pragma unroll
           for (int p = 0; p < TP; p++) {
-            const int slot = ((st & 1) * TP + p) * 64 + lane;
+            const int slot = NDT_STAGE_TILE(p) * 64 + lane;
 #pragma unroll
             for (int j = 0; j < Q_GROUP; j++) {
               if (q1 - 1 - j < 0) continue;
@@ -941,6 +957,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
           TL_STAMP(5);
         }
       }
+#undef NDT_STAGE_TILE
       __builtin_amdgcn_wave_barrier();
       if (Q.count > 0) Q.drain(Q.count);
       TL_STAMP(5);

@@ -58,7 +58,8 @@ class Profile(C.Structure):
                 ("update_launches", C.c_longlong), ("async_fallbacks", C.c_longlong), ("stream_launches", C.c_longlong),
                 ("stream_carried", C.c_longlong), ("stream_redone", C.c_longlong), ("cloud_uploads", C.c_longlong), ("cloud_upload_bytes", C.c_longlong),
                 ("cloud_transfers", C.c_longlong), ("cloud_promotions", C.c_longlong),
-                ("stream_reserved_slots", C.c_longlong), ("stream_launch_slots", C.c_longlong), ("score_only_sweeps", C.c_longlong)]
+                ("stream_reserved_slots", C.c_longlong), ("stream_launch_slots", C.c_longlong), ("score_only_sweeps", C.c_longlong),
+                ("async_waves_per_simd", C.c_longlong), ("async_launch_slots", C.c_longlong)]
 
 
 class InfParams(C.Structure):
@@ -131,6 +132,7 @@ SYMBOLS = [
     "mi355ndt_version", "mi355ndt_device_count", "mi355ndt_host_numa_node", "mi355ndt_default_params", "mi355ndt_create", "mi355ndt_destroy",
     "mi355ndt_set_params", "mi355ndt_get_params", "mi355ndt_set_stream", "mi355ndt_last_error",
     "mi355ndt_set_target", "mi355ndt_set_source", "mi355ndt_promote_source_to_target", "mi355ndt_align", "mi355ndt_get_aligned", "mi355ndt_get_incremental",
+    "mi355ndt_get_partial_rows",
     "mi355ndt_get_fitness_score", "mi355ndt_fitness_score_T", "mi355ndt_prefilter", "mi355ndt_use_prefiltered", "mi355ndt_derivatives", "mi355ndt_compute_hessian", "mi355ndt_derivatives_T", "mi355ndt_get_grid", "mi355ndt_get_voxels",
     "mi355ndt_batch_reserve", "mi355ndt_batch_set_target", "mi355ndt_batch_set_source", "mi355ndt_batch_set_clouds", "mi355ndt_batch_bind_device",
     "mi355ndt_batch_build_targets", "mi355ndt_batch_align", "mi355ndt_batch_size", "mi355ndt_batch_pose_records", "mi355ndt_batch_fitness_scores",
@@ -166,6 +168,7 @@ OPT_STREAM_RESERVE = 5         # mi355ndt_option: workgroup slots the stream's l
 OPT_STREAM_THRESHOLD = 4       # mi355ndt_option: pairs a stream launch hands over to the next one (-1 = auto, 0 = none)
 WARN_TOLERANCE_ARITH = 1       # mi355ndt_result.status under OPT_ARITH = 1: fewer than 4,096 hits at the final pose, or stopped at the iteration cap
 OPT_ARITH = 7                  # mi355ndt_option: 0 = the reference recipe's arithmetic, one rounding per operation (default), 1 = tolerance arithmetic (held to 1e-4 m / 1e-5 rad, not to bits)
+OPT_SWEEP_WAVES = 14           # mi355ndt_option: waves per SIMD of the exact ndt_omp / DIRECT7 body in the one-launch align: 0 = automatic (default), 2, 3 (the lean body); no result word depends on it
 OPT_F32_SUM_ORDER = 1          # mi355ndt_option: 0 = (t0 + t1) + t2 (canonical), 1 = (t0 + t2) + t1 (Eigen 3.3 SSE predux pairing)
 OPT_SCORE_ONLY_LAST_SWEEP = 8  # mi355ndt_option: 1 (default) = the one-launch align's last sweep of a pair evaluates the score alone, 0 = all 43 sums; same bits
 OPT_KF_FITNESS_CELL_MM = 9     # mi355ndt_option: cell size [mm] of the index keyframe_fitness_scores builds over a searched keyframe (default 100); no result bit depends on it
@@ -211,6 +214,7 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_align.argtypes = [vp, vp, C.POINTER(Result)]
     L.mi355ndt_get_aligned.argtypes = [vp, vp, sz]
     L.mi355ndt_get_incremental.argtypes = [vp, i, vp, vp]
+    L.mi355ndt_get_partial_rows.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int)]
     L.mi355ndt_get_fitness_score.argtypes = [vp, C.c_double, vp, vp]
     L.mi355ndt_fitness_score_T.argtypes = [vp, vp, C.c_double, vp, vp]
     L.mi355ndt_prefilter.argtypes = [vp, vp, sz, sz, i, C.c_double, C.c_double, C.c_float, vp, sz, sz, C.POINTER(sz)]
@@ -525,6 +529,15 @@ class Engine:
         a, b = np.zeros(16, np.float32), np.zeros(16, np.float32)
         self._chk(self.lib.mi355ndt_get_incremental(self.h, pair, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)), "get_incremental")
         return a.reshape(4, 4).T.copy(), b.reshape(4, 4).T.copy()
+
+    def partial_rows(self) -> np.ndarray:
+        """[pairs, rows per pair, 44] f64: the partial rows (score, g, H, hits) the last sweep of every pair of the bound batch left on the device."""
+        rpp = C.c_int()
+        self._chk(self.lib.mi355ndt_get_partial_rows(self.h, None, 0, C.byref(rpp)), "get_partial_rows")
+        B = self.lib.mi355ndt_batch_size(self.h)
+        out = np.zeros((B, rpp.value, 44), np.float64)
+        self._chk(self.lib.mi355ndt_get_partial_rows(self.h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(rpp)), "get_partial_rows")
+        return out
 
     def fitness_score(self, max_range: float = float("inf"), T=None):
         """getFitnessScore(max_range); T = explicit 4x4 transform (default: final pose of the last align)."""

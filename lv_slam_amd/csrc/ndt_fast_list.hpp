@@ -1,7 +1,7 @@
 // ndt_fast_list.hpp -- the kernel instantiations of the tolerance arithmetic (ORD = 2: MI355NDT_OPT_ARITH = 1; ndt_sweep.hpp, eval_hit_fast), compiled in a
 // translation unit of their own (mi355_ndt_fast.hip) beside the other two; mi355_ndt.hip declares them `extern template`.  DIRECT1 / DIRECT7, both
 // classes: the batch-mode sweep, the latency mode's fine sweeps, the one-launch align.  Kernels only: no device function crosses the units.
-// The list is the ORD = 2 row of sweep_exists (ndt_host_sweep.hpp), the predicate the host's dispatcher is guarded by: a change there is a change here.
+// The list is the ORD = 2 row of sweep_exists (ndt_sweep_exists.hpp), the predicate the host's dispatcher is guarded by: a change there is a change here.
 #pragma once
 #include "ndt_ord1_list.hpp"      // (the argument-list macros)
 #define NDT_FAST_KERNELS(X)                                                                                   \

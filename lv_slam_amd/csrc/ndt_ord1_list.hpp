@@ -1,7 +1,7 @@
 // ndt_ord1_list.hpp -- the kernel instantiations with the second f32 sum order (ORD = 1: MI355NDT_OPT_F32_SUM_ORDER = 1).  They are compiled
 // in a translation unit of their own (mi355_ndt_ord1.hip) so that the two halves of the library build side by side; mi355_ndt.hip
 // declares them `extern template`.  Kernels only: no device function crosses the two units.
-// The list is the ORD = 1 row of sweep_exists (ndt_host_sweep.hpp), the predicate the host's dispatcher is guarded by, spelled out as text because
+// The list is the ORD = 1 row of sweep_exists (ndt_sweep_exists.hpp), the predicate the host's dispatcher is guarded by, spelled out as text because
 // explicit instantiation needs that -- plus k_sweep_pca_kd<1>, the literal kernel of ndt_pca + KDTREE.  A change there is a change here.
 #pragma once
 #define NDT_SWEEP_ARGS_T (const float*, size_t, const PairState*, const GridDesc*, const BitWord*, const VoxelRec*, double*, int, const int*, SweepCtl*, SweepCtl*, \

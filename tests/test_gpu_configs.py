@@ -9,6 +9,7 @@ converged flag, SE(3) inside the north-star tolerance (trans < 1e-4 m, rot < 1e-
 import numpy as np
 import pytest
 
+import sweep_matrix as M
 from conftest import se3_err
 from lv_slam_amd import ndt, synth
 from oracle import oracle_py as O
@@ -327,3 +328,82 @@ def test_host_cloud_batch_upload_paths_agree():
         assert ref[k]["iterations"] == ro["iterations"]
         dt, dr = se3_err(ro["final"], ref[k]["final"])
         assert dt < 1e-4 and dr < 1e-5
+
+
+ASYNC_MODES = {1: ndt.DIRECT1, 7: ndt.DIRECT7, 26: ndt.DIRECT26, 27: ndt.KDTREE}
+
+
+def ragged_batch_on_both_routes(pca, K, order, lean):
+    """One resident batch of ten 4,096-point targets with sources of RAGGED_COUNTS points, every third guess 0.35 m off, aligned by the lockstep
+    rounds (MI355NDT_OPT_ASYNC_ALIGN = 0) and by the forced one-launch align (2), with the score-only last sweep off and on.
+    order: 0 / 1 = the f32 sum order of the exact arithmetic, 2 = the tolerance arithmetic; lean: the three-wave body (MI355NDT_OPT_SWEEP_WAVES = 3,
+    else 2).  Returns {(score_only, route): (results, incremental transforms of pairs 0, 5 and 9, profile)} after asserting that every result
+    word, the incremental transforms and the profile's hit count are the same on both routes."""
+    ids = list(range(400, 400 + len(RAGGED_COUNTS)))
+    T, S, host, n = resident_batch(ids, 64)
+    assert n == 4096
+    B = len(ids)
+    G = np.stack([synth.default_guess() for _ in range(B)])
+    G[::3, 0, 3] += 0.35
+    kw = dict(resolution=2.0 if K == 26 else 1.0, trans_epsilon=0.01, max_iterations=64, neighbor_mode=ASYNC_MODES[K], variant=pca)
+    out = {}
+    for score_only in (0, 1):
+        for route in (0, 2):
+            eng = ndt.Engine(ndt.default_params(**kw))
+            for o, v in ((ndt.OPT_ARITH, int(order == 2)), (ndt.OPT_F32_SUM_ORDER, order % 2), (ndt.OPT_ASYNC_ALIGN, route),
+                         (ndt.OPT_SCORE_ONLY_LAST_SWEEP, score_only), (ndt.OPT_SWEEP_WAVES, 3 if lean else 2)):
+                eng.set_option(o, v)
+                assert eng.get_option(o) == v
+            eng.batch_bind_device(T.data_ptr(), [n] * B, n, S.data_ptr(), RAGGED_COUNTS, n)
+            eng.batch_build_targets()
+            eng.profile_enable(True); eng.profile_reset()
+            res = eng.batch_align(G)
+            pr = eng.profile_get()
+            eng.profile_enable(False)
+            incs = [eng.get_incremental(k) for k in (0, 5, 9)]
+            eng.close()
+            out[(score_only, route)] = (res, incs, pr)
+        (r0, i0, p0), (r2, i2, p2) = out[(score_only, 0)], out[(score_only, 2)]
+        for k, (x, y) in enumerate(zip(r0, r2)):
+            assert x["final"].tobytes() == y["final"].tobytes(), (score_only, k, RAGGED_COUNTS[k])
+            for w in ("score", "trans_probability"):                  # (bits, so that a NaN would compare too)
+                assert np.float64(x[w]).tobytes() == np.float64(y[w]).tobytes(), (score_only, k, RAGGED_COUNTS[k], w, x[w], y[w])
+            for w in ("iterations", "converged", "sweeps", "hits_last", "status"):
+                assert x[w] == y[w], (score_only, k, RAGGED_COUNTS[k], w, x[w], y[w])
+        for (a0, b0), (a2, b2) in zip(i0, i2):
+            assert a0.tobytes() == a2.tobytes() and b0.tobytes() == b2.tobytes(), score_only
+        assert p0["sweep_hits"] == p2["sweep_hits"] > 0, (score_only, p0, p2)
+        assert p0["update_launches"] > 2 and p0["sweep_launches"] > 3, p0       # the rounds really were rounds
+    return out
+
+
+@pytest.mark.parametrize("row", M.ALIGN_ROWS, ids=M.row_id)
+def test_every_one_launch_instantiation_equals_the_rounds(row):
+    """Every k_align_async instantiation (tests/sweep_matrix.py: 14 exact, 4 tolerance, 2 lean), selected as the dispatcher selects it -- by
+    neighbor_mode, variant, MI355NDT_OPT_F32_SUM_ORDER, MI355NDT_OPT_ARITH and MI355NDT_OPT_SWEEP_WAVES --, against the round-based align of the
+    same configuration: every result word of every pair."""
+    pca, K, order, lean = row
+    out = ragged_batch_on_both_routes(pca, K, order, lean)
+    for score_only in (0, 1):
+        res, _, pr = out[(score_only, 2)]
+        assert pr["sweep_launches"] == 1 and pr["update_launches"] == 0 and pr["async_fallbacks"] == 0, pr
+        assert (pr["score_only_sweeps"] > 0) == bool(score_only), pr     # (the option reaches every instantiation)
+        if (pca, K) == (0, 7) and order != 2:
+            assert pr["async_waves_per_simd"] == (3 if lean else 2), pr
+        if K != 26:                                             # (ndt_omp / ndt_pca + DIRECT26 at 2 m: see test_one_launch_align_equals_the_round_based_align)
+            assert len({r["iterations"] for r in res}) >= 2     # the batch is uneven
+    if order == 2:
+        # the tolerance arithmetic really served: some score word differs from the exact arithmetic's
+        exact = ragged_batch_on_both_routes(pca, K, 0, 0)[(1, 2)][0]
+        assert any(np.float64(x["score"]).tobytes() != np.float64(y["score"]).tobytes() for x, y in zip(out[(1, 2)][0], exact))
+
+
+@pytest.mark.parametrize("order", M.PCA_KD_ROWS)
+def test_pca_kdtree_has_no_one_launch_kernel_and_takes_the_rounds(order):
+    """ndt_pca + KDTREE (k_sweep_pca_kd): asked for the one-launch align, the engine runs the lockstep rounds -- no persistent launch is
+    attempted, so no fall-back is counted -- and the profile says so"""
+    out = ragged_batch_on_both_routes(1, 27, order, 0)
+    for score_only in (0, 1):
+        pr = out[(score_only, 2)][2]
+        assert pr["update_launches"] > 2 and pr["sweep_launches"] > 3 and pr["async_fallbacks"] == 0 and pr["score_only_sweeps"] == 0, pr
+        assert pr["update_launches"] == out[(score_only, 0)][2]["update_launches"] and pr["sweep_launches"] == out[(score_only, 0)][2]["sweep_launches"]

@@ -4,10 +4,16 @@ tests/test_sweep_entries_gpu.py -- the guard of the reference itself and the anc
 The oracle evaluates the reference's f32 recipe, ref_sweep the mathematics in f64, so what separates them is the recipe's own rounding: every one of
 the 43 numbers (score, g, H) must agree within K_EXACT * 2^-24 * majorant of THAT entry.  The scenes are also shown not to be vacuous, on the
 reference alone: partial neighbourhoods, ndt_pca weights of 0 and of >= 100, Hessian entries far below the largest one, the asymmetry of H."""
+import os
+import re
+import subprocess
+
 import numpy as np
 import pytest
 
 import ndt_ref as R
+import sweep_matrix as M
+from conftest import ROOT
 from oracle import oracle_py as O
 
 K_EXACT = 4          # measured maximum over all cases: 2.34 (a one-hit sweep; glibc exp); 4 leaves room for another libm's last bit in exp
@@ -64,3 +70,232 @@ def test_the_scenes_are_not_vacuous(pose):
             H, mH = row[7:].reshape(6, 6), maj[7:].reshape(6, 6)
             seen += abs(H[3, 4] - H[4, 3]) > 64 * K_EXACT * R.EPS32 * (mH[3, 4] + mH[4, 3])
     assert seen >= 1
+
+
+# ------------------------------------------------------------------------------------------------- DIRECT26 and the radius search
+# The same bar for the two searches past DIRECT1 / DIRECT7.  Measured maximum over all cases, the "tie" scene included: 2.31 (ndt_pca + KDTREE, entry
+# H[4][4] of the one-point sweep of "mid", pose "near"); DIRECT26 1.76, omp + KDTREE 1.74.  Under 4: K_EXACT holds for all four searches.
+NEW_K = (26, 27)
+
+
+@pytest.mark.parametrize("K", NEW_K)
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_oracle_agrees_with_the_f64_reference_under_direct26_and_kdtree(variant, K):
+    worst = (0.0,)
+    for sn, pn, n in R.cases(tie=True):
+        row, maj, hits, hpp, orow, ohits = R.reference(sn, pn, n, variant, K)
+        assert hits == ohits, (sn, pn, n)
+        assert np.all(np.isfinite(row)) and np.all(np.isfinite(orow)) and np.all(maj >= np.abs(row))
+        u = R.units(orow, row, maj)
+        worst = max(worst, (float(u.max()), int(u.argmax()), sn, pn, n))
+        assert np.all(np.abs(orow - row) <= K_EXACT * R.EPS32 * maj), (sn, pn, n, float(u.max()), int(u.argmax()))
+    print(f"variant {variant} K {K}: largest |oracle - ref| / (2^-24 majorant) = {worst[0]:.3f} at entry {worst[1]} of {worst[2:]}")
+    assert worst[0] > 0.01
+
+
+@pytest.mark.parametrize("pose", R.POSES)
+def test_the_scenes_are_not_vacuous_for_direct26_and_kdtree(pose):
+    """on the reference alone.  DIRECT26 probes the 26 cells AROUND the point's own (no centre cell: ndt_ref.OFFSETS26), so a full neighbourhood is
+    26 leaves; a point of a corner cell of the block meets 7."""
+    n = 513
+    for sn in R.SCENES:
+        hpp = R.reference(sn, pose, n, O.VARIANT_OMP, 26)[3]
+        assert (hpp == 26).any() and ((hpp > 0) & (hpp < 9)).any() and (hpp == 0).any(), sn
+        # KDTREE: some leaf of the 3 x 3 x 3 block around a point is rejected by the radius, some point meets more than DIRECT7 could, some none
+        src, T, Rj = R.sweep_inputs(sn, pose, n)
+        _, leaves, bounds, prm = R.oracle_grid(sn, O.VARIANT_OMP, 27)
+        kd = R.reference(sn, pose, n, O.VARIANT_OMP, 27)[3]
+        block = R.reference(sn, pose, n, O.VARIANT_OMP, 26)[3] + R.reference(sn, pose, n, O.VARIANT_OMP, 1)[3]
+        assert np.all(kd <= block) and (kd < block).any() and (kd > 7).any() and (kd == 0).any(), sn
+        # and the radius is decided close to its edge: some accepted and some rejected leaf within 2 % of the squared radius
+        x = R._lookup(leaves, bounds, prm, src, T, Rj, 1)[0]
+        d2 = ((x[:, None, :] - leaves["centroid"][None].astype(np.float64)) ** 2).sum(2) / (R.named_scene(sn).leaf ** 2)
+        assert ((d2 > 0.98) & (d2 < 1)).any() and ((d2 > 1) & (d2 < 1.02)).any(), sn
+
+
+def test_the_tie_scene_decides_the_order_rule():
+    """ndt_pca + KDTREE on "tie": two leaves at the SAME f32 squared distance from the first source point, weights 9 and 10.  With the tie broken
+    the other way at least one entry moves by more than 100 x the widest bar any sweep test holds it to (K_EXACT 2^-24 majorant)."""
+    _, leaves, bounds, prm = R.oracle_grid(R.TIE, O.VARIANT_PCA, 27)
+    src, T, Rj = R.sweep_inputs(*R.TIE_CASE)
+    x, _, slots = R._lookup(leaves, bounds, prm, src, T, Rj, 27)
+    assert np.array_equal(x[0], np.float64(R.TieScene.TIE_POINT))
+    (a, hit_a), (b, hit_b) = slots[0], slots[1]
+    assert hit_a[0] and hit_b[0] and a[0] < b[0] and not any(hit[0] for _, hit in slots[2:])
+    ca, cb = leaves["centroid"][a[0]], leaves["centroid"][b[0]]
+    assert ca.dtype == np.float32 and np.array_equal(src[0] - ca, cb - src[0])                # mirror images, exactly, in f32
+    d2 = [np.float32((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) for d in (src[0] - ca, src[0] - cb)]
+    assert d2[0] == d2[1] < np.float32(1)
+    wa, wb = int(leaves["weight"][a[0]]), int(leaves["weight"][b[0]])
+    assert wa != wb and wa > 0 and wb > 0
+    row, maj, hits, hpp = R.ref_sweep(leaves, bounds, prm, src, T, Rj, 27)
+    swapped = R.ref_sweep(leaves, bounds, prm, src, T, Rj, 27, tie_last_first=True)
+    assert hits == swapped[2] and np.array_equal(hpp, swapped[3]) and list(hpp) == [2, 3, 2, 1, 0, 0]
+    # the edge point: B's centroid at an f32 squared distance EQUAL to float(resolution^2) -- not met, the test being strict; `<=` would meet it
+    e = R.TieScene.EDGE_ROW
+    de = src[e] - cb
+    assert np.float32((de[0] * de[0] + de[1] * de[1]) + de[2] * de[2]) == np.float32(float(prm.resolution) * float(prm.resolution))
+    assert b[0] not in [int(pos[e]) for pos, hit in slots if hit[e]] and hpp[e] == 1
+    moved = np.abs(row - swapped[0]) / (K_EXACT * R.EPS32 * maj)
+    print(f"tie rule reversed: entries move by up to {moved.max():.3g} x the bar (entry {int(moved.argmax())})")
+    assert moved.max() > 100
+    # the oracle takes the lower leaf index first
+    orow = R.reference(*R.TIE_CASE, O.VARIANT_PCA, 27)[4]
+    assert np.all(np.abs(orow - row) <= K_EXACT * R.EPS32 * maj) and not np.all(np.abs(orow - swapped[0]) <= 100 * K_EXACT * R.EPS32 * maj)
+    # ndt_omp sums without weights: there the rule moves nothing past rounding
+    _, lo, bo, po = R.oracle_grid(R.TIE, O.VARIANT_OMP, 27)
+    assert np.allclose(R.ref_sweep(lo, bo, po, src, T, Rj, 27)[0], R.ref_sweep(lo, bo, po, src, T, Rj, 27, tie_last_first=True)[0], rtol=1e-12, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------- computeHessian and calculateScore
+# Both are f64 throughout on both sides, so the oracle meets the reference within the f64 bar of tests/test_sweep_entries_gpu.py,
+# (2 hits + 2 x 27) 2^-53 majorant (measured: 0.042 of it for H, 0.014 for the score); in units of 2^-24 majorant that is ~5e-9, and K_EXACT
+# needs no second constant for the Hessian's recipe.  What the recipe changes is its INPUTS: the leaf's f64 inverse covariance, which far from the origin
+# is asymmetric by ~1e-9 of its entries (cov(a, b) is computed from S[a] mu[b], not S[b] mu[a]) -- ref_sweep therefore reads it as
+# updateHessian does, unsymmetrised; symmetrising it first moves H by 160 of these bars at offset (500, -300, 40).
+def f64_bar(hits, maj):
+    return (2 * hits + 2 * 27) * R.EPS64 * maj
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_compute_hessian_and_calculate_score_oracle_against_the_reference(variant):
+    worst_h, worst_s, hits_seen = (0.0,), (0.0,), set()
+    for case in R.tangent_cases():
+        H, mH, hits, Ho = R.hessian_reference(*case, variant)
+        assert hits > 0 and np.all(np.isfinite(H)) and np.all(mH >= np.abs(H))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.where(Ho == H, 0.0, np.abs(Ho - H) / f64_bar(hits, mH))
+        worst_h = max(worst_h, (float(u.max()), int(u.argmax())) + case)
+        assert np.all(np.abs(Ho - H) <= f64_bar(hits, mH)), (case, float(u.max()))
+        s, ms, shits, so = R.score_reference(*case, variant)
+        assert shits == hits and ms >= abs(s) > 0                      # the radius search of both hooks is the same search
+        worst_s = max(worst_s, (abs(so - s) / f64_bar(shits, ms),) + case)
+        assert abs(so - s) <= f64_bar(shits, ms), (case, s, so)
+        hits_seen.add(hits)
+        # the Hessian's recipe is not the sweep's: against the sweep's own H block (f32 covariances, f32 r) it is off by far more than this bar
+        src, _, T32, _, _ = R.tangent_case(*case)
+        sweep_H = R.ref_sweep(*R.oracle_grid(case[0], O.VARIANT_OMP, 27)[1:], src, T32, T32[:3, :3], 27)[0][7:]
+        assert not np.all(np.abs(sweep_H - H) <= 100 * f64_bar(hits, mH))
+    print(f"variant {variant}: computeHessian |oracle - ref| / f64 bar <= {worst_h[0]:.3f} at entry {worst_h[1]} of {worst_h[2:]}; "
+          f"calculateScore <= {worst_s[0]:.3f} of {worst_s[1:]}")
+    assert len(hits_seen) > 6
+
+
+# ------------------------------------------------------------------------------------------------- the matrix is the predicate
+CSRC = os.path.join(ROOT, "lv_slam_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    """tests/cpp/sweep_matrix_main.cpp, built with the sanitizers on that program alone: the rows for which each predicate says yes"""
+    exe = str(tmp_path_factory.mktemp("sweep_matrix") / "sweep_matrix_main")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "sweep_matrix_main.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stderr == "", run.stderr
+    t = {"sweep": set(), "euler": set(), "lean": set(), "asked": {"sweep": 0, "euler": 0, "lean": 0}}
+    for l in run.stdout.splitlines():
+        w = l.split()
+        if w[0] == "const":
+            t["it_batch"] = int(w[1])
+            continue
+        t["asked"][w[0]] += 1
+        if int(w[-1]):
+            t[w[0]].add(tuple(int(x) for x in w[1:-1]))
+    return t
+
+
+def _strip_comments(text):
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _tags(text):
+    """every k_sweep<...> / k_sweep_pca_kd<...> / k_align_async<...> tag of a header, comments aside: [(kernel, [argument text, ...])]"""
+    return [(m.group(1), [a.strip() for a in m.group(2).split(",")]) for m in re.finditer(r"\b(k_sweep_pca_kd|k_sweep|k_align_async)<([^<>]*)>", _strip_comments(text))]
+
+
+def _listed(header):
+    """the tags of a text list of explicit instantiations as tuples of ints, defaults filled in: ("k_sweep", pca, K, it, fine, ord, model),
+    ("k_sweep_pca_kd", ord), ("k_align_async", pca, K, ord, lean)"""
+    val = {"true": 1, "false": 0}
+    out = []
+    for kern, args in _tags(open(os.path.join(CSRC, header)).read()):
+        a = [val[x] if x in val else int(x) for x in args]
+        if kern == "k_sweep":
+            a += [8, 0, 0, 0][len(a) - 2:]               # template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0, int PM = 0>
+            assert len(a) == 6
+        elif kern == "k_align_async":
+            a += [0][len(a) - 3:]                        # template <bool PCA, int K, int ORD, bool LEAN = false>
+            assert len(a) == 4
+        else:
+            assert len(a) == 1
+        out.append((kern,) + tuple(a))
+    assert len(out) == len(set(out)), "an instantiation is listed twice"
+    return set(out)
+
+
+def _expected_list(table, ord_):
+    """what the text list of sum order / arithmetic `ord_` must hold, from the predicates' table"""
+    it8 = table["it_batch"]
+    want = {("k_sweep", pca, K, it, int(it != it8), o, 0) for pca, K, o, it in table["sweep"] if o == ord_}
+    want |= {("k_sweep", 0, K, it8, 0, o, 1) for K, o in table["euler"] if o == ord_}
+    want |= {("k_align_async", pca, K, o, 0) for pca, K, o, it in table["sweep"] if o == ord_ and it == it8}
+    want |= {("k_align_async", pca, K, o, 1) for pca, K, o in table["lean"] if o == ord_}
+    if ord_ in M.PCA_KD_ROWS and ord_ == 1:
+        want.add(("k_sweep_pca_kd", 1))
+    return want
+
+
+def test_the_test_matrices_are_the_predicates(table):
+    assert table["asked"] == {"sweep": 2 * 11 * 5 * 7, "euler": 11 * 5, "lean": 2 * 11 * 5} and table["it_batch"] == M.IT_BATCH
+    assert len(set(M.SWEEP_ROWS)) == len(M.SWEEP_ROWS) == 42 and set(M.SWEEP_ROWS) == table["sweep"]
+    assert len(set(M.EULER_ROWS)) == len(M.EULER_ROWS) == 8 and set(M.EULER_ROWS) == table["euler"]
+    # k_align_async: every batch-mode row of sweep_exists, plus the lean bodies
+    align = {(pca, K, o, 0) for pca, K, o, it in table["sweep"] if it == table["it_batch"]} | {(pca, K, o, 1) for pca, K, o in table["lean"]}
+    assert len(set(M.ALIGN_ROWS)) == len(M.ALIGN_ROWS) == 20 and set(M.ALIGN_ROWS) == align
+    # the two kernels outside the predicates: ndt_pca + KDTREE is exactly the row sweep_exists leaves out of an otherwise full K = 27 column,
+    # and PCL's class has the one kernel
+    assert M.PCA_KD_ROWS == [0, 1] and all((0, 27, o, 8) in table["sweep"] and (1, 27, o, 8) not in table["sweep"] for o in M.PCA_KD_ROWS)
+    assert M.PCL_ROWS == [(27, 0)]
+    assert len(M.SWEEP_ROWS) + len(M.PCA_KD_ROWS) + len(M.EULER_ROWS) + len(M.PCL_ROWS) + len(M.ALIGN_ROWS) == 73
+    # the GPU tests' families are the matrix, each row once
+    assert sorted(M.EXACT_BATCH + M.TOLERANCE_BATCH + M.FINE) == sorted(M.SWEEP_ROWS)
+
+
+def test_the_text_lists_are_the_predicates_rows(table):
+    assert _listed("ndt_ord1_list.hpp") == _expected_list(table, 1)
+    assert _listed("ndt_fast_list.hpp") == _expected_list(table, 2)
+    assert len(_listed("ndt_ord1_list.hpp")) == 7 + 4 + 8 + 1 + 7 + 1 and len(_listed("ndt_fast_list.hpp")) == 4 + 8 + 4
+
+
+def test_the_launchers_name_no_instantiation_outside_the_table(table):
+    text = open(os.path.join(CSRC, "ndt_host_sweep.hpp")).read()
+    assert '#include "ndt_sweep_exists.hpp"' in text and "constexpr bool sweep_exists" not in text
+    code = _strip_comments(text)
+    euler_K = sorted(int(k) for k in re.findall(r"launch_sweep_euler_k<(\d+)>", code))
+    seen = {"generic": 0, "euler": set(), "pcl": set(), "kd": set(), "align": 0}
+    for kern, a in _tags(text):
+        a = [x.replace("SWEEP_IT_BATCH", str(M.IT_BATCH)) for x in a]
+        if kern == "k_sweep_pca_kd":
+            seen["kd"].add(int(a[0]))
+        elif kern == "k_align_async":
+            assert a == ["PCA", "K", "ORD", "LEAN"]                      # launch_async_t: named by its own template tags
+            seen["align"] += 1
+        elif a[0].startswith("decltype"):
+            # the one generic launch: its tags come from dispatch_sweep, which is guarded by sweep_exists
+            assert a == ["decltype(P)::value", "decltype(KK)::value", "it", "it != 8", "decltype(O)::value"]
+            seen["generic"] += 1
+        elif a[-1] == "1":
+            assert a[:4] == ["false", "K", "8", "false"]
+            seen["euler"] |= {(K, int(a[4])) for K in euler_K}
+        else:
+            assert a[-1] == "2" and a[0] == "false" and a[2:4] == ["8", "false"]
+            seen["pcl"].add((int(a[1]), int(a[4])))
+    assert seen == {"generic": 1, "euler": table["euler"], "pcl": set(M.PCL_ROWS), "kd": set(M.PCA_KD_ROWS), "align": 1}
+    # dispatch_sweep instantiates its callee under `if constexpr (sweep_exists(...))` alone, and launch_async_t is reached through it (or with
+    # the lean tags, under `if constexpr (lean_exists(...))`)
+    assert len(re.findall(r"if constexpr \(sweep_exists\(decltype\(P\)::value, decltype\(KK\)::value, decltype\(O\)::value, decltype\(IT\)::value\)\)", code)) == 1
+    calls = re.findall(r"launch_async_t<([^<>]*)>\(", code)
+    assert sorted(calls) == sorted(["false, 7, decltype(O)::value, true", "decltype(P)::value, decltype(KK)::value, decltype(O)::value"])
+    assert "if constexpr (lean_exists(decltype(P)::value, decltype(KK)::value, decltype(O)::value))" in code
+    assert "euler_sweep_exists(sc.K, ord)" in code

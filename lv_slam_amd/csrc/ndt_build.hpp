@@ -14,7 +14,7 @@ __device__ __forceinline__ int mm_dec_max(unsigned e) { return (int)(e ^ 0x80000
 __device__ __forceinline__ int mm_dec_min(unsigned e) { return (int)(~e ^ 0x80000000u); }
 
 // getMinMax3D over finite points (voxel_grid_covariance_omp_impl.hpp:72, 211-216)
-#define MM_ILP 4
+#define MM_ILP 3        // (3 x 12 loaded floats: 52 VGPRs, three waves per SIMD beside two lean align workgroups -- four make 64 registers and two waves)
 struct __attribute__((packed, aligned(4))) MmQuad { float v[4]; };
 __global__ void __launch_bounds__(256) k_minmax(const float* __restrict__ tgt, size_t pitch, const int* __restrict__ cnt, unsigned* mm) {
   const int b = blockIdx.y;

@@ -77,6 +77,7 @@ static int build_targets_impl(mi355ndt_handle* h, const GridExtras make) {
     unsigned *vin = (npass & 1) ? h->d_vals_a : h->d_vals_b, *vout = (npass & 1) ? h->d_vals_b : h->d_vals_a;
     // (no key kernel: the first pass's histogram computes the cell indices from the points and writes them, ndt_segsort.hpp)
     const RsPoints points = {h->d_tgt, h->d_tgt_cnt, h->d_grid, cb, kin};
+    if (!rs_disjoint(kin, vin, kout, vout, total)) { h->err = "target build: the sort's two buffer pairs overlap"; return MI355NDT_ERR_STATE; }
     for (int p = 0; p < npass; p++) {
       rs_pass(s, plan.bits, kin, vin, kout, vout, pitch, p * plan.bits, h->d_rs_hist, h->d_rs_offs, tiles, B, p == 0, p == 0 ? &points : nullptr);
       std::swap(kin, kout); std::swap(vin, vout);

@@ -269,6 +269,7 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
         k_olb_grid<<<(K + 63) / 64, 64, 0, s>>>(reinterpret_cast<unsigned*>(w.mm.p), (float)h->ol_cell_mm * 1e-3f, items, K, L.nwc, gds, heads, stat);
         const RsPoints points = {X, cnt, gds, KFI_CELL_BITS, w.keys};
         unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
+        if (!rs_disjoint(ka, va, kb, vb, seg)) { h->err = "outlier batch: the sort's two buffer pairs overlap"; return MI355NDT_ERR_STATE; }
         for (int ps = 0; ps < plan.passes; ps++) {
           rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0, ps == 0 ? &points : nullptr);
           std::swap(ka, kb); std::swap(va, vb);

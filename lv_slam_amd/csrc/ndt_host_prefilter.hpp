@@ -103,6 +103,7 @@ static PfbSorted pfb_positions(hipStream_t s, VoxelScratch& w, const PfbChain& c
     k_pfa_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
     k_pfa_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, items, K, tiles, w.keep, w.grid, w.keys, w.flag);
     const RsPlan plan = rs_plan(10);               // 513 key values: one pass
+    assert(rs_disjoint(w.keys, w.vals, w.keys + seg, w.vals + seg, seg));
     rs_pass(s, plan.bits, w.keys, w.vals, w.keys + seg, w.vals + seg, rp, 0, w.hist, w.offs, tiles, K, true);
     keys = w.keys + seg; vals = w.vals + seg;
     k_pfa_heads<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, keys, vals, w.keep, items, K, tiles, w.grid, w.flag);
@@ -112,6 +113,7 @@ static PfbSorted pfb_positions(hipStream_t s, VoxelScratch& w, const PfbChain& c
       k_pfb_grid<<<(K + 63) / 64, 64, 0, s>>>(w.mm, c.leaf, w.grid, items, K, res);
       k_pfb_keys<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, items, K, tiles, w.keep, w.grid, w.keys);
       unsigned *ka = w.keys, *va = w.vals, *kb = w.keys + seg, *vb = w.vals + seg;
+      assert(rs_disjoint(ka, va, kb, vb, seg));
       for (int ps = 0; ps < plan.passes; ps++) {
         rs_pass(s, plan.bits, ka, va, kb, vb, rp, ps * plan.bits, w.hist, w.offs, tiles, K, ps == 0);
         std::swap(ka, kb); std::swap(va, vb);

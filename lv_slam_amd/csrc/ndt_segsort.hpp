@@ -11,6 +11,7 @@
 // A tile is 4096 consecutive positions handled by 4 waves, each owning 1024 consecutive positions in 16 rounds of 64, so the
 // order inside a tile is (wave, round, lane) = position order, which is what makes the pass stable.
 #pragma once
+#include <cassert>
 #include "ndt_types.hpp"
 
 #define RS_MAX_BITS 11
@@ -164,39 +165,58 @@ __global__ void __launch_bounds__((1 << BITS) > 1024 ? 1024 : (1 << BITS)) k_rs_
 }
 
 // stable scatter of one tile.  FIRST: the point id of position i is i itself (no id array to read yet).
+//
+// Registers decide how many of these waves fit beside a running align launch, so the sixteen rounds are taken in
+// groups of RS_GROUP with a scheduling fence between groups: only one group's loads, addresses and match masks are live at a time.
+// Phase 1 keeps 12 bits per position -- its rank in its (wave, round, digit) group and the group's leader lane; a leader knows its own
+// lane, so its leader field carries the group's size minus one -- two rounds to a register.  Keys (and ids) are not held from phase 1 to
+// phase 2: phase 2 reads them again (from L2), so kin / vin must not overlap kout / vout.
+#define RS_GROUP 4
 template <int BITS, bool FIRST>
 __global__ void __launch_bounds__(RS_THREADS) k_rs_scatter(const unsigned* __restrict__ kin, const unsigned* __restrict__ vin,
-                                                            unsigned* kout, unsigned* vout, size_t pitch, int shift,
+                                                            unsigned* __restrict__ kout, unsigned* __restrict__ vout, size_t pitch, int shift,
                                                             const unsigned* __restrict__ offs, int tiles, int n_targets) {
   constexpr int RS_NB = 1 << BITS;
+  static_assert(RS_ROUNDS % RS_GROUP == 0 && RS_GROUP % 2 == 0, "whole groups, whole info registers");
   __shared__ unsigned run[RS_THREADS / 64][RS_NB];
   int b, tile;
   if (!xcd_map(tiles, n_targets, tile, b)) return;   // a target's tiles on one XCD: its scattered writes combine in that L2
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   for (int d = threadIdx.x; d < (RS_THREADS / 64) * RS_NB; d += RS_THREADS) (&run[0][0])[d] = 0;
   __syncthreads();
-  const unsigned* K = kin + (size_t)b * pitch;
-  const unsigned* V = vin + (size_t)b * pitch;
+  // everything about a round but the lane is wave-uniform: one 32-bit count of the share's positions inside the segment and one
+  // lane pointer per array, the rounds at constant offsets from them
   const size_t wbase = (size_t)tile * RS_TILE + (size_t)w * (RS_TILE / 4);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  unsigned key[RS_ROUNDS], val[RS_ROUNDS], info[RS_ROUNDS];
-#pragma unroll
-  for (int r = 0; r < RS_ROUNDS; r++) {
-    const size_t i = wbase + r * 64 + lane;
-    key[r] = i < pitch ? K[i] : 0u;
-    val[r] = FIRST ? (unsigned)i : (i < pitch ? V[i] : 0u);
-  }
+  const int nw = wbase >= pitch ? 0 : (pitch - wbase < (size_t)(RS_TILE / 4) ? (int)(pitch - wbase) : RS_TILE / 4);
+  const unsigned* K = kin + (size_t)b * pitch + wbase + lane;
+  const unsigned* V = vin + (size_t)b * pitch + wbase + lane;
+  const unsigned id0 = (unsigned)wbase + (unsigned)lane;
+  unsigned* runw = run[w];
+  unsigned info[RS_ROUNDS / 2];
   // phase 1: this wave's digit counts, and for every position its rank inside its (wave, round, digit) group
 #pragma unroll
-  for (int r = 0; r < RS_ROUNDS; r++) {
-    const size_t i = wbase + r * 64 + lane;
-    const bool valid = i < pitch;
-    const unsigned d = (key[r] >> shift) & (RS_NB - 1);
-    const unsigned long long m = rs_match<BITS>(d, valid);
-    const unsigned rank = (unsigned)__popcll(m & lt), c = (unsigned)__popcll(m);
-    const unsigned leader = valid ? (unsigned)__ffsll((long long)m) - 1u : (unsigned)lane;
-    if (valid && rank == 0) run[w][d] += c;
-    info[r] = rank | (leader << 8) | (c << 16);
+  for (int g = 0; g < RS_ROUNDS / RS_GROUP; g++) {
+    unsigned key[RS_GROUP];
+#pragma unroll
+    for (int q = 0; q < RS_GROUP; q++) {
+      const int o = (g * RS_GROUP + q) * 64;
+      key[q] = o + lane < nw ? K[o] : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < RS_GROUP; q++) {
+      const int r = g * RS_GROUP + q;
+      const bool valid = r * 64 + lane < nw;
+      const unsigned d = (key[q] >> shift) & (RS_NB - 1);
+      const unsigned long long m = rs_match<BITS>(d, valid);
+      const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      const unsigned c = (unsigned)__popcll(m);
+      const bool lead = valid && rank == 0;
+      if (lead) runw[d] += c;
+      const unsigned f = lead ? c - 1u : (valid ? (unsigned)__ffsll((long long)m) - 1u : 0u);
+      const unsigned nf = rank | (f << 6);
+      info[r / 2] = (r & 1) ? (info[r / 2] | (nf << 16)) : nf;
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __syncthreads();
   // counts -> start offsets: digit d of this tile starts at offs[..][d]; waves follow each other in position order
@@ -210,16 +230,29 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_scatter(const unsigned* __res
   unsigned* KO = kout + (size_t)b * pitch;
   unsigned* VO = vout + (size_t)b * pitch;
 #pragma unroll
-  for (int r = 0; r < RS_ROUNDS; r++) {
-    const size_t i = wbase + r * 64 + lane;
-    const bool valid = i < pitch;
-    const unsigned d = (key[r] >> shift) & (RS_NB - 1);
-    const unsigned rank = info[r] & 0xffu, leader = (info[r] >> 8) & 0xffu, c = info[r] >> 16;
-    unsigned prev = 0;
-    if (valid && rank == 0) { prev = run[w][d]; run[w][d] = prev + c; }
-    prev = __shfl(prev, (int)leader);
-    if (valid) { KO[prev + rank] = key[r]; VO[prev + rank] = val[r]; }
-    __builtin_amdgcn_wave_barrier();
+  for (int g = 0; g < RS_ROUNDS / RS_GROUP; g++) {
+    unsigned key[RS_GROUP], val[RS_GROUP];
+#pragma unroll
+    for (int q = 0; q < RS_GROUP; q++) {
+      const int o = (g * RS_GROUP + q) * 64;
+      key[q] = o + lane < nw ? K[o] : 0u;
+      val[q] = FIRST ? id0 + (unsigned)o : (o + lane < nw ? V[o] : 0u);
+    }
+#pragma unroll
+    for (int q = 0; q < RS_GROUP; q++) {
+      const int r = g * RS_GROUP + q;
+      const bool valid = r * 64 + lane < nw;
+      const unsigned d = (key[q] >> shift) & (RS_NB - 1);
+      const unsigned nf = info[r / 2] >> ((r & 1) * 16);
+      const unsigned rank = nf & 63u, f = (nf >> 6) & 63u;
+      const bool lead = valid && rank == 0;
+      unsigned prev = 0;
+      if (lead) { prev = runw[d]; runw[d] = prev + f + 1u; }
+      prev = __shfl(prev, lead ? lane : (int)f);
+      if (valid) { KO[prev + rank] = key[q]; VO[prev + rank] = val[q]; }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 }
 
@@ -235,6 +268,12 @@ static inline void rs_pass_bits(hipStream_t s, const unsigned* kin, const unsign
 }
 // `first`: the point id of position i is i itself (no id array to read yet)
 // `points`: (first pass of a target build) the histogram kernel computes the keys from the points and writes them to points->keys = kin
+// NO IN-PLACE PASS: the scatter reads kin (and vin) a second time while tiles write kout / vout, so the n_segments * pitch words behind kin
+// and vin must not overlap those behind kout and vout.  The host functions that hop between two buffer pairs check rs_disjoint once.
+static inline bool rs_disjoint(const unsigned* kin, const unsigned* vin, const unsigned* kout, const unsigned* vout, size_t words, bool first = false) {
+  auto apart = [words](const unsigned* a, const unsigned* b) { return a + words <= b || b + words <= a; };
+  return apart(kin, kout) && apart(kin, vout) && apart(kout, vout) && (first || (apart(vin, kout) && apart(vin, vout) && apart(kin, vin)));
+}
 static inline void rs_pass(hipStream_t s, int bits, const unsigned* kin, const unsigned* vin, unsigned* kout, unsigned* vout, size_t pitch, int shift,
                            unsigned* hist, unsigned* offs, int tiles, int n_segments, bool first, const RsPoints* points = nullptr) {
   if (bits == 8) rs_pass_bits<8>(s, kin, vin, kout, vout, pitch, shift, hist, offs, tiles, n_segments, first, points);
@@ -251,6 +290,7 @@ static inline RsSorted rs_sort_one_segment(hipStream_t s, int field_bits, unsign
   const RsPlan plan = rs_plan(field_bits);
   const int tiles = (int)((pitch + RS_TILE - 1) / RS_TILE);
   RsSorted r = {ka, va, kb, vb};
+  assert(rs_disjoint(ka, va, kb, vb, pitch));
   for (int p = 0; p < plan.passes; p++) {
     rs_pass(s, plan.bits, r.keys, r.vals, r.keys_free, r.vals_free, pitch, p * plan.bits, hist, offs, tiles, 1, points && p == 0, p == 0 ? points : nullptr);
     std::swap(r.keys, r.keys_free); std::swap(r.vals, r.vals_free);

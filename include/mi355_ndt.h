@@ -326,6 +326,32 @@ int mi355ndt_get_partial_rows(mi355ndt_handle* h, double* out, size_t capacity, 
 /* target grid of pair `pair`: bounds (min_b_, max_b_, div_b_) and searchable voxels in ascending idx order */
 int mi355ndt_get_grid(mi355ndt_handle* h, int pair, int min_b[3], int max_b[3], int div_b[3], int* n_voxels);
 int mi355ndt_get_voxels(mi355ndt_handle* h, int pair, mi355ndt_voxel* out, size_t capacity);
+/* One target's part of one buffer of the target build, raw, as the build's kernels left it (the stage tests read every kernel's output with it).
+ * Read-only: waits for the handle's stream, copies to the host, launches nothing.  Valid only directly after a synchronous
+ * mi355ndt_batch_build_targets: MI355NDT_ERR_STATE in stream mode and when the grids are not valid; MI355NDT_ERR_BAD_ARG for an unknown `which`,
+ * for a buffer that build did not make (centroids, f64 inverse covariances, kd weights, tolerance records, sorted points) and when
+ * capacity_bytes is too small.  *bytes receives the size; `out` may be NULL to ask for it alone.  Per-leaf buffers hold n_voxels entries. */
+enum mi355ndt_build_buffer {
+  MI355NDT_BUILD_MINMAX = 0,         /* 6 unsigned: the encoded extremes min x y z, max x y z (0 = no finite point) */
+  MI355NDT_BUILD_GRIDDESC = 1,       /* the grid descriptor: int min_b[3] max_b[3] div_b[3] mul1 mul2, float leaf inv_leaf, int ncells nwords status n_voxels, unsigned word_off rec_off */
+  MI355NDT_BUILD_WORDS = 2,          /* nwords x {uint64 bits, uint32 prefix, uint32 pad} */
+  MI355NDT_BUILD_KEYS = 3,           /* pitch unsigned: the sorted cell keys */
+  MI355NDT_BUILD_IDS = 4,            /* pitch unsigned: the point index of every sorted position */
+  MI355NDT_BUILD_HEAD_CNT = 5,       /* n_slices unsigned */
+  MI355NDT_BUILD_HEADS = 6,          /* n_slices x slice_cap unsigned (the first head_cnt of every slice are written) */
+  MI355NDT_BUILD_SEG_START = 7,      /* n_voxels unsigned */
+  MI355NDT_BUILD_SUMS = 8,           /* n_voxels x 9 double: S0 S1 S2 C00 C01 C02 C11 C12 C22 */
+  MI355NDT_BUILD_CENT = 9,           /* n_voxels x 3 float */
+  MI355NDT_BUILD_VOX_IDX = 10,       /* n_voxels int */
+  MI355NDT_BUILD_VOX_N = 11,         /* n_voxels int (-1: dead) */
+  MI355NDT_BUILD_ICOV64 = 12,        /* n_voxels x 9 double */
+  MI355NDT_BUILD_KD_WEIGHT = 13,     /* n_voxels int */
+  MI355NDT_BUILD_RECS_FAST = 14,     /* n_voxels x 64 bytes: float mh[3] ml[3] c[6] pad[3], int weight */
+  MI355NDT_BUILD_SORTED_POINTS = 15, /* pitch x 4 float (MI355NDT_LEAF_SORTED engines only) */
+  MI355NDT_BUILD_INFO = 16,          /* 2 unsigned, pair-independent: bitmap words of the batch, cells of its largest grid */
+  MI355NDT_BUILD_GEOMETRY = 17       /* 5 uint64, pair-independent: pitch, records per pair, n_slices, slice_cap, key bits */
+};
+int mi355ndt_get_build_buffer(mi355ndt_handle* h, int which, int pair, void* out, size_t capacity_bytes, size_t* bytes);
 
 /* ---- batch: n independent (target, source, guess) triples on one GPU ---------------------------- */
 /* (BASELINE.json configs 3-5; the single-registration calls above are the n = 1 case) */

@@ -183,6 +183,52 @@ int mi355ndt_get_voxels(mi355ndt_handle* h, int pair, mi355ndt_voxel* out, size_
   return MI355NDT_OK;
 }
 
+// One target's part of one buffer of the last synchronous build, raw, for the stage tests: nothing is launched, nothing on the device changes.
+int mi355ndt_get_build_buffer(mi355ndt_handle* h, int which, int pair, void* out, size_t capacity_bytes, size_t* bytes) {
+  if (!h) return MI355NDT_ERR_BAD_HANDLE;
+  NOT_IN_STREAM(h);
+  if (!bytes || pair < 0 || pair >= h->n_pairs) return MI355NDT_ERR_BAD_ARG;
+  *bytes = 0;
+  GridDesc g;
+  if (int rc = read_grid_desc(h, pair, g)) return rc;        // (ERR_STATE unless h->built.valid; waits for the stream)
+  const size_t pitch = h->tgt_pitch, rpp = h->recs_per_pair, nv = (size_t)g.n_voxels;
+  const unsigned nsl = ls_slices(pitch), scap = ls_slice_cap(h->prm.min_points_per_voxel);
+  const GridExtras& made = h->built.made;
+  const void* src = nullptr;
+  size_t n = 0;
+  unsigned long long geo[5];
+  switch (which) {
+    case MI355NDT_BUILD_MINMAX:    src = h->d_minmax + (size_t)pair * 6; n = 6 * sizeof(unsigned); break;
+    case MI355NDT_BUILD_GRIDDESC:  src = &g; n = sizeof g; break;
+    case MI355NDT_BUILD_WORDS:     src = h->d_words + g.word_off; n = (size_t)g.nwords * sizeof(BitWord); break;
+    case MI355NDT_BUILD_KEYS:      src = h->d_keys_b + (size_t)pair * pitch; n = pitch * sizeof(unsigned); break;
+    case MI355NDT_BUILD_IDS:       src = h->d_vals_b + (size_t)pair * pitch; n = pitch * sizeof(unsigned); break;
+    case MI355NDT_BUILD_HEAD_CNT:  src = h->d_head_cnt + (size_t)pair * nsl; n = (size_t)nsl * sizeof(unsigned); break;
+    case MI355NDT_BUILD_HEADS:     src = h->d_heads + (size_t)pair * nsl * scap; n = (size_t)nsl * scap * sizeof(unsigned); break;
+    case MI355NDT_BUILD_SEG_START: src = h->d_seg_start + g.rec_off; n = nv * sizeof(unsigned); break;
+    case MI355NDT_BUILD_SUMS:      src = h->d_sums + (size_t)g.rec_off * 9; n = nv * 9 * sizeof(double); break;
+    case MI355NDT_BUILD_CENT:      if (!made.cent) return MI355NDT_ERR_BAD_ARG; src = h->d_cent + (size_t)g.rec_off * 3; n = nv * 3 * sizeof(float); break;
+    case MI355NDT_BUILD_VOX_IDX:   src = h->d_vox_idx + g.rec_off; n = nv * sizeof(int); break;
+    case MI355NDT_BUILD_VOX_N:     src = h->d_vox_n + g.rec_off; n = nv * sizeof(int); break;
+    case MI355NDT_BUILD_ICOV64:    if (!made.icov64) return MI355NDT_ERR_BAD_ARG; src = h->d_icov64 + (size_t)g.rec_off * 9; n = nv * 9 * sizeof(double); break;
+    case MI355NDT_BUILD_KD_WEIGHT: if (!made.kdw) return MI355NDT_ERR_BAD_ARG; src = h->d_kdw + g.rec_off; n = nv * sizeof(int); break;
+    case MI355NDT_BUILD_RECS_FAST: if (!made.recs_fast) return MI355NDT_ERR_BAD_ARG; src = h->d_recs_fast + g.rec_off; n = nv * sizeof(VoxelRecF); break;
+    case MI355NDT_BUILD_SORTED_POINTS: if (!h->leaf_sorted || !h->d_sorted) return MI355NDT_ERR_BAD_ARG; src = h->d_sorted + (size_t)pair * pitch; n = pitch * sizeof(float4); break;
+    case MI355NDT_BUILD_INFO:      src = h->d_word_off; n = 2 * sizeof(unsigned); break;
+    case MI355NDT_BUILD_GEOMETRY:
+      geo[0] = pitch; geo[1] = rpp; geo[2] = nsl; geo[3] = scap; geo[4] = (unsigned long long)h->built.cb;
+      src = geo; n = sizeof geo; break;
+    default: return MI355NDT_ERR_BAD_ARG;
+  }
+  *bytes = n;
+  if (!out) return MI355NDT_OK;
+  if (capacity_bytes < n) return MI355NDT_ERR_BAD_ARG;
+  if (n == 0) return MI355NDT_OK;
+  if (which == MI355NDT_BUILD_GRIDDESC || which == MI355NDT_BUILD_GEOMETRY) { memcpy(out, src, n); return MI355NDT_OK; }
+  HIPCHK(h, hipMemcpy(out, src, n, hipMemcpyDeviceToHost));  // (the stream is idle: read_grid_desc waited for it)
+  return MI355NDT_OK;
+}
+
 // replaces the static convertTransform helpers (ndt_omp.h:209-228); f32, the way Eigen 3.3 evaluates
 // Translation3f * AngleAxisf(X) * AngleAxisf(Y) * AngleAxisf(Z) (third-party, restated from its published algorithm: AngleAxis::toRotationMatrix,
 // Transform::rotate = linear() * R with coefficient-wise 3x3 products, a 3-term sum reduced as t0 + (t1 + t2))

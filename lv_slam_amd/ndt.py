@@ -133,7 +133,7 @@ SYMBOLS = [
     "mi355ndt_set_params", "mi355ndt_get_params", "mi355ndt_set_stream", "mi355ndt_last_error",
     "mi355ndt_set_target", "mi355ndt_set_source", "mi355ndt_promote_source_to_target", "mi355ndt_align", "mi355ndt_get_aligned", "mi355ndt_get_incremental",
     "mi355ndt_get_partial_rows",
-    "mi355ndt_get_fitness_score", "mi355ndt_fitness_score_T", "mi355ndt_prefilter", "mi355ndt_use_prefiltered", "mi355ndt_derivatives", "mi355ndt_compute_hessian", "mi355ndt_derivatives_T", "mi355ndt_get_grid", "mi355ndt_get_voxels",
+    "mi355ndt_get_fitness_score", "mi355ndt_fitness_score_T", "mi355ndt_prefilter", "mi355ndt_use_prefiltered", "mi355ndt_derivatives", "mi355ndt_compute_hessian", "mi355ndt_derivatives_T", "mi355ndt_get_grid", "mi355ndt_get_voxels", "mi355ndt_get_build_buffer",
     "mi355ndt_batch_reserve", "mi355ndt_batch_set_target", "mi355ndt_batch_set_source", "mi355ndt_batch_set_clouds", "mi355ndt_batch_bind_device",
     "mi355ndt_batch_build_targets", "mi355ndt_batch_align", "mi355ndt_batch_size", "mi355ndt_batch_pose_records", "mi355ndt_batch_fitness_scores",
     "mi355ndt_profile_enable", "mi355ndt_profile_reset", "mi355ndt_profile_get", "mi355ndt_synchronize",
@@ -280,6 +280,7 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_compute_hessian.argtypes = [vp, vp, vp]
     L.mi355ndt_get_grid.argtypes = [vp, i, vp, vp, vp, vp]
     L.mi355ndt_get_voxels.argtypes = [vp, i, vp, sz]
+    L.mi355ndt_get_build_buffer.argtypes = [vp, i, i, vp, sz, C.POINTER(sz)]
     L.mi355ndt_batch_reserve.argtypes = [vp, i, sz, sz]
     L.mi355ndt_batch_set_target.argtypes = [vp, i, vp, sz, sz]
     L.mi355ndt_batch_set_source.argtypes = [vp, i, vp, sz, sz]
@@ -458,6 +459,19 @@ def _result_dict(r: Result) -> dict:
     return dict(final=np.array(r.final_colmajor, np.float32).reshape(4, 4).T.copy(),
                 trans_probability=r.trans_probability, score=r.score, iterations=r.iterations,
                 converged=bool(r.converged), sweeps=r.sweeps, status=r.status, hits_last=r.hits_last)
+
+
+# mi355ndt_build_buffer: name -> (number, element type) of Engine.get_build_buffer
+GRIDDESC_DTYPE = np.dtype([("min_b", "<i4", 3), ("max_b", "<i4", 3), ("div_b", "<i4", 3), ("mul1", "<i4"), ("mul2", "<i4"), ("leaf", "<f4"), ("inv_leaf", "<f4"),
+                           ("ncells", "<i4"), ("nwords", "<i4"), ("status", "<i4"), ("n_voxels", "<i4"), ("word_off", "<u4"), ("rec_off", "<u4")])
+BITWORD_DTYPE = np.dtype([("bits", "<u8"), ("prefix", "<u4"), ("pad", "<u4")])
+RECF_DTYPE = np.dtype([("mh", "<f4", 3), ("ml", "<f4", 3), ("c", "<f4", 6), ("pad", "<f4", 3), ("weight", "<i4")])
+BUILD_BUFFERS = {
+    "minmax": (0, np.dtype("<u4")), "griddesc": (1, GRIDDESC_DTYPE), "words": (2, BITWORD_DTYPE), "keys": (3, np.dtype("<u4")), "ids": (4, np.dtype("<u4")),
+    "head_cnt": (5, np.dtype("<u4")), "heads": (6, np.dtype("<u4")), "seg_start": (7, np.dtype("<u4")), "sums": (8, np.dtype("<f8")), "cent": (9, np.dtype("<f4")),
+    "vox_idx": (10, np.dtype("<i4")), "vox_n": (11, np.dtype("<i4")), "icov64": (12, np.dtype("<f8")), "kd_weight": (13, np.dtype("<i4")),
+    "recs_fast": (14, RECF_DTYPE), "sorted_points": (15, np.dtype("<f4")), "info": (16, np.dtype("<u4")), "geometry": (17, np.dtype("<u8")),
+}
 
 
 class Engine:
@@ -982,6 +996,16 @@ class Engine:
         dt = np.dtype([("idx", "<i4"), ("n", "<i4"), ("mean", "<f8", 3), ("icov", "<f4", 9), ("weight", "<i4")], align=True)
         assert dt.itemsize == C.sizeof(Voxel)
         return np.frombuffer(bytes(arr), dtype=dt)[:nv].copy()
+
+    def get_build_buffer(self, which, pair: int = 0) -> np.ndarray:
+        """One target's part of one buffer of the last synchronous batch_build_targets (mi355ndt_get_build_buffer), decoded by BUILD_BUFFERS:
+        `which` is a name of that table or its number.  Read-only; NDTError -2 for a buffer the build did not make."""
+        code, dt = BUILD_BUFFERS[which] if isinstance(which, str) else next(v for v in BUILD_BUFFERS.values() if v[0] == which)
+        nb = C.c_size_t(0)
+        self._chk(self.lib.mi355ndt_get_build_buffer(self.h, code, pair, None, 0, C.byref(nb)), "get_build_buffer")
+        raw = np.zeros(max(nb.value, 1), np.uint8)
+        self._chk(self.lib.mi355ndt_get_build_buffer(self.h, code, pair, raw.ctypes.data_as(C.c_void_p), nb.value, C.byref(nb)), "get_build_buffer")
+        return raw[:nb.value].view(dt).copy()
 
     # -- batch
     def batch_reserve(self, n_pairs, max_target_pts, max_source_pts):

@@ -53,6 +53,25 @@ int main(void) {
     assert got == exp
 
 
+def test_build_buffer_codes_match_header(lib, tmp_path):
+    """Engine.get_build_buffer's table names every value of enum mi355ndt_build_buffer with the header's number; the hook refuses a NULL handle"""
+    import subprocess
+    hdr = open(os.path.join(ROOT, "include", "mi355_ndt.h")).read()
+    body = re.search(r"enum mi355ndt_build_buffer \{(.*?)\};", hdr, re.S).group(1)
+    names = re.findall(r"\b(MI355NDT_BUILD_[A-Z0-9_]+)\s*=", body)
+    assert len(names) == len(ndt.BUILD_BUFFERS) == 18
+    src = tmp_path / "bb.c"
+    src.write_text('#include <stdio.h>\n#include "mi355_ndt.h"\nint main(void) {\n' +
+                   "".join(f'  printf("%d ", {n});\n' for n in names) + "  return 0;\n}\n")
+    exe = tmp_path / "bb"
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = {n[len("MI355NDT_BUILD_"):].lower(): int(v) for n, v in zip(names, subprocess.check_output([str(exe)]).split())}
+    assert got == {k: v[0] for k, v in ndt.BUILD_BUFFERS.items()}
+    assert ndt.GRIDDESC_DTYPE.itemsize == 76 and ndt.BITWORD_DTYPE.itemsize == 16 and ndt.RECF_DTYPE.itemsize == 64
+    nb = C.c_size_t(7)
+    assert lib.mi355ndt_get_build_buffer(None, 0, 0, None, 0, C.byref(nb)) == -1
+
+
 def test_default_params_are_reference_ctor_defaults(lib):
     p = ndt.default_params()
     # ndt_omp_impl2.hpp:53-83; voxel_grid_covariance_omp.h:204-205

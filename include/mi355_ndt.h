@@ -40,7 +40,7 @@ extern "C" {
 #define MI355NDT_ERR_GRID        (-4)  /* target grid unusable: reference int32 guard
                                           (voxel_grid_covariance_omp_impl.hpp:75-84) or engine cell cap */
 #define MI355NDT_ERR_NO_DEVICE   (-5)
-#define MI355NDT_ERR_UNSUPPORTED (-6)  /* a surface or configuration MI355NDT_OPT_POSE_MODEL = 1 or MI355NDT_OPT_NDT_CLASS = 1 does not serve (mi355ndt_last_error says which) */
+#define MI355NDT_ERR_UNSUPPORTED (-6)  /* a surface or configuration MI355NDT_OPT_POSE_MODEL = 1, MI355NDT_OPT_NDT_CLASS = 1 or a non-zero MI355NDT_OPT_GROUND_CLASS does not serve (mi355ndt_last_error says which) */
 /* Positive: a warning that rides in mi355ndt_result.status, never a return code.  Set only under MI355NDT_OPT_ARITH = 1: the registration is of a kind the
  * tolerance arithmetic is not meant for -- fewer than MI355NDT_TOLERANCE_MIN_HITS (point, voxel) hits at the final pose (the Hessian of a handful of points:
  * ~1e-7 per f32 term times its condition number is no tolerance-level perturbation any more) or a run that stopped at the iteration cap (an oscillating run
@@ -298,7 +298,23 @@ enum mi355ndt_option {
    * MI355NDT_OPT_NDT_CLASS = 1) ignores the option.  No result word depends on it: both bodies write the same rows bit for bit.  Setting it while
    * a stream is open: MI355NDT_ERR_STATE; any other value: MI355NDT_ERR_BAD_ARG.  The environment variable MI355NDT_SWEEP_WAVES sets the
    * default for engines created afterwards.  mi355ndt_profile.async_waves_per_simd reports what the last launch took. */
-  MI355NDT_OPT_SWEEP_WAVES = 14
+  MI355NDT_OPT_SWEEP_WAVES = 14,
+  /* pclomp_ground::NormalDistributionsTransformGround (include/ndt_omp/ndt_ground.h, ndt_ground_impl.hpp), the class scan_matching_odom_nodelet
+   * configures as ground_s2k.  0 (default): off -- pclomp's class, every result word as without the option.  1: flag_class 1, the value its
+   * computeTransformation hard-codes: only points whose LAST neighbour (in the search's order) is a horizontal leaf (normal within 10 degrees of
+   * z) add their sums, and rows and columns 0, 1, 5 of the Hessian and the gradient are zeroed, so only z, roll and pitch move.  2: flag_class 2:
+   * vertical leaves (more than 80 degrees), rows and columns 2, 3, 4 zeroed.  3: flag_class 0: every point, nothing zeroed.  Under 1, 2 and 3
+   * alike the reference evaluates every hit twice into the gradient and the Hessian and once into the score, so g and H are twice ndt_omp's over
+   * the same hits, and its convergence test has no `nr_iterations_ &&` guard: an align can end after its first step.  The leaf's normal is the
+   * eigenvector of the smallest eigenvalue of its un-inflated covariance; the angle is acos(|n_z|) * 180 / 3.1415926, compared strictly.
+   * Served: mi355ndt_batch_align, mi355ndt_align, mi355ndt_derivatives (the doubled and masked sums), mi355ndt_calculate_score and the fitness
+   * scores (unchanged), with variant = OMP, DIRECT1 / DIRECT7 / DIRECT26, both f32 sum orders, always through the lockstep (update, sweep) rounds;
+   * MI355NDT_OPT_ARITH and latency mode are ignored.  Refused with MI355NDT_ERR_UNSUPPORTED and a message, nothing changed: variant = PCA, the
+   * live More-Thuente configuration (its computeHessian is unmasked), KDTREE (the last neighbour of a radius search is FLANN's to order),
+   * MI355NDT_OPT_POSE_MODEL = 1 or MI355NDT_OPT_NDT_CLASS = 1 beside a non-zero value, mi355ndt_sequence_run*, mi355ndt_stream_begin,
+   * mi355ndt_compute_hessian, mi355ndt_derivatives_T.  Setting the option while a stream is open: MI355NDT_ERR_STATE; any other value:
+   * MI355NDT_ERR_BAD_ARG.  A resident target that lacks the leaves' class codes is rebuilt by the next align under 1 or 2. */
+  MI355NDT_OPT_GROUND_CLASS = 15
 };
 int mi355ndt_set_option(mi355ndt_handle* h, int option, int value);
 int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value);
@@ -350,6 +366,12 @@ enum mi355ndt_build_buffer {
   MI355NDT_BUILD_SORTED_POINTS = 15, /* pitch x 4 float (MI355NDT_LEAF_SORTED engines only) */
   MI355NDT_BUILD_INFO = 16,          /* 2 unsigned, pair-independent: bitmap words of the batch, cells of its largest grid */
   MI355NDT_BUILD_GEOMETRY = 17       /* 5 uint64, pair-independent: pitch, records per pair, n_slices, slice_cap, key bits */
+};
+/* ... and the one buffer only a build under MI355NDT_OPT_GROUND_CLASS = 1 / 2 makes (MI355NDT_ERR_BAD_ARG after any other build), numbered on from
+ * the table above: n_voxels unsigned char, the class of every leaf record -- 0 dead (not a neighbour), 1 normal within 10 degrees of the z axis,
+ * 2 beyond 80 degrees, 3 neither. */
+enum mi355ndt_build_buffer_ground {
+  MI355NDT_BUILD_LEAF_CLASS = 18
 };
 int mi355ndt_get_build_buffer(mi355ndt_handle* h, int which, int pair, void* out, size_t capacity_bytes, size_t* bytes);
 

@@ -77,6 +77,9 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   // not in the reference: the tolerance arithmetic (MI355NDT_OPT_ARITH; held to 1e-4 m / 1e-5 rad instead of to the CPU restatement's bits, 1.2-1.6x faster on
   // full scans); a registration it is not meant for is re-run in the default arithmetic by computeTransformation
   inline void setArithmetic(int mode) { mi355ndt_set_option(h_, MI355NDT_OPT_ARITH, mode); }
+  // not in the reference: pclomp_ground's registration on this object (MI355NDT_OPT_GROUND_CLASS: 0 off, 1 / 2 / 3 = flag_class 1 / 2 / 0); returns
+  // the engine's code.  NormalDistributionsTransformGround below is this object constructed with 1.
+  inline int setGroundClass(int ground_class) { return mi355ndt_set_option(h_, MI355NDT_OPT_GROUND_CLASS, ground_class); }
   // ndt_omp.h:232 (impl2:1006-1040): negative log-likelihood of an already transformed cloud against the target grid
   inline double calculateScore(const PointCloudSource& cloud) const {
     double s = 0;
@@ -163,6 +166,19 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   double trans_probability_;
   const void* dev_src_;          // the cloud object (and its size) the device holds as the source
   size_t dev_src_n_;
+};
+
+// pclomp_ground::NormalDistributionsTransformGround (include/ndt_omp/ndt_ground.h; src/ndt_omp/ndt_omp.cpp:9-14): the adaptor above with
+// MI355NDT_OPT_GROUND_CLASS = 1, the flag_class its computeTransformation hard-codes.  scan_matching_odom_nodelet.cpp:329 becomes
+//     mi355ndt::NormalDistributionsTransformGround<PointT, PointT> ground_s2k;
+// and every setter of :121-126 compiles unchanged (ndt_ground.h has ndt_omp.h's).
+template <typename PointSource, typename PointTarget>
+class NormalDistributionsTransformGround : public NormalDistributionsTransform<PointSource, PointTarget> {
+ public:
+  explicit NormalDistributionsTransformGround(int device = 0) : NormalDistributionsTransform<PointSource, PointTarget>(MI355NDT_VARIANT_OMP, device) {
+    this->reg_name_ = "NormalDistributionsTransformGround";
+    if (this->setGroundClass(1) != MI355NDT_OK) throw std::runtime_error("MI355NDT_OPT_GROUND_CLASS is not known to this libmi355ndt");
+  }
 };
 
 }  // namespace mi355ndt

@@ -76,8 +76,10 @@
 #ifndef NDT_SINGLE_TU      // the ORD = 1 instantiations come from mi355_ndt_ord1.hip (built side by side with this file)
 #include "ndt_ord1_list.hpp"
 #include "ndt_fast_list.hpp"
+#include "ndt_ground_list.hpp"
 #define NDT_DECLARE extern template
 NDT_ORD1_KERNELS(NDT_DECLARE)
+NDT_GROUND_ORD1_KERNELS(NDT_DECLARE)
 NDT_FAST_KERNELS(NDT_DECLARE)
 #endif
 

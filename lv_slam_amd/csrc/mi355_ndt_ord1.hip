@@ -11,5 +11,7 @@
 #include "ndt_sweep_kd.hpp"
 #include "ndt_async.hpp"
 #include "ndt_ord1_list.hpp"
+#include "ndt_ground_list.hpp"
 #define NDT_DEFINE template
 NDT_ORD1_KERNELS(NDT_DEFINE)
+NDT_GROUND_ORD1_KERNELS(NDT_DEFINE)

@@ -508,7 +508,8 @@ __global__ void __launch_bounds__(64 * LS_WAVES) k_leafsum_tree(const float* __r
 // second pass of applyFilter (impl:282-367; pca impl:364-397): one thread per searchable leaf
 __global__ void __launch_bounds__(256) k_voxels(const GridDesc* __restrict__ gd, const double* __restrict__ sums,
                                                  VoxelRec* recs, int* vox_n, double eig_mult, int pca, double* icov64, int* kd_weight,
-                                                 VoxelRecF* recs_fast /* tolerance arithmetic only, else null */) {
+                                                 VoxelRecF* recs_fast /* tolerance arithmetic only, else null */,
+                                                 unsigned char* leaf_class = nullptr /* MI355NDT_OPT_GROUND_CLASS = 1 / 2 only */) {
   const int b = blockIdx.y;
   const GridDesc& g = gd[b];
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -578,5 +579,13 @@ __global__ void __launch_bounds__(256) k_voxels(const GridDesc* __restrict__ gd,
   // ndt_pca + KDTREE reads the weight of EVERY leaf radiusSearch returns: (int)dimension_2d_ as computed (also when the
   // inverse failed afterwards), and the constructor's 0 for an eigen-failed leaf (voxel_grid_covariance_pca.h:143)
   if (kd_weight) kd_weight[g.rec_off + id] = kd_w;
+  // pclomp_ground's gate (ndt_ground_impl.hpp:503-507): the leaf's normal is column 0 of evecs_, the eigenvector of the smallest eigenvalue of the
+  // un-inflated covariance (impl:333-335; Vm is not touched by the inflation above), normalised again; its angle to the z axis in the
+  // reference's own degrees (180 / 3.1415926, not pi), compared strictly (:527-544).  A leaf that is no neighbour (impl:395) has no class.
+  if (leaf_class) {
+    const double nn = sqrt((Vm[0] * Vm[0] + Vm[3] * Vm[3]) + Vm[6] * Vm[6]);
+    const double angle2xy = acos(fabs(Vm[6] / nn)) * 180 / 3.1415926;
+    leaf_class[g.rec_off + id] = (unsigned char)(n_out == -1 ? LEAF_CLASS_NONE : (angle2xy < 10 ? LEAF_CLASS_HORIZONTAL : (angle2xy > 80 ? LEAF_CLASS_VERTICAL : LEAF_CLASS_OTHER)));
+  }
 }
 

@@ -233,6 +233,8 @@ struct mi355ndt_handle {
   int arith = 0;                                  // MI355NDT_OPT_ARITH: 0 = the reference recipe's arithmetic, one rounding per operation; 1 = tolerance arithmetic (ndt_sweep.hpp: eval_hit_fast)
   DevBuf<VoxelRecF> d_recs_fast;                  // ... and the records its sweeps read (k_voxels writes them beside d_recs)
   int pose_model = 0;                             // MI355NDT_OPT_POSE_MODEL: 0 = ndt_omp_impl2.hpp (SE(3) tangent), 1 = ndt_omp_impl.hpp (Euler angles; ndt_grid_state.hpp says what it serves)
+  int ground_class = 0;                           // MI355NDT_OPT_GROUND_CLASS: 0 = off; 1 / 2 / 3 = pclomp_ground's flag_class 1 / 2 / 0 (ndt_grid_state.hpp says what it serves)
+  DevBuf<unsigned char> d_leaf_class;             // ... and, for 1 / 2, the class code of every leaf record (k_voxels writes it beside d_recs; SweepConst::leaf_class)
   int ndt_class = 0;                              // MI355NDT_OPT_NDT_CLASS: 0 = pclomp's class (pose_model says which implementation), 1 = pcl::NormalDistributionsTransform (f64; ndt_grid_state.hpp)
   DevBuf<double> d_pcl_rows;                      // ... and its per-pair rows as doubles, EULER_ROW_WORDS a pair slot (SweepConst::pcl_rows)
   DevBuf<float> d_euler_rows;                     // ... and its per-pair rows, EULER_ROW_WORDS floats a pair slot (SweepConst::euler_rows)
@@ -370,7 +372,10 @@ static int check_params(const mi355ndt_params& p) {
 // does the tolerance arithmetic (MI355NDT_OPT_ARITH = 1) serve this engine's configuration?  (mt_is_live, is_pca_kd, grid_extras: ndt_grid_state.hpp)
 // the pose model, the arithmetic and the grid extras of this engine's aligns, class and options taken together (ndt_grid_state.hpp)
 static int eff_model(const mi355ndt_handle* h) { return class_model(h->ndt_class, h->pose_model); }
-static GridExtras eff_extras(const mi355ndt_handle* h, bool live = false) { return grid_extras(h->prm, model_arith(h->pose_model, h->arith, h->ndt_class), live, h->ndt_class); }
+static int eff_ground(const mi355ndt_handle* h) { return h->ground_class; }
+static GridExtras eff_extras(const mi355ndt_handle* h, bool live = false) {
+  return grid_extras(h->prm, model_arith(h->pose_model, h->arith, h->ndt_class, h->ground_class), live, h->ndt_class, h->ground_class);
+}
 static bool fast_served(const mi355ndt_handle* h) { return eff_extras(h).recs_fast; }
 // the rows of the Euler model for this align's pairs, or null under model 0: what the set-up kernels, k_update and the sweeps are given
 static float* euler_rows_of(const mi355ndt_handle* h) { return eff_model(h) == POSE_MODEL_EULER ? h->d_euler_rows.p : nullptr; }
@@ -379,7 +384,8 @@ static double* pcl_rows_of(const mi355ndt_handle* h) { return h->ndt_class == ND
 // a surface model 1 does not serve at all (sequence runs, streams, computeHessian, an explicit sweep pose)
 #define NOT_EULER(h, what) do { \
     if ((h)->ndt_class == NDT_CLASS_PCL) { (h)->err = what ": not served under MI355NDT_OPT_NDT_CLASS = 1"; return MI355NDT_ERR_UNSUPPORTED; } \
-    if ((h)->pose_model == POSE_MODEL_EULER) { (h)->err = what ": not served under MI355NDT_OPT_POSE_MODEL = 1"; return MI355NDT_ERR_UNSUPPORTED; } } while (0)
+    if ((h)->pose_model == POSE_MODEL_EULER) { (h)->err = what ": not served under MI355NDT_OPT_POSE_MODEL = 1"; return MI355NDT_ERR_UNSUPPORTED; } \
+    if ((h)->ground_class != GROUND_CLASS_NONE) { (h)->err = what ": not served under a non-zero MI355NDT_OPT_GROUND_CLASS"; return MI355NDT_ERR_UNSUPPORTED; } } while (0)
 
 // "Do the grids serve this call?" -- asked by ensure_grids (ndt_host_build.hpp) and nowhere else; it builds the wanted flavour when they do not.
 //   GRIDS_ANY     any valid grid will do (the fitness scores read the base records alone); none: this configuration's is built
@@ -405,7 +411,7 @@ static void clouds_reset(mi355ndt_handle* h, bool tgt, bool src) {
   if (src) { std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0); h->have_source = false; }
 }
 // May an align of this configuration be ONE persistent launch (ndt_async.hpp)?  Asked by mi355ndt_batch_align and by mi355ndt_stream_begin.
-static bool async_served(const mi355ndt_handle* h) { return h->async_align && !mt_is_live(h->prm) && !is_pca_kd(h->prm) && model_leaves_rounds(h->pose_model, h->ndt_class); }
+static bool async_served(const mi355ndt_handle* h) { return h->async_align && !mt_is_live(h->prm) && !is_pca_kd(h->prm) && model_leaves_rounds(h->pose_model, h->ndt_class, h->ground_class); }
 // algorithmic bytes of sweeping `points` points: every point is streamed (12 B) and probes K table words
 static double sweep_alg_bytes(double points, int K) { return points * (12.0 + 4.0 * K); }
 // resident workgroup slots of a sweep launch or a persistent launch; `fast`: the tolerance arithmetic's kernels serve it.  (Callers decide

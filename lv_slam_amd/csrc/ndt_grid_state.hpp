@@ -31,6 +31,7 @@ struct GridExtras {
   bool icov64;      // f64 inverse covariances: computeHessian, calculateScore
   bool kdw;         // per-leaf weights of ndt_pca + KDTREE (dead leaves included)
   bool recs_fast;   // the tolerance arithmetic's records (and, without centroids, its tree leaf sums)
+  bool leaf_class = false;  // one class code per leaf record: the gated sweeps of MI355NDT_OPT_GROUND_CLASS = 1 / 2 (false wherever four entries are listed)
 };
 // What a configuration needs: a pure function of (parameters, MI355NDT_OPT_ARITH, live).  live: "as if the More-Thuente loop were live", the
 // flavour calculateScore and computeHessian read whatever the configuration.  MI355NDT_OPT_ARITH = 1 is served for DIRECT1 / DIRECT7 with the dead
@@ -74,6 +75,34 @@ static inline GridExtras grid_extras(const mi355ndt_params& p, int arith, bool l
   return {true, true, false, false};
 }
 
+// ---- MI355NDT_OPT_GROUND_CLASS: 0 = none of it; 1 / 2 / 3 = pclomp_ground::NormalDistributionsTransformGround (ndt_ground_impl.hpp) with
+// flag_class 1 (horizontal leaves; rows and columns 0, 1, 5 held), 2 (vertical leaves; 2, 3, 4 held), 0 (every point, nothing held).  The class is
+// ndt_omp model 0 with a per-point gate on the class of the last neighbour, a doubled gradient and Hessian, the mask and a convergence test
+// without the iteration guard.  What it is served for is answered by the overloads below and nowhere else: ndt_omp, the DIRECT searches, the dead
+// More-Thuente loop, the exact arithmetic (MI355NDT_OPT_ARITH is ignored), the lockstep rounds.  Ground class 0 gives the answers above.
+enum { GROUND_CLASS_NONE = 0, GROUND_CLASS_HORIZONTAL = 1, GROUND_CLASS_VERTICAL = 2, GROUND_CLASS_ALL = 3 };
+static inline bool ground_class_valid(int ground) { return ground >= GROUND_CLASS_NONE && ground <= GROUND_CLASS_ALL; }
+// does a sweep of this class gate its points (and read the leaves' class codes)?  Class 3 is the ungated ndt_omp sweep.
+static inline bool ground_gated(int ground) { return ground == GROUND_CLASS_HORIZONTAL || ground == GROUND_CLASS_VERTICAL; }
+static inline int model_arith(int pose_model, int arith, int ndt_class, int ground) { return ground != GROUND_CLASS_NONE ? 0 : model_arith(pose_model, arith, ndt_class); }
+static inline bool model_leaves_rounds(int pose_model, int ndt_class, int ground) { return ground == GROUND_CLASS_NONE && model_leaves_rounds(pose_model, ndt_class); }
+static inline const char* model_refuses(const mi355ndt_params& p, int pose_model, int ndt_class, int ground) {
+  if (ground == GROUND_CLASS_NONE) return model_refuses(p, pose_model, ndt_class);
+  if (ndt_class == NDT_CLASS_PCL) return "MI355NDT_OPT_GROUND_CLASS is not served together with MI355NDT_OPT_NDT_CLASS = 1 (pclomp_ground is built on pclomp's class)";
+  if (pose_model == POSE_MODEL_EULER) return "MI355NDT_OPT_GROUND_CLASS is not served together with MI355NDT_OPT_POSE_MODEL = 1 (ndt_ground_impl.hpp is the SE(3) variant)";
+  if (p.variant == MI355NDT_VARIANT_PCA) return "MI355NDT_OPT_GROUND_CLASS serves variant = OMP alone (pclomp_ground has no weights)";
+  if (mt_is_live(p)) return "MI355NDT_OPT_GROUND_CLASS does not serve the live More-Thuente configuration (step_size <= trans_epsilon / 2): its computeHessian is unmasked";
+  if (p.neighbor_mode == MI355NDT_KDTREE) return "MI355NDT_OPT_GROUND_CLASS serves DIRECT1 / DIRECT7 / DIRECT26 alone (the last neighbour of a radius search is FLANN's to order)";
+  return nullptr;
+}
+// what a configuration of this class needs: the class-0 extras at the exact arithmetic, and the class codes where the sweep is gated
+static inline GridExtras grid_extras(const mi355ndt_params& p, int arith, bool live, int ndt_class, int ground) {
+  GridExtras e = grid_extras(p, ground != GROUND_CLASS_NONE ? 0 : arith, live, ndt_class);
+  e.leaf_class = ground_gated(ground);
+  return e;
+}
+
 static inline bool grids_serve(const GridsBuilt& b, const GridExtras& need) {
-  return b.valid && (b.made.cent || !need.cent) && (b.made.icov64 || !need.icov64) && (b.made.kdw || !need.kdw) && (b.made.recs_fast || !need.recs_fast);
+  return b.valid && (b.made.cent || !need.cent) && (b.made.icov64 || !need.icov64) && (b.made.kdw || !need.kdw) && (b.made.recs_fast || !need.recs_fast) &&
+         (b.made.leaf_class || !need.leaf_class);
 }

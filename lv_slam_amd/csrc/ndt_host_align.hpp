@@ -47,7 +47,7 @@ static int align_pump(mi355ndt_handle* h, SweepConst sc, int B) {
     }
     k_update<<<B, UPD_THREADS, 0, s>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, 1, h->d_results, h->d_active,
                                        h->d_active_list, h->d_ctl + h->ctl_idx, h->prof ? h->d_hits : nullptr, h->prm.step_size, h->prm.trans_epsilon,
-                                       h->prm.max_iterations, 0, 0, nullptr, nullptr);
+                                       h->prm.max_iterations, 0, 0, nullptr, nullptr, 0);
     sc.seq_no = (int)(enq + 2);
     rc = launch_sweep(h, sc);
     if (rc) return rc;
@@ -112,7 +112,7 @@ static int batch_align_impl(mi355ndt_handle* h, const float* guesses, mi355ndt_r
   if (!guesses || !out) return MI355NDT_ERR_BAD_ARG;
   if (h->n_pairs <= 0 || !h->d_tgt || !h->d_src) return MI355NDT_ERR_STATE;
   const bool mt_live = mt_is_live(h->prm);                       // impl2:888: More-Thuente loop + computeHessian are live
-  if (const char* why = model_refuses(h->prm, h->pose_model, h->ndt_class)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }   // (nothing touched)
+  if (const char* why = model_refuses(h->prm, h->pose_model, h->ndt_class, h->ground_class)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }   // (nothing touched)
   int rc = ensure_grids(h, GRIDS_CONFIG);
   if (rc) return rc;
   rc = prep_align_ws(h);
@@ -172,12 +172,12 @@ static int batch_align_impl(mi355ndt_handle* h, const float* guesses, mi355ndt_r
       if (h->prof) HIPCHK(h, ev_begin(h, h->ev_update));
       k_update<<<B, UPD_THREADS, 0, s>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, dact + k,
                                 h->d_active_list, h->d_ctl + h->ctl_idx, h->prof ? h->d_hits : nullptr,
-                                h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations, 0, mt_live ? 1 : 0, euler_rows_of(h), pcl_rows_of(h));
+                                h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations, 0, mt_live ? 1 : 0, euler_rows_of(h), pcl_rows_of(h), eff_ground(h));
       if (mt_live) {      // pairs whose More-Thuente loop iterated get their Hessian from computeHessian (impl2:999-1000)
         launch_hessian(h, sc);
         k_update<<<B, UPD_THREADS, 0, s>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, dact + k,
                                   h->d_active_list, h->d_ctl + h->ctl_idx, nullptr,
-                                  h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations, 0, 2, nullptr, nullptr);
+                                  h->prm.step_size, h->prm.trans_epsilon, h->prm.max_iterations, 0, 2, nullptr, nullptr, 0);
       }
       if (h->prof) HIPCHK(h, ev_end(h, h->ev_update));
       int r = launch_sweep(h, sc);

@@ -65,6 +65,7 @@ static int build_targets_impl(mi355ndt_handle* h, const GridExtras make) {
   if (make.icov64) HIPCHK(h, h->d_icov64.reserve(h->d_recs.cap * 9));
   if (fast_recs) HIPCHK(h, h->d_recs_fast.reserve(h->d_recs.cap));
   if (want_kdw) HIPCHK(h, h->d_kdw.reserve(h->d_recs.cap));
+  if (make.leaf_class) HIPCHK(h, h->d_leaf_class.reserve(h->d_recs.cap));
   {
     unsigned *ka = h->d_keys_a, *kb = h->d_keys_b;
     // stable sort by cell inside every target's segment (ndt_segsort.hpp): rs_plan(cb) passes, result in kb / d_vals_b
@@ -105,7 +106,8 @@ static int build_targets_impl(mi355ndt_handle* h, const GridExtras make) {
   }
   k_voxels<<<dim3((unsigned)((rpp + 255) / 256), B), 256, 0, s>>>(h->d_grid, h->d_sums, h->d_recs, h->d_vox_n,
                                                                   h->prm.min_covar_eigvalue_mult, h->prm.variant == MI355NDT_VARIANT_PCA,
-                                                                  make.icov64 ? h->d_icov64 : nullptr, want_kdw ? h->d_kdw : nullptr, fast_recs ? h->d_recs_fast : nullptr);
+                                                                  make.icov64 ? h->d_icov64 : nullptr, want_kdw ? h->d_kdw : nullptr, fast_recs ? h->d_recs_fast : nullptr,
+                                                                  make.leaf_class ? h->d_leaf_class.p : nullptr);
   HIPCHK(h, hipGetLastError());
   if (h->prof) {
     if (build_events) HIPCHK(h, ev_end(h, h->ev_build));

@@ -60,7 +60,7 @@ static int run_hook_sweep(mi355ndt_handle* h, double* score, double g[6], double
   int rc = launch_sweep(h, sc);
   if (rc) return rc;
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 0, nullptr, nullptr);
+                                    nullptr, 0, 0, 0, 1, 0, nullptr, nullptr, eff_ground(h));
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -83,7 +83,7 @@ int mi355ndt_derivatives(mi355ndt_handle* h, const double p[6], double* score, d
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   if (!p) return MI355NDT_ERR_BAD_ARG;
   // (model 1: p = [t; roll pitch yaw] -- the cloud is moved by convertTransform(p), the rows are taken from p: k_set_pose_p)
-  if (const char* why = model_refuses(h->prm, h->pose_model, h->ndt_class)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
+  if (const char* why = model_refuses(h->prm, h->pose_model, h->ndt_class, h->ground_class)) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
   int rc = hook_ready(h);
   if (rc) return rc;
   double* dp = (double*)h->d_hook.p;
@@ -113,7 +113,7 @@ int mi355ndt_compute_hessian(mi355ndt_handle* h, const double p[6], double H[36]
   make_sweep_const(h, sc);
   launch_hessian(h, sc);
   k_update<<<1, UPD_THREADS, 0, h->stream>>>(h->d_state, h->d_partials, h->rows_per_pair, h->pts_per_chunk, h->fine_it ? 1 : 0, h->d_results, h->d_active, h->d_active_list, h->d_ctl,
-                                    nullptr, 0, 0, 0, 1, 2, nullptr, nullptr);
+                                    nullptr, 0, 0, 0, 1, 2, nullptr, nullptr, 0);
   PairState S;
   HIPCHK(h, hipMemcpyAsync(&S, h->d_state, sizeof(PairState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -212,6 +212,7 @@ int mi355ndt_get_build_buffer(mi355ndt_handle* h, int which, int pair, void* out
     case MI355NDT_BUILD_VOX_N:     src = h->d_vox_n + g.rec_off; n = nv * sizeof(int); break;
     case MI355NDT_BUILD_ICOV64:    if (!made.icov64) return MI355NDT_ERR_BAD_ARG; src = h->d_icov64 + (size_t)g.rec_off * 9; n = nv * 9 * sizeof(double); break;
     case MI355NDT_BUILD_KD_WEIGHT: if (!made.kdw) return MI355NDT_ERR_BAD_ARG; src = h->d_kdw + g.rec_off; n = nv * sizeof(int); break;
+    case MI355NDT_BUILD_LEAF_CLASS: if (!made.leaf_class) return MI355NDT_ERR_BAD_ARG; src = h->d_leaf_class + g.rec_off; n = nv * sizeof(unsigned char); break;
     case MI355NDT_BUILD_RECS_FAST: if (!made.recs_fast) return MI355NDT_ERR_BAD_ARG; src = h->d_recs_fast + g.rec_off; n = nv * sizeof(VoxelRecF); break;
     case MI355NDT_BUILD_SORTED_POINTS: if (!h->leaf_sorted || !h->d_sorted) return MI355NDT_ERR_BAD_ARG; src = h->d_sorted + (size_t)pair * pitch; n = pitch * sizeof(float4); break;
     case MI355NDT_BUILD_INFO:      src = h->d_word_off; n = 2 * sizeof(unsigned); break;

@@ -206,8 +206,13 @@ int mi355ndt_set_option(mi355ndt_handle* h, int option, int value) {
   if (!h) return MI355NDT_ERR_BAD_HANDLE;
   // (what a stream's launches and its contexts' synchronous re-runs compute with was fixed at mi355ndt_stream_begin: not changed mid-stream)
   if (h->ss && (option == MI355NDT_OPT_F32_SUM_ORDER || option == MI355NDT_OPT_ARITH || option == MI355NDT_OPT_ASYNC_ALIGN ||
-                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL || option == MI355NDT_OPT_NDT_CLASS ||
+                       option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP || option == MI355NDT_OPT_POSE_MODEL || option == MI355NDT_OPT_NDT_CLASS || option == MI355NDT_OPT_GROUND_CLASS ||
                        option == MI355NDT_OPT_SWEEP_WAVES)) NOT_IN_STREAM(h);
+  if (option == MI355NDT_OPT_GROUND_CLASS) {
+    if (!ground_class_valid(value)) return MI355NDT_ERR_BAD_ARG;
+    h->ground_class = value;                     // (what it serves and needs of the grids: ndt_grid_state.hpp; the next align builds the class codes a resident target lacks)
+    return MI355NDT_OK;
+  }
   if (option == MI355NDT_OPT_NDT_CLASS) {
     if (value != NDT_CLASS_OMP && value != NDT_CLASS_PCL) return MI355NDT_ERR_BAD_ARG;
     h->ndt_class = value;                        // (what class 1 serves and needs of the grids: ndt_grid_state.hpp; the next align rebuilds what a resident target lacks)
@@ -288,6 +293,7 @@ int mi355ndt_get_option(const mi355ndt_handle* h, int option, int* value) {
   if (option == MI355NDT_OPT_SWEEP_WAVES) { *value = h->sweep_waves; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_POSE_MODEL) { *value = h->pose_model; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_NDT_CLASS) { *value = h->ndt_class; return MI355NDT_OK; }
+  if (option == MI355NDT_OPT_GROUND_CLASS) { *value = h->ground_class; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_ASYNC_ALIGN) { *value = h->async_force ? 2 : (h->async_align ? 1 : 0); return MI355NDT_OK; }
   if (option == MI355NDT_OPT_SCORE_ONLY_LAST_SWEEP) { *value = h->score_only_last; return MI355NDT_OK; }
   if (option == MI355NDT_OPT_DEBUG_ASYNC_ABORT) { *value = h->debug_abort_pos == 0xFFFFFFFFu ? -1 : (int)h->debug_abort_pos; return MI355NDT_OK; }

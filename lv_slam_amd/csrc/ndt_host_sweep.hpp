@@ -45,7 +45,7 @@ static int prep_align_ws(mi355ndt_handle* h) {
     const bool fine_served = sweep_exists(false, neighbor_K(h->prm.neighbor_mode), 0, h->fine_tiles);
     // "small": fewer batch-mode items than two per resident wave; a sequence run sweeps ONE pair at a time whatever the number of frames
     const bool small = h->seq_running || (long long)B * h->chunks_per_pair * QUARTERS < 4LL * h->n_cu * WAVES;
-    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small && model_leaves_rounds(h->pose_model, h->ndt_class)) ? h->fine_tiles : 0;
+    h->fine_it = (h->latency_mode && fine_served && !mt_is_live(h->prm) && small && model_leaves_rounds(h->pose_model, h->ndt_class, h->ground_class)) ? h->fine_tiles : 0;
   }
   if (eff_model(h) == POSE_MODEL_EULER) HIPCHK(h, h->d_euler_rows.reserve((size_t)B * EULER_ROW_WORDS));
   if (h->ndt_class == NDT_CLASS_PCL) HIPCHK(h, h->d_pcl_rows.reserve((size_t)B * EULER_ROW_WORDS));
@@ -91,6 +91,8 @@ static void make_sweep_const(const mi355ndt_handle* h, SweepConst& sc) {
   sc.pcl_rows = pcl_rows_of(h);
   sc.icov64 = h->d_icov64.p;
   sc.d2 = d2;
+  sc.leaf_class = ground_gated(h->ground_class) ? h->d_leaf_class.p : nullptr;
+  sc.gate_code = ground_gated(h->ground_class) ? h->ground_class : 0;          // (GROUND_CLASS_HORIZONTAL / _VERTICAL are LEAF_CLASS_HORIZONTAL / _VERTICAL)
 }
 
 // The arithmetic a sweep runs in: 2 = tolerance arithmetic (MI355NDT_OPT_ARITH = 1; instantiated for DIRECT1 / DIRECT7 with the dead More-Thuente
@@ -121,6 +123,9 @@ static int launch_sweep_euler(mi355ndt_handle* h, const SweepConst& sc, int ord,
   return MI355NDT_OK;
 }
 
+// the gated sweep of MI355NDT_OPT_GROUND_CLASS = 1 / 2 (launch_sweep_ground): its launcher names its kernels in a file of its own
+#include "ndt_host_ground.hpp"
+
 static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs = -1) {
   // persistent waves: SWEEP_WPE workgroups per CU pull (pair, chunk, quarter) items until the per-XCD queues are dry
   const int ord = sweep_ord(h, sc);
@@ -142,6 +147,9 @@ static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs 
   } else if (h->pose_model == POSE_MODEL_EULER) {
     const int rc = launch_sweep_euler(h, sc, ord, grid, ctl, ctl_next);
     if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_POSE_MODEL = 1"; return rc; }
+  } else if (ground_gated(h->ground_class)) {      // pclomp_ground, flag_class 1 / 2: the gated probe stage (class 3 is the plain ndt_omp sweep below)
+    const int rc = launch_sweep_ground(h, sc, ord, grid, ctl, ctl_next);
+    if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_GROUND_CLASS = 1 / 2"; return rc; }
   } else if (!h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)
     const dim3 kdgrid((unsigned)h->chunks_per_pair, (unsigned)h->n_pairs);
     auto kd = ord == 1 ? k_sweep_pca_kd<1> : k_sweep_pca_kd<0>;

@@ -258,8 +258,9 @@ __device__ inline void pose_to_final(PairState& S) {
 
 // impl2:175-179: the step of length a_t taken at iteration count `it` ends the pair.  Reads the count and the step length alone, never
 // the sweep's sums: it is decided as soon as the step is scheduled (PairState::last_sweep).
-__device__ inline bool step_ends_pair(const int it, const double a_t, const double eps, const int max_iterations) {
-  return (it > max_iterations) || (it && (fabs(a_t) < eps));
+// ground (MI355NDT_OPT_GROUND_CLASS != 0): ndt_ground_impl.hpp:173 has no `nr_iterations_ &&` in front of the step test, so the first step can end the pair.
+__device__ inline bool step_ends_pair(const int it, const double a_t, const double eps, const int max_iterations, const bool ground = false) {
+  return (it > max_iterations) || ((ground || it) && (fabs(a_t) < eps));
 }
 
 // The body of the while loop of computeTransformation (impl2:131-183) with computeStepLengthMT (impl2:841-1003), for one pair
@@ -275,7 +276,8 @@ template <int PM = 0>
 __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res, double step_max, double eps, int max_iterations, int mt,
                                              volatile double* sol = nullptr /* non-null: the solve comes from newton_solve_side */,
                                              const bool rebased = false /* S.reb_pn / S.reb_inc hold the re-basing of this step already */,
-                                             const bool score_only_last = false, float* rows = nullptr, double* rows64 = nullptr) {
+                                             const bool score_only_last = false, float* rows = nullptr, double* rows64 = nullptr,
+                                             const int ground = 0 /* MI355NDT_OPT_GROUND_CLASS: the convergence rule above; S holds the doubled, masked sums already */) {
   double pn[6];
   float inc[16];
   const bool pre = PM == 0 && (mt == 0) && (S.phase == PH_STEP) && !rebased;     // wave-uniform: nothing has been written yet
@@ -314,7 +316,7 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     }
     for (int a = 0; a < 16; a++) S.inc_cm[a] = inc[a];                           // impl2:163
     for (int a = 0; a < 6; a++) S.p[a] = pn[a];                                  // impl2:166
-    const bool conv = step_ends_pair(S.it, S.a_t, eps, max_iterations);
+    const bool conv = step_ends_pair(S.it, S.a_t, eps, max_iterations, ground != 0);
 #ifdef NDT_DEBUG_LAST_SWEEP
     if (S.last_sweep && !conv) printf("newton_update: last_sweep set for a step that does not end the pair (it %d, a_t %g)\n", S.it, S.a_t);
 #endif
@@ -345,7 +347,7 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
       if constexpr (PM == 1) euler_step(S.p, z, 0.0, pn, S.inc_cm);              // impl.hpp:771-772
       else newton_rebase<false>(S.p, z, 0.0, pn, S.inc_cm);
       for (int a = 0; a < 6; a++) S.p[a] = pn[a];
-      const bool conv = step_ends_pair(S.it, 0.0, eps, max_iterations);
+      const bool conv = step_ends_pair(S.it, 0.0, eps, max_iterations, ground != 0);
       S.it++;
       if (conv) { finalize_pair(S, res, 1); return NEWTON_DONE; }
       continue;
@@ -359,7 +361,7 @@ __device__ __forceinline__ int newton_update(PairState& S, mi355ndt_result* res,
     S.a_t = a_t;
     // the test that follows this step's sweep (above), on the same operands: S.it and a_t are final here.  With the More-Thuente loop
     // live (mt != 0) the sweep's gradient feeds that loop, so it is never marked.
-    S.last_sweep = (mt == 0 && score_only_last && step_ends_pair(S.it, a_t, eps, max_iterations)) ? 1 : 0;
+    S.last_sweep = (mt == 0 && score_only_last && step_ends_pair(S.it, a_t, eps, max_iterations, ground != 0)) ? 1 : 0;
     S.phi0 = -S.score;                                                           // impl2:846
     S.dphi0 = dphi0 >= 0 ? -dphi0 : dphi0;                                       // impl2:849, 860
     pose_to_sweep<PM>(xt, S, rows, rows64);                                              // impl2:900 / impl.hpp:811-821

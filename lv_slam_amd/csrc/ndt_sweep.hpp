@@ -639,9 +639,13 @@ struct BatchD { unsigned slot; double m0, m1, m2; double C[9]; };            // 
 // 23 rows (set by the item body; no member at all for PM = 0, whose kernels keep their register tables).
 // PM = 2 (MI355NDT_OPT_NDT_CLASS = 1, K = 27 alone): hits are evaluated by eval_hit_pcl -- the staged points as for PM = 1, `rw` the pair's rows as
 // doubles and the grid's f64 inverse covariances, which a batch fetches in place of the record's f32 ones.
+// GATE (MI355NDT_OPT_GROUND_CLASS = 1 / 2, pclomp_ground's per-point gate): the probe stage has decided already which points' hits enter the
+// queue and has kept dead leaves out of it (sweep_item), so every queued hit is evaluated as ndt_omp's.  The tag changes nothing in here; it
+// states which instantiations exist.
 struct NoRows {};
-template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0, bool LEAN = false>
+template <bool PCA, int K, int ORD, bool SO, int Q_CAP, bool W_LATE = false, int PM = 0, bool LEAN = false, bool GATE = false>
 struct HitQueue {
+  static_assert(!GATE || (!PCA && PM == 0 && ORD != 2 && !SO && !LEAN && !W_LATE && (K == 1 || K == 7 || K == 26)), "the gated sweep: ndt_omp, DIRECT searches, exact arithmetic, full rows");
   static_assert(PM == 0 || ((PM == 1 || PM == 2) && !PCA && ORD != 2 && !SO), "the Euler model: ndt_omp, exact arithmetic, full rows");
   static_assert(PM != 2 || (K == 27 && ORD == 0), "PCL's class: the radius search, one instantiation");
   typename std::conditional<PM == 1, EulerRows, typename std::conditional<PM == 2, PclCtx, NoRows>::type>::type rw;
@@ -771,7 +775,12 @@ struct HitQueue {
 // hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
 // PM = 1 (MI355NDT_OPT_POSE_MODEL, the lockstep rounds only): phase A stages the moved point and the ORIGINAL point, phase B is eval_hit_euler over
 // the pair's rows sc.euler_rows[b] (written by whoever wrote the pair's T: k_init_state, k_set_pose_p, newton_update).
-template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false, int PM = 0, bool LEAN = false>
+// GATE (MI355NDT_OPT_GROUND_CLASS = 1 / 2, the lockstep rounds only): computeDerivatives_seg (ndt_ground_impl.hpp:484-546) adds a point's sums
+// only if the class of the LAST neighbour the search returned is the wanted one.  Probes run last to first here, so the first live neighbour the
+// probe stage meets is that one: its class code (sc.leaf_class, a byte per record, loaded where ndt_pca loads its weights) fixes the point's
+// verdict, and the point's hits are pushed only if it is sc.gate_code.  A leaf with code 0 (nr_points == -1) is no neighbour (impl:395) and
+// neither decides nor enters the queue.  A point without a live neighbour pushes nothing -- what both classes add for it.
+template <bool PCA, int K, int IT, bool FINE, int ORD, bool ASYNC, bool SO = false, int PM = 0, bool LEAN = false, bool GATE = false>
 __device__ __forceinline__ void sweep_item(const int b, const int rem, const float* __restrict__ src, const size_t pitch, const PairState* st,
                                            const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
                                            double* partials, const int rows_per_pair, const SweepConst& sc, const float* __restrict__ cent,
@@ -785,6 +794,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   static_assert(PM == 0 || (!PCA && !FAST && !ASYNC && !FINE && !SO), "the Euler model takes the lockstep rounds: ndt_omp, exact arithmetic, batch items");
   static_assert(PM != 2 || (K == 27 && ORD == 0 && IT == 8), "PCL's class: the radius search, batch items");
   static_assert(!LEAN || (ASYNC && !FINE && PM == 0 && IT == 8), "the lean body belongs to the one-launch align");
+  static_assert(!GATE || (!PCA && !FAST && !ASYNC && !FINE && !SO && PM == 0 && IT == 8 && (K == 1 || K == 7 || K == 26)), "the gated sweep takes the lockstep rounds: ndt_omp, DIRECT searches, exact arithmetic, batch items");
   typedef SweepTune<PCA, K, ORD, LEAN> Tune;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // ndt_pca's per-hit multiplier is the product of the hit's own weight and those of the point's LATER hits, known only in phase A.
@@ -799,7 +809,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   constexpr int Q_NEED = (IT / TP > 1 ? 64 : 0) + TP * (K < Q_GROUP ? K : Q_GROUP) * 64;
   constexpr int Q_CAP = FAST ? (Q_NEED <= 128 ? 128 : Q_NEED <= 256 ? 256 : Q_NEED <= 512 ? 512 : 1024) : ((K > 1 && K <= Q_GROUP) ? 1024 : 512);
   static_assert(Q_NEED <= Q_CAP, "hit queue");
-  typedef HitQueue<PCA, K, ORD, SO, Q_CAP, false, PM, LEAN> Queue;
+  typedef HitQueue<PCA, K, ORD, SO, Q_CAP, false, PM, LEAN, GATE> Queue;
   auto& q_ent = item_lds<unsigned[WAVES][Q_CAP], 0>();
   auto& q_w = item_lds<typename Queue::QW[PCAQ ? WAVES : 1][PCAQ ? Q_CAP : 1], 1>();
   // TP tiles of 64 points are probed together ("super-tile"): their point transforms, then ALL their bitmap loads, then all
@@ -825,6 +835,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
   const float* X = src + (size_t)b * 3 * pitch;
   const BitWord* W = words + g.word_off;
   const VoxelRec* R = recs + g.rec_off;
+  const unsigned char* LC = nullptr;                                           // GATE: the class codes of this grid's records
+  if constexpr (GATE) LC = sc.leaf_class + g.rec_off;
   const bool grid_ok = (g.status == GRID_OK);
   float T[12], Rj[9];
   if constexpr (ASYNC) pose_from_words(pose_w, T, Rj);
@@ -902,6 +914,9 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
         double suf[TP];
 #pragma unroll
         for (int p = 0; p < TP; p++) suf[p] = 1.0;
+        int verdict[TP];                             // GATE: the class code of the point's deciding neighbour (0: none met yet)
+#pragma unroll
+        for (int p = 0; p < TP; p++) verdict[p] = LEAF_CLASS_NONE;
         // Q_GROUP probes of every tile of the super-tile at a time: all their bitmap loads in flight together (then all
         // ndt_pca weight loads), then the ballots -- one L2 round trip per stage.
 #pragma unroll
@@ -933,6 +948,8 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
               const bool occ = bitmap_rank(bwv[p][j], cellv[p][j], idv[p][j]);
               wiv[p][j] = occ ? 1 : VOX_DEAD;
               if (PCAQ) { if (occ) wiv[p][j] = R[idv[p][j]].weight; }
+              // the gate needs the leaf's class now; code 0 = a dead leaf, which phase B would filter too late to keep it from deciding
+              if constexpr (GATE) { if (occ) { const int code = (int)LC[idv[p][j]]; wiv[p][j] = code == LEAF_CLASS_NONE ? VOX_DEAD : code; } }
               if (KD && occ) {                     // FLANN L2_Simple distance to the leaf's f32 centroid
                 const float* cp = cent + 3 * (size_t)(g.rec_off + idv[p][j]);
                 const float dx = kx[p] - cp[0], dy = ky[p] - cp[1], dz = kz[p] - cp[2];
@@ -946,7 +963,11 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
 #pragma unroll
             for (int j = 0; j < Q_GROUP; j++) {
               if (q1 - 1 - j < 0) continue;
-              const bool hit = wiv[p][j] != VOX_DEAD;     // empty cell, or nr_points == -1: not a neighbour (impl:395)
+              bool hit = wiv[p][j] != VOX_DEAD;           // empty cell, or nr_points == -1: not a neighbour (impl:395)
+              if constexpr (GATE) {                       // the first live neighbour met = the reference's last one: its class is the point's
+                if (hit && verdict[p] == LEAF_CLASS_NONE) verdict[p] = wiv[p][j];
+                hit = hit && verdict[p] == sc.gate_code;
+              }
               if (PCAQ && hit) suf[p] *= (double)wiv[p][j];
               Q.push(hit, (unsigned)slot, idv[p][j], suf[p]);
             }
@@ -1091,7 +1112,7 @@ __device__ __forceinline__ void sweep_rows_d1(const int b, const int rem0, const
   }
 }
 
-template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0, int PM = 0>
+template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0, int PM = 0, bool GATE = false>
 __global__ void __launch_bounds__(SWEEP_THREADS, (SweepTune<PCA, K, ORD>::WPE))
 k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict__ st,
         const GridDesc* __restrict__ gd, const BitWord* __restrict__ words, const VoxelRec* __restrict__ recs,
@@ -1186,7 +1207,7 @@ k_sweep(const float* __restrict__ src, size_t pitch, const PairState* __restrict
       const int rem = item % items_per_pair;        // the pair's work item = its partial row
       TL_STAMP(0);
 
-      sweep_item<PCA, K, IT, FINE, ORD, false, false, PM>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0, tl);
+      sweep_item<PCA, K, IT, FINE, ORD, false, false, PM, false, GATE>(b, rem, src, pitch, st, gd, words, recs, partials, rows_per_pair, sc, cent, grid_of, exp_tab, 0u, 0, 0, tl);
       if (next_static) { round++; item = wx + round * xw; }
       else item = __builtin_amdgcn_readfirstlane(next_item);
     }

@@ -13,7 +13,10 @@
 // launch_async picks it when the launch's AsyncLaunch::lean says so).
 // Under MI355NDT_OPT_POSE_MODEL = 1: k_sweep<false, K, 8, false, ORD, 1> for the four K and ORD = 0 / 1 (euler_sweep_exists, launch_sweep_euler).
 // Under MI355NDT_OPT_NDT_CLASS = 1: k_sweep<false, 27, 8, false, 0, 2> alone (the radius search, the f64 evaluation: launch_sweep).
+// Under MI355NDT_OPT_GROUND_CLASS = 1 / 2: k_sweep<false, K, 8, false, ORD, 0, true>, the gated probe stage, for the DIRECT searches and ORD = 0 / 1
+// (ground_sweep_exists, launch_sweep_ground; the ORD = 1 rows are spelled out in ndt_ground_list.hpp).  Class 3 runs the ungated rows.
 constexpr int SWEEP_IT_BATCH = 8;
+constexpr bool ground_sweep_exists(int K, int ord) { return (K == 1 || K == 7 || K == 26) && (ord == 0 || ord == 1); }
 constexpr bool euler_sweep_exists(int K, int ord) { return (K == 1 || K == 7 || K == 26 || K == 27) && (ord == 0 || ord == 1); }
 constexpr bool sweep_exists(bool pca, int K, int ord, int it) {
   if ((K != 1 && K != 7 && K != 26 && K != 27) || (pca && K == 27)) return false;

@@ -120,7 +120,14 @@ struct SweepConst {
   const double* pcl_rows;
   const double* icov64;
   double d2;
+  // MI355NDT_OPT_GROUND_CLASS = 1 / 2 only (the gated kernels; else null / 0): one class code per leaf record (LEAF_CLASS_*, written by k_voxels
+  // beside d_recs) and the code a point's deciding neighbour must have for the point's hits to be evaluated.
+  const unsigned char* leaf_class;
+  int gate_code;
 };
+// pclomp_ground's classes of a leaf by the angle of its normal to the z axis (ndt_ground_impl.hpp:503-507, 527-544), as k_voxels writes them
+enum { LEAF_CLASS_NONE = 0 /* not a neighbour: nr_points == -1 */, LEAF_CLASS_HORIZONTAL = 1 /* angle2xy < 10 */, LEAF_CLASS_VERTICAL = 2 /* angle2xy > 80 */,
+       LEAF_CLASS_OTHER = 3 };
 
 // Neighbour offsets in the reference's probe order.  DIRECT1: voxel_grid_covariance_omp_impl.hpp:441;
 // DIRECT7: impl:423-430; DIRECT26: pcl::getAllNeighborCellIndices() (PCL 1.8 voxel_grid.h) = 13 "half"

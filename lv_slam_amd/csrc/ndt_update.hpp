@@ -151,8 +151,20 @@ __device__ __forceinline__ bool sums_live(const int lane, const bool h_only, con
   if (score_hits_only) return lane == COL_SCORE || lane == COL_HITS;
   return lane < NACC;
 }
-__device__ __forceinline__ void store_sums(PairState& S, const int lane, const double v, const bool h_only, const bool score_hits_only, unsigned long long* hits_total) {
+// MI355NDT_OPT_GROUND_CLASS (ground = 1 / 2 / 3): what pclomp_ground does to the sums of a sweep.  Every hit is evaluated twice into the point's
+// gradient and Hessian and once into its score (ndt_ground_impl.hpp:519, 522), so g and H are twice the sums over the same hits -- exact in f64 --
+// and the score is as summed; then class 1 zeroes rows and columns 0, 1, 5 of H and g(0), g(1), g(5), class 2 rows and columns 2, 3, 4
+// (:554-567); class 3 (flag_class 0) masks nothing.  A masked entry is +0.0 whatever was summed.
+__device__ __forceinline__ double ground_sum(const int lane, const double v, const int ground) {
+  if (ground == 0 || lane < 1 || lane >= COL_HITS) return v;
+  const int masked = ground == 1 ? 0x23 : (ground == 2 ? 0x1C : 0);               // bit a: pose component a is held
+  const int i = lane < COL_H ? lane - 1 : (lane - COL_H) / 6, j = lane < COL_H ? lane - 1 : (lane - COL_H) % 6;
+  return (((masked >> i) | (masked >> j)) & 1) ? 0.0 : 2.0 * v;
+}
+__device__ __forceinline__ void store_sums(PairState& S, const int lane, const double v_in, const bool h_only, const bool score_hits_only, unsigned long long* hits_total,
+                                           const int ground = 0) {
   if (!sums_live(lane, h_only, score_hits_only)) return;
+  const double v = ground_sum(lane, v_in, ground);
   if (lane == 0) S.score = v;
   else if (lane < 7) S.g[lane - 1] = v;
   else if (lane < 43) S.H[lane - 7] = v;
@@ -203,7 +215,7 @@ template <bool SC1, bool STATE_FIRST, int PM = 0>
 __device__ __forceinline__ int update_block(const PairState* Sg, PairState& S, double (*sm)[NACC], volatile double* sol, const double* __restrict__ rows, int n_src,
                                             const int pts_per_chunk, const bool chunk_rows, mi355ndt_result* res, unsigned long long* hits_total,
                                             const double step_max, const double eps, const int max_iterations, const int reduce_only, const int mt, Timeline* tl,
-                                            float* pose_rows = nullptr, double* pose_rows64 = nullptr) {
+                                            float* pose_rows = nullptr, double* pose_rows64 = nullptr, const int ground = 0 /* MI355NDT_OPT_GROUND_CLASS */) {
   state_to_lds<SC1>(S, Sg, threadIdx.x, UPD_THREADS);
   if (threadIdx.x == 0) sol[6] = 0.0;
   if (STATE_FIRST) {
@@ -215,7 +227,7 @@ __device__ __forceinline__ int update_block(const PairState* Sg, PairState& S, d
   const int lane = threadIdx.x & 63;
   const int nchunks = (n_src + pts_per_chunk - 1) / pts_per_chunk;
   const double v = reduce_pair_rows<SC1>(rows, nchunks, sums_live(lane, mt == 2, false), sm, chunk_rows);   // the Hessian pass fills H only
-  if (threadIdx.x < 64) store_sums(S, lane, v, mt == 2, false, hits_total);
+  if (threadIdx.x < 64) store_sums(S, lane, v, mt == 2, false, hits_total, ground);
   __syncthreads();                                                               // lane 0 reads what lanes 0..43 just stored
   if (tl) tl->stamp(9);
   if (threadIdx.x >= 128) return UPD_EXIT;
@@ -227,7 +239,7 @@ __device__ __forceinline__ int update_block(const PairState* Sg, PairState& S, d
   if (reduce_only) return NEWTON_DONE;
   // (latency mode: the re-basing of p for this step was computed under the sweep, by its extra workgroup -- ndt_sweep.hpp; the tag says so)
   const bool rebased = mt == 0 && S.phase == PH_STEP && S.reb_tag == (long long)S.sweeps;
-  return newton_update<PM>(S, res, step_max, eps, max_iterations, mt, mt == 0 ? sol : nullptr, PM == 0 && rebased, false, pose_rows, pose_rows64);
+  return newton_update<PM>(S, res, step_max, eps, max_iterations, mt, mt == 0 ? sol : nullptr, PM == 0 && rebased, false, pose_rows, pose_rows64, ground);
 }
 
 // One block per pair.  `rows_per_pair` = stored rows per pair (the row stride).
@@ -235,7 +247,8 @@ NDT_KERNEL void __launch_bounds__(UPD_THREADS, 2)
 k_update(PairState* st, const double* __restrict__ partials, int rows_per_pair, int pts_per_chunk, int chunk_rows, mi355ndt_result* results,
          int* active_counter, int* active_list, SweepCtl* ctl, unsigned long long* hits_total,
          double step_max, double eps, int max_iterations, int reduce_only, int mt, float* euler_rows /* non-null: MI355NDT_OPT_POSE_MODEL 1 */,
-         double* pcl_rows /* non-null (with euler_rows): MI355NDT_OPT_NDT_CLASS 1 */) {
+         double* pcl_rows /* non-null (with euler_rows): MI355NDT_OPT_NDT_CLASS 1 */,
+         int ground /* MI355NDT_OPT_GROUND_CLASS: non-zero = the sums doubled and masked, the convergence rule of ndt_ground_impl.hpp:173 (pose model 0 alone) */) {
   __shared__ double sm[UPD_WAVES][NACC];
   __shared__ double sol[SOL_WORDS];
   __shared__ PairState S;
@@ -245,7 +258,7 @@ k_update(PairState* st, const double* __restrict__ partials, int rows_per_pair, 
                                      step_max, eps, max_iterations, reduce_only, mt, nullptr, euler_rows + (size_t)b * EULER_ROW_WORDS,
                                      pcl_rows ? pcl_rows + (size_t)b * EULER_ROW_WORDS : nullptr)
       : update_block<false, true>(&st[b], S, sm, sol, partials + (size_t)b * rows_per_pair * NACC, 0, pts_per_chunk, chunk_rows != 0, &results[b], hits_total,
-                                  step_max, eps, max_iterations, reduce_only, mt, nullptr);
+                                  step_max, eps, max_iterations, reduce_only, mt, nullptr, nullptr, nullptr, ground);
   if (rc == UPD_EXIT) return;
   if (threadIdx.x == 0 && rc == NEWTON_SWEEP) {
     atomicAdd(active_counter, 1);

@@ -178,6 +178,9 @@ OPT_POSE_MODEL = 12           # mi355ndt_option: 0 (default) = ndt_omp_impl2.hpp
 POSE_MODELS = {"se3": 0, "euler": 1}
 OPT_NDT_CLASS = 13            # mi355ndt_option: 0 (default) = pclomp::NormalDistributionsTransform; 1 = pcl::NormalDistributionsTransform, PCL's f64 class (registration_method = NDT): radius search, Euler pose vector, f64 evaluation
 NDT_CLASSES = {"omp": 0, "pcl": 1}
+OPT_GROUND_CLASS = 15         # mi355ndt_option: 0 (default) = off; 1 / 2 / 3 = pclomp_ground::NormalDistributionsTransformGround with flag_class 1 (horizontal leaves) / 2 (vertical leaves) / 0 (every point): gated sweeps, doubled g and H, masked Newton steps
+GROUND_CLASSES = {None: 0, "horizontal": 1, "vertical": 2, "all": 3}
+GROUND_FLAG_CLASS = {1: 1, 2: 2, 0: 3}   # the reference's flag_class -> the option's value
 PREFILTER_EXTENDED = 0x50467832  # MI355NDT_PREFILTER_EXTENDED: PrefilterParams.extended of the base of a PrefilterParamsEx
 DOWNSAMPLE_VOXELGRID = 0       # pcl::VoxelGrid, the prefiltering nodelet's default downsample_method
 DOWNSAMPLE_APPROX_VOXELGRID = 1  # pcl::ApproximateVoxelGrid
@@ -472,6 +475,7 @@ BUILD_BUFFERS = {
     "vox_idx": (10, np.dtype("<i4")), "vox_n": (11, np.dtype("<i4")), "icov64": (12, np.dtype("<f8")), "kd_weight": (13, np.dtype("<i4")),
     "recs_fast": (14, RECF_DTYPE), "sorted_points": (15, np.dtype("<f4")), "info": (16, np.dtype("<u4")), "geometry": (17, np.dtype("<u8")),
 }
+GROUND_BUILD_BUFFERS = {"leaf_class": (18, np.dtype("u1"))}   # enum mi355ndt_build_buffer_ground: what a build under OPT_GROUND_CLASS = 1 / 2 makes beside those
 
 
 class Engine:
@@ -1000,7 +1004,8 @@ class Engine:
     def get_build_buffer(self, which, pair: int = 0) -> np.ndarray:
         """One target's part of one buffer of the last synchronous batch_build_targets (mi355ndt_get_build_buffer), decoded by BUILD_BUFFERS:
         `which` is a name of that table or its number.  Read-only; NDTError -2 for a buffer the build did not make."""
-        code, dt = BUILD_BUFFERS[which] if isinstance(which, str) else next(v for v in BUILD_BUFFERS.values() if v[0] == which)
+        table = {**BUILD_BUFFERS, **GROUND_BUILD_BUFFERS}
+        code, dt = table[which] if isinstance(which, str) else next(v for v in table.values() if v[0] == which)
         nb = C.c_size_t(0)
         self._chk(self.lib.mi355ndt_get_build_buffer(self.h, code, pair, None, 0, C.byref(nb)), "get_build_buffer")
         raw = np.zeros(max(nb.value, 1), np.uint8)
@@ -1293,6 +1298,9 @@ class NormalDistributionsTransform:
     ndt_class="omp" (default) is pclomp's class; ndt_class="pcl" is pcl::NormalDistributionsTransform, the class select_registration_method
     hands out for registration_method = NDT (mi355ndt_set_option(MI355NDT_OPT_NDT_CLASS, 1)): the Euler pose vector, the radius search and an
     f64 evaluation.  PCL's class has neither setNeighborhoodSearchMethod nor setNumThreads, and neither has this object then.
+
+    ground_class="horizontal" | "vertical" | "all" (default None: off) is pclomp_ground::NormalDistributionsTransformGround with flag_class
+    1 | 2 | 0 (mi355ndt_set_option(MI355NDT_OPT_GROUND_CLASS, 1 | 2 | 3)): variant OMP, DIRECT1 / DIRECT7 / DIRECT26, step_size > trans_epsilon / 2.
     """
 
     _NOT_IN_PCL = ("setNeighborhoodSearchMethod", "setNumThreads")
@@ -1302,7 +1310,10 @@ class NormalDistributionsTransform:
             raise AttributeError(f"pcl::NormalDistributionsTransform has no {name}")
         return object.__getattribute__(self, name)
 
-    def __init__(self, variant: int = VARIANT_OMP, device: int = 0, pose_model: str = "se3", ndt_class: str = "omp", engine: "Engine | None" = None):
+    def __init__(self, variant: int = VARIANT_OMP, device: int = 0, pose_model: str = "se3", ndt_class: str = "omp", engine: "Engine | None" = None,
+                 ground_class: "str | None" = None):
+        if ground_class not in GROUND_CLASSES:
+            raise ValueError("ground_class must be None, 'horizontal', 'vertical' or 'all'")
         if pose_model not in POSE_MODELS:
             raise ValueError(f"pose_model must be one of {sorted(POSE_MODELS)}")
         if ndt_class not in NDT_CLASSES:
@@ -1318,6 +1329,8 @@ class NormalDistributionsTransform:
             self._eng.set_option(OPT_POSE_MODEL, POSE_MODELS[pose_model])
         if NDT_CLASSES[ndt_class]:
             self._eng.set_option(OPT_NDT_CLASS, NDT_CLASSES[ndt_class])
+        if GROUND_CLASSES[ground_class]:
+            self._eng.set_option(OPT_GROUND_CLASS, GROUND_CLASSES[ground_class])
         self._final = np.eye(4, dtype=np.float32)
         self._converged = False
         self._nr_iterations = 0
@@ -1453,3 +1466,19 @@ class NormalDistributionsTransform:
     @property
     def engine(self) -> Engine:
         return self._eng
+
+
+class NormalDistributionsTransformGround(NormalDistributionsTransform):
+    """pclomp_ground::NormalDistributionsTransformGround (include/ndt_omp/ndt_ground.h): the setters of NormalDistributionsTransform, which are
+    the reference's (ndt_ground.h has ndt_omp.h's), over MI355NDT_OPT_GROUND_CLASS.  flag_class is the reference's number and 1 by default, the
+    value its computeTransformation hard-codes: 1 horizontal leaves, 2 vertical leaves, 0 every point."""
+
+    def __init__(self, flag_class: int = 1, device: int = 0, engine: "Engine | None" = None):
+        if flag_class not in GROUND_FLAG_CLASS:
+            raise ValueError("flag_class must be 0, 1 or 2")
+        super().__init__(VARIANT_OMP, device, engine=engine, ground_class={v: k for k, v in GROUND_CLASSES.items()}[GROUND_FLAG_CLASS[flag_class]])
+        self._flag_class = flag_class
+
+    def getFlagClass(self) -> int:
+        return self._flag_class
+

@@ -15,8 +15,8 @@
 //                   computeDerivatives + computeStepLengthMT, include/ndt_omp/ndt_omp_impl2.hpp:87-188, 196-305, 841-1003;
 //                   step_size <= eps/2 only: [k_update -> k_hessian -> k_update -> k_sweep]*, impl2:622-714, 920-1000)
 // Build: __graft_entry__.build() compiles three translation units side by side and links them: this file, mi355_ndt_ord1.hip (the kernel
-// instantiations of the second f32 sum order) and mi355_ndt_fast.hip (those of the tolerance arithmetic); -DNDT_SINGLE_TU builds everything
-// from this file alone.
+// instantiations of the second f32 sum order) and mi355_ndt_fast.hip (those of the tolerance arithmetic), each its ORD's rows of the one table
+// of sweep and align kernels (ndt_sweep_exists.hpp); -DNDT_SINGLE_TU builds everything from this file alone.
 // Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp (the Newton control they call: ndt_newton.hpp) / ndt_hessian.hpp / ndt_upload.hpp / ndt_pose_record.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_prefilter_batch.hpp / ndt_prefilter_approx.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
 // C-ABI lives in ndt_engine.hpp and the ndt_host_*.hpp headers listed at the end of this file, one per surface.  It stays ONE translation unit
 // (the non-template kernels of the headers would collide across units).  Data layout in HBM: DESIGN.md.  Built with -ffp-contract=off: every
@@ -73,14 +73,10 @@
 #include "ndt_hostmem.hpp"
 #include "ndt_grid_state.hpp"
 #include "ndt_sweep_waves.hpp"
-#ifndef NDT_SINGLE_TU      // the ORD = 1 instantiations come from mi355_ndt_ord1.hip (built side by side with this file)
-#include "ndt_ord1_list.hpp"
-#include "ndt_fast_list.hpp"
-#include "ndt_ground_list.hpp"
-#define NDT_DECLARE extern template
-NDT_ORD1_KERNELS(NDT_DECLARE)
-NDT_GROUND_ORD1_KERNELS(NDT_DECLARE)
-NDT_FAST_KERNELS(NDT_DECLARE)
+#ifndef NDT_SINGLE_TU      // the ORD = 1 / 2 rows of the table come from mi355_ndt_ord1.hip / mi355_ndt_fast.hip (built side by side with this file)
+#define NDT_TU ELSEWHERE
+#define NDT_TU_X extern template
+NDT_KERNELS_OF_TU
 #endif
 
 // ------------------------------------------------------------------------------------ host side, in dependency order
@@ -90,7 +86,7 @@ NDT_FAST_KERNELS(NDT_DECLARE)
 #include "ndt_host_upload.hpp"     // reserve, bind, host-cloud uploads
 #include "ndt_host_profile.hpp"    // ev_*, mi355ndt_profile_*
 #include "ndt_host_build.hpp"      // target build
-#include "ndt_host_sweep.hpp"      // sweep dispatch, launch_sweep, launch_async
+#include "ndt_host_sweep.hpp"      // the table's kernel lookup, launch_sweep, launch_async
 #include "ndt_host_align.hpp"      // batch align, single-registration surface
 #include "ndt_host_hooks.hpp"      // parity hooks and getters
 #include "ndt_host_fitness.hpp"    // fitness scores, calculateScore

@@ -1,26 +1,25 @@
-// ndt_host_sweep.hpp -- what every align path launches: the align workspace and the SweepConst of a configuration, the dispatcher from the
-// run-time (pca, K, ord, item shape) to a kernel instantiation, launch_sweep, launch_hessian, and the one persistent launch (launch_async).
+// ndt_host_sweep.hpp -- what every align path launches: the align workspace and the SweepConst of a configuration, the lookup from a run-time
+// tag to a kernel instantiation, launch_sweep, launch_hessian, and the one persistent launch (launch_async).
 #pragma once
 
 // ---- which kernel serves ------------------------------------------------------------------------
-// sweep_exists, euler_sweep_exists, SWEEP_IT_BATCH: the instantiations of k_sweep / k_align_async that exist (host-only, shared with the tests)
+// The table of the instantiations of k_sweep / k_sweep_pca_kd / k_align_async (host-only, shared with the tests): a run-time tag is looked up
+// among its rows, and a row alone names a kernel.  nullptr: no such instantiation.
 #include "ndt_sweep_exists.hpp"
-// Run-time (pca, K, ord, it) -> compile-time tags: calls f(bool_constant<pca>, IC<K>, IC<ord>, IC<it>) for the one combination that matches and
-// returns what it returns; MI355NDT_ERR_UNSUPPORTED when no such instantiation exists.  f is only ever instantiated for combinations of
-// sweep_exists, so it may name the kernel outright.
-template <int N> using IC = std::integral_constant<int, N>;
-template <class F>
-static int dispatch_sweep(bool pca, int K, int ord, int it, F&& f) {
-  int rc = MI355NDT_ERR_UNSUPPORTED;
-  auto one = [&](auto P, auto KK, auto O, auto IT) {
-    if constexpr (sweep_exists(decltype(P)::value, decltype(KK)::value, decltype(O)::value, decltype(IT)::value))
-      if (pca == decltype(P)::value && K == decltype(KK)::value && ord == decltype(O)::value && it == decltype(IT)::value) rc = f(P, KK, O, IT);
-  };
-  auto by_it = [&](auto P, auto KK, auto O) { one(P, KK, O, IC<SWEEP_IT_BATCH>{}); one(P, KK, O, IC<1>{}); one(P, KK, O, IC<2>{}); };
-  auto by_ord = [&](auto P, auto KK) { by_it(P, KK, IC<0>{}); by_it(P, KK, IC<1>{}); by_it(P, KK, IC<2>{}); };
-  auto by_K = [&](auto P) { by_ord(P, IC<1>{}); by_ord(P, IC<7>{}); by_ord(P, IC<26>{}); by_ord(P, IC<27>{}); };
-  by_K(std::false_type{}); by_K(std::true_type{});
-  return rc;
+static_assert(SWEEP_IT_BATCH == 8, "the IT column of the table's batch-mode rows");
+using SweepKernel = void (*) NDT_SWEEP_ARGS_T;
+using KdKernel = void (*) NDT_KD_ARGS_T;
+static SweepKernel sweep_kernel(const SweepTag& t) {
+#define NDT_ROW(PCA, K, IT, ORD, PM, GATE) if (same(t, SweepTag{PCA, K, IT, ORD, PM, GATE})) return NDT_SWEEP_TAG(PCA, K, IT, ORD, PM, GATE);
+  NDT_SWEEP_ROWS(NDT_ROW)
+#undef NDT_ROW
+  return nullptr;
+}
+static KdKernel kd_kernel(int ord) {
+#define NDT_ROW(ORD) if (ord == ORD) return NDT_KD_TAG(ORD);
+  NDT_KD_ROWS(NDT_ROW)
+#undef NDT_ROW
+  return nullptr;
 }
 
 // ---- two or three waves per SIMD in a persistent launch (MI355NDT_OPT_SWEEP_WAVES) ----------------
@@ -107,24 +106,11 @@ static const VoxelRec* sweep_recs(const mi355ndt_handle* h, const SweepConst& sc
   return sweep_ord(h, sc) == 2 ? reinterpret_cast<const VoxelRec*>(h->d_recs_fast.p) : h->d_recs;
 }
 
-// the Euler model's sweep: run-time (K, ord) -> its instantiation
-template <int K>
-static void launch_sweep_euler_k(mi355ndt_handle* h, const SweepConst& sc, int ord, dim3 grid, SweepCtl* ctl, SweepCtl* ctl_next) {
-  auto kern = ord == 1 ? k_sweep<false, K, SWEEP_IT_BATCH, false, 1, 1> : k_sweep<false, K, SWEEP_IT_BATCH, false, 0, 1>;
-  kern<<<grid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_partials, h->items_per_pair, h->d_active_list, ctl,
-                                              ctl_next, sc, h->d_cent, h->d_grid_of_use);
-}
-static int launch_sweep_euler(mi355ndt_handle* h, const SweepConst& sc, int ord, dim3 grid, SweepCtl* ctl, SweepCtl* ctl_next) {
-  if (sc.pca || h->fine_it || !euler_sweep_exists(sc.K, ord) || !sc.euler_rows) return MI355NDT_ERR_UNSUPPORTED;
-  if (sc.K == 1) launch_sweep_euler_k<1>(h, sc, ord, grid, ctl, ctl_next);
-  else if (sc.K == 7) launch_sweep_euler_k<7>(h, sc, ord, grid, ctl, ctl_next);
-  else if (sc.K == 26) launch_sweep_euler_k<26>(h, sc, ord, grid, ctl, ctl_next);
-  else launch_sweep_euler_k<27>(h, sc, ord, grid, ctl, ctl_next);
-  return MI355NDT_OK;
-}
-
-// the gated sweep of MI355NDT_OPT_GROUND_CLASS = 1 / 2 (launch_sweep_ground): its launcher names its kernels in a file of its own
-#include "ndt_host_ground.hpp"
+// The three families beside the SE(3) sweeps have rows with ORD = 0 / 1 alone, so wherever one of them launches, sweep_recs(h, sc) is h->d_recs
+// (the tolerance arithmetic's records go to ORD = 2 only): launch_sweep passes sweep_recs to every kernel of the table.
+#define NDT_ROW(PCA, K, IT, ORD, PM, GATE) && !((PM != 0 || GATE) && ORD == 2)
+static_assert(true NDT_SWEEP_ROWS(NDT_ROW), "a row of the Euler model, of PCL's class or of the gated sweep reads the tolerance arithmetic's records");
+#undef NDT_ROW
 
 static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs = -1) {
   // persistent waves: SWEEP_WPE workgroups per CU pull (pair, chunk, quarter) items until the per-XCD queues are dry
@@ -137,34 +123,35 @@ static int launch_sweep(mi355ndt_handle* h, const SweepConst& sc, int max_pairs 
     grid.x = (unsigned)std::max(1LL, std::min((long long)grid.x, (items + WAVES - 1) / WAVES));
     if (sc.rebase_block) grid.x += 1;              // + the workgroup that computes the next update's re-basing instead of sweeping
   }
+  // the family, what it needs besides its kernel, and what it says when it is not served
+  SweepTag t{sc.pca != 0, sc.K, h->fine_it ? h->fine_it : SWEEP_IT_BATCH, ord, 0, false};
+  bool ready = true;
+  const char* why = "no sweep kernel serves this configuration";
   if (h->ndt_class == NDT_CLASS_PCL) {             // pcl::NormalDistributionsTransform: one kernel -- the radius search, the f64 evaluation
-    if (sc.pca || h->fine_it || sc.K != 27 || !sc.pcl_rows || !sc.icov64 || !h->built.made.icov64 || !h->built.made.cent) {
-      h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_NDT_CLASS = 1";
-      return MI355NDT_ERR_UNSUPPORTED;
-    }
-    k_sweep<false, 27, SWEEP_IT_BATCH, false, 0, 2><<<grid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_partials,
-                                                                                           h->items_per_pair, h->d_active_list, ctl, ctl_next, sc, h->d_cent, h->d_grid_of_use);
+    t.pm = 2;
+    ready = !sc.pca && !h->fine_it && sc.pcl_rows && sc.icov64 && h->built.made.icov64 && h->built.made.cent;
+    why = "no sweep kernel serves this configuration under MI355NDT_OPT_NDT_CLASS = 1";
   } else if (h->pose_model == POSE_MODEL_EULER) {
-    const int rc = launch_sweep_euler(h, sc, ord, grid, ctl, ctl_next);
-    if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_POSE_MODEL = 1"; return rc; }
-  } else if (ground_gated(h->ground_class)) {      // pclomp_ground, flag_class 1 / 2: the gated probe stage (class 3 is the plain ndt_omp sweep below)
-    const int rc = launch_sweep_ground(h, sc, ord, grid, ctl, ctl_next);
-    if (rc) { h->err = "no sweep kernel serves this configuration under MI355NDT_OPT_GROUND_CLASS = 1 / 2"; return rc; }
-  } else if (!h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)
+    t.pm = 1;
+    ready = !sc.pca && !h->fine_it && sc.euler_rows;
+    why = "no sweep kernel serves this configuration under MI355NDT_OPT_POSE_MODEL = 1";
+  } else if (ground_gated(h->ground_class)) {      // pclomp_ground, flag_class 1 / 2: the gated probe stage (class 3 is the plain ndt_omp sweep)
+    t.gate = true;
+    ready = !sc.pca && !h->fine_it && sc.leaf_class && h->built.made.leaf_class && (sc.gate_code == 1 || sc.gate_code == 2);
+    why = "no sweep kernel serves this configuration under MI355NDT_OPT_GROUND_CLASS = 1 / 2";
+  }
+  if (t.pm == 0 && !t.gate && !h->fine_it && sc.pca && sc.K == 27) {     // ndt_pca + KDTREE: order-dependent weights, the literal kernel (ndt_sweep_kd.hpp)
+    const KdKernel kd = kd_kernel(ord);
+    if (!kd) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
     const dim3 kdgrid((unsigned)h->chunks_per_pair, (unsigned)h->n_pairs);
-    auto kd = ord == 1 ? k_sweep_pca_kd<1> : k_sweep_pca_kd<0>;
     kd<<<kdgrid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, h->d_recs, h->d_cent, h->d_kdw, h->d_partials,
                                                 h->chunks_per_pair, h->d_active_list, ctl, ctl_next, sc);
   } else {
     // (the f32 sum order is a template parameter: the alternative order costs no instruction, only a second set of instantiations)
-    const int rc = dispatch_sweep(sc.pca != 0, sc.K, ord, h->fine_it ? h->fine_it : SWEEP_IT_BATCH, [&](auto P, auto KK, auto O, auto IT) {
-      constexpr int it = decltype(IT)::value;
-      k_sweep<decltype(P)::value, decltype(KK)::value, it, it != SWEEP_IT_BATCH, decltype(O)::value><<<grid, SWEEP_THREADS, 0, h->stream>>>(
-          h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, sweep_recs(h, sc), h->d_partials, h->items_per_pair, h->d_active_list, ctl, ctl_next, sc,
-          h->d_cent, h->d_grid_of_use);
-      return MI355NDT_OK;
-    });
-    if (rc) { h->err = "no sweep kernel serves this configuration"; return rc; }
+    const SweepKernel kern = ready ? sweep_kernel(t) : nullptr;
+    if (!kern) { h->err = why; return MI355NDT_ERR_UNSUPPORTED; }
+    kern<<<grid, SWEEP_THREADS, 0, h->stream>>>(h->d_src, h->src_pitch, h->d_state, h->d_grid, h->d_words, sweep_recs(h, sc), h->d_partials, h->items_per_pair,
+                                                h->d_active_list, ctl, ctl_next, sc, h->d_cent, h->d_grid_of_use);
   }
   h->ctl_idx ^= 1;                                // the block this sweep zeroed is the one the next update fills
   if (h->prof) HIPCHK(h, ev_end(h, h->ev_sweep));
@@ -200,9 +187,9 @@ struct AsyncLaunch {
 };
 #define NDT_CTX_ARGS(i) L.tab.c[i].src, L.tab.c[i].pitch, L.tab.c[i].st, L.tab.c[i].gd, L.tab.c[i].words, L.tab.c[i].recs, L.tab.c[i].partials, L.tab.c[i].src_cnt, \
                         L.tab.c[i].arrived, L.tab.c[i].cent
-template <bool PCA, int K, int ORD, bool LEAN = false>
+template <bool PCA, int K, int ORD, bool LEAN>
 static int launch_async_t(mi355ndt_handle* h, const SweepConst& sc, const AsyncLaunch& L) {
-  auto kern = k_align_async<PCA, K, ORD, LEAN>;
+  auto kern = NDT_ALIGN_TAG(PCA, K, ORD, LEAN);
   // (asked once per instantiation and device: the query sits between the prepare kernel and the launch, on the host's critical path)
   // (engines on several host threads come through here at once: the cached answer is an atomic, the query writes into a local)
   static std::atomic<int> per_cu_of_device[64];
@@ -236,12 +223,16 @@ static int launch_async(mi355ndt_handle* h, const SweepConst& sc, const AsyncLau
     if (L.ev_prepared) HIPCHK(h, hipEventRecord(L.ev_prepared, s));
   }
   if (h->prof) HIPCHK(h, ev_begin(h, h->ev_sweep));
-  // (a one-launch align sweeps batch-mode items; ORD as the sweeps of this engine have it: sweep_ord)
-  const int rc = dispatch_sweep(sc.pca != 0, sc.K, sweep_ord(h, sc), SWEEP_IT_BATCH, [&](auto P, auto KK, auto O, auto) {
-    if constexpr (lean_exists(decltype(P)::value, decltype(KK)::value, decltype(O)::value))
-      if (L.lean) return launch_async_t<false, 7, decltype(O)::value, true>(h, sc, L);
-    return launch_async_t<decltype(P)::value, decltype(KK)::value, decltype(O)::value>(h, sc, L);
-  });
+  // (a one-launch align sweeps batch-mode items; ORD as the sweeps of this engine have it: sweep_ord; the lean body when the launch asks for
+  // it and the table has the row)
+  const int rc = [&] {
+    AlignTag t{sc.pca != 0, sc.K, sweep_ord(h, sc), false};
+    t.lean = L.lean && lean_exists(t.pca, t.K, t.ord);
+#define NDT_ROW(PCA, K, ORD, LEAN) if (same(t, AlignTag{PCA, K, ORD, LEAN})) return launch_async_t<PCA, K, ORD, LEAN>(h, sc, L);
+    NDT_ALIGN_ROWS(NDT_ROW)
+#undef NDT_ROW
+    return (int)MI355NDT_ERR_UNSUPPORTED;
+  }();
   if (h->prof) HIPCHK(h, ev_end(h, h->ev_sweep));
   return rc;
 }

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstddef>
 #include "mi355_ndt.h"
+#include "ndt_sweep_exists.hpp"    // lean_exists: the LEAN rows of the table of align kernels
 
 // mi355ndt_set_option(MI355NDT_OPT_SWEEP_WAVES, value): 0 = automatic, 2, 3; not while a stream is open (its launches' geometry, its reserve and
 // its hand-over threshold were sized at mi355ndt_stream_begin)
@@ -15,8 +16,8 @@ static inline int sweep_waves_option_rc(bool in_stream, int value) {
 
 // k_align_async<false, 7, ORD, true>, ORD = 0 / 1, is the exact ndt_omp / DIRECT7 launch with the lean item body (SweepTune, ndt_sweep.hpp): 168
 // registers, three workgroups per CU, 768 slots instead of 512.  `ord`: 0 / 1 = the f32 sum orders, 2 = the tolerance arithmetic.  The lockstep
-// rounds (hence the Euler model and MI355NDT_OPT_NDT_CLASS = 1, which never leave them) have no such body.
-constexpr bool lean_exists(bool pca, int K, int ord) { return !pca && K == 7 && (ord == 0 || ord == 1); }
+// rounds (hence the Euler model and MI355NDT_OPT_NDT_CLASS = 1, which never leave them) have no such body.  lean_exists(pca, K, ord)
+// (ndt_sweep_exists.hpp) says whether the table has the row.
 
 // The lean body pays for the third wave with the mid-evaluation record prefetch, so a batch's records have to come out of L2.  What the host
 // knows without a readback:

@@ -209,43 +209,6 @@ def _strip_comments(text):
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
-def _tags(text):
-    """every k_sweep<...> / k_sweep_pca_kd<...> / k_align_async<...> tag of a header, comments aside: [(kernel, [argument text, ...])]"""
-    return [(m.group(1), [a.strip() for a in m.group(2).split(",")]) for m in re.finditer(r"\b(k_sweep_pca_kd|k_sweep|k_align_async)<([^<>]*)>", _strip_comments(text))]
-
-
-def _listed(header):
-    """the tags of a text list of explicit instantiations as tuples of ints, defaults filled in: ("k_sweep", pca, K, it, fine, ord, model),
-    ("k_sweep_pca_kd", ord), ("k_align_async", pca, K, ord, lean)"""
-    val = {"true": 1, "false": 0}
-    out = []
-    for kern, args in _tags(open(os.path.join(CSRC, header)).read()):
-        a = [val[x] if x in val else int(x) for x in args]
-        if kern == "k_sweep":
-            a += [8, 0, 0, 0][len(a) - 2:]               # template <bool PCA, int K, int IT = 8, bool FINE = false, int ORD = 0, int PM = 0>
-            assert len(a) == 6
-        elif kern == "k_align_async":
-            a += [0][len(a) - 3:]                        # template <bool PCA, int K, int ORD, bool LEAN = false>
-            assert len(a) == 4
-        else:
-            assert len(a) == 1
-        out.append((kern,) + tuple(a))
-    assert len(out) == len(set(out)), "an instantiation is listed twice"
-    return set(out)
-
-
-def _expected_list(table, ord_):
-    """what the text list of sum order / arithmetic `ord_` must hold, from the predicates' table"""
-    it8 = table["it_batch"]
-    want = {("k_sweep", pca, K, it, int(it != it8), o, 0) for pca, K, o, it in table["sweep"] if o == ord_}
-    want |= {("k_sweep", 0, K, it8, 0, o, 1) for K, o in table["euler"] if o == ord_}
-    want |= {("k_align_async", pca, K, o, 0) for pca, K, o, it in table["sweep"] if o == ord_ and it == it8}
-    want |= {("k_align_async", pca, K, o, 1) for pca, K, o in table["lean"] if o == ord_}
-    if ord_ in M.PCA_KD_ROWS and ord_ == 1:
-        want.add(("k_sweep_pca_kd", 1))
-    return want
-
-
 def test_the_test_matrices_are_the_predicates(table):
     assert table["asked"] == {"sweep": 2 * 11 * 5 * 7, "euler": 11 * 5, "lean": 2 * 11 * 5} and table["it_batch"] == M.IT_BATCH
     assert len(set(M.SWEEP_ROWS)) == len(M.SWEEP_ROWS) == 42 and set(M.SWEEP_ROWS) == table["sweep"]
@@ -262,40 +225,140 @@ def test_the_test_matrices_are_the_predicates(table):
     assert sorted(M.EXACT_BATCH + M.TOLERANCE_BATCH + M.FINE) == sorted(M.SWEEP_ROWS)
 
 
-def test_the_text_lists_are_the_predicates_rows(table):
-    assert _listed("ndt_ord1_list.hpp") == _expected_list(table, 1)
-    assert _listed("ndt_fast_list.hpp") == _expected_list(table, 2)
-    assert len(_listed("ndt_ord1_list.hpp")) == 7 + 4 + 8 + 1 + 7 + 1 and len(_listed("ndt_fast_list.hpp")) == 4 + 8 + 4
+# ------------------------------------------------------------------------------------------------- the table is the matrix, the code, the binary
+TABLE_HPP = os.path.join(CSRC, "ndt_sweep_exists.hpp")
+KERNELS = r"\b(k_sweep_pca_kd|k_sweep|k_align_async)"
 
 
-def test_the_launchers_name_no_instantiation_outside_the_table(table):
-    text = open(os.path.join(CSRC, "ndt_host_sweep.hpp")).read()
-    assert '#include "ndt_sweep_exists.hpp"' in text and "constexpr bool sweep_exists" not in text
-    code = _strip_comments(text)
-    euler_K = sorted(int(k) for k in re.findall(r"launch_sweep_euler_k<(\d+)>", code))
-    seen = {"generic": 0, "euler": set(), "pcl": set(), "kd": set(), "align": 0}
-    for kern, a in _tags(text):
-        a = [x.replace("SWEEP_IT_BATCH", str(M.IT_BATCH)) for x in a]
-        if kern == "k_sweep_pca_kd":
-            seen["kd"].add(int(a[0]))
-        elif kern == "k_align_async":
-            assert a == ["PCA", "K", "ORD", "LEAN"]                      # launch_async_t: named by its own template tags
-            seen["align"] += 1
-        elif a[0].startswith("decltype"):
-            # the one generic launch: its tags come from dispatch_sweep, which is guarded by sweep_exists
-            assert a == ["decltype(P)::value", "decltype(KK)::value", "it", "it != 8", "decltype(O)::value"]
-            seen["generic"] += 1
-        elif a[-1] == "1":
-            assert a[:4] == ["false", "K", "8", "false"]
-            seen["euler"] |= {(K, int(a[4])) for K in euler_K}
+def _rows(macro):
+    """the rows of one X-macro row list of the table header, as tuples of ints, in the order written: a parser of the test's own (the body of
+    `#define <macro>(R)` up to the first line that does not end in a backslash, comments aside, every R(...) of it)"""
+    m = re.search(r"^#define %s\(R\)((?:[^\n]*\\\n)*[^\n]*)\n" % macro, open(TABLE_HPP).read(), flags=re.M)
+    body = _strip_comments(m.group(1)).replace("\\\n", " ")
+    val = {"true": 1, "false": 0}
+    rows = [tuple(val[x] if x in val else int(x) for x in (a.strip() for a in args.split(","))) for args in re.findall(r"\bR\(([^()]*)\)", body)]
+    assert re.sub(r"\bR\([^()]*\)", "", body).strip() == "", "something in the list that is no row"
+    return rows
+
+
+@pytest.fixture(scope="module")
+def rows():
+    r = {"sweep": _rows("NDT_SWEEP_ROWS"), "kd": _rows("NDT_KD_ROWS"), "align": _rows("NDT_ALIGN_ROWS")}
+    for name, width in (("sweep", 6), ("kd", 1), ("align", 4)):
+        assert all(len(x) == width for x in r[name]) and len(set(r[name])) == len(r[name]), f"{name}: a row is listed twice"
+    return r
+
+
+@pytest.fixture(scope="module")
+def tag_table(tmp_path_factory):
+    """`sweep_matrix_main tags`, sanitizers on: sweep_exists(SweepTag) and align_exists(AlignTag) over every tag of a wide box, ground_sweep_exists"""
+    exe = str(tmp_path_factory.mktemp("sweep_tags") / "sweep_matrix_main")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "sweep_matrix_main.cpp"), "-o", exe])
+    run = subprocess.run([exe, "tags"], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stderr == "", run.stderr
+    t = {"tag": set(), "align": set(), "ground": set(), "asked": {"tag": 0, "align": 0, "ground": 0}}
+    for l in run.stdout.splitlines():
+        w = l.split()
+        t["asked"][w[0]] += 1
+        if int(w[-1]):
+            t[w[0]].add(tuple(int(x) for x in w[1:-1]))
+    return t
+
+
+def _matrix_sweep_rows():
+    """tests/sweep_matrix.py's four k_sweep families as rows of the table: (pca, K, it, ord, pm, gate)"""
+    return ([(pca, K, it, o, 0, 0) for pca, K, o, it in M.SWEEP_ROWS] + [(0, K, M.IT_BATCH, o, 1, 0) for K, o in M.EULER_ROWS] +
+            [(0, K, M.IT_BATCH, o, 2, 0) for K, o in M.PCL_ROWS] + [(0, K, M.IT_BATCH, o, 0, 1) for K, o in M.GROUND_ROWS])
+
+
+def test_the_table_is_the_matrix(rows, table, tag_table):
+    """1: the three row lists of ndt_sweep_exists.hpp are tests/sweep_matrix.py, each row once, and every predicate and wrapper says yes for the
+    rows and for nothing else of a box wider than what exists"""
+    assert sorted(rows["sweep"]) == sorted(_matrix_sweep_rows()) and len(rows["sweep"]) == 57
+    assert sorted(x[0] for x in rows["kd"]) == M.PCA_KD_ROWS and len(rows["kd"]) == 2
+    assert sorted(rows["align"]) == sorted(M.ALIGN_ROWS) and len(rows["align"]) == 20
+    assert len(M.GROUND_ROWS) == len(set(M.GROUND_ROWS)) == 6
+    assert len(rows["sweep"]) + len(rows["kd"]) + len(rows["align"]) == 79
+    # Euler for four K, ground for three, PCL the single row, kd for both orders
+    assert sorted({K for _, K, _, _, pm, _ in rows["sweep"] if pm == 1}) == [1, 7, 26, 27] and sorted({K for _, K, _, _, _, g in rows["sweep"] if g}) == [1, 7, 26]
+    assert [r for r in rows["sweep"] if r[4] == 2] == [(0, 27, 8, 0, 2, 0)] and sorted(rows["kd"]) == [(0,), (1,)]
+    # what each translation unit gets: the ORD = 1 rows (28, and the three gated ones), the ORD = 2 rows (16)
+    by_ord = lambda o: [r for r in rows["sweep"] if r[3] == o] + [r for r in rows["kd"] if r[0] == o] + [r for r in rows["align"] if r[2] == o]
+    assert len([r for r in by_ord(1) if not (len(r) == 6 and r[5])]) == 28 and len([r for r in by_ord(1) if len(r) == 6 and r[5]]) == 3
+    assert len(by_ord(2)) == 16 and len(by_ord(0)) + len(by_ord(1)) + len(by_ord(2)) == 79
+    # the predicates over the wide boxes: yes for the rows, 0 for every tag the table lacks
+    assert tag_table["asked"] == {"tag": 2 * 11 * 5 * 7 * 5 * 2, "align": 2 * 11 * 5 * 2, "ground": 11 * 5}
+    assert tag_table["tag"] == set(rows["sweep"]) and tag_table["align"] == set(rows["align"])
+    # the wrappers are the table's families: SE(3), Euler, gated, lean
+    assert table["sweep"] == {(pca, K, o, it) for pca, K, it, o, pm, g in rows["sweep"] if pm == 0 and not g}
+    assert table["euler"] == {(K, o) for pca, K, it, o, pm, g in rows["sweep"] if pm == 1}
+    assert tag_table["ground"] == {(K, o) for pca, K, it, o, pm, g in rows["sweep"] if g} == set(M.GROUND_ROWS)
+    assert table["lean"] == {(pca, K, o) for pca, K, o, lean in rows["align"] if lean} == {(0, 7, 0), (0, 7, 1)}
+    # the column FINE is gone: only the batch item size and the two fine ones occur, and k_sweep's tag derives FINE from IT
+    assert {r[2] for r in rows["sweep"]} == {1, 2, M.IT_BATCH} == {1, 2, table["it_batch"]}
+
+
+def _code(name):
+    return _strip_comments(open(os.path.join(CSRC, name)).read())
+
+
+def test_nobody_else_names_an_instantiation():
+    """2: comments aside, a k_sweep< / k_sweep_pca_kd< / k_align_async< tag occurs in lv_slam_amd/csrc in the table header's three tag macros alone
+    (the kernels' own definitions name no tag), the tag macros are only ever handed a row's own columns, launch_async_t< is called from the
+    align rows' expansion alone, and the lean row is asked for only under lean_exists"""
+    sources = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".hip", ".h")))
+    assert "ndt_sweep_exists.hpp" in sources and not {"ndt_ord1_list.hpp", "ndt_fast_list.hpp", "ndt_ground_list.hpp", "ndt_host_ground.hpp"} & set(sources)
+    tag_macros = {"NDT_SWEEP_TAG": ("PCA, K, IT, ORD, PM, GATE", "k_sweep<PCA, K, IT, (IT != SWEEP_IT_BATCH), ORD, PM, GATE>"),
+                  "NDT_KD_TAG": ("ORD", "k_sweep_pca_kd<ORD>"), "NDT_ALIGN_TAG": ("PCA, K, ORD, LEAN", "k_align_async<PCA, K, ORD, LEAN>")}
+    for f in sources:
+        lines = _code(f).splitlines()
+        named = [l.strip() for l in lines if re.search(KERNELS + r"\s*<", l)]
+        if f == "ndt_sweep_exists.hpp":
+            assert sorted(named) == sorted(f"#define {m}({args}) {tag}" for m, (args, tag) in tag_macros.items())
         else:
-            assert a[-1] == "2" and a[0] == "false" and a[2:4] == ["8", "false"]
-            seen["pcl"].add((int(a[1]), int(a[4])))
-    assert seen == {"generic": 1, "euler": table["euler"], "pcl": set(M.PCL_ROWS), "kd": set(M.PCA_KD_ROWS), "align": 1}
-    # dispatch_sweep instantiates its callee under `if constexpr (sweep_exists(...))` alone, and launch_async_t is reached through it (or with
-    # the lean tags, under `if constexpr (lean_exists(...))`)
-    assert len(re.findall(r"if constexpr \(sweep_exists\(decltype\(P\)::value, decltype\(KK\)::value, decltype\(O\)::value, decltype\(IT\)::value\)\)", code)) == 1
-    calls = re.findall(r"launch_async_t<([^<>]*)>\(", code)
-    assert sorted(calls) == sorted(["false, 7, decltype(O)::value, true", "decltype(P)::value, decltype(KK)::value, decltype(O)::value"])
-    assert "if constexpr (lean_exists(decltype(P)::value, decltype(KK)::value, decltype(O)::value))" in code
-    assert "euler_sweep_exists(sc.K, ord)" in code
+            assert named == [], (f, named)
+        for m, (args, _) in tag_macros.items():      # every use of a tag macro passes the columns of the row being expanded, never a literal
+            for used in re.findall(r"\b%s\(([^()]*)\)" % m, "\n".join(lines)):
+                assert used == args, (f, m, used)
+    # ... and the uses sit in row expansions: `#define <row macro>(<columns>) ...` lines, and launch_async_t's own template tags
+    host = _code("ndt_host_sweep.hpp")
+    for l in host.splitlines():
+        if re.search(r"\bNDT_(SWEEP|KD|ALIGN)_TAG\(", l):
+            assert l.startswith("#define NDT_ROW(") or l.strip() == "auto kern = NDT_ALIGN_TAG(PCA, K, ORD, LEAN);", l
+    assert not any(re.search(r"\bNDT_(SWEEP|KD|ALIGN)_TAG\(", _code(f)) for f in sources if f not in ("ndt_sweep_exists.hpp", "ndt_host_sweep.hpp"))
+    calls = [(f, l.strip()) for f in sources for l in _code(f).splitlines() if "launch_async_t<" in l]
+    assert calls == [("ndt_host_sweep.hpp", "#define NDT_ROW(PCA, K, ORD, LEAN) if (same(t, AlignTag{PCA, K, ORD, LEAN})) return launch_async_t<PCA, K, ORD, LEAN>(h, sc, L);")]
+    assert re.search(r"#define NDT_ROW\(PCA, K, ORD, LEAN\)[^\n]*\n\s*NDT_ALIGN_ROWS\(NDT_ROW\)\n#undef NDT_ROW", host)
+    assert "t.lean = L.lean && lean_exists(t.pca, t.K, t.ord);" in host and len(re.findall(r"\.lean\s*=[^=]", host)) == 1
+    # the three translation units expand the table and nothing else: each for its own ORD
+    for tu, name, x in (("mi355_ndt.hip", "ELSEWHERE", "extern template"), ("mi355_ndt_ord1.hip", "ORD1", "template"), ("mi355_ndt_fast.hip", "FAST", "template")):
+        assert re.search(r"#define NDT_TU %s\n#define NDT_TU_X %s\nNDT_KERNELS_OF_TU\n" % (name, x), _code(tu)), tu
+    table_hpp = _code("ndt_sweep_exists.hpp")
+    in_tu = {(tu, int(o)): int(v) for tu, o, v in re.findall(r"#define NDT_ROW_IN_TU_([A-Z0-9]+)_(\d) (\d)", table_hpp)}
+    assert in_tu == {(tu, o): int(o in own) for tu, own in (("ORD1", (1,)), ("FAST", (2,)), ("ELSEWHERE", (1, 2))) for o in (0, 1, 2)}
+
+
+def _stubs(path):
+    """the host-side launch stubs of the three kernel templates that a file defines, from nm and c++filt: [("k_sweep", (0, 7, 8, 0, 0, 0, 0)), ...]"""
+    assert os.path.exists(path), f"{path}: __graft_entry__.build() leaves it"
+    syms = subprocess.run(["nm", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    names = subprocess.run(["c++filt"], input=syms, capture_output=True, text=True, check=True).stdout
+    val = {"true": 1, "false": 0}
+    return [(k, tuple(val[x] if x in val else int(x) for x in (a.strip() for a in args.split(","))))
+            for k, args in re.findall(r"\b__device_stub__" + KERNELS[2:] + r"<([^<>]*)>\(", names)]
+
+
+def test_the_binary_is_the_table(rows):
+    """3: the library holds a launch stub for exactly the 79 rows, and each of the three objects build() leaves defines exactly the rows of its
+    own ORD: the kernels of the second sum order and of the tolerance arithmetic are compiled beside the first unit, not in it"""
+    it8 = M.IT_BATCH
+    want = ([("k_sweep", (pca, K, it, int(it != it8), o, pm, g)) for pca, K, it, o, pm, g in rows["sweep"]] + [("k_sweep_pca_kd", r) for r in rows["kd"]] +
+            [("k_align_async", r) for r in rows["align"]])
+    ord_of = lambda s: s[1][{"k_sweep": 4, "k_sweep_pca_kd": 0, "k_align_async": 2}[s[0]]]
+    assert len(want) == len(set(want)) == 79
+    lib = _stubs(os.path.join(ROOT, "lv_slam_amd", "libmi355ndt.so"))
+    assert sorted(lib) == sorted(want)
+    for obj, ords, n in (("mi355_ndt.hip.o", (0,), 32), ("mi355_ndt_ord1.hip.o", (1,), 28 + 3), ("mi355_ndt_fast.hip.o", (2,), 16)):
+        got = _stubs(os.path.join(CSRC, obj))
+        assert sorted(got) == sorted(s for s in want if ord_of(s) in ords) and len(got) == n, obj

@@ -16,7 +16,7 @@
 #include "ndt_update.hpp"
 #include "ndt_pose_record.hpp"
 #include "ndt_async.hpp"
-#include "ndt_ord1_list.hpp"    // NDT_ASYNC_ARGS_T
+#include "ndt_sweep_exists.hpp"    // NDT_ASYNC_ARGS_T
 // the lean item body alone, full and score-only, at the lean kernel's launch bounds
 template <int ORD, bool SO>
 __global__ void __launch_bounds__(SWEEP_THREADS, 3)

@@ -537,7 +537,7 @@ int mi355ndt_use_prefiltered(mi355ndt_handle* h, int role);
  * (vertical_angle_calibration, :183-220): in f64, Eigen 3.3's cross, normalize (a point on the z axis keeps a zero axis and is scaled by
  * cos), AngleAxisd::toRotationMatrix and 3x3 product restated operation for operation, no FMA, the result cast to f32; a point with a
  * non-finite coordinate is left as it is.  The gate and the centroids see the moved and calibrated points.
- * downsample_method = MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID is pcl::ApproximateVoxelGrid (PCL 1.8.1 approximate_voxel_grid.hpp, x, y, z only):
+ * downsample_method = MI355NDT_DOWNSAMPLE_APPROX_VOXELGRID is pcl::ApproximateVoxelGrid (PCL 1.8.1 approximate_voxel_grid.hpp; the intensity: mi355ndt_prefilter_params_ex2):
  * inv = 1.0f / leaf; cell = (int)floor(coord * inv), the product f32; a history table of 512 entries indexed by
  * (ix * 7171 + iy * 3079 + iz * 4231) & 511, walked in input order; a point whose entry holds another cell flushes it -- f32 sum / (float)count
  * is appended to the output --; after the last point the non-empty entries are flushed in table order.  A cell can appear more than once and
@@ -571,12 +571,40 @@ typedef struct mi355ndt_prefilter_params_ex {
 } mi355ndt_prefilter_params_ex;
 int mi355ndt_prefilter_params_ex_default(mi355ndt_prefilter_params_ex* p);
 
+/* The fourth channel of pcl::PointXYZI, behind the two structs above in the same way: mi355ndt_prefilter_params keeps its 96 bytes and
+ * mi355ndt_prefilter_params_ex its size and offsets, and every function that takes a `const mi355ndt_prefilter_params*` also takes
+ * `&ex2.ex.base`.  With base.extended == MI355NDT_PREFILTER_EXTENDED2 the three fields of `ex` are read as under MI355NDT_PREFILTER_EXTENDED,
+ * and intensity_offset_bytes >= 0 names an f32 in every input record -- the point's intensity -- that goes through the chain beside x, y, z:
+ *   the base_link move leaves it alone, also for a point it does not move;
+ *   use_angle_calibration ZEROES it: vertical_angle_calibration builds a fresh point and assigns x, y, z (prefiltering_nodelet.cpp:207-210), the
+ *     PointXYZI constructor leaves intensity = 0, so with the calibration on every output intensity is +0.0f -- a quirk of the reference,
+ *     reproduced;
+ *   a point the gate drops takes its intensity with it; a kept point's non-finite intensity is kept and goes into the sums as f32 gives it;
+ *   VOXELGRID: the f32 sum of the voxel's intensities in input order / (float)count (CentroidPoint<PointXYZI>, AccumulatorIntensity), what
+ *     mi355ndt_window_keyframe does; APPROX_VOXELGRID: the history entry's fourth sum (downsample_all_data_), from zero, in input order,
+ *     divided by (float)count at every flush; no down-sampling, or a leaf too small: the kept point's own;
+ *   the outlier removals: a survivor keeps its own, the row is compacted with the points' and its tail zeroed.
+ * x, y, z come out word for word as without it.  PCL 1.8.1's rules as restated in tools/prefilter_xyzi_ref.py, unpinned.
+ * MI355NDT_ERR_BAD_ARG, before anything is staged: intensity_offset_bytes + 4 > stride_bytes, an offset below 12 (it would overlap x, y, z),
+ * an offset that is no multiple of 4, reserved != 0.  intensity_offset_bytes = -1: no intensity, every word as under
+ * MI355NDT_PREFILTER_EXTENDED. */
+#define MI355NDT_PREFILTER_EXTENDED2 0x50467833   /* "PFx3" */
+typedef struct mi355ndt_prefilter_params_ex2 {
+  mi355ndt_prefilter_params_ex ex;      /* ex.base.extended = MI355NDT_PREFILTER_EXTENDED2 */
+  int    intensity_offset_bytes;        /* -1: no intensity; >= 0: an f32 at that offset of every record */
+  int    reserved;                      /* 0 */
+} mi355ndt_prefilter_params_ex2;
+int mi355ndt_prefilter_params_ex2_default(mi355ndt_prefilter_params_ex2* p);
+
 /* mi355ndt_prefilter with the nodelet's whole parameter set (p: a mi355ndt_prefilter_params or the base of a mi355ndt_prefilter_params_ex;
  * NULL: the defaults): the base_link move, the calibration, the gate and the
  * down-sampling method of p, by the batch surface's kernels over this one cloud.  The result stays resident exactly as after
  * mi355ndt_prefilter -- mi355ndt_use_prefiltered and mi355ndt_prefilter_outliers follow unchanged --, and with the default method and no
  * calibration its words are mi355ndt_prefilter's.  A leaf too small for the cloud is no error: the kept points go out in input order and
- * mi355ndt_last_error says so.  MI355NDT_ERR_BAD_ARG for what mi355ndt_prefilter and mi355ndt_batch_prefilter refuse. */
+ * mi355ndt_last_error says so.  MI355NDT_ERR_BAD_ARG for what mi355ndt_prefilter and mi355ndt_batch_prefilter refuse.
+ * With an intensity (mi355ndt_prefilter_params_ex2) the resident result has a fourth row, and the intensity is written into out_pts at the
+ * input's offset: out_stride_bytes must hold it, else MI355NDT_ERR_BAD_ARG.  mi355ndt_prefilter_outliers carries the row and writes it to its
+ * out_pts likewise (the same condition on its out stride); mi355ndt_use_prefiltered hands x, y, z to the registration as ever. */
 int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t stride_bytes, const mi355ndt_prefilter_params* p,
                          void* out_pts, size_t out_capacity, size_t out_stride_bytes, size_t* n_out);
 
@@ -591,7 +619,13 @@ int mi355ndt_prefilter_p(mi355ndt_handle* h, const void* pts, size_t n, size_t s
  * the batch unchanged: device buffers bound, a NULL cloud with a count, a stride below 12, a NaN resolution, a NaN in the transform, an unknown
  * downsample_method, a non-finite angle_calibration_rad, slots outside the batch.  MI355NDT_ERR_BAD_ARG also for a filtered cloud that does not fit its slot: mi355ndt_last_error names the first such
  * slot, and every slot the call touched is recorded as empty.  The resident prefilter result, the keyframes and their indexes are left as
- * they were.  MI355NDT_OPT_PREFILTER_GROUP. */
+ * they were.  MI355NDT_OPT_PREFILTER_GROUP.
+ * With an intensity (mi355ndt_prefilter_params_ex2) the filtered intensities go into a plane per side beside the slots' rows ([slot][pitch],
+ * made by the first such call that touches the side, dropped by mi355ndt_batch_reserve), and every slot the call fills is marked as carrying
+ * one.  Every other route that fills a slot -- mi355ndt_batch_set_*, mi355ndt_batch_set_clouds, the keyframe setters,
+ * mi355ndt_batch_bind_device, this call without an intensity -- clears the mark; mi355ndt_batch_remove_outliers compacts the marked slots'
+ * intensities with their points; the builds, the aligns, the fitness scores and the sequence run do not look at it.  A call that fails
+ * leaves the marks of the slots it touched clear. */
 int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n,
                              const void* const* targets, const size_t* target_counts,
                              const void* const* sources, const size_t* source_counts, size_t stride_bytes,
@@ -603,6 +637,10 @@ int mi355ndt_batch_prefilter(mi355ndt_handle* h, int first_pair, int n,
  * MI355NDT_ERR_STATE in stream mode. */
 int mi355ndt_batch_get_cloud(mi355ndt_handle* h, int pair, int role, void* out_pts, size_t out_capacity,
                              size_t out_stride_bytes, size_t* n_out);
+/* ... and with the slot's intensity as an f32 at out_intensity_offset_bytes (>= 12, a multiple of 4, inside the record) of every record:
+ * what the batch prefilter left there, zeros for a slot that carries none (mi355ndt_keyframe_get's rule). */
+int mi355ndt_batch_get_cloud_i(mi355ndt_handle* h, int pair, int role, void* out_pts, size_t out_capacity,
+                               size_t out_stride_bytes, int out_intensity_offset_bytes, size_t* n_out);
 
 /* mi355ndt_sequence_run over RAW scans: the same call with the batch prefilter in front, no scan downloaded in between.  The batch is
  * reserved for the raw counts.  stats->upload_ms covers the staging of the raw scans, *prefilter_ms (may be NULL) the prefilter's kernels
@@ -717,6 +755,21 @@ int mi355ndt_keyframe_get(mi355ndt_handle* h, int id, void* out_pts, size_t out_
                           int out_intensity_offset_bytes, size_t* n);
 int mi355ndt_keyframe_release(mi355ndt_handle* h, int id);
 int mi355ndt_keyframe_count(const mi355ndt_handle* h);
+/* Resident scans.  The resident prefilter result (after mi355ndt_prefilter* / mi355ndt_prefilter_outliers), or the cloud a batch slot holds
+ * (role 1 = source, 2 = target; with its intensity when the slot carries one), becomes a keyframe of 3 or 4 channels by a device-to-device
+ * copy on the engine's stream into rows the keyframe owns: nothing in the store aliases a slot or the prefilter result, and the source is left
+ * as it was.  Pending uploads and kernels into the source are ordered before the copy.  An empty cloud gives an empty keyframe.
+ * MI355NDT_ERR_STATE in stream mode, and for mi355ndt_keyframe_from_prefiltered when no result is resident; MI355NDT_ERR_BAD_ARG for a bad slot
+ * or role and for a side that has never been given a cloud. */
+int mi355ndt_keyframe_from_prefiltered(mi355ndt_handle* h, int* id);
+int mi355ndt_keyframe_from_slot(mi355ndt_handle* h, int pair, int role, int* id);
+/* mi355ndt_window_keyframe over resident scans: scan k is keyframe ids[k] as it is stored -- the same rules, the same words as over the
+ * same clouds given as host records, and nothing crosses PCIe on the way in (cloud_uploads does not move).  with_intensity != 0: a keyframe
+ * of four channels; a scan stored with three contributes +0 for every point.  An id may appear more than once; a released or unknown id is
+ * MI355NDT_ERR_BAD_ARG with the store's message.  The scans' keyframes are left as they were: the host releases them when the window has
+ * closed. */
+int mi355ndt_window_keyframe_ids(mi355ndt_handle* h, int n_scans, const int* ids, const double* rel_poses, float leaf,
+                                 int with_intensity, int* id, size_t* n_out);
 /* mi355ndt_map_cloud over resident keyframes: the same result, word for word, as mi355ndt_map_cloud over the same clouds,
  * with nothing crossing PCIe on the way in (cloud_uploads does not move).  A keyframe may appear more than once. */
 int mi355ndt_map_cloud_keyframes(mi355ndt_handle* h, int n_keyframes, const int* ids, const double* poses, double resolution,

@@ -116,6 +116,11 @@ struct mi355ndt_handle {
   int *d_tgt_cnt = nullptr, *d_src_cnt = nullptr;   // views: d_tgt_cnt_own / d_src_cnt_own or the stream context's input block
   std::vector<int> h_tgt_cnt, h_src_cnt;
   std::vector<int> up_tgt_cnt, up_src_cnt;        // what d_tgt_cnt / d_src_cnt currently hold (uploads are skipped when unchanged)
+  // the slots' intensity, a plane per side beside the rows: [slot][pitch], made by the first mi355ndt_batch_prefilter with an intensity that
+  // touches the side, dropped by mi355ndt_batch_reserve; and per slot whether its row holds the cloud's intensity -- set by that prefilter, kept
+  // by mi355ndt_batch_remove_outliers, cleared by every other route that fills the slot (cloud_changed / clouds_reset, below)
+  DevBuf<float> d_tgt_i, d_src_i;
+  std::vector<unsigned char> tgt_has_i, src_has_i;
   bool have_target = false, have_source = false;  // written by cloud_changed / clouds_reset (below) alone, with the host counts
   GridsBuilt built{};                             // what the resident grids hold (ndt_grid_state.hpp): filled at the end of build_targets_impl, asked by ensure_grids
   bool aligned_once = false;                      // d_state / d_results hold the outcome of an align of the CURRENT batch
@@ -140,8 +145,11 @@ struct mi355ndt_handle {
   DevBuf<double> d_fit;
   DevBuf<BitWord> d_fwords; DevBuf<unsigned> d_fruns;
   DevBuf<int> d_fit_items; DevBuf<float> d_fit_T;
-  // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls)
-  DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0;
+  // prefilter result (mi355ndt_use_prefiltered reads it after any number of other calls): [pf_ch][pf_pitch], x, y, z and -- pf_ch == 4, a
+  // prefilter called with an intensity offset -- the intensity
+  DevBuf<float> d_pf_out; int pf_count = 0; size_t pf_pitch = 0; int pf_ch = 3;
+  int pf_ioff = -1;                               // ... at this byte offset of the input's records, where the read-backs write it
+  bool pf_resident = false;                       // a prefilter call has left a result (an empty one owns no rows)
   // outlier removal over it (mi355ndt_prefilter_outliers): the index rebuilt by every call, dist[] and its pinned twin
   CloudIndex ol_index; DevBuf<float> d_ol_dist; PinBuf<float> h_ol_dist;
   int ol_cell_mm = 100;                           // MI355NDT_OPT_OUTLIER_CELL_MM
@@ -395,20 +403,30 @@ enum GridWant { GRIDS_ANY, GRIDS_CONFIG, GRIDS_LIVE };
 static int ensure_grids(mi355ndt_handle* h, GridWant want);
 // A slot's cloud changed: `n` consecutive slots of one side from `first_pair` now hold counts[0 .. n) points.  A new target leaves the grids
 // describing a cloud that is gone.  (Under up_mtx: mi355ndt_batch_set_target / _source may run on several threads, distinct pairs.)
+// has_intensity: the slots' intensity rows hold these clouds' intensities (the batch prefilter, the outlier removal over such a slot).
 template <typename N>
-static void cloud_changed(mi355ndt_handle* h, bool tgt, int first_pair, int n, const N* counts) {
+static void cloud_changed(mi355ndt_handle* h, bool tgt, int first_pair, int n, const N* counts, bool has_intensity = false) {
   std::lock_guard<std::mutex> lk(h->up_mtx);
   std::vector<int>& cnt = tgt ? h->h_tgt_cnt : h->h_src_cnt;
-  for (int k = 0; k < n; k++) cnt[(size_t)(first_pair + k)] = (int)counts[k];
+  std::vector<unsigned char>& has_i = tgt ? h->tgt_has_i : h->src_has_i;
+  has_i.resize(cnt.size(), 0);
+  for (int k = 0; k < n; k++) { cnt[(size_t)(first_pair + k)] = (int)counts[k]; has_i[(size_t)(first_pair + k)] = has_intensity ? 1 : 0; }
   (tgt ? h->have_target : h->have_source) = true;
   if (tgt) h->built.valid = false;
 }
-static void cloud_changed(mi355ndt_handle* h, bool tgt, int pair, size_t count) { cloud_changed(h, tgt, pair, 1, &count); }
+static void cloud_changed(mi355ndt_handle* h, bool tgt, int pair, size_t count, bool has_intensity = false) { cloud_changed(h, tgt, pair, 1, &count, has_intensity); }
+// the intensity row of a slot of the engine's own batch that carries one (else null)
+static float* slot_intensity_row(mi355ndt_handle* h, bool tgt, int pair) {
+  const std::vector<unsigned char>& has_i = tgt ? h->tgt_has_i : h->src_has_i;
+  DevBuf<float>& plane = tgt ? h->d_tgt_i : h->d_src_i;
+  if ((size_t)pair >= has_i.size() || !has_i[(size_t)pair] || !plane || (tgt ? h->d_tgt != h->d_tgt_own : h->d_src != h->d_src_own)) return nullptr;
+  return plane + (size_t)pair * (tgt ? h->tgt_pitch : h->src_pitch);
+}
 // The slots of a side hold nothing any more (their rows were re-allocated, the batch got another shape, an alias ended).
 static void clouds_reset(mi355ndt_handle* h, bool tgt, bool src) {
   std::lock_guard<std::mutex> lk(h->up_mtx);
-  if (tgt) { std::fill(h->h_tgt_cnt.begin(), h->h_tgt_cnt.end(), 0); h->have_target = false; h->built.valid = false; }
-  if (src) { std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0); h->have_source = false; }
+  if (tgt) { std::fill(h->h_tgt_cnt.begin(), h->h_tgt_cnt.end(), 0); h->tgt_has_i.assign(h->h_tgt_cnt.size(), 0); h->have_target = false; h->built.valid = false; }
+  if (src) { std::fill(h->h_src_cnt.begin(), h->h_src_cnt.end(), 0); h->src_has_i.assign(h->h_src_cnt.size(), 0); h->have_source = false; }
 }
 // May an align of this configuration be ONE persistent launch (ndt_async.hpp)?  Asked by mi355ndt_batch_align and by mi355ndt_stream_begin.
 static bool async_served(const mi355ndt_handle* h) { return h->async_align && !mt_is_live(h->prm) && !is_pca_kd(h->prm) && model_leaves_rounds(h->pose_model, h->ndt_class, h->ground_class); }

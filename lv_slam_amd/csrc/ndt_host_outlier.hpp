@@ -53,6 +53,12 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
   int rc = outlier_params_check(h, *p, "prefilter_outliers");
   if (rc) return rc;
   if (!h->d_pf_out) { h->err = "prefilter_outliers: no prefilter result is resident (mi355ndt_prefilter first)"; return MI355NDT_ERR_STATE; }
+  const size_t ch = (size_t)h->pf_ch;               // (a result with an intensity row: compacted with the points, written out at the input's offset)
+  if (ch == 4 && out_pts && (size_t)h->pf_ioff + 4 > out_stride) {
+    h->err = "prefilter_outliers: the resident result carries an intensity at byte " + std::to_string(h->pf_ioff) + " of a record; out_stride_bytes " +
+             std::to_string(out_stride) + " cannot hold it";
+    return MI355NDT_ERR_BAD_ARG;
+  }
   *n_out = 0;
   if (stats) memset(stats, 0, sizeof *stats);
   const size_t n = (size_t)h->pf_count, pitch = h->pf_pitch;
@@ -64,7 +70,7 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
   const float r2 = (float)(p->radius * p->radius);
   VoxelScratch& w = h->vs;
   VsNeed need;
-  need.pitch = pitch; need.x = 3 * pitch; need.stat = 2;
+  need.pitch = pitch; need.x = ch * pitch; need.stat = 2;
   rc = vs_reserve(h, need);
   if (rc) return rc;
   HIPCHK(h, h->d_ol_dist.reserve(pitch));
@@ -101,10 +107,11 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
     memset(mean_distances, 0, n * sizeof(float));
   }
   exscan_ints(s, w.flag, pitch, w.tmp, w.pos);
-  HIPCHK(h, hipMemsetAsync(w.x, 0, 3 * pitch * sizeof(float), s));
-  k_ol_compact<<<gx, 256, 0, s>>>(rows, pitch, w.flag, w.pos, w.x);
+  HIPCHK(h, hipMemsetAsync(w.x, 0, ch * pitch * sizeof(float), s));
+  if (ch == 4) k_ol_compact<true><<<gx, 256, 0, s>>>(rows, pitch, w.flag, w.pos, w.x);
+  else k_ol_compact<false><<<gx, 256, 0, s>>>(rows, pitch, w.flag, w.pos, w.x);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(rows, w.x, 3 * pitch * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(rows, w.x, ch * pitch * sizeof(float), hipMemcpyDeviceToDevice, s));
   HIPCHK(h, hipMemcpyAsync(w.h_ret, w.pos + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(w.h_ret + 1, w.flag + (pitch - 1), sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
@@ -118,7 +125,8 @@ int mi355ndt_prefilter_outliers(mi355ndt_handle* h, const mi355ndt_outlier_param
 // ---- the same stage over the clouds batch slots hold, K clouds per launch chain (ndt_outlier_batch.hpp) ---------------------------------
 // The scratch of a group of K clouds of segment pitch rp, per point: the staged rows 12 B + the index pools (points in cell order 12, ids 4, run
 // starts 4, at most 16 of bitmap: kfi_layout) + dist 4 + two key and two id arrays (sort ping-pong) 16 + flag 4 + pos 4 + keep 1 + the sort's
-// tile histograms and offsets 4: 81 B.  Groups are cut as the batch prefilter cuts them, under the same budget.
+// tile histograms and offsets 4: 81 B (85 with the staged intensity plane, when some slot of the call carries one).  Groups are cut as the
+// batch prefilter cuts them, under the same budget.
 #define OLB_POINT_BYTES 81
 
 // where the pools of a group sit in the scratch's blob (vs.out), in bytes; [0, runs) is zeroed before every group
@@ -179,11 +187,13 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
     }
   if (kernels_ms) *kernels_ms = 0.0;
   const int n_cl = (int)cl.size();
+  bool with_i = false;                                  // some cloud's slot carries its intensity: the plane is staged and compacted beside the rows
+  for (const Cl& c : cl) with_i = with_i || slot_intensity_row(h, c.tgt, c.pair);
   if (n_cl) {
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t rp_all = (maxn + 63) & ~(size_t)63;
-    const int group = pfb_group_size(h, OLB_POINT_BYTES, rp_all, n_cl);
+    const int group = pfb_group_size(h, OLB_POINT_BYTES + (with_i ? 4 : 0), rp_all, n_cl);
     // the groups: a group's segment pitch is its own largest count, and its k-NN table is made here, before anything is enqueued
     struct Grp { int g0, K; size_t rp; std::vector<int> tab; int gmax; };
     std::vector<Grp> groups;
@@ -202,11 +212,12 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
         fit_item_table(g.K, nblk, part0, [](int) { return true; },
                        [&](int k) { return std::array<int, 3>{(int)cl[(size_t)(g0 + k)].n, (int)cl[(size_t)(g0 + k)].n, 0}; }, g.tab, g.gmax);
       }
-      need.tab = std::max(need.tab, (((size_t)g.K * sizeof(PfbItem) + 15) & ~(size_t)15) + (size_t)g.K * sizeof(OlbCloud) + g.tab.size() * sizeof(int));
+      need.tab = std::max(need.tab, (((size_t)g.K * sizeof(PfbItem) + 15) & ~(size_t)15) + (size_t)g.K * sizeof(OlbCloud) + g.tab.size() * sizeof(int) +
+                                    (with_i ? 8 + (size_t)g.K * sizeof(float*) : 0));
       groups.push_back(std::move(g));
     }
     // sized once, for `group` clouds of the call's largest count: no group needs more, and the sort's tiles are counted per cloud
-    need.clouds = (size_t)group; need.pitch = (size_t)group * rp_all; need.x = 3 * need.pitch;
+    need.clouds = (size_t)group; need.pitch = (size_t)group * rp_all; need.x = (with_i ? 4 : 3) * need.pitch;
     need.out = (olb_layout((size_t)group, rp_all).bytes + 3) / 4;
     need.part = (size_t)OLB_STAT_DOUBLES * group; need.stat = OLB_RES_WORDS(group);
     rc = vs_reserve(h, need);
@@ -234,7 +245,8 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
       float* dist = reinterpret_cast<float*>(blob + L.dist);
       float* X = w.x;
       // the tables: the clouds' slots, their views, the k-NN launch's items
-      const size_t at_cl = (K * sizeof(PfbItem) + 15) & ~(size_t)15, at_tab = at_cl + (size_t)K * sizeof(OlbCloud), tab_bytes = at_tab + g.tab.size() * sizeof(int);
+      const size_t at_cl = (K * sizeof(PfbItem) + 15) & ~(size_t)15, at_tab = at_cl + (size_t)K * sizeof(OlbCloud);
+      const size_t at_oi = (at_tab + g.tab.size() * sizeof(int) + 7) & ~(size_t)7, tab_bytes = at_oi + (with_i ? (size_t)K * sizeof(float*) : 0);
       static_assert(sizeof(OlbCloud) % 8 == 0, "the tables' layout");
       unsigned char* ht = w.h_tab;
       unsigned char* dt = w.tab;
@@ -247,7 +259,9 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
         hcl[k] = OlbCloud{KfiView{&heads[k].gd, words + (size_t)k * L.nwc, runs + (size_t)k * (rp + 1), sorted + (size_t)k * 3 * rp, ids + (size_t)k * rp,
                                   X + (size_t)k * 3 * rp, (unsigned)rp, (int)c.n},
                           dist + (size_t)k * rp, (int*)w.flag + (size_t)k * rp};
+        if (with_i) reinterpret_cast<float**>(ht + at_oi)[k] = slot_intensity_row(h, c.tgt, c.pair);
       }
+      const PfbInt pi = {with_i ? X + 3 * seg : nullptr, with_i ? reinterpret_cast<float* const*>(dt + at_oi) : nullptr};
       if (!g.tab.empty()) memcpy(ht + at_tab, g.tab.data(), g.tab.size() * sizeof(int));
       w.pending = true;
       HIPCHK(h, hipMemcpyAsync(dt, ht, tab_bytes, hipMemcpyHostToDevice, s));
@@ -261,7 +275,8 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
       HIPCHK(h, hipMemsetAsync(w.flag, 0, seg * sizeof(int), s));
       HIPCHK(h, hipMemsetAsync(blob, 0, L.runs, s));     // headers, descriptors, counts and bitmaps (k_fit_mark ORs into the last)
       k_olb_begin<<<(6 * K + 2 + 255) / 256, 256, 0, s>>>(reinterpret_cast<unsigned*>(w.mm.p), res, cnt, items, K);
-      k_olb_stage<<<xcd_grid(tiles, K), 256, 0, s>>>(items, K, tiles, X, rp);
+      if (with_i) k_olb_stage<true><<<xcd_grid(tiles, K), 256, 0, s>>>(items, K, tiles, X, rp, pi);
+      else k_olb_stage<false><<<xcd_grid(tiles, K), 256, 0, s>>>(items, K, tiles, X, rp, pi);
       if (Kn > 0) {
         // K indexes at once: extremes, the cell rule, the segmented sort whose first pass computes the keys from the points, mark, rank, runs, gather
         const int gx = (int)((rp + 255) / 256);
@@ -291,7 +306,8 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
       k_pfb_scan_totals<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, tiles, K);
       k_pfb_scan_offsets<<<K, 1024, 0, s>>>(w.tmp, tiles, items, K, res);
       k_pfb_scan_apply<<<xcd_grid(tiles, K), 1024, 0, s>>>(w.flag, rp, w.tmp, w.pos, tiles, K);
-      k_olb_emit<<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, w.flag, w.pos, items, res, K, tiles);
+      if (with_i) k_olb_emit<true><<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, w.flag, w.pos, items, res, K, tiles, pi);
+      else k_olb_emit<false><<<xcd_grid(tiles, K), 256, 0, s>>>(X, rp, w.flag, w.pos, items, res, K, tiles, pi);
       HIPCHK(h, hipGetLastError());
       if (kernels_ms) HIPCHK(h, hipEventRecord(ev[1], s));
       rc = compute_enqueued(h);                         // later uploads into these slots wait for the emit
@@ -307,7 +323,7 @@ static int batch_outliers_impl(mi355ndt_handle* h, int first_pair, int n, int si
       for (int k = 0; k < K; k++) {
         const Cl& c = cl[(size_t)(g.g0 + k)];
         const size_t m = (size_t)ret[k];
-        cloud_changed(h, c.tgt, c.pair, m);
+        cloud_changed(h, c.tgt, c.pair, m, slot_intensity_row(h, c.tgt, c.pair) != nullptr);
         size_t* out = c.tgt ? target_counts_out : source_counts_out;
         if (out) out[c.pair - first_pair] = m;
         mi355ndt_outlier_stats* st = c.tgt ? target_stats : source_stats;

@@ -63,6 +63,12 @@ int mi355ndt_batch_reserve(mi355ndt_handle* h, int n_pairs, size_t max_tgt, size
   rc = alloc_side(h, true, n_pairs, tp);
   if (rc == MI355NDT_OK) rc = alloc_side(h, false, n_pairs, sp);
   if (rc) return rc;
+  if (h->d_tgt_i || h->d_src_i) {                 // the slots' intensity planes go: the next batch prefilter with an intensity makes them anew
+    for (hipStream_t cs : h->copy_stream) HIPCHK(h, hipStreamSynchronize(cs));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->d_tgt_i = DevBuf<float>(); h->d_src_i = DevBuf<float>();
+  }
+  h->tgt_has_i.assign((size_t)n_pairs, 0); h->src_has_i.assign((size_t)n_pairs, 0);
   h->n_pairs = n_pairs;
   h->tgt_pitch = tp; h->src_pitch = sp;
   h->d_tgt = h->d_tgt_own; h->d_src = h->d_src_own;
@@ -94,8 +100,9 @@ static int compute_enqueued(mi355ndt_handle* h) {       // call after enqueueing
 // hipMemcpyAsync + one k_deinterleave_multi launch + one event, whatever the number of clouds in it: with one cloud per transfer the ~50 us of
 // HIP calls per cloud, serialised under the engine's lock, held the staging of a 271-pair batch to 60 GB/s of records read whatever the number
 // of staging threads (round 6, tools/host_stage_probe.cpp: the same compaction alone reaches 180-195 GB/s at eight threads on the same host).
-// ioff >= 0: the record's f32 at that byte offset (its intensity) travels as a fourth word and lands in a fourth row behind x, y, z
-struct UpItem { float* d_base; size_t pitch; int pair; const void* pts; size_t n, stride; int ioff = -1; };
+// ioff >= 0: the record's f32 at that byte offset (its intensity) travels as a fourth word and lands in a fourth row: behind x, y, z, or --
+// d_i not null -- in the `pitch` floats at d_i
+struct UpItem { float* d_base; size_t pitch; int pair; const void* pts; size_t n, stride; int ioff = -1; float* d_i = nullptr; };
 static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
   if (cnt < 1 || cnt > UP_GROUP_MAX) return MI355NDT_ERR_BAD_ARG;
   size_t total = 0;                               // words staged: 3 per point (4 with the intensity, each such cloud starting on a 16-byte boundary)
@@ -149,6 +156,7 @@ static int upload_items(mi355ndt_handle* h, const UpItem* it, int cnt) {
     } else if (stride == 12) { if (n) memcpy(dst, p, n * 12); }
     else for (size_t i = 0; i < n; i++) memcpy(dst + 3 * i, p + i * stride, 12);
     tab.e[k].src_off = off; tab.e[k].n = (int)n; tab.e[k].w4 = ioff >= 0; tab.e[k].rows = it[k].d_base + (size_t)it[k].pair * 3 * it[k].pitch; tab.e[k].pitch = it[k].pitch;
+    tab.e[k].row4 = it[k].d_i ? it[k].d_i : tab.e[k].rows + 3 * it[k].pitch;
     off += (ioff >= 0 ? 4 : 3) * n;
     max_pitch = std::max(max_pitch, it[k].pitch);
   }

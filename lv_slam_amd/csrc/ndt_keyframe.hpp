@@ -15,7 +15,9 @@
 #define KF_CHUNK   1024              // window positions per workgroup of k_kf_window (four per lane)
 #define KF_THREADS 256
 
-struct KfScan { const float* rows; unsigned start, pitch; };   // scan k: its x,y,z(,intensity) rows of `pitch` floats; window index of its first point
+// scan k: its x, y, z rows of `pitch` floats; the window index of its first point; its intensity row (null: the scan carries none, and a window
+// with an intensity reads +0 for its points)
+struct KfScan { const float* rows; unsigned start, pitch; const float* irow; };
 
 // One workgroup per 1,024 positions of the window; position g < n is point g - sc[k].start of scan k (binary search once per lane, then a
 // walk, as k_mc_transform does).  PCL 1.8 transformPointCloud with a double matrix: per coordinate
@@ -42,7 +44,7 @@ __global__ void __launch_bounds__(KF_THREADS) k_kf_window(const KfScan* __restri
       const KfScan e = sc[k];
       const int j = g - (int)e.start;
       const float x = e.rows[j], y = e.rows[e.pitch + j], z = e.rows[2 * (size_t)e.pitch + j];
-      if (ch == 4) w = e.rows[3 * (size_t)e.pitch + j];
+      if (ch == 4 && e.irow) w = e.irow[j];
       o[0] = x; o[1] = y; o[2] = z;
       ok = finite3(x, y, z);
       if (ok && k > 0) {

@@ -165,11 +165,14 @@ __global__ void __launch_bounds__(256) k_ol_flag(const float* __restrict__ dist,
   flag[i] = (i < (size_t)n && !((double)dist[i] > threshold)) ? 1 : 0;
 }
 
-// the survivors, in order, into rows of the same pitch (the caller has zeroed `out`: the tail stays zero to the pitch)
+// the survivors, in order, into rows of the same pitch (the caller has zeroed `out`: the tail stays zero to the pitch).  INTENSITY: the rows
+// are [4][pitch] and the fourth is compacted with the same pos[].
+template <bool INTENSITY>
 __global__ void __launch_bounds__(256) k_ol_compact(const float* __restrict__ rows, size_t pitch, const int* __restrict__ flag,
                                                     const int* __restrict__ pos, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= pitch || !flag[i]) return;
   const int o = pos[i];
   out[o] = rows[i]; out[pitch + o] = rows[pitch + i]; out[2 * pitch + o] = rows[2 * pitch + i];
+  if constexpr (INTENSITY) out[3 * pitch + o] = rows[3 * pitch + i];
 }

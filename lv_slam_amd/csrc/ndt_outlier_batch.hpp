@@ -36,18 +36,23 @@ __global__ void __launch_bounds__(256) k_olb_begin(unsigned* mm, int* res, int* 
   if (i < K) cnt[i] = items[i].n;
 }
 
-// Stage: the slot's points into the cloud's segment, zeros behind them to the segment's pitch
-__global__ void __launch_bounds__(256) k_olb_stage(const PfbItem* __restrict__ items, int K, int nx, float* X, size_t rp) {
+// Stage: the slot's points into the cloud's segment, zeros behind them to the segment's pitch.  INTENSITY: the intensity row of a slot that
+// carries one (pi.out[b], the row the emit compacts into) goes into the cloud's row of the plane beside the segments (pi.in).
+template <bool INTENSITY>
+__global__ void __launch_bounds__(256) k_olb_stage(const PfbItem* __restrict__ items, int K, int nx, float* X, size_t rp, const PfbInt pi) {
   int b, bx;
   if (!xcd_map(nx, K, bx, b)) return;
   const PfbItem it = items[b];
   float* Xb = X + (size_t)b * 3 * rp;
+  const float* si = nullptr;
+  if constexpr (INTENSITY) si = pi.out[b];
   const size_t end = std::min(rp, (size_t)(bx + 1) * RS_TILE);
   for (size_t i = (size_t)bx * RS_TILE + threadIdx.x; i < end; i += 256) {
     const bool in = i < (size_t)it.n;
     Xb[i] = in ? it.out[i] : 0.f;
     Xb[rp + i] = in ? it.out[it.out_pitch + i] : 0.f;
     Xb[2 * rp + i] = in ? it.out[2 * it.out_pitch + i] : 0.f;
+    if constexpr (INTENSITY) if (si) pi.in[(size_t)b * rp + i] = in ? si[i] : 0.f;
   }
 }
 
@@ -180,9 +185,11 @@ __global__ void __launch_bounds__(256) k_olb_flag(const float* __restrict__ dist
 
 // Emit: the survivors, in order, from the staged copy into the slot's rows; the rows between the new count (res[b], k_pfb_scan_offsets) and
 // the old one are zeroed -- behind the old count they are zero already, as an upload leaves them.  Survivors land below the new count and
-// zeros at or above it: no two threads write one row, and nobody reads the slot.
+// zeros at or above it: no two threads write one row, and nobody reads the slot.  INTENSITY: the same for the intensity row of a slot that
+// carries one, out of the staged plane.
+template <bool INTENSITY>
 __global__ void __launch_bounds__(256) k_olb_emit(const float* __restrict__ X, size_t rp, const int* __restrict__ flag, const int* __restrict__ pos,
-                                                  const PfbItem* __restrict__ items, const int* __restrict__ res, int K, int nx) {
+                                                  const PfbItem* __restrict__ items, const int* __restrict__ res, int K, int nx, const PfbInt pi) {
   int b, bx;
   if (!xcd_map(nx, K, bx, b)) return;
   const PfbItem it = items[b];
@@ -190,12 +197,21 @@ __global__ void __launch_bounds__(256) k_olb_emit(const float* __restrict__ X, s
   const float* Xb = X + (size_t)b * 3 * rp;
   const int* fb = flag + (size_t)b * rp;
   const int* pb = pos + (size_t)b * rp;
+  const float* Ib = nullptr;
+  float* oi = nullptr;
+  if constexpr (INTENSITY) { Ib = pi.in + (size_t)b * rp; oi = pi.out[b]; }
   const size_t end = std::min(std::min(rp, n), (size_t)(bx + 1) * RS_TILE);
   for (size_t i = (size_t)bx * RS_TILE + threadIdx.x; i < end; i += 256) {
     if (fb[i]) {
       const size_t o = (size_t)pb[i];
-      if (o < m) { it.out[o] = Xb[i]; it.out[it.out_pitch + o] = Xb[rp + i]; it.out[2 * it.out_pitch + o] = Xb[2 * rp + i]; }
+      if (o < m) {
+        it.out[o] = Xb[i]; it.out[it.out_pitch + o] = Xb[rp + i]; it.out[2 * it.out_pitch + o] = Xb[2 * rp + i];
+        if constexpr (INTENSITY) if (oi) oi[o] = Ib[i];
+      }
     }
-    if (i >= m) { it.out[i] = 0.f; it.out[it.out_pitch + i] = 0.f; it.out[2 * it.out_pitch + i] = 0.f; }
+    if (i >= m) {
+      it.out[i] = 0.f; it.out[it.out_pitch + i] = 0.f; it.out[2 * it.out_pitch + i] = 0.f;
+      if constexpr (INTENSITY) if (oi) oi[i] = 0.f;
+    }
   }
 }

@@ -100,22 +100,29 @@ __device__ __forceinline__ int pf_is_head(const unsigned* __restrict__ keys, con
 }
 
 // what the head at position i emits: the voxel's centroid -- the f32 sum of its points in input order, divided by (float)count -- or, without
-// down-sampling, the point itself
+// down-sampling, the point itself.  INTENSITY: XI, the cloud's row of the intensity plane, is walked beside the rows (AccumulatorIntensity: the
+// same f32 sum in the same order, the same division) into si; without it neither is touched.
+template <bool INTENSITY = false>
 __device__ __forceinline__ void pf_emit_point(const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ keys,
-                                              const unsigned* __restrict__ vals, int downsample, size_t i, float& sx, float& sy, float& sz) {
+                                              const unsigned* __restrict__ vals, int downsample, size_t i, float& sx, float& sy, float& sz,
+                                              const float* __restrict__ XI, float& si) {
   if (downsample) {
     const unsigned key = keys[i];
     sx = sy = sz = 0.f;
+    if constexpr (INTENSITY) si = 0.f;
     int cnt = 0;
     for (size_t j = i; j < pitch && keys[j] == key; j++) {           // AccumulatorXYZ: xyz += p (f32), input order
       const unsigned pi = vals[j];
       sx += X[pi]; sy += X[pitch + pi]; sz += X[2 * pitch + pi];
+      if constexpr (INTENSITY) si += XI[pi];
       cnt++;
     }
     const float fn = (float)cnt;
     sx /= fn; sy /= fn; sz /= fn;                                    // xyz / n
+    if constexpr (INTENSITY) si /= fn;
   } else {
     sx = X[i]; sy = X[pitch + i]; sz = X[2 * pitch + i];
+    if constexpr (INTENSITY) si = XI[i];
   }
 }
 

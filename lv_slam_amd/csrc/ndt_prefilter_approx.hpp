@@ -118,28 +118,38 @@ __global__ void __launch_bounds__(256) k_pfa_heads(const float* __restrict__ X, 
 
 // Emit: the head of every run sums it in sorted order -- input order inside the bucket -- up to the next head or the end of the bucket, divides by
 // (float)count and writes at its rank; nothing is written at or past the slot's pitch (such a cloud has raised the overflow word).
+// INTENSITY: the history entry's fourth sum (downsample_all_data_: the entry's VectorXf holds x, y, z and intensity) -- from zero, in the same
+// order, divided at the same flush -- from XI, the cloud's row of the intensity plane, into oi.
+template <bool INTENSITY>
 __device__ __forceinline__ void pfa_emit_run(const float* __restrict__ X, size_t pitch, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
-                                             const unsigned char* __restrict__ heads, const int* __restrict__ pos, size_t i, const PfbItem& it) {
+                                             const unsigned char* __restrict__ heads, const int* __restrict__ pos, size_t i, const PfbItem& it,
+                                             const float* __restrict__ XI, float* oi) {
   if (!heads[i]) return;
   const unsigned k = keys[i];
-  float sx = 0.f, sy = 0.f, sz = 0.f;
+  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
   int cnt = 0;
   size_t j = i;
   do {                                                                // centroid += p (f32), input order
     const unsigned pi = vals[j];
     sx += X[pi]; sy += X[pitch + pi]; sz += X[2 * pitch + pi];
+    if constexpr (INTENSITY) si += XI[pi];
     cnt++;
     j++;
   } while (j < pitch && keys[j] == k && !heads[j]);
   const float fn = (float)cnt;
   sx /= fn; sy /= fn; sz /= fn;                                       // centroid / (float)count
+  if constexpr (INTENSITY) si /= fn;
   const bool flushed = j < pitch && keys[j] == k;                     // by the point that opens the bucket's next run
   const size_t o = (size_t)pos[flushed ? (size_t)vals[j] : pitch - PFA_BUCKETS + k];
-  if (o < it.out_pitch) { it.out[o] = sx; it.out[it.out_pitch + o] = sy; it.out[2 * it.out_pitch + o] = sz; }
+  if (o < it.out_pitch) {
+    it.out[o] = sx; it.out[it.out_pitch + o] = sy; it.out[2 * it.out_pitch + o] = sz;
+    if constexpr (INTENSITY) oi[o] = si;
+  }
 }
+template <bool INTENSITY>
 __global__ void __launch_bounds__(256) k_pfa_emit(const float* __restrict__ X, size_t rp, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
                                                   const unsigned char* __restrict__ keep, const int* __restrict__ flag, const int* __restrict__ pos,
-                                                  const PfGrid* __restrict__ grid, const PfbItem* __restrict__ items, int K, int nx) {
+                                                  const PfGrid* __restrict__ grid, const PfbItem* __restrict__ items, int K, int nx, const PfbInt pi) {
   int b, bx;
   if (!xcd_map(nx, K, bx, b)) return;
   const PfGrid g = grid[b];
@@ -150,12 +160,18 @@ __global__ void __launch_bounds__(256) k_pfa_emit(const float* __restrict__ X, s
   const unsigned char* kp = keep + (size_t)b * rp;
   const int* fb = flag + (size_t)b * rp;
   const int* pb = pos + (size_t)b * rp;
+  const float* Ib = nullptr;
+  float* oi = nullptr;
+  if constexpr (INTENSITY) { Ib = pi.in + (size_t)b * rp; oi = pi.out[b]; }
   const size_t rq = rp - PFA_BUCKETS;
   const size_t end = std::min(rp, (size_t)(bx + 1) * RS_TILE);
   for (size_t i = (size_t)bx * RS_TILE + threadIdx.x; i < end; i += 256) {
-    if (g.status == 0) { pfa_emit_run(Xb, rp, kb, vb, kp, pb, i, it); continue; }
+    if (g.status == 0) { pfa_emit_run<INTENSITY>(Xb, rp, kb, vb, kp, pb, i, it, Ib, oi); continue; }
     if (i >= rq || !fb[i]) continue;
     const size_t o = (size_t)pb[i];
-    if (o < it.out_pitch) { it.out[o] = Xb[i]; it.out[it.out_pitch + o] = Xb[rp + i]; it.out[2 * it.out_pitch + o] = Xb[2 * rp + i]; }
+    if (o < it.out_pitch) {
+      it.out[o] = Xb[i]; it.out[it.out_pitch + o] = Xb[rp + i]; it.out[2 * it.out_pitch + o] = Xb[2 * rp + i];
+      if constexpr (INTENSITY) oi[o] = Ib[i];
+    }
   }
 }

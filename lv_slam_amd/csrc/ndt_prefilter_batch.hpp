@@ -6,6 +6,8 @@
 // kernel here gives a cloud `nx` workgroups placed by xcd_map like the sort's own: a cloud's rows, keys and ids stay in one XCD's L2 from the
 // flag kernel to the emit.  Positions are size_t wherever a cloud index is multiplied in (271 clouds of 131,072 points: 35.5 M positions).
 // The per-point arithmetic -- the gate, the voxel key, the head test, the centroid walk -- is ndt_prefilter.hpp's, called from both files.
+// A group that carries PointXYZI's intensity has a plane I[cloud][rp] behind its rows (PfbInt): the staging fills it and the emit kernels'
+// INTENSITY instantiations walk it; gate, keys, sort, heads and scans never look at it, and the [cloud][3][rp] addressing is what it was.
 #pragma once
 #include "ndt_prefilter.hpp"
 #include "ndt_segsort.hpp"
@@ -15,6 +17,10 @@
 struct PfbItem { float* out; unsigned long long out_pitch; int n, id; };
 // the optional rigid move in front of the gate, row-major 3x4: m[4 * a + c] = T(a, c)
 struct PfbMove { int on; float m[12]; };
+// the fourth channel of a group, a plane of its own beside the [cloud][3][rp] rows: in = I[cloud][rp], and per cloud the row its filtered
+// intensities go to -- out_pitch floats, position for position the item's rows (null: this cloud carries none).  Only the staging and the
+// emit kernels look at it, and only in their INTENSITY instantiations.
+struct PfbInt { float* in; float* const* out; };
 // result words of a group of K clouds: [0, K) filtered counts, [K] the first cloud whose count exceeds its slot, [K + 1] the first cloud whose
 // leaf is too small for its extent (INT_MAX: none)
 #define PFB_RES_WORDS(K) ((size_t)(K) + 2)
@@ -118,9 +124,10 @@ __global__ void __launch_bounds__(1024) k_pfb_scan_apply(const int* __restrict__
 }
 
 // Emit: straight into the cloud's slot rows.  Nothing is written at or past the slot's pitch (such a cloud has raised the overflow word).
+template <bool INTENSITY>
 __global__ void __launch_bounds__(256) k_pfb_emit(const float* __restrict__ X, size_t rp, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
                                                   const int* __restrict__ flag, const int* __restrict__ pos, const PfGrid* __restrict__ grid, int downsample,
-                                                  const PfbItem* __restrict__ items, int K, int nx) {
+                                                  const PfbItem* __restrict__ items, int K, int nx, const PfbInt pi) {
   int b, bx;
   if (!xcd_map(nx, K, bx, b)) return;
   const int ds = downsample && grid[b].status == 0;
@@ -130,12 +137,18 @@ __global__ void __launch_bounds__(256) k_pfb_emit(const float* __restrict__ X, s
   const unsigned* vb = vals + (size_t)b * rp;
   const int* fb = flag + (size_t)b * rp;
   const int* pb = pos + (size_t)b * rp;
+  const float* Ib = nullptr;
+  float* oi = nullptr;
+  if constexpr (INTENSITY) { Ib = pi.in + (size_t)b * rp; oi = pi.out[b]; }
   const size_t end = std::min(rp, (size_t)(bx + 1) * RS_TILE);
   for (size_t i = (size_t)bx * RS_TILE + threadIdx.x; i < end; i += 256) {
     if (!fb[i]) continue;
-    float sx, sy, sz;
-    pf_emit_point(Xb, rp, kb, vb, ds, i, sx, sy, sz);
+    float sx, sy, sz, si = 0.f;
+    pf_emit_point<INTENSITY>(Xb, rp, kb, vb, ds, i, sx, sy, sz, Ib, si);
     const size_t o = (size_t)pb[i];
-    if (o < it.out_pitch) { it.out[o] = sx; it.out[it.out_pitch + o] = sy; it.out[2 * it.out_pitch + o] = sz; }
+    if (o < it.out_pitch) {
+      it.out[o] = sx; it.out[it.out_pitch + o] = sy; it.out[2 * it.out_pitch + o] = sz;
+      if constexpr (INTENSITY) oi[o] = si;
+    }
   }
 }

@@ -25,8 +25,9 @@ NDT_KERNEL void __launch_bounds__(256) k_deinterleave(const float* __restrict__ 
 }
 
 // ... and several clouds of one transfer at once (grid.y = cloud): ndt_host_upload.hpp, upload_items.  A cloud staged with its intensity (w4: four
-// words per record) fills a fourth row; the others are read and written exactly as before.
-struct DeintTab { int cnt, pad_; struct { unsigned long long src_off; float* rows; unsigned long long pitch; int n, w4; } e[16]; };
+// words per record) fills a fourth row -- row4: behind the three (a keyframe's, a window scan's) or wherever the host says (the prefilter's
+// intensity plane lies beside its [cloud][3][rp] rows) --; the others are read and written exactly as before.
+struct DeintTab { int cnt, pad_; struct { unsigned long long src_off; float* rows; unsigned long long pitch; int n, w4; float* row4; } e[16]; };
 NDT_KERNEL void __launch_bounds__(256) k_deinterleave_multi(const float* __restrict__ packed, const DeintTab tab) {
   const int c = blockIdx.y;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -38,7 +39,7 @@ NDT_KERNEL void __launch_bounds__(256) k_deinterleave_multi(const float* __restr
   if (tab.e[c].w4) {
     float w = 0.f;
     if (i < (size_t)tab.e[c].n) { const float4 r = *(const float4*)(xyz + 4 * i); x = r.x; y = r.y; z = r.z; w = r.w; }
-    rows[3 * pitch + i] = w;
+    tab.e[c].row4[i] = w;
   } else if (i < (size_t)tab.e[c].n) { x = xyz[3 * i]; y = xyz[3 * i + 1]; z = xyz[3 * i + 2]; }
   rows[i] = x; rows[pitch + i] = y; rows[2 * pitch + i] = z;
 }

@@ -4,7 +4,8 @@
 GlobalGraphNodelet::cloud_callback (src/global_graph/global_graph_nodelet.cpp:202-244).  Both are host-side policy, as they are in the
 reference; the window map itself -- moving the scans into the window's first frame, appending them, the VoxelGrid -- is ONE call into the
 engine (Engine.window_keyframe, mi355ndt_window_keyframe) when the window closes, and the keyframe's cloud stays on the device under the id
-that call returns.
+that call returns.  A scan may also be the id of a resident keyframe (Engine.keyframe_from_slot, keyframe_from_prefiltered): a window of
+ids closes through Engine.window_keyframe_ids, no scan crosses PCIe again, and the scans' ids are released once the window has closed.
 """
 from __future__ import annotations
 
@@ -83,7 +84,8 @@ class WindowKeyframer:
     """cloud_callback's branch over (odom, scan) pairs.  The frame the updater accepts first opens a window (:202-211); a frame it rejects
     is appended to the open window with the relative pose w_odom.inverse() * odom (:237-244); the next frame it accepts closes the window
     -- the window map becomes a keyframe (:212-229) -- and opens the next one (:230-235).  The window is kept on the host as a list of scans
-    and relative poses; nothing is computed until it closes."""
+    and relative poses; nothing is computed until it closes.  A scan is an array or the int id of a resident keyframe -- one kind per
+    window: a window that mixes them is a ValueError."""
 
     def __init__(self, engine, delta_trans: float = 2.0, delta_angle: float = 2.0, leaf: float = 0.1, intensity: bool = False):
         self.engine = engine
@@ -104,8 +106,21 @@ class WindowKeyframer:
         self.w_seq = seq
         self.w_accum = self.updater.accum_distance                # (:209, :235: read after update())
 
+    @staticmethod
+    def _is_id(scan) -> bool:
+        return isinstance(scan, (int, np.integer)) and not isinstance(scan, (bool, np.bool_))
+
     def _close(self) -> WindowKeyframe:
-        kid, n = self.engine.window_keyframe(self.w_scans, self.w_rel, self.leaf, self.intensity)
+        by_id = [self._is_id(s) for s in self.w_scans]
+        if any(by_id) and not all(by_id):
+            raise ValueError("a window holds resident scan ids or host scans, not both")
+        if by_id[0]:
+            ids = [int(s) for s in self.w_scans]
+            kid, n = self.engine.window_keyframe_ids(ids, self.w_rel, self.leaf, self.intensity)
+            for i in dict.fromkeys(ids):                          # (an id may appear twice in a window: released once)
+                self.engine.keyframe_release(i)
+        else:
+            kid, n = self.engine.window_keyframe(self.w_scans, self.w_rel, self.leaf, self.intensity)
         return WindowKeyframe(kid, n, self.w_odom, self.w_seq, self.w_accum, len(self.w_scans))
 
     def push(self, odom, scan, seq: int | None = None):
@@ -118,6 +133,8 @@ class WindowKeyframer:
             out = None if first else self._close()
             self._open(odom, scan, seq)
             return out
+        if self._is_id(scan) != self._is_id(self.w_scans[0]):
+            raise ValueError("a window holds resident scan ids or host scans, not both")
         self.w_scans.append(scan)
         self.w_rel.append(isometry_inverse(self.w_odom) @ np.asarray(odom, np.float64))
         return None

@@ -112,6 +112,12 @@ class PrefilterParamsEx(C.Structure):
     _fields_ = [("base", PrefilterParams), ("downsample_method", C.c_int), ("use_angle_calibration", C.c_int), ("angle_calibration_rad", C.c_double)]
 
 
+class PrefilterParamsEx2(C.Structure):
+    """mi355ndt_prefilter_params_ex2: the byte offset of the records' intensity behind a PrefilterParamsEx whose base.extended says so
+    (PREFILTER_EXTENDED2); every call that takes a PrefilterParams pointer takes byref(ex2.ex.base)."""
+    _fields_ = [("ex", PrefilterParamsEx), ("intensity_offset_bytes", C.c_int), ("reserved", C.c_int)]
+
+
 class SeqParams(C.Structure):
     _fields_ = [("keyframe_delta_trans", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double)]
 
@@ -147,6 +153,8 @@ SYMBOLS = [
     "mi355ndt_outlier_params_default", "mi355ndt_prefilter_outliers", "mi355ndt_batch_remove_outliers", "mi355ndt_sequence_run_raw_outliers",
     "mi355ndt_prefilter_params_default", "mi355ndt_batch_prefilter", "mi355ndt_batch_get_cloud", "mi355ndt_sequence_run_raw",
     "mi355ndt_prefilter_p", "mi355ndt_prefilter_params_ex_default",
+    "mi355ndt_prefilter_params_ex2_default", "mi355ndt_batch_get_cloud_i",
+    "mi355ndt_keyframe_from_prefiltered", "mi355ndt_keyframe_from_slot", "mi355ndt_window_keyframe_ids",
     "mi355ndt_gicp_params_default", "mi355ndt_gicp_set_params", "mi355ndt_gicp_set_target", "mi355ndt_gicp_set_source", "mi355ndt_gicp_set_target_keyframe",
     "mi355ndt_gicp_set_source_keyframe", "mi355ndt_gicp_covariances", "mi355ndt_gicp_correspondences", "mi355ndt_gicp_cost", "mi355ndt_gicp_align",
     "mi355ndt_gicp_get_aligned",
@@ -182,6 +190,7 @@ OPT_GROUND_CLASS = 15         # mi355ndt_option: 0 (default) = off; 1 / 2 / 3 = 
 GROUND_CLASSES = {None: 0, "horizontal": 1, "vertical": 2, "all": 3}
 GROUND_FLAG_CLASS = {1: 1, 2: 2, 0: 3}   # the reference's flag_class -> the option's value
 PREFILTER_EXTENDED = 0x50467832  # MI355NDT_PREFILTER_EXTENDED: PrefilterParams.extended of the base of a PrefilterParamsEx
+PREFILTER_EXTENDED2 = 0x50467833  # MI355NDT_PREFILTER_EXTENDED2: PrefilterParams.extended of the base of a PrefilterParamsEx2
 DOWNSAMPLE_VOXELGRID = 0       # pcl::VoxelGrid, the prefiltering nodelet's default downsample_method
 DOWNSAMPLE_APPROX_VOXELGRID = 1  # pcl::ApproximateVoxelGrid
 ANGLE_CALIBRATION_RAD = 0.11 * math.pi / 180   # vertical_angle_calibration's constant (prefiltering_nodelet.cpp:190)
@@ -232,6 +241,11 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_prefilter_p.argtypes = [vp, vp, sz, sz, C.POINTER(PrefilterParams), vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_batch_prefilter.argtypes = [vp, i, i, vp, vp, vp, vp, sz, C.POINTER(PrefilterParams), vp, vp]
     L.mi355ndt_batch_get_cloud.argtypes = [vp, i, i, vp, sz, sz, C.POINTER(sz)]
+    L.mi355ndt_prefilter_params_ex2_default.argtypes = [C.POINTER(PrefilterParamsEx2)]
+    L.mi355ndt_batch_get_cloud_i.argtypes = [vp, i, i, vp, sz, sz, i, C.POINTER(sz)]
+    L.mi355ndt_keyframe_from_prefiltered.argtypes = [vp, C.POINTER(i)]
+    L.mi355ndt_keyframe_from_slot.argtypes = [vp, i, i, C.POINTER(i)]
+    L.mi355ndt_window_keyframe_ids.argtypes = [vp, i, vp, vp, C.c_float, i, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_sequence_run_raw.argtypes = [vp, i, vp, vp, sz, vp, C.POINTER(PrefilterParams), C.POINTER(SeqParams), vp, vp, C.POINTER(SeqStats), vp, vp]
     L.mi355ndt_gicp_params_default.argtypes = [C.POINTER(GicpParams)]
     L.mi355ndt_gicp_set_params.argtypes = [vp, C.POINTER(GicpParams)]
@@ -394,11 +408,17 @@ _DOWNSAMPLE_METHODS = {"VOXELGRID": DOWNSAMPLE_VOXELGRID, "APPROX_VOXELGRID": DO
 
 
 def _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method="VOXELGRID",
-                      angle_calibration=False) -> PrefilterParamsEx:
+                      angle_calibration=False, intensity=False):
     """The keywords of Engine.batch_prefilter / sequence_run_raw / prefilter_p as a PrefilterParamsEx, whose `base` the calls are given (no
     library call: a bad transform, an unknown downsample_method and a non-finite calibration angle are refused here).  downsample_method:
     the nodelet's strings ("NONE" is downsample_resolution <= 0); angle_calibration: False, True (the reference's 0.11 degrees) or the
-    angle in radians."""
+    angle in radians.  intensity: the same behind a PrefilterParamsEx2 that names column 3 of the records (byte 12) as their intensity; its
+    ex.base is what the calls are given (_base_ref)."""
+    if intensity:
+        x2 = PrefilterParamsEx2()
+        x2.ex = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
+        x2.ex.base.extended, x2.intensity_offset_bytes, x2.reserved = PREFILTER_EXTENDED2, 12, 0
+        return x2
     if downsample_method not in _DOWNSAMPLE_METHODS:
         raise ValueError(f"downsample_method must be one of {list(_DOWNSAMPLE_METHODS)} (no down-sampling: downsample_resolution <= 0)")
     switch = isinstance(angle_calibration, (bool, np.bool_))
@@ -416,6 +436,11 @@ def _prefilter_params(distance_near, distance_far, downsample_resolution, use_di
     x.use_angle_calibration = int(bool(angle_calibration)) if switch else 1
     x.angle_calibration_rad = rad
     return x
+
+
+def _base_ref(prm):
+    """byref of the PrefilterParams at the head of a PrefilterParamsEx or a PrefilterParamsEx2: what every C call takes"""
+    return C.byref(prm.ex.base if isinstance(prm, PrefilterParamsEx2) else prm.base)
 
 
 _OUTLIER_KEYS = ("method", "mean_k", "stddev_mul", "radius", "min_neighbors")
@@ -584,11 +609,16 @@ class Engine:
         return v.value
 
     def prefilter(self, cloud, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True,
-                  fetch=True, outlier=None):
+                  fetch=True, outlier=None, intensity=False):
         """PrefilteringNodelet distance_filter + VoxelGrid downsample (defaults of launch/dlo_kitti.launch:30-36).
         Returns the filtered [M,3] cloud (or just M when fetch=False; the result stays on the GPU for use_prefiltered).
         outlier: a dict of prefilter_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the nodelet's third stage runs on
-        the resident result before anything is fetched, and what is returned is what prefilter_outliers returns."""
+        the resident result before anything is fetched, and what is returned is what prefilter_outliers returns.
+        intensity: prefilter_p's keyword (the call then goes through prefilter_p: clouds are [N,4] in and out)."""
+        if intensity:
+            out = self.prefilter_p(cloud, distance_near, distance_far, downsample_resolution, use_distance_filter, fetch=fetch and outlier is None,
+                                   intensity=True)
+            return out if outlier is None else self.prefilter_outliers(**{"fetch": fetch, "intensity": True, **outlier})
         a = _as_points(cloud)
         n_out = C.c_size_t()
         if outlier is not None:
@@ -599,39 +629,47 @@ class Engine:
                                               int(use_distance_filter), float(distance_near), float(distance_far),
                                               float(downsample_resolution), out.ctypes.data_as(C.c_void_p) if fetch else None,
                                               a.shape[0], 12, C.byref(n_out)), "prefilter")
-        self._pf_count = n_out.value
+        self._pf_count, self._pf_ch = n_out.value, 3
         return out[: n_out.value].copy() if fetch else n_out.value
 
     def prefilter_p(self, cloud, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None,
-                    downsample_method="VOXELGRID", angle_calibration=False, fetch=True):
+                    downsample_method="VOXELGRID", angle_calibration=False, fetch=True, intensity=False):
         """mi355ndt_prefilter_p: prefilter with the nodelet's whole parameter set (batch_prefilter's keywords) over one cloud.  The result is
-        resident as after prefilter: use_prefiltered and prefilter_outliers follow.  Returns the filtered [M,3] cloud (M when fetch=False)."""
-        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
-        a = _as_points(cloud)
+        resident as after prefilter: use_prefiltered and prefilter_outliers follow.  Returns the filtered [M,3] cloud (M when fetch=False).
+        intensity: column 3 of the [N,>=4] cloud is the points' intensity and goes through the chain (PointXYZI: averaged per voxel, zeroed
+        by the calibration); the result is [M,4] and stays resident with its fourth row."""
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration,
+                                intensity)
+        a = self._records(cloud, intensity)
         n_out = C.c_size_t()
-        out = np.zeros((a.shape[0], 3), np.float32) if fetch else None
-        self._chk(self.lib.mi355ndt_prefilter_p(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.strides[0] if a.shape[0] else 12, C.byref(prm.base),
-                                                out.ctypes.data_as(C.c_void_p) if fetch else None, a.shape[0], 12, C.byref(n_out)), "prefilter_p")
-        self._pf_count = n_out.value
+        w = 4 if intensity else 3
+        out = np.zeros((a.shape[0], w), np.float32) if fetch else None
+        self._chk(self.lib.mi355ndt_prefilter_p(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], 4 * a.shape[1], _base_ref(prm),
+                                                out.ctypes.data_as(C.c_void_p) if fetch else None, a.shape[0], 4 * w, C.byref(n_out)), "prefilter_p")
+        self._pf_count, self._pf_ch = n_out.value, w
         return out[: n_out.value].copy() if fetch else n_out.value
 
-    def prefilter_outliers(self, method="STATISTICAL", mean_k=20, stddev_mul=1.0, radius=0.8, min_neighbors=2, fetch=True, return_stats=False):
+    def prefilter_outliers(self, method="STATISTICAL", mean_k=20, stddev_mul=1.0, radius=0.8, min_neighbors=2, fetch=True, return_stats=False,
+                           intensity=False):
         """PrefilteringNodelet::outlier_removal over the resident prefilter result, in place (mi355ndt_prefilter_outliers): "STATISTICAL"
         (pcl::StatisticalOutlierRemoval, the nodelet's in-code default) or "RADIUS" (pcl::RadiusOutlierRemoval -- which the reference never
         runs: prefiltering_nodelet.cpp:71-78).  Returns the surviving [M,3] cloud (or just M when fetch=False); with return_stats also a
-        dict: dist (f32 per input point, input order), n_in, n_valid, mean, stddev, threshold (zeros for RADIUS)."""
+        dict: dist (f32 per input point, input order), n_in, n_valid, mean, stddev, threshold (zeros for RADIUS).
+        intensity: the survivors come back as [M,4] with their intensities (zeros when the resident result carries none); without it
+        [M,3], whatever the resident result carries."""
         if isinstance(method, str):                # (an unknown name becomes 0, which the library refuses with its own message)
             method = {"STATISTICAL": OUTLIER_STATISTICAL, "RADIUS": OUTLIER_RADIUS}.get(method.upper(), 0)
         prm = OutlierParams(int(method), int(mean_k), float(stddev_mul), float(radius), int(min_neighbors))
         n_in = getattr(self, "_pf_count", 0)
         n_out, st = C.c_size_t(), OutlierStats()
-        out = np.zeros((n_in, 3), np.float32) if fetch else None
+        w = max(4 if intensity else 3, getattr(self, "_pf_ch", 3))       # (a resident intensity row is written out: the records hold it)
+        out = np.zeros((n_in, w), np.float32) if fetch else None
         dist = np.zeros(n_in, np.float32) if return_stats else None
         self._chk(self.lib.mi355ndt_prefilter_outliers(self.h, C.byref(prm), dist.ctypes.data_as(C.c_void_p) if return_stats else None,
-                                                       out.ctypes.data_as(C.c_void_p) if fetch else None, n_in, 12, C.byref(n_out),
+                                                       out.ctypes.data_as(C.c_void_p) if fetch else None, n_in, 4 * w, C.byref(n_out),
                                                        C.byref(st)), "prefilter_outliers")
         self._pf_count = n_out.value
-        res = out[: n_out.value].copy() if fetch else n_out.value
+        res = np.ascontiguousarray(out[: n_out.value, : 4 if intensity else 3]) if fetch else n_out.value
         if not return_stats:
             return res
         return res, dict(dist=dist, n_in=st.n_in, n_valid=st.n_valid, mean=st.mean, stddev=st.stddev, threshold=st.threshold)
@@ -697,6 +735,38 @@ class Engine:
         self._chk(self.lib.mi355ndt_window_keyframe(self.h, K, ptrs, counts, 4 * widths.pop(), 12 if intensity else -1,
                                                     pcm.ctypes.data_as(C.c_void_p), float(leaf), C.byref(kid), C.byref(n_out)), "window_keyframe")
         return kid.value, n_out.value
+
+    def window_keyframe_ids(self, ids, rel_poses, leaf: float = 0.1, intensity: bool = False):
+        """window_keyframe over resident scans (mi355ndt_window_keyframe_ids): scan k is keyframe ids[k] as it is stored (keyframe_add,
+        keyframe_from_prefiltered, keyframe_from_slot); the same rules, the same words, and nothing is uploaded.  intensity: a keyframe of
+        four channels (a scan stored with three contributes +0).  An id may appear twice.  The scans' keyframes are left as they were.
+        Returns (keyframe id, points)."""
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        K = ids.shape[0]
+        if K == 0:
+            raise ValueError("a window has at least one scan")
+        P = np.ascontiguousarray(np.asarray(rel_poses, np.float64).reshape(-1, 4, 4))
+        if P.shape[0] != K:
+            raise ValueError("one 4x4 relative pose per scan")
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(K, 16)        # column-major per scan
+        kid, n_out = C.c_int(-1), C.c_size_t()
+        self._chk(self.lib.mi355ndt_window_keyframe_ids(self.h, K, ids.ctypes.data_as(C.c_void_p), pcm.ctypes.data_as(C.c_void_p), float(leaf),
+                                                        int(bool(intensity)), C.byref(kid), C.byref(n_out)), "window_keyframe_ids")
+        return kid.value, n_out.value
+
+    def keyframe_from_prefiltered(self) -> int:
+        """The resident prefilter result (after prefilter / prefilter_p / prefilter_outliers) becomes a keyframe, device to device, with
+        its intensity when it has one; returns its id.  The result stays resident."""
+        kid = C.c_int(-1)
+        self._chk(self.lib.mi355ndt_keyframe_from_prefiltered(self.h, C.byref(kid)), "keyframe_from_prefiltered")
+        return kid.value
+
+    def keyframe_from_slot(self, pair: int, target: bool) -> int:
+        """The cloud batch slot `pair` holds on its target (or source) side becomes a keyframe, device to device, with its intensity when
+        the slot carries one (batch_prefilter / sequence_run_raw with intensity=True); returns its id.  The slot is left as it was."""
+        kid = C.c_int(-1)
+        self._chk(self.lib.mi355ndt_keyframe_from_slot(self.h, int(pair), 2 if target else 1, C.byref(kid)), "keyframe_from_slot")
+        return kid.value
 
     def keyframe_add(self, cloud, intensity: bool = False) -> int:
         """A host cloud as it is becomes a resident keyframe; returns its id."""
@@ -1047,7 +1117,8 @@ class Engine:
         self._chk(self.lib.mi355ndt_batch_set_clouds(self.h, first_pair, n, ptr(tp), ptr(tc), ptr(sp), ptr(sc), stride, threads), "batch_set_clouds")
 
     def batch_prefilter(self, targets, sources, first_pair=0, distance_near=0.5, distance_far=100.0, downsample_resolution=0.1,
-                        use_distance_filter=True, transform=None, outlier=None, downsample_method="VOXELGRID", angle_calibration=False):
+                        use_distance_filter=True, transform=None, outlier=None, downsample_method="VOXELGRID", angle_calibration=False,
+                        intensity=False):
         """mi355ndt_batch_prefilter: lists of RAW clouds ([N,>=3], x,y,z first; either list may be None) through PrefilteringNodelet's distance
         filter and VoxelGrid down-sampling (Engine.prefilter's rules and keyword defaults) into the batch slots first_pair ...; batch_reserve
         comes first, sized for the FILTERED clouds.  transform: a 4x4 applied to every raw point first (the nodelet's base_link move).
@@ -1056,13 +1127,19 @@ class Engine:
         vertical_angle_calibration, after the move and before the gate.
         outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the nodelet's third stage runs
         over the same slots and sides right after, and the counts returned are those after both stages.
+        intensity: column 3 of the [N,>=4] clouds is the points' intensity and goes through the chain into the slots' intensity rows
+        (batch_get_cloud(intensity=True), keyframe_from_slot); the outlier stage keeps the survivors'.
         Returns (target counts, source counts) after the filter, None for a side not given."""
+        if intensity:
+            for c in list(targets or []) + list(sources or []):
+                self._records(c, True)
         if targets is None and sources is None:
             raise ValueError("give targets, sources or both")
         if targets is not None and sources is not None and len(targets) != len(sources):
             raise ValueError("one source per target")
         oprm = None if outlier is None else _outlier_dict(outlier)
-        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration,
+                                intensity)
         n = len(targets if targets is not None else sources)
         both = _cloud_table(list(targets or []) + list(sources or []), widen=True)     # (one stride for the whole call)
         nt = len(targets) if targets is not None else 0
@@ -1071,7 +1148,7 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         tt, ts = tabs
         self._chk(self.lib.mi355ndt_batch_prefilter(self.h, int(first_pair), n, ptr(tt and tt[0]), ptr(tt and tt[1]), ptr(ts and ts[0]), ptr(ts and ts[1]),
-                                                    both[3], C.byref(prm.base), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
+                                                    both[3], _base_ref(prm), ptr(outs[0]), ptr(outs[1])), "batch_prefilter")
         if oprm is not None:
             self._chk(self.lib.mi355ndt_batch_remove_outliers(self.h, int(first_pair), n, (2 if targets is not None else 0) | (1 if sources is not None else 0),
                                                               C.byref(oprm), ptr(outs[0]), ptr(outs[1]), None, None), "batch_remove_outliers")
@@ -1104,10 +1181,16 @@ class Engine:
             return counts
         return counts + tuple(None if a is None else [{k: getattr(a[j], k) for k, _ in OutlierStats._fields_} for j in range(n)] for a in st)
 
-    def batch_get_cloud(self, pair: int, target: bool) -> np.ndarray:
-        """The points batch slot `pair` holds on its target (or source) side, [M,3] f32, whatever route filled it."""
+    def batch_get_cloud(self, pair: int, target: bool, intensity: bool = False) -> np.ndarray:
+        """The points batch slot `pair` holds on its target (or source) side, [M,3] f32, whatever route filled it.  intensity: [M,4], with
+        the intensities batch_prefilter(intensity=True) left in the slot (zeros for a slot filled by any other route)."""
         role, m = 2 if target else 1, C.c_size_t()
         self._chk(self.lib.mi355ndt_batch_get_cloud(self.h, int(pair), role, None, 0, 12, C.byref(m)), "batch_get_cloud")
+        if intensity:
+            out = np.zeros((m.value, 4), np.float32)
+            self._chk(self.lib.mi355ndt_batch_get_cloud_i(self.h, int(pair), role, out.ctypes.data_as(C.c_void_p), m.value, 16, 12, C.byref(m)),
+                      "batch_get_cloud_i")
+            return out
         out = np.zeros((m.value, 3), np.float32)
         self._chk(self.lib.mi355ndt_batch_get_cloud(self.h, int(pair), role, out.ctypes.data_as(C.c_void_p), m.value, 12, C.byref(m)), "batch_get_cloud")
         return out
@@ -1244,14 +1327,19 @@ class Engine:
 
     def sequence_run_raw(self, frames, stamps, keyframe_delta_trans=5.0, keyframe_delta_angle=0.17, keyframe_delta_time=1.0,
                          distance_near=0.5, distance_far=100.0, downsample_resolution=0.1, use_distance_filter=True, transform=None, raw_records=False,
-                         outlier=None, downsample_method="VOXELGRID", angle_calibration=False):
+                         outlier=None, downsample_method="VOXELGRID", angle_calibration=False, intensity=False):
         """mi355ndt_sequence_run_raw: sequence_run over RAW scans, the batch prefilter (batch_prefilter's keywords) in front and no scan
         downloaded in between.  outlier: a dict of batch_remove_outliers' keywords (may be empty: the nodelet's in-code defaults) -- the
         nodelet's third stage runs between the prefilter and the run (mi355ndt_sequence_run_raw_outliers); the filtered counts and
-        prefilter_ms then cover both stages.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
+        prefilter_ms then cover both stages.  intensity: batch_prefilter's keyword -- the frames' slots (target side) carry the filtered
+        intensities afterwards; the run itself does not look at them.  Returns (list of per-frame dicts, stats dict with prefilter_ms added, filtered counts); raw_records=True
         returns the (SeqFrame * n, Result * n) arrays in place of the dicts."""
-        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration)
+        prm = _prefilter_params(distance_near, distance_far, downsample_resolution, use_distance_filter, transform, downsample_method, angle_calibration,
+                                intensity)
         oprm = None if outlier is None else _outlier_dict(outlier)
+        if intensity:
+            for f in frames:
+                self._records(f, True)
         clouds, ptrs, cnts, stride = _cloud_table(frames)
         n = len(clouds)
         st = np.ascontiguousarray(stamps, np.float64)
@@ -1260,7 +1348,7 @@ class Engine:
         sp = SeqParams(keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time)
         out, res, stats = (SeqFrame * n)(), (Result * n)(), SeqStats()
         filtered, pf_ms = np.zeros(max(n, 1), np.uint64), C.c_double()
-        head = (self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride, st.ctypes.data_as(C.c_void_p), C.byref(prm.base))
+        head = (self.h, n, ptrs.ctypes.data_as(C.c_void_p), cnts.ctypes.data_as(C.c_void_p), stride, st.ctypes.data_as(C.c_void_p), _base_ref(prm))
         tail = (C.byref(sp), C.cast(out, C.c_void_p), C.cast(res, C.c_void_p), C.byref(stats), filtered.ctypes.data_as(C.c_void_p), C.byref(pf_ms))
         if oprm is None:
             self._chk(self.lib.mi355ndt_sequence_run_raw(*head, *tail), "sequence_run_raw")

@@ -981,6 +981,54 @@ int mi355ndt_icp_batch_align(mi355ndt_handle* h, const float* guesses_colmajor, 
 int mi355ndt_icp_batch_get_aligned(mi355ndt_handle* h, int slot, void* out_pts, size_t out_stride_bytes);
 int mi355ndt_icp_batch_stats(mi355ndt_handle* h, int* rounds, int* requests);
 
+/* ---- exact k-nearest and radius search over resident keyframes ---------------------------------------------------- */
+/* replaces pcl::KdTreeFLANN::nearestKSearch / radiusSearch over a keyframe a host would otherwise download (mi355ndt_keyframe_get) and
+ * build a kd-tree over on the CPU: the search the fitness scores, ICP, the GICP covariances and the outlier removals run internally, as a
+ * surface of its own, over the keyframe's one spatial index (found, whichever surface built it, or built here from
+ * MI355NDT_OPT_KF_FITNESS_CELL_MM and kept until mi355ndt_keyframe_release; no result word depends on the cell size).  The rules are the
+ * engine's, restated in tools/knn_ref.py:
+ *   - searchable points: three finite coordinates; a keyframe without one (or without a point) gives count 0 everywhere;
+ *   - the query: a point, moved by T_colmajor (4x4 f32; NULL: not moved) as ((T0 x + T1 y) + T2 z) + T3, every operation rounded on its
+ *     own; a query that is not finite before or after the move finds nothing (count 0);
+ *   - the distance: d2 = (dx*dx + dy*dy) + dz*dz in f32;
+ *   - the order: ascending (d2, id): A TIE GOES TO THE LOWER POINT ID.  FLANN's order among equal distances is not observable and is
+ *     not reproduced;
+ *   - k-NN: the k first points in that order (1 <= k <= 64), kept iff (double)d2 <= max_range * max_range -- INCLUSIVE, ICP's rule;
+ *     max_range +inf by default; counts[q] = the filled slots;
+ *   - radius: within iff d2 < r2, r2 = (float)(radius * radius) -- STRICT, RadiusOutlierRemoval's rule and rounding; counts[q] = ALL the
+ *     searchable points within, the lists hold the max_nn nearest of them (1 <= max_nn <= 64);
+ *   - unused list slots: id -1, d2 +inf.
+ * ids / d2 are [n][k] (or [n][max_nn]) row-major, counts [n].  query_order: how the queries are dealt to the lanes -- the input order, or
+ * sorted by their cell in the searched keyframe's lattice (a wave's lanes then walk similar rings; one sort per item); both give identical
+ * words.  MI355NDT_KNN_ORDER_AUTO follows the measurement in DESIGN.md section 8 (tools/keyframe_knn_timing.py): cell order for 4,096 or
+ * more queries from the host (20-24 % faster when they arrive in no order, 0.05 ms slower when they are ordered already), input order
+ * for fewer and for queries that are a resident keyframe (a window keyframe's points are in cell order as they are).
+ * mi355ndt_keyframe_knn_ids: E (searched keyframe, query keyframe, pose) items in one launch chain and one wait, the queries read in
+ * place (cloud_uploads does not move); relposes f64 [E][16] column-major, cast entry-wise to f32 as mi355ndt_keyframe_fitness_scores casts
+ * them; the results are concatenated in item order; total_queries must equal the sum of the query keyframes' counts.
+ * Errors, each with a message: MI355NDT_ERR_STATE in stream mode; MI355NDT_ERR_BAD_ARG for an unknown or released id, k or max_nn outside
+ * 1..64, a NaN or negative max_range or radius, stride_bytes < 12, a NULL output, a wrong total_queries.  A refused call writes nothing,
+ * changes nothing and builds nothing.  n == 0 and n_items == 0 are MI355NDT_OK with nothing written.  Synchronous, one wait for the
+ * device per call; no keyframe is written. */
+#define MI355NDT_KNN_ORDER_AUTO  0
+#define MI355NDT_KNN_ORDER_INPUT 1
+#define MI355NDT_KNN_ORDER_CELL  2
+#define MI355NDT_KNN_MAX_K 64
+typedef struct mi355ndt_knn_params {
+  int    k;            /* 1 .. MI355NDT_KNN_MAX_K */
+  double max_range;    /* >= 0; +inf: no limit */
+  int    query_order;  /* MI355NDT_KNN_ORDER_* */
+} mi355ndt_knn_params;
+int mi355ndt_knn_params_default(mi355ndt_knn_params* p);   /* k 1, max_range +inf, query_order MI355NDT_KNN_ORDER_AUTO */
+int mi355ndt_keyframe_knn(mi355ndt_handle* h, int kf_id, const void* queries, size_t n, size_t stride_bytes, const float* T_colmajor /* may be NULL */,
+                          const mi355ndt_knn_params* p, int* ids /* [n][k] */, float* d2 /* [n][k] */, int* counts /* [n] */);
+int mi355ndt_keyframe_knn_ids(mi355ndt_handle* h, int n_items, const int* searched_ids, const int* query_ids,
+                              const double* relposes /* 16 per item, column-major f64 */, const mi355ndt_knn_params* p, size_t total_queries,
+                              int* ids, float* d2, int* counts);
+int mi355ndt_keyframe_radius_search(mi355ndt_handle* h, int kf_id, const void* queries, size_t n, size_t stride_bytes,
+                                    const float* T_colmajor /* may be NULL */, double radius, int max_nn, int query_order,
+                                    int* ids /* [n][max_nn] */, float* d2 /* [n][max_nn] */, int* counts /* [n] */);
+
 /* profiling: HIP-event timing of the engine's own kernels on the engine's stream */
 int mi355ndt_profile_enable(mi355ndt_handle* h, int on);
 int mi355ndt_profile_reset(mi355ndt_handle* h);

@@ -11,6 +11,8 @@
 //   ICP           : [k_icp_step -> k_icp_final]*, one round trip per iteration (pcl::IterativeClosestPoint; the 3x3 SVD, the criteria and
 //                   the loop on the host: ndt_icp.hpp, icp_outer.hpp, ndt_host_icp.hpp); the batch: [table copy -> k_icp_step_batch ->
 //                   k_icp_final_batch]* for all candidates of a loop check (ndt_host_icp_batch.hpp)
+//   search        : [index build] -> [k_knn_keys -> radix sort per item] -> k_kf_knn (ring walk) + k_kf_knn (exhaustive): exact k-nearest and
+//                   radius search over resident keyframes, one launch chain and one wait per call (ndt_knn.hpp, ndt_host_knn.hpp)
 //   align         : k_init_state -> k_sweep -> [k_update -> k_sweep]*      (computeTransformation +
 //                   computeDerivatives + computeStepLengthMT, include/ndt_omp/ndt_omp_impl2.hpp:87-188, 196-305, 841-1003;
 //                   step_size <= eps/2 only: [k_update -> k_hessian -> k_update -> k_sweep]*, impl2:622-714, 920-1000)
@@ -63,6 +65,7 @@
 #include "ndt_kffitness.hpp"
 #include "ndt_outlier.hpp"
 #include "ndt_outlier_batch.hpp"
+#include "ndt_knn.hpp"
 #include "ndt_gicp.hpp"
 #include "gicp_bfgs.hpp"
 #include "gicp_lockstep.hpp"
@@ -96,6 +99,7 @@ NDT_KERNELS_OF_TU
 #include "ndt_host_keyframe.hpp"   // window map, keyframe store, consumers by id
 #include "ndt_host_kffitness.hpp"  // fitness scores of edges between keyframes, information matrices
 #include "ndt_host_outlier.hpp"    // outlier removal over the prefilter result and over batch slots
+#include "ndt_host_knn.hpp"        // k-nearest and radius search over resident keyframes
 #include "ndt_host_gicp.hpp"       // GICP: covariances, correspondences, cost, BFGS driver, align
 #include "ndt_host_gicp_batch.hpp" // GICP: all candidates of a loop check in one lockstep batch
 #include "ndt_host_icp.hpp"        // ICP: correspondences, align (the estimate, the criteria and the loop: icp_outer.hpp)

@@ -94,6 +94,11 @@ class IcpParams(C.Structure):
                 ("corr_dist_threshold", C.c_double), ("min_number_correspondences", C.c_int), ("use_reciprocal_correspondences", C.c_int)]
 
 
+class KnnParams(C.Structure):
+    """mi355ndt_knn_params: k (1 .. 64), max_range (kept iff (double)d2 <= max_range^2; +inf: no limit), query_order (KNN_ORDER_*)."""
+    _fields_ = [("k", C.c_int), ("max_range", C.c_double), ("query_order", C.c_int)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("final_colmajor", C.c_float * 16), ("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("matches", C.c_int),
                 ("mse", C.c_double)]
@@ -164,7 +169,10 @@ SYMBOLS = [
     "mi355ndt_icp_set_source_keyframe", "mi355ndt_icp_correspondences", "mi355ndt_icp_align", "mi355ndt_icp_get_aligned",
     "mi355ndt_icp_batch_reserve", "mi355ndt_icp_batch_set_source", "mi355ndt_icp_batch_set_source_keyframe", "mi355ndt_icp_batch_align",
     "mi355ndt_icp_batch_get_aligned", "mi355ndt_icp_batch_stats",
+    "mi355ndt_knn_params_default", "mi355ndt_keyframe_knn", "mi355ndt_keyframe_knn_ids", "mi355ndt_keyframe_radius_search",
 ]
+KNN_ORDER_AUTO, KNN_ORDER_INPUT, KNN_ORDER_CELL = 0, 1, 2   # MI355NDT_KNN_ORDER_*: how keyframe_knn deals its queries to the lanes; no result word depends on it
+KNN_MAX_K = 64                 # MI355NDT_KNN_MAX_K
 ICP_BATCH_MAX = 64             # MI355NDT_ICP_BATCH_MAX: slots of one mi355ndt_icp_batch_align
 ICP_STATES = ["NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES"]   # mi355ndt_icp_state
 GICP_BATCH_MAX = 64            # MI355NDT_GICP_BATCH_MAX: slots of one mi355ndt_gicp_batch_align
@@ -279,6 +287,10 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_icp_batch_align.argtypes = [vp, vp, vp]
     L.mi355ndt_icp_batch_get_aligned.argtypes = [vp, i, vp, sz]
     L.mi355ndt_icp_batch_stats.argtypes = [vp, C.POINTER(i), vp]
+    L.mi355ndt_knn_params_default.argtypes = [C.POINTER(KnnParams)]
+    L.mi355ndt_keyframe_knn.argtypes = [vp, i, vp, sz, sz, vp, C.POINTER(KnnParams), vp, vp, vp]
+    L.mi355ndt_keyframe_knn_ids.argtypes = [vp, i, vp, vp, vp, C.POINTER(KnnParams), sz, vp, vp, vp]
+    L.mi355ndt_keyframe_radius_search.argtypes = [vp, i, vp, sz, sz, vp, C.c_double, i, i, vp, vp, vp]
     L.mi355ndt_map_cloud.argtypes = [vp, i, vp, vp, sz, vp, C.c_double, vp, sz, sz, C.POINTER(sz)]
     L.mi355ndt_window_keyframe.argtypes = [vp, i, vp, vp, sz, i, vp, C.c_float, C.POINTER(i), C.POINTER(sz)]
     L.mi355ndt_keyframe_add.argtypes = [vp, vp, sz, sz, i, C.POINTER(i)]
@@ -837,6 +849,60 @@ class Engine:
                                                             pcm.ctypes.data_as(C.c_void_p), mr, scores.ctypes.data_as(C.c_void_p),
                                                             inliers.ctypes.data_as(C.c_void_p)), "keyframe_fitness_scores")
         return scores[:E], inliers[:E]
+
+    # -- exact k-nearest and radius search over resident keyframes (pcl::KdTreeFLANN over a keyframe that stays on the device)
+    @staticmethod
+    def _knn_out(n: int, k: int):
+        """result arrays as the library leaves untouched slots: id -1, d2 +inf, count 0"""
+        return np.full((n, k), -1, np.int32), np.full((n, k), np.inf, np.float32), np.zeros(n, np.int32)
+
+    def keyframe_knn(self, kid: int, queries, k: int, max_range: float = float("inf"), T=None, query_order: int = KNN_ORDER_AUTO):
+        """The k nearest searchable points of resident keyframe `kid` for every query ([n,>=3] floats, moved by the 4x4 f32 pose T when
+        given): (ids [n,k] int32, d2 [n,k] float32, counts [n] int32), ascending (d2, id) -- a tie goes to the lower point id -- kept iff
+        (double)d2 <= max_range^2; unused slots hold -1 / +inf.  tools/knn_ref.py restates every word.  The keyframe stays on the device."""
+        q = _as_points(queries) if len(queries) else np.zeros((0, 3), np.float32)
+        n = q.shape[0]
+        p = KnnParams(int(k), float(max_range), int(query_order))
+        ids, d2, cnt = self._knn_out(n, max(int(k), 1))
+        t = _colmajor(T) if T is not None else None
+        self._chk(self.lib.mi355ndt_keyframe_knn(self.h, int(kid), q.ctypes.data_as(C.c_void_p), n, 4 * q.shape[1],
+                                                 t.ctypes.data_as(C.c_void_p) if t is not None else None, C.byref(p),
+                                                 ids.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)), "keyframe_knn")
+        return ids, d2, cnt
+
+    def keyframe_knn_ids(self, searched_ids, query_ids, relposes, k: int, max_range: float = float("inf"), query_order: int = KNN_ORDER_AUTO,
+                         total_queries: int | None = None):
+        """keyframe_knn for E (searched keyframe, query keyframe, 4x4 f64 pose) items in one launch chain and one wait, the queries read
+        in place (nothing is uploaded); the poses are cast to f32 as keyframe_fitness_scores casts them.  Returns (ids, d2, counts)
+        concatenated in item order; total_queries (default: asked of the store) must be the sum of the query keyframes' counts."""
+        a = np.ascontiguousarray(searched_ids, np.int32).ravel()
+        b = np.ascontiguousarray(query_ids, np.int32).ravel()
+        E = len(a)
+        P = np.asarray(relposes, np.float64).reshape(-1, 4, 4)
+        if len(b) != E or P.shape[0] != E:
+            raise ValueError("one id of each side and one 4x4 relative pose per item")
+        if total_queries is None:
+            total_queries = sum(self.keyframe_get(int(x), fetch=False) for x in b)
+        pcm = np.ascontiguousarray(np.transpose(P, (0, 2, 1))).reshape(E, 16)        # column-major per item
+        p = KnnParams(int(k), float(max_range), int(query_order))
+        ids, d2, cnt = self._knn_out(int(total_queries), max(int(k), 1))
+        self._chk(self.lib.mi355ndt_keyframe_knn_ids(self.h, E, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), pcm.ctypes.data_as(C.c_void_p),
+                                                     C.byref(p), int(total_queries), ids.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p),
+                                                     cnt.ctypes.data_as(C.c_void_p)), "keyframe_knn_ids")
+        return ids, d2, cnt
+
+    def keyframe_radius_search(self, kid: int, queries, radius: float, max_nn: int, T=None, query_order: int = KNN_ORDER_AUTO):
+        """Radius search over resident keyframe `kid`: within iff d2 < (float)(radius * radius), strictly.  counts [n] = ALL the searchable
+        points within; (ids, d2) [n,max_nn] = the max_nn nearest of them in ascending (d2, id), unused slots -1 / +inf."""
+        q = _as_points(queries) if len(queries) else np.zeros((0, 3), np.float32)
+        n = q.shape[0]
+        ids, d2, cnt = self._knn_out(n, max(int(max_nn), 1))
+        t = _colmajor(T) if T is not None else None
+        self._chk(self.lib.mi355ndt_keyframe_radius_search(self.h, int(kid), q.ctypes.data_as(C.c_void_p), n, 4 * q.shape[1],
+                                                           t.ctypes.data_as(C.c_void_p) if t is not None else None, float(radius), int(max_nn),
+                                                           int(query_order), ids.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p),
+                                                           cnt.ctypes.data_as(C.c_void_p)), "keyframe_radius_search")
+        return ids, d2, cnt
 
     # -- GICP (pclomp::GeneralizedIterativeClosestPoint, registration_method = GICP_OMP): one pair, synchronous (the batch form follows)
     def gicp_set_params(self, p: GicpParams):

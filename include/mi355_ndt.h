@@ -411,6 +411,24 @@ int mi355ndt_batch_size(const mi355ndt_handle* h);
  * targets first if they are not built; MI355NDT_ERR_STATE in stream mode.  The loop detector's verification of K candidates against one
  * new keyframe (loop_detector.hpp:148-281) is one batch_align + one call of this (lv_slam_amd/loop_closure.py). */
 int mi355ndt_batch_fitness_scores(mi355ndt_handle* h, const float* T_colmajor, double max_range, double* scores, long long* n_inliers);
+/* Many start poses per pair scored in one call.  For item e: the score and the hit count that one computeDerivatives sweep (ndt_omp_impl2.hpp:196-305)
+ * yields for pair pairs[e] of the bound batch with its source moved by the f32 matrix poses_colmajor[16 e .. 16 e + 15] -- the first sweep of an
+ * align from that guess (impl2:102-129).  Gradient and Hessian are not evaluated.  scores[e] and hits[e] (hits may be NULL) are bit for bit what
+ * mi355ndt_derivatives_T(T_e, any Rj) returns on a one-pair engine that holds the pair's two clouds with the same parameters and the same
+ * MI355NDT_OPT_F32_SUM_ORDER, latency mode off; a row's bits depend on the pair, the pose and the input order alone.  Items may name pairs in any
+ * order, a pair many times or not at all; a pair whose target has no searchable voxel scores 0.0 with 0 hits.  Host clouds and keyframe ids in
+ * the slots; the grids are built first if they are not.  Synchronous: one copy of the call's tables in, two launches, one wait.  The call has a
+ * pose table, a row buffer and a landing block of its own: the pair states, the results of the last mi355ndt_batch_align, the partial rows
+ * (mi355ndt_get_partial_rows) and the incremental transforms (mi355ndt_get_incremental) are what they were.  n_items == 0 launches nothing.
+ * Served: variant OMP and PCA with DIRECT1 / DIRECT7 / DIRECT26, OMP with KDTREE, both f32 sum orders.
+ * Refused before anything is enqueued, nothing changed, with a mi355ndt_last_error text: MI355NDT_ERR_STATE in stream mode;
+ * MI355NDT_ERR_UNSUPPORTED for ndt_pca + KDTREE (order-dependent weights, a kernel of its own), MI355NDT_OPT_POSE_MODEL = 1,
+ * MI355NDT_OPT_NDT_CLASS = 1, a non-zero MI355NDT_OPT_GROUND_CLASS, and MI355NDT_OPT_ARITH = 1 (its grids are tree-summed and its records are
+ * another layout: serving it is a later change); MI355NDT_ERR_BAD_ARG for n_items above MI355NDT_SCORE_POSES_MAX_ITEMS, a pair index outside
+ * the batch and a pose with a non-finite entry.  This is not a call of the reference: lv_slam_amd/loop_closure.py (verify_candidates_search)
+ * uses it to pick the start of a loop check from a lattice of poses around the guess. */
+#define MI355NDT_SCORE_POSES_MAX_ITEMS 65536
+int mi355ndt_batch_score_poses(mi355ndt_handle* h, int n_items, const int* pairs, const float* poses_colmajor, double* scores, long long* hits);
 /* Pose records of the last mi355ndt_batch_align for the multi-GPU gather, written on the device into a caller-owned DEVICE
  * buffer of `capacity` 96-byte records {float final[16] column-major; float score; int32 iterations; int32 converged;
  * int32 pair_id; int32 pad[4]}: record k describes batch slot k and carries pair_id = id_base + k * id_stride (round-robin

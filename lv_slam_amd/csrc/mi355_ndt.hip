@@ -19,7 +19,7 @@
 // Build: __graft_entry__.build() compiles three translation units side by side and links them: this file, mi355_ndt_ord1.hip (the kernel
 // instantiations of the second f32 sum order) and mi355_ndt_fast.hip (those of the tolerance arithmetic), each its ORD's rows of the one table
 // of sweep and align kernels (ndt_sweep_exists.hpp); -DNDT_SINGLE_TU builds everything from this file alone.
-// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp (the Newton control they call: ndt_newton.hpp) / ndt_hessian.hpp / ndt_upload.hpp / ndt_pose_record.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_prefilter_batch.hpp / ndt_prefilter_approx.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
+// Kernels live in ndt_build.hpp / ndt_sweep.hpp / ndt_update.hpp (the Newton control they call: ndt_newton.hpp) / ndt_hessian.hpp / ndt_upload.hpp / ndt_pose_record.hpp / ndt_pose_scores.hpp / ndt_fitness.hpp / ndt_prefilter.hpp / ndt_prefilter_batch.hpp / ndt_prefilter_approx.hpp / ndt_keyframe.hpp / ndt_kffitness.hpp / ...; the host side of the
 // C-ABI lives in ndt_engine.hpp and the ndt_host_*.hpp headers listed at the end of this file, one per surface.  It stays ONE translation unit
 // (the non-template kernels of the headers would collide across units).  Data layout in HBM: DESIGN.md.  Built with -ffp-contract=off: every
 // f32/f64 step of the reference recipe is a separately rounded operation.
@@ -76,10 +76,12 @@
 #include "ndt_hostmem.hpp"
 #include "ndt_grid_state.hpp"
 #include "ndt_sweep_waves.hpp"
+#include "ndt_pose_scores.hpp"
 #ifndef NDT_SINGLE_TU      // the ORD = 1 / 2 rows of the table come from mi355_ndt_ord1.hip / mi355_ndt_fast.hip (built side by side with this file)
 #define NDT_TU ELSEWHERE
 #define NDT_TU_X extern template
 NDT_KERNELS_OF_TU
+NDT_POSE_SCORE_KERNELS_OF_TU   // (no rows of the table: the pose scores' own list, ndt_pose_scores.hpp)
 #endif
 
 // ------------------------------------------------------------------------------------ host side, in dependency order
@@ -93,6 +95,7 @@ NDT_KERNELS_OF_TU
 #include "ndt_host_align.hpp"      // batch align, single-registration surface
 #include "ndt_host_hooks.hpp"      // parity hooks and getters
 #include "ndt_host_fitness.hpp"    // fitness scores, calculateScore
+#include "ndt_host_pose_scores.hpp" // many start poses per pair scored in one call
 #include "ndt_host_voxel.hpp"      // the scratch and the steps shared by the four voxel surfaces below
 #include "ndt_host_prefilter.hpp"  // prefilter
 #include "ndt_host_mapcloud.hpp"   // map cloud

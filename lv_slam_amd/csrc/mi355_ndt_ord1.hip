@@ -12,6 +12,8 @@
 #include "ndt_sweep_kd.hpp"
 #include "ndt_async.hpp"
 #include "ndt_sweep_exists.hpp"
+#include "ndt_pose_scores.hpp"
 #define NDT_TU ORD1
 #define NDT_TU_X template
 NDT_KERNELS_OF_TU
+NDT_POSE_SCORE_KERNELS_OF_TU   // (the ORD = 1 rows of the pose scores' own list, ndt_pose_scores.hpp)

@@ -270,6 +270,9 @@ struct mi355ndt_handle {
   PinBuf<int> h_pin_active;
   HipEvent ev_burst[2];                           // one per in-flight burst of align rounds
   DevBuf<unsigned long long> d_hits;              // [0] (point,voxel) evaluations, all sweeps; [1] score-only sweeps of the one-launch align
+  // mi355ndt_batch_score_poses (ndt_host_pose_scores.hpp): the call's tables (pinned twin -> device), its rows and its mapped landing block
+  // (n scores, n hit counts) -- all its own: the align workspace above is not touched
+  struct PoseScores { PinBuf<unsigned char> h_tab; DevBuf<unsigned char> d_tab; DevBuf<double> d_rows; PinBuf<double> h_out; } pose_scores;
   DevBuf<float> d_hook;                           // 16 + 9 floats, 6 doubles
   DevBuf<float> d_aligned;
   PinBuf<float> h_pin_aligned;                    // pinned landing buffer of get_aligned

@@ -772,7 +772,8 @@ struct HitQueue {
 };
 
 // SO: score-only item (the pair's last sweep, PairState::last_sweep): the same probe stage, hit queue, 64-hit batches and ndt_pca weights; each
-// hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (one-launch align only).
+// hit is evaluated by eval_score / eval_score_fast and the row carries the score and the hit count alone (the one-launch align, and
+// k_pose_scores of ndt_pose_scores.hpp, whose items are nothing else).
 // PM = 1 (MI355NDT_OPT_POSE_MODEL, the lockstep rounds only): phase A stages the moved point and the ORIGINAL point, phase B is eval_hit_euler over
 // the pair's rows sc.euler_rows[b] (written by whoever wrote the pair's T: k_init_state, k_set_pose_p, newton_update).
 // GATE (MI355NDT_OPT_GROUND_CLASS = 1 / 2, the lockstep rounds only): computeDerivatives_seg (ndt_ground_impl.hpp:484-546) adds a point's sums
@@ -789,7 +790,7 @@ __device__ __forceinline__ void sweep_item(const int b, const int rem, const flo
                                            Timeline& tl) {
   constexpr bool KD = (K == 27);
   constexpr bool FAST = (ORD == 2);                // tolerance arithmetic (eval_hit_fast): `recs` holds VoxelRecF records
-  static_assert(!SO || (ASYNC && !FINE), "score-only items belong to the one-launch align");
+  static_assert(!SO || (ASYNC && !FINE), "score-only items: the one-launch align's last sweep and the pose scores (ndt_pose_scores.hpp), both with the pose in words");
   static_assert(!FAST || K == 1 || K == 7, "tolerance arithmetic is instantiated for DIRECT1 / DIRECT7");
   static_assert(PM == 0 || (!PCA && !FAST && !ASYNC && !FINE && !SO), "the Euler model takes the lockstep rounds: ndt_omp, exact arithmetic, batch items");
   static_assert(PM != 2 || (K == 27 && ORD == 0 && IT == 8), "PCL's class: the radius search, batch items");

@@ -108,6 +108,79 @@ def verify_candidates(engine: ndt.Engine, target, candidates, guesses, max_range
     return select_matching_and_bow(converged, scores, finals, bow, thresh)
 
 
+LATTICE_DX = LATTICE_DY = (-2.0, -1.0, 0.0, 1.0, 2.0)      # [m]  pose_lattice's default offsets: two leaves of a 1 m grid either way ...
+LATTICE_DYAW = (-0.1, 0.0, 0.1)                            # [rad] ... and a yaw step that moves a point 30 m out by three of them
+
+
+def pose_lattice(guess, dx=LATTICE_DX, dy=LATTICE_DY, dyaw=LATTICE_DYAW) -> np.ndarray:
+    """Start poses around a loop guess: [G,4,4] float32.  Entry 0 is the guess itself, bit for bit; then, for every (ddx, ddy, psi) of
+    dx x dy x dyaw in that order except (0, 0, 0), [Rz(psi) R | t + (ddx, ddy, 0)] from the guess's R and t -- computed in f64, cast once,
+    last row exactly 0 0 0 1.  Not in the reference, whose loop check has the one guess (loop_detector.hpp:171-172)."""
+    g32 = np.array(guess, np.float32)
+    if g32.shape != (4, 4):
+        raise ValueError("guess must be 4x4")
+    G64 = g32.astype(np.float64)
+    off = np.array([(x, y, p) for x in dx for y in dy for p in dyaw if not (x == 0 and y == 0 and p == 0)], np.float64).reshape(-1, 3)
+    c, s = np.cos(off[:, 2:3]), np.sin(off[:, 2:3])
+    # Rz(psi) R row by row -- rows 0 and 1 of R mixed, row 2 kept -- each entry two products and one sum, rounded where they stand
+    P = np.zeros((len(off), 4, 4))
+    P[:, 0, :3] = c * G64[0, :3] - s * G64[1, :3]
+    P[:, 1, :3] = s * G64[0, :3] + c * G64[1, :3]
+    P[:, 2, :3] = G64[2, :3]
+    P[:, :3, 3] = G64[:3, 3]
+    P[:, :2, 3] += off[:, :2]
+    P32 = P.astype(np.float32)
+    P32[:, 3] = np.float32([0, 0, 0, 1])
+    return np.concatenate([g32[None], P32])
+
+
+def pick_starts(scores) -> list[int]:
+    """Per row of scores [K,G] (candidate k, lattice pose j) the lattice index of the highest score; a tie goes to the lowest index, so the
+    guess (index 0) wins ties and wins when nothing hits."""
+    S = np.asarray(scores, np.float64)
+    return [int(np.argmax(row)) for row in S.reshape(S.shape[0], -1)]
+
+
+def verify_candidates_search(engine: ndt.Engine, target, candidates, guesses, lattice=None, max_range: float = float("inf"), thresh: float = 0.5,
+                             bow=None):
+    """verify_candidates with a search over start poses in front of the aligns: the slots are filled as verify_candidates fills them, ONE
+    batch_score_poses scores pose_lattice(guesses[c], **lattice) for every candidate c (lattice: a dict of pose_lattice's dx / dy / dyaw,
+    None = its defaults), every candidate starts from its best-scoring pose (pick_starts), and from there on it is verify_candidates' own
+    flow: ONE batch_align, ONE batch_fitness_scores, select_matching or select_matching_and_bow.  NDT at 0.5-1 m leaves converges from a
+    metre or two; a loop guess after a long loop is often further off, and the reference's fitness threshold then turns the missed basin
+    into a missed loop.  This is NOT in the reference; a lattice of one pose (dx = dy = dyaw = (0,)) is verify_candidates word for word.
+    Returns verify_candidates' tuple plus the picked lattice index of every candidate (None for one that `bow` does not name)."""
+    K = len(candidates)
+    if K == 0:
+        return None, None, DBL_MAX, 0, []
+    G = np.asarray(guesses, np.float32)
+    if G.shape != (K, 4, 4):
+        raise ValueError(f"guesses must be [{K},4,4]")
+    slots = list(range(K)) if bow is None else list(dict.fromkeys(int(c) for _, c in bow))
+    if not slots:
+        return None, None, DBL_MAX, 0, [None] * K
+    is_id = lambda c: isinstance(c, (int, np.integer))
+    size = lambda c: engine.keyframe_get(c, fetch=False) if is_id(c) else len(c)
+    tgt = target if is_id(target) else ndt._as_points(target)
+    srcs = [candidates[c] if is_id(candidates[c]) else ndt._as_points(candidates[c]) for c in slots]
+    engine.batch_reserve(len(slots), max(size(tgt), 1), max(max(size(s) for s in srcs), 1))
+    for k, s in enumerate(srcs):
+        (engine.batch_set_target_keyframe if is_id(tgt) else engine.batch_set_target)(k, tgt)
+        (engine.batch_set_source_keyframe if is_id(s) else engine.batch_set_source)(k, s)
+    L = np.stack([pose_lattice(G[c], **(lattice or {})) for c in slots])               # [slots, n_poses, 4, 4]
+    n_poses = L.shape[1]
+    sc_l, _ = engine.batch_score_poses(np.repeat(np.arange(len(slots)), n_poses), L.reshape(-1, 4, 4))
+    picked = pick_starts(sc_l.reshape(len(slots), n_poses))
+    res = engine.batch_align(L[np.arange(len(slots)), picked])
+    sc, _ = engine.batch_fitness_scores(max_range)
+    converged, scores, finals, picks = [False] * K, [DBL_MAX] * K, [None] * K, [None] * K
+    for k, c in enumerate(slots):
+        converged[c], scores[c], finals[c], picks[c] = res[k]["converged"], float(sc[k]), res[k]["final"], picked[k]
+    if bow is None:
+        return (*select_matching(converged, scores, finals, thresh), picks)
+    return (*select_matching_and_bow(converged, scores, finals, bow, thresh), picks)
+
+
 def verify_candidates_ndt(engine: ndt.Engine, target, candidates, guesses, max_range: float = float("inf"), thresh: float = 0.5, bow=None):
     """verify_candidates for registration_method = NDT (pcl::NormalDistributionsTransform, the factory's fall-back): the same arguments, the
     same tuple, on an engine whose MI355NDT_OPT_NDT_CLASS is 1 (registrations.select_registration_method makes one).  The batch surface serves

@@ -170,7 +170,9 @@ SYMBOLS = [
     "mi355ndt_icp_batch_reserve", "mi355ndt_icp_batch_set_source", "mi355ndt_icp_batch_set_source_keyframe", "mi355ndt_icp_batch_align",
     "mi355ndt_icp_batch_get_aligned", "mi355ndt_icp_batch_stats",
     "mi355ndt_knn_params_default", "mi355ndt_keyframe_knn", "mi355ndt_keyframe_knn_ids", "mi355ndt_keyframe_radius_search",
+    "mi355ndt_batch_score_poses",
 ]
+SCORE_POSES_MAX_ITEMS = 65536  # MI355NDT_SCORE_POSES_MAX_ITEMS: items of one mi355ndt_batch_score_poses
 KNN_ORDER_AUTO, KNN_ORDER_INPUT, KNN_ORDER_CELL = 0, 1, 2   # MI355NDT_KNN_ORDER_*: how keyframe_knn deals its queries to the lanes; no result word depends on it
 KNN_MAX_K = 64                 # MI355NDT_KNN_MAX_K
 ICP_BATCH_MAX = 64             # MI355NDT_ICP_BATCH_MAX: slots of one mi355ndt_icp_batch_align
@@ -320,6 +322,7 @@ def load_library(path: str = LIB_PATH):
     L.mi355ndt_batch_size.argtypes = [vp]
     L.mi355ndt_batch_pose_records.argtypes = [vp, i, i, vp, sz]
     L.mi355ndt_batch_fitness_scores.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.mi355ndt_batch_score_poses.argtypes = [vp, i, vp, vp, vp, vp]
     L.mi355ndt_profile_enable.argtypes = [vp, i]
     L.mi355ndt_profile_reset.argtypes = [vp]
     L.mi355ndt_profile_get.argtypes = [vp, C.POINTER(Profile)]
@@ -1315,6 +1318,26 @@ class Engine:
                                                          scores.ctypes.data_as(C.c_void_p), inliers.ctypes.data_as(C.c_void_p)),
                   "batch_fitness_scores")
         return scores[:n], inliers[:n]
+
+    def batch_score_poses(self, pairs, poses):
+        """The score and the hit count of one derivative sweep for every (pair of the bound batch, 4x4 f32 pose) item, in one call
+        (mi355ndt_batch_score_poses): (scores float64[n], hits int64[n]).  pairs: n slot indices, in any order, repeated or left out at
+        will; poses: [n,4,4], or one [4,4] for all items.  Item e's two words are bit for bit derivatives_T(poses[e], any Rj) of a one-pair
+        engine holding pair pairs[e]'s clouds; no gradient, no Hessian, and nothing of the batch's align state changes.  Not a call of the
+        reference: loop_closure.verify_candidates_search picks start poses with it."""
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).ravel())
+        n = int(pr.shape[0])
+        M = np.asarray(poses, np.float32)
+        if M.shape == (4, 4):
+            M = np.broadcast_to(M, (n, 4, 4))
+        if M.shape != (n, 4, 4):
+            raise ValueError(f"poses must be [{n},4,4] or [4,4]")
+        t = np.ascontiguousarray(np.transpose(M, (0, 2, 1))).reshape(n, 16)
+        scores = np.zeros(max(n, 1), np.float64)
+        hits = np.zeros(max(n, 1), np.int64)
+        self._chk(self.lib.mi355ndt_batch_score_poses(self.h, n, pr.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                      scores.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p)), "batch_score_poses")
+        return scores[:n], hits[:n]
 
     def synchronize(self):
         self._chk(self.lib.mi355ndt_synchronize(self.h), "synchronize")
